@@ -18,19 +18,25 @@ Default precision: bf16x2 (hi+lo split bf16 MFMA operands), the mode whose PDE l
 (--prec bf16) are reported under `other_precision_mode`.
 --leads B: BASELINE configs[2], B field samples x 37 265 points in one step (place_lead_batch).
 
-Protocol: `first_block_ms` (the `warmup` + `steps` replays straight after the capture), a pre-warm to a steady clock, then `--blocks` (10) blocks of
-`steps` replays, each bracketed by barrier + synchronize; `ms_per_step` is the median block, every block time the MAX over the ranks.  Lead batches
-start every block from a restored state and check that it stayed finite (a draw of the fields that hits the reference formula's NaN is discarded).
-N > 1 over RCCL: the measurement runs as segment graphs + host-issued all-reduces; with DPN_BENCH_TRY_FORMS=1 the one-graph form (all-reduces
-captured) is tried at the END and reported if faster -- a stall of that trial keeps the finished line (exit code 0).  Environment: DPN_BENCH_WATCHDOG_S (300), DPN_PG_TIMEOUT_S (600),
+Protocol of a plain run: `warmup` replays, a pre-warm to a steady clock (untimed, --no-prewarm skips it), the state from right after
+the capture restored, then ONE timed block of `steps` replays, bracketed by barrier + synchronize; `ms_per_step` is that block / `steps`, the MAX over the ranks.
+The timed steps therefore start from the same parameters and optimiser state from run to run, however many replays the clock took to settle, and
+`--dump-outputs DIR` writes what the last of them computed (loss, gradient norm, every gradient and updated parameter as DIR/<name>.npy, float32).
+Protocol of `--full`: `first_block_ms` (the `warmup` + `steps` replays straight after the capture), a pre-warm to a steady clock, then `--blocks`
+(10) blocks of `steps` replays; `ms_per_step` is the median block, every block time the MAX over the ranks; then every extra listed below.
+Lead batches start every block from a restored state and check that it stayed finite (a draw of the fields that hits the reference formula's NaN
+is discarded).
+N > 1 over RCCL: the measurement runs as segment graphs + host-issued all-reduces; with --full and DPN_BENCH_TRY_FORMS=1 the one-graph form (all-reduces
+captured) is tried at the END and reported if faster -- a stall of that trial keeps the finished line (exit code 14).  Environment: DPN_BENCH_WATCHDOG_S (300), DPN_PG_TIMEOUT_S (600),
 DPN_BENCH_TRIAL_WATCHDOG_S (90), DPN_BENCH_TRY_FORMS=1 (the end-of-run trial: opt-in), DPN_BENCH_CAPTURE_COLLECTIVES=0|1 (pin the form), DPN_BENCH_RCCL_ONE_RANK=1 /
 DPN_BENCH_ONE_DEVICE=1 + DPN_BENCH_BACKEND=gloo (exercise the N > 1 code path on a one-GPU box), DPN_BENCH_SPLIT_STEP=1.
 
-Prints ONE JSON line on rank 0: the contract keys, `roofline` (the fused forward + Jacobian kernel, MFMA-bound; duration from device-clock stamp
+Prints ONE JSON line on rank 0: the contract keys, `config`, `switches` (every DPN_* variable and non-default frozen switch) and `collective`
+(devices, buckets); with --full also `roofline` (the fused forward + Jacobian kernel, MFMA-bound; duration from device-clock stamp
 nodes around its launch INSIDE the replayed step graph, `roofline.in_step`; `kernel_ms_eager_pair` = a HIP event pair around eager launches),
-`roofline_hbm_kernel` (dpn_wgrad_kernel, backward stage 1), `pde_losses` (the six scalars of the workload), `switches` (every DPN_* variable and
-non-default frozen switch), `collective` (devices, buckets, per-rank times, exposed all-reduce time, step-form trial), `other_precision_mode`,
-`lead_batch_probe` (8 fields in one step), `cpu_baseline` (the oracle on the host cores, reference schedule + shared-derivative variant).
+`roofline_hbm_kernel` (dpn_wgrad_kernel, backward stage 1), `pde_losses` (the six scalars of the workload), `collective` per-rank times, exposed
+all-reduce time and step-form trial, `other_precision_mode`, `lead_batch_full` (61 fields in one step), `lead_batch_probe` (8 fields),
+`cpu_baseline` (the oracle on the host cores, reference schedule + shared-derivative variant).
 """
 import argparse
 import json
@@ -84,6 +90,26 @@ def synth_batch(n_points, device, seed, lon=257, lat=145, dx=27000.0, dy=27000.0
     b = dict(field_data=field, forecast_h=fh, x=x.reshape(-1, 1), y=y.reshape(-1, 1), t=t.reshape(-1, 1), f=f.reshape(-1, 1).float(),
              coord_data=cd)
     return {k: v.to(device) for k, v in b.items()}
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, loss, opt, net):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy in float32 -- the loss, the global gradient norm of the clip,
+    every parameter's gradient (grad.<name>) and every parameter as the optimiser left it (param.<name>): 2 x 5.6 M values, 45 MB."""
+    import numpy as np
+    names = {id(p): n for n, p in net.named_parameters()}
+    arrays = {'loss': loss, 'grad_norm': opt.grad_norm}
+    for p, g in zip(opt.params, opt._slots):               # the flat buffer's view of each gradient: what the step's backward wrote
+        arrays['grad.' + names[id(p)]] = g
+        arrays['param.' + names[id(p)]] = p
+    total = sum(v.numel() * 4 for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit('bench.py --dump-outputs: %d bytes of outputs exceed the %d-byte limit' % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), v.detach().float().cpu().numpy())
 
 
 def cpu_baseline(sample_points, seed, share_derivatives=False):
@@ -177,15 +203,20 @@ def main():
     ap.add_argument('--prec', default=os.environ.get('DPN_PREC', 'bf16x2'), choices=['bf16', 'bf16x2'],
                     help='bf16x2 (default): the parity-grade mode (PDE losses within 1e-4 of the fp32 reference); bf16: plain bf16 operands')
     ap.add_argument('--no-graph', action='store_true', help='do not capture the step in a hipGraph')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='the long run: the headline timed as the median of --blocks blocks, then the rooflines, power samples, '
+                                                        'the other precision mode, the configs[2] legs, the PDE losses and the CPU baseline (off: the headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last of them computed as DIR/<name>.npy (float32): loss, grad_norm, grad.<parameter>, '
+                         'param.<parameter> (updated); a plain run gives the same inputs to that step on every run')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-sample', type=int, default=0, help='points of the CPU baseline sample (0 = the workload itself: all --points)')
     ap.add_argument('--cpu-threads', type=int, default=0, help='threads for the CPU baseline (0 = min(32, cores))')
-    ap.add_argument('--no-alt', action='store_true', help='skip the short run of the other precision mode')
-    ap.add_argument('--no-power', action='store_true', help='skip the rocm-smi clock / socket power samples (about 5 s)')
-    ap.add_argument('--blocks', type=int, default=10, help='timed blocks of --steps replays each; ms_per_step is the median block')
+    ap.add_argument('--no-alt', action='store_true', help='with --full: skip the short run of the other precision mode')
+    ap.add_argument('--no-power', action='store_true', help='with --full: skip the rocm-smi clock / socket power samples (about 5 s)')
+    ap.add_argument('--blocks', type=int, default=10, help='with --full: timed blocks of --steps replays each; ms_per_step is the median block')
     ap.add_argument('--no-prewarm', action='store_true', help='skip the untimed replays that bring the clock to a steady state (their number depends on timing: '
-                                                              'a run that must do a fixed number of optimiser steps -- tests comparing two runs -- switches them off)')
-    ap.add_argument('--no-lead-probe', action='store_true', help='skip the configs[2] legs of the default run: the full-size 61-lead batch (scaled and default initialisation, '
+                                                              'a --full run that must do a fixed number of optimiser steps -- tests comparing two runs -- switches them off)')
+    ap.add_argument('--no-lead-probe', action='store_true', help='with --full: skip the configs[2] legs: the full-size 61-lead batch (scaled and default initialisation, '
                                                                  '15 steps each) and the 8-lead probe (about 6 s of GPU work in all)')
     ap.add_argument('--init', default=None, choices=['default', 'scaled'],
                     help='weight initialisation: default = PyTorch\'s (what configs[1] is measured on since round 1), scaled = ~1/sqrt(fan_in) uniform '
@@ -250,6 +281,7 @@ def main():
         return lb
     lead = make_leads(args.leads) if args.leads > 1 else None
     crit = torch.nn.MSELoss()
+    step_loss = [None]                             # the loss of the last step run through make_step's one-graph form
     # N > 1 (or DPN_BENCH_SPLIT_STEP=1 on one GPU, to time the same code path): three graph segments with a bucket all-reduce behind each
     split_step = world > 1 or one_rank_rccl or os.environ.get('DPN_BENCH_SPLIT_STEP') == '1'
     # DPN_BENCH_CAPTURE_COLLECTIVES=1: capture the bucket all-reduces inside ONE graph with the segments (opt-in: measured with a one-rank
@@ -273,6 +305,8 @@ def main():
                                          batch['forecast_h'], crit, lf, 0, 0, dev)
             loss.backward(one)                         # persistent seed: no ones_like fill per step
             opt.step()                                 # global-norm clip (2.5e7) + Adam in the HIP library
+            step_loss[0] = loss.detach()               # (captured: the graph's output, which every replay rewrites; detached, so that no
+                                                       # autograd graph of an earlier step stays alive into the capture)
             return loss
 
         if not split_step:
@@ -281,8 +315,9 @@ def main():
         staged = StagedPdeStep(m, opt, lead_batches[n_leads] if n_leads > 1 else batch, lf, lead_batch=n_leads > 1)
         return list(staged.stages) + [opt.step], staged
 
-    def run(prec, steps, warmup, use_graph, leads=None, blocks=None, steady=None):
-        """Build model + optimiser, capture the step, measure.  Protocol:
+    def run(prec, steps, warmup, use_graph, leads=None, blocks=None, steady=None, plain=False):
+        """Build model + optimiser, capture the step, measure.  plain: `warmup` replays, the pre-warm of 2., the state from right after the capture
+        restored, then ONE timed block of `steps` replays.  Otherwise (--full and its extra legs) the protocol of VERDICT r4 item 3:
           1. `first_block`: `warmup` untimed steps, then `steps` timed ones, straight after the capture -- what rounds 1-4 reported.  The GPU has
              been idle through the capture; its clock ramps over the first tens of milliseconds, so a 20-step block is taken ON
              the ramp.
@@ -368,6 +403,7 @@ def main():
         # NaN operands (which run FASTER: constant bit patterns toggle less).  So every block of a lead-batch run starts from the same state (parameters,
         # Adam moments, step counter as they were after the capture), restored OUTSIDE the timed bracket, and is checked to have stayed finite.
         snap = None
+        every_block_restored = n_leads > 1         # plain runs of one field restore the snapshot in front of the timed block only
         blocks_finite = []
         local_times = []                           # this rank's own clock per block (block_time returns the MAX over the ranks)
 
@@ -382,10 +418,10 @@ def main():
                 opt._v_flat.copy_(snap[2])
                 opt.step_count.copy_(snap[3])
 
-        def block_time(fn, k):
+        def block_time(fn, k, restore=False):
             if dog is not None:
                 dog.beat('a block of %d steps' % k)
-            if snap is not None:
+            if snap is not None and (every_block_restored or restore):
                 restore_snapshot()
             if world > 1:
                 torch.distributed.barrier()
@@ -404,7 +440,7 @@ def main():
                 t_ = torch.tensor([dt_], dtype=torch.float64, device=dev if torch.distributed.get_backend() == 'nccl' else 'cpu')
                 torch.distributed.all_reduce(t_, op=torch.distributed.ReduceOp.MAX)
                 dt_ = float(t_.item())
-            if snap is not None:
+            if every_block_restored:
                 # (the first moments are enough: a non-finite gradient at any step of the block stays in m = b1 m + (1 - b1) g, and finite moments
                 # cannot produce a non-finite parameter -- one reduction instead of one per parameter tensor)
                 blocks_finite.append(bool(torch.isfinite(opt._m_flat).all()))
@@ -445,20 +481,20 @@ def main():
                 if dog is not None:
                     dog.sync = sync
         fn = eager if graphs is None else replayer(graphs)
-        if n_leads > 1:
+        if n_leads > 1 or plain:
             torch.cuda.synchronize()
             snap = take_snapshot()
-        # 1. the first block, cold (rounds 1-4's protocol)
+        # 1. the first block, cold (rounds 1-4's protocol; a plain run times no block here)
         for _ in range(warmup):
             fn()
         if snap is not None:                       # (the warm-up replays belong to no block: the first block starts from the snapshot like every other)
             torch.cuda.synchronize()
-        first = block_time(fn, steps)
+        first = None if plain else block_time(fn, steps)
         # 2. pre-warm to a steady clock
         prewarm_s, prewarm_replays = 0.0, 0
         if steady:
             last = None
-            pw = 20 if snap is None else min(20, steps)
+            pw = min(20, steps) if every_block_restored else 20
             while prewarm_s < 4.0:
                 dt_ = block_time(fn, pw) * (20.0 / pw)
                 prewarm_s += dt_ * pw / 20.0
@@ -466,24 +502,24 @@ def main():
                 if last is not None and prewarm_s >= 0.5 and abs(dt_ - last) <= 0.01 * last:
                     break
                 last = dt_
-        # 3. the timed blocks
+        # 3. the timed blocks (plain: one, from the snapshot -- its inputs do not depend on how many replays the pre-warm took)
         times = []
-        while len(times) < blocks and (len(times) < min(3, blocks) or sum(times) < 8.0):
-            times.append(block_time(fn, steps))
-        tt = torch.tensor([first] + times, dtype=torch.float64)
-        own = local_times[-len(times):]            # the timed blocks as this rank's clock saw them
-        mine = sorted(own)[len(own) // 2] / steps * 1e3
+        if plain:
+            times.append(block_time(fn, steps, restore=True))
+        else:
+            while len(times) < blocks and (len(times) < min(3, blocks) or sum(times) < 8.0):
+                times.append(block_time(fn, steps))
         per_rank = None
-        if world > 1:                              # (first / times are already the MAX over the ranks, block by block)
+        if world > 1 and not plain:                # (first / times are already the MAX over the ranks, block by block)
+            own = local_times[-len(times):]        # the timed blocks as this rank's clock saw them
             every = [None] * world
-            torch.distributed.all_gather_object(every, mine)
+            torch.distributed.all_gather_object(every, sorted(own)[len(own) // 2] / steps * 1e3)
             per_rank = {'ms_per_step': [round(v, 4) for v in every], 'min': min(every), 'max': max(every), 'slowest_rank': int(max(range(world), key=lambda r: every[r])),
                         'fastest_rank': int(min(range(world), key=lambda r: every[r]))}
-        first, times = float(tt[0]), [float(v) for v in tt[1:]]
         med = sorted(times)[len(times) // 2]
         rec.update({'model': m, 'optimizer': opt, 'dt': med, 'graphed': graphs is not None, 'fn': fn, 'first_block_s': first, 'block_s': times,
                     'prewarm_s': prewarm_s, 'prewarm_replays': prewarm_replays, 'per_rank': per_rank, 'staged': staged, 'graphs': graphs,
-                    'n_reduce': n_reduce, 'replayer': replayer, 'blocks_finite': blocks_finite if snap is not None else None,
+                    'n_reduce': n_reduce, 'replayer': replayer, 'blocks_finite': blocks_finite if every_block_restored else None,
                     'recapture': (lambda: capture_one_graph() if (split_step and len(graphs) == 1) else capture_segments()) if graphs is not None else None,
                     'capture_one_graph': capture_one_graph, 'block_time': block_time, 'all_agree': all_agree, 'local_times': local_times, 'sync': sync})
         return rec
@@ -554,7 +590,7 @@ def main():
     dog = D.Watchdog(float(os.environ.get('DPN_BENCH_WATCHDOG_S', '300')), rank) if world > 1 else None
     from deepphysinet_amd import config as C
     weights_init[0] = args.init or ('scaled' if args.leads > 1 else 'default')
-    rec = run(args.prec, args.steps, args.warmup, not args.no_graph)
+    rec = run(args.prec, args.steps, args.warmup, not args.no_graph, plain=not args.full)
     # Lead batches: 61 random fields on default-initialised weights is an ill-conditioned start (losses of 4e13, half the points on clip bounds) and within the
     # first few optimiser steps the reference's own vapour formula can produce a NaN at one of the 2.3 M points (q_s = 0.622 e_s / (p - 0.378 e_s) with an
     # exactly cancelling denominator, interface_physics.py:165-185) -- whether it does is a matter of the last bits.  A run whose blocks did
@@ -567,17 +603,19 @@ def main():
         from deepphysinet_amd.encoder_ops import reset_enc_status
         reset_enc_status()                         # (sticky, set by the discarded attempt's non-finite weights)
         lead = make_leads(args.leads, shift=len(lead_attempts))
-        rec = run(args.prec, args.steps, args.warmup, not args.no_graph)
+        rec = run(args.prec, args.steps, args.warmup, not args.no_graph, plain=not args.full)
     if dog is not None:
         dog.stop()                                 # the timed region is over: what follows (rooflines on rank 0, the final barrier) has no collectives in flight
     m, dt, graphed, step_fn = rec['model'], rec['dt'], rec['graphed'], rec['fn']
+    if args.dump_outputs and rank == 0:            # NOW, like the PDE losses below: nothing may run the step again in front of it
+        dump_outputs(args.dump_outputs, rec['staged'].loss if rec['staged'] is not None else step_loss[0], rec['optimizer'], m.physics_net)
     pde_losses_out = finite_out = None             # evaluated NOW: nothing below may add optimiser steps in front of them
-    if rank == 0 and args.leads == 1:
+    if rank == 0 and args.leads == 1 and args.full:
         with torch.no_grad():                      # the six scaled PDE-loss scalars of the timed workload (SURVEY 8d asks for them next to the rate)
             terms = m.pde_loss_terms(batch['x'], batch['y'], batch['t'], batch['f'], batch['field_data'], batch['coord_data'], batch['forecast_h'])
         pde_losses_out = dict(zip(('motion_u', 'motion_v', 'continuous', 'energy', 'vapor', 'gas'), [float(v) for v in terms.cpu()]))
 
-    if rank == 0 and args.leads > 1:               # configs[2]: the six scalars averaged over the fields, and whether the run stayed finite
+    if rank == 0 and args.leads > 1 and args.full:  # configs[2]: the six scalars averaged over the fields, and whether the run stayed finite
         with torch.no_grad():
             _, terms = m.place_lead_batch(lead['x'], lead['y'], lead['t'], lead['f'], lead['field_data'], lead['coord_data'], lead['forecast_h'], crit,
                                           m.train_cfg['losses']['loss_factor'])
@@ -607,15 +645,18 @@ def main():
                    'step_segments': n_segments,           # N > 1: two backward segments (lead batches: three) + the optimiser, or one graph with the collectives captured
                    'step_form': rec['step_form'], 'collectives_in_graph': bool(split_step and graphed and n_segments == 1),
                    'graph_branches': list(C.FROZEN.branches)},
-        # ms_per_step is the MEDIAN of `timed_blocks` blocks of `steps` replays each, taken after the clock has settled (`prewarm_*`); the first block
-        # -- `warmup` + `steps` replays straight after the capture, the protocol of rounds 1-4 -- is reported beside it
+        # ms_per_step is the MEDIAN of `timed_blocks` blocks of `steps` replays each (a plain run: one block), taken after the clock has settled
+        # (`prewarm_*`); with --full the first block -- `warmup` + `steps` replays straight after the capture, the protocol of rounds 1-4 -- is
+        # reported beside it
         'timed_seconds': sum(rec['block_s']), 'timed_blocks': len(rec['block_s']),
         'block_ms_per_step': [round(b_ / args.steps * 1e3, 5) for b_ in rec['block_s']],
-        'first_block_ms': rec['first_block_s'] / args.steps * 1e3, 'prewarm_s': round(rec['prewarm_s'], 3), 'prewarm_replays': rec['prewarm_replays'],
+        'prewarm_s': round(rec['prewarm_s'], 3), 'prewarm_replays': rec['prewarm_replays'],
         'algorithmic_tflops_step': pts_per_s * ALG_FLOP_STEP / 1e12,
         'collective': coll,
         'switches': C.snapshot(),                   # every DPN_* variable of the environment + the frozen switches that differ from their defaults
     }
+    if rec['first_block_s'] is not None:
+        out['first_block_ms'] = rec['first_block_s'] / args.steps * 1e3
     if pde_losses_out is not None:
         out['pde_losses'] = pde_losses_out
     if finite_out is not None:
@@ -636,7 +677,7 @@ def main():
         coll['step_form_trial'] = rec['step_form_trial']
     if rec['per_rank']:
         coll['per_rank'] = rec['per_rank']
-    if sync is not None and rec['graphs'] is not None and len(rec['graphs']) > 1:
+    if args.full and sync is not None and rec['graphs'] is not None and len(rec['graphs']) > 1:
         # how long the optimiser segment actually WAITS for each bucket's all-reduce (an event pair around every wait, 20 replays): the part of
         # the collectives that the backward segments did not hide
         evs = []
@@ -779,7 +820,7 @@ def main():
                                          'executed_mfma_frac_of_peak': args.points * 6 * EXEC_MAC_BWD1 * 2 * nsplit / (b_ms * 1e-3) / MFMA_PEAK_BF16}
         return roof, roof_hbm
 
-    if rank == 0:
+    if rank == 0 and args.full:
         out['roofline'], out['roofline_hbm_kernel'] = kernel_rooflines(m, args.prec, in_step_kernel_times(rec))
         out['roofline']['step_frac_of_peak'] = pts_per_s / world * ALG_FLOP_STEP / MFMA_PEAK_BF16
         if not args.no_power and world == 1:
@@ -882,6 +923,7 @@ def main():
                                    'host_cpu': cpu_model, 'host_logical_cores': os.cpu_count(),
                                    'shared_jacobian_variant': {'value': v2, 'seconds_per_pass': secs2,
                                                                'note': 'same oracle, the 18 distinct derivatives taken once (SURVEY 8d variant ii)'}}
+    if rank == 0:
         from deepphysinet_amd.encoder_ops import check_enc_status
         try:
             check_enc_status()                     # an encoder weight left the range of the f16 hi+lo operand split during the run (or went non-finite)?
@@ -902,13 +944,14 @@ def main():
     # worked around here), and nothing of that kind may stand between an 8-GPU run and its line.
     stash = {'line': None, 'printed': False, 'lock': threading.Lock()}
     tdog = None
-    want_trial = (rec.get('graphed') and split_step and not one_graph_collectives and os.environ.get('DPN_BENCH_CAPTURE_COLLECTIVES') is None
+    want_trial = (args.full and rec.get('graphed') and split_step and not one_graph_collectives and os.environ.get('DPN_BENCH_CAPTURE_COLLECTIVES') is None
                   and rec.get('sync') is not None and torch.distributed.get_backend() == 'nccl' and rec.get('graphs') is not None and len(rec['graphs']) > 1
                   and os.environ.get('DPN_BENCH_TRY_FORMS', '0') == '1')
     if os.environ.get('DPN_BENCH_TRY_FORMS', '0') == '1' and not want_trial and rank == 0:
         # asked for and not run must be visible in the line (the default single-rank flow has released the measured step for the other-precision
         # and lead-batch runs by now: pass --no-alt --no-lead-probe with DPN_BENCH_RCCL_ONE_RANK=1)
-        coll['step_form_trial'] = {'skipped': 'the measured step is no longer held (--no-alt --no-lead-probe keep it) or it was not a captured multi-segment RCCL step'}
+        coll['step_form_trial'] = {'skipped': 'the measured step is no longer held (--no-alt --no-lead-probe keep it) or it was not a captured multi-segment RCCL step'
+                                   if args.full else 'the trial runs with --full only'}
     if want_trial:
         trial = {'segments_ms': None, 'one_graph_ms': None, 'error': None, 'segment_form_result': None}
         phase = ['start']

@@ -297,6 +297,44 @@ def test_bench_starts_its_own_ranks():
     assert out['config']['workload'].startswith('configs[3]') and out['collective']['HSA_ENABLE_IPC_MODE_LEGACY'] == '0'
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_the_same_outputs_every_run(tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline only, timed over exactly --steps replays, and --dump-outputs writes what the last of
+    them computed.  The timed steps start from the state right after the capture, so a run that pre-warmed the clock and one that did not
+    (--no-prewarm) dump bitwise equal outputs."""
+    env = dict(os.environ)
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'DPN_BENCH_BACKEND', 'DPN_BENCH_ONE_DEVICE', 'DPN_BENCH_RCCL_ONE_RANK', 'DPN_BENCH_SPLIT_STEP'):
+        env.pop(k, None)
+    outs, dirs = [], []
+    for i, extra in enumerate(([], ['--no-prewarm'])):
+        d = str(tmp_path / ('run%d' % i))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '3', '--points', '4096',
+                            '--dump-outputs', d] + extra, env=env, capture_output=True, text=True, timeout=1200)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1, lines
+        outs.append(json.loads(lines[0]))
+        dirs.append(d)
+    for o in outs:
+        assert all(k in o for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'))
+        assert o['steps'] == 4 and o['timed_blocks'] == 1 and o['ms_per_step'] > 0
+        assert abs(o['timed_seconds'] * 1e3 / 4 - o['ms_per_step']) <= 1e-9 * o['ms_per_step']
+        assert abs(o['value'] - 4096 * 4 / o['timed_seconds']) <= 1e-9 * o['value']
+        assert not {'roofline', 'roofline_hbm_kernel', 'power', 'other_precision_mode', 'lead_batch_full', 'lead_batch_probe', 'cpu_baseline',
+                    'pde_losses', 'first_block_ms'} & set(o), sorted(o)
+    assert outs[0]['prewarm_replays'] > 0 and outs[1]['prewarm_replays'] == 0
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) and len(names) == 2 + 2 * 155, names[:5]
+    assert 'loss.npy' in names and 'grad_norm.npy' in names
+    total = 0
+    for n in names:
+        a, b = np.load(os.path.join(dirs[0], n)), np.load(os.path.join(dirs[1], n))
+        assert a.dtype == np.float32 and np.isfinite(a).all(), n
+        assert np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 * 2 ** 20
+    assert float(np.load(os.path.join(dirs[0], 'loss.npy'))) > 0
+
+
 def test_bench_two_ranks_with_a_lead_batch_run_the_staged_captured_step():
     """`bench.py --gpus 2 --leads 3` (configs[2] per rank, sharded: configs[3] as SURVEY 8d defines it) runs the staged step
     -- three captured backward segments with a bucket all-reduce behind each, then the optimiser -- not an eager step with one collective."""
@@ -304,7 +342,7 @@ def test_bench_two_ranks_with_a_lead_batch_run_the_staged_captured_step():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--leads', '3', '--steps', '2', '--warmup', '1', '--points', '4096',
-                        '--no-cpu-baseline', '--no-alt'], env=env, capture_output=True, text=True, timeout=1200)
+                        '--full', '--no-cpu-baseline', '--no-alt'], env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
     assert out['n_gpus'] == 2 and out['config']['leads'] == 3 and out['config']['step_segments'] == 4 and out['config']['hip_graph'] is True
@@ -320,7 +358,7 @@ def test_bench_eight_ranks_on_one_device_run_the_scaling_benchmarks_code_path():
     env = dict(os.environ, DPN_BENCH_ONE_DEVICE='1', DPN_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1', '--points', '512', '--blocks', '2',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1', '--points', '512', '--full', '--blocks', '2',
                         '--no-prewarm', '--no-cpu-baseline', '--no-alt', '--no-power', '--no-lead-probe'], env=env, capture_output=True, text=True, timeout=2400)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
@@ -343,7 +381,7 @@ def test_bench_step_with_rccl_collectives_on_one_rank():
     outs = []
     for e in (env, {k: v for k, v in env.items() if k != 'DPN_BENCH_RCCL_ONE_RANK'}):
         r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2', '--points', '4096',
-                            '--no-cpu-baseline', '--no-alt', '--no-prewarm', '--blocks', '1', '--no-lead-probe'], env=e, capture_output=True, text=True,
+                            '--full', '--no-cpu-baseline', '--no-alt', '--no-prewarm', '--blocks', '1', '--no-lead-probe'], env=e, capture_output=True, text=True,
                            timeout=1200)
         assert r.returncode == 0, r.stderr[-3000:]
         outs.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1]))
@@ -371,7 +409,7 @@ def test_bench_trial_of_the_one_graph_form_keeps_the_segment_forms_line_when_it_
     env = dict(os.environ, DPN_BENCH_RCCL_ONE_RANK='1', DPN_BENCH_TRY_FORMS='1', HSA_ENABLE_IPC_MODE_LEGACY='0', MASTER_ADDR='127.0.0.1')
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'DPN_BENCH_BACKEND', 'DPN_BENCH_ONE_DEVICE', 'DPN_BENCH_CAPTURE_COLLECTIVES'):
         env.pop(k, None)
-    args = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2', '--points', '4096', '--no-cpu-baseline', '--no-alt',
+    args = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2', '--points', '4096', '--full', '--no-cpu-baseline', '--no-alt',
             '--no-prewarm', '--blocks', '2', '--no-lead-probe', '--no-power']
     r = subprocess.run(args, env=dict(env, MASTER_PORT=str(_free_port()), DPN_BENCH_TRIAL_TEST_STALL='replay', DPN_BENCH_TRIAL_WATCHDOG_S='5'),
                        capture_output=True, text=True, timeout=1200)
