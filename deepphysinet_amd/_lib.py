@@ -71,6 +71,7 @@ class DpnEncBwd(Structure):
 
 
 class DpnGemm16Problem(Structure):
+    """include/dpn_hip_experiments.h: the strided-GEMM description of dpn_wgrad16's core (layout mirror only: no entry point takes it)."""
     _fields_ = [(n, c_void_p) for n in ('A', 'B', 'C', 'asum', 'bias')] + [(n, c_int32) for n in ('M', 'N', 'K', 'ldc')] + \
                [(n, c_int64) for n in ('a_sm', 'a_sk', 'b_sn', 'b_sk')]
 
@@ -172,11 +173,6 @@ EXPORTS = {
 # Shelved experiments (include/dpn_hip_experiments.h): compiled only into libdpn_hip_exp.so (`python -m deepphysinet_amd.build --experiments`), which also
 # holds every product symbol; reached through load_experiments() by the code paths behind the matching frozen switches (config.py)
 EXPERIMENT_EXPORTS = {
-    'dpn_gemm16_partial_floats': (c_int64, [c_int, c_void_p, c_int]),
-    'dpn_gemm16': (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
-    'dpn_conv16_kp': (c_int64, [c_int]),
-    'dpn_conv16_split': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'dpn_conv16': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'dpn_gemm_fp8': (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
 }
 EXP_LIB_PATH = os.path.join(_HERE, 'libdpn_hip_exp.so')

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = [os.path.join(HERE, 'csrc', 'dpn_kernels.hip'), os.path.join(HERE, 'csrc', 'dpn_encoder.hip'),
         os.path.join(HERE, 'csrc', 'dpn_sampler.hip'), os.path.join(HERE, 'csrc', 'dpn_fp8.hip'),
         os.path.join(HERE, 'csrc', 'dpn_encoder_chain.hip')]
-DEPS = SRCS + [os.path.join(HERE, 'csrc', 'dpn_layout.h'), os.path.join(HERE, 'csrc', 'dpn_fwd_tiles.h'), os.path.join(HERE, 'csrc', 'dpn_fwd_pp.h'), os.path.join(HERE, 'csrc', 'dpn_fwd_tiles_persist.h'), os.path.join(os.path.dirname(HERE), 'include', 'dpn_hip.h'),
+DEPS = SRCS + [os.path.join(HERE, 'csrc', 'dpn_layout.h'), os.path.join(HERE, 'csrc', 'dpn_fwd_tiles.h'), os.path.join(os.path.dirname(HERE), 'include', 'dpn_hip.h'),
                os.path.join(os.path.dirname(HERE), 'include', 'dpn_hip_experiments.h')]
 LIB = os.path.join(HERE, 'libdpn_hip.so')
 
@@ -67,11 +67,11 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
 
 
 EXP_LIB = os.path.join(HERE, 'libdpn_hip_exp.so')
-EXP_UNITS = (4, 5)            # dpn_fp8.hip (the non-scaled fp8 GEMM), dpn_encoder_chain.hip (dpn_conv16*, dpn_gemm16): include/dpn_hip_experiments.h
+EXP_UNITS = (4,)              # dpn_fp8.hip (the non-scaled fp8 GEMM): include/dpn_hip_experiments.h
 
 
 def build_experiments(force: bool = False) -> str:
-    """libdpn_hip_exp.so: the product objects with the units that hold shelved kernels recompiled -DDPN_EXPERIMENTS (their entry points are
+    """libdpn_hip_exp.so: the product objects with the unit that holds shelved kernels recompiled -DDPN_EXPERIMENTS (their entry points are
     compiled out of the product library).  Tests of those kernels and the tools under tools/ that measure them load it."""
     build_library()
     deps = DEPS + [os.path.join(os.path.dirname(HERE), 'include', 'dpn_hip_experiments.h')]

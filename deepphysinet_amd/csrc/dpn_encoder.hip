@@ -314,7 +314,7 @@ DEV void attn_bwd_key_role(const AttnArgs& a, char* smem) {
 
 __global__ __launch_bounds__(kAT) void dpn_attn_bwd_kernel(AttnArgs a0) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // grid.z = 3 * field + role (round 6: the key role's dV and dK are two roles; DPN_ATTN_BWD_ROLES=2 launches rounds 3-5's two: a0.roles)
+    // grid.z = 3 * field + role (round 6: the key role's dV and dK are two roles while batch <= 2; larger batches launch rounds 3-5's two: a0.roles)
     const int roles = a0.roles, role = blockIdx.z % roles;
     const AttnArgs a = attn_field(a0, blockIdx.z / roles);
     // (ablation builds, wrong results on purpose: tools/variant_build.py --unit=2 -DATTN_ABL_NOQ | -DATTN_ABL_NOK time one role alone)
@@ -501,9 +501,8 @@ int dpn_attn_bwd(const float* q, const float* k, const float* v, const float* o,
     unsigned long long bit;
     if (dpn_first_use_on_device(done, bit)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dpn_attn_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kAttnLds); done.fetch_or(bit, std::memory_order_release); }
     // Round 6: three roles per field (dQ | dK | dV) while the launch does not fill the chip -- one field: 216 workgroups, 9.2 against 11.0 us per launch, the step
-    // -7.7 us (profiles/round6_attn_bwd_roles.txt); lead batches keep two (61 fields: 56.4 against 56.5 ms).  DPN_ATTN_BWD_ROLES=2|3 overrides.
-    const char* er = getenv("DPN_ATTN_BWD_ROLES");
-    a.roles = er ? ((er[0] == '2') ? 2 : 3) : (batch <= 2 ? 3 : 2);
+    // -7.7 us (profiles/round6_attn_bwd_roles.txt); lead batches keep two (61 fields: 56.4 against 56.5 ms).
+    a.roles = batch <= 2 ? 3 : 2;
     hipLaunchKernelGGL(dpn_attn_bwd_kernel, dim3((L + 31) / 32, kH, a.roles * batch), dim3(kAT), kAttnLds, s, a);
     return (int)hipGetLastError();
 }

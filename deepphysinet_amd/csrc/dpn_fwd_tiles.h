@@ -330,85 +330,6 @@ DEV void dpe_tile(float (&d)[16], const Args& a, const int c, const int t, const
         d[r + 1] = -fr * s;
     }
 }
-// ---- Round 6: the same features with their memory operands FRONT-LOADED (used by dpn_fwd_pp_kernel).  pe3_frag / pe6_frag_dot / dpe_tile above fetch the lane's
-// coordinate (through a pointer selected by the wave's k-step) and one frequency per angle INSIDE every fragment; the *_x forms take the coordinate and the
-// four frequencies of a fragment as values, so that the caller issues ALL loads of a phase first, then the arithmetic -- identical operations in identical order
-// (bit-identical results: tools/fwd_dump.py).  Measured: in the ping-pong kernel, where a service interval is ONE wave per SIMD with nothing to hide a latency
-// behind, a fragment of four angles went from 1 350 to ~900 cycles (the arithmetic alone is 4 x 146: tools/microbench/valu_ilp.hip); in dpn_fwd_tiles_kernel and
-// dpn_bwd_tiles_kernel the same change measured neutral to -1 % (the partner workgroup's waves cover the latencies there) and they keep the forms above.
-template <class Args>
-DEV float load_xi(const Args& a, const int c, const int64_t pc) {          // x / dx / (lon-1): two fp32 divisions (interface_physics.py:324-326); t: one
-    // all three coordinates are fetched and the VALUE is selected: a pointer selected by the (wave-uniform, run-time) c makes hipcc index the kernel-argument
-    // block, which then lives in scratch memory (136 bytes of private segment and a scratch load per use -- seen, round 6)
-    const float xr = a.x[pc], yr = a.y[pc], tr = a.t[pc];
-    const float raw = (c == 0) ? xr : (c == 1) ? yr : tr;
-    const float d1 = (c == 0) ? a.geo.dx : (c == 1) ? a.geo.dy : a.geo.pred_t_span;
-    const float d2 = (c == 0) ? a.geo.lon_m1 : (c == 1) ? a.geo.lat_m1 : 1.0f;
-    return raw / d1 / d2;
-}
-DEV f32x4 load_fr4(const float* freqs, const int idx) { return *reinterpret_cast<const f32x4*>(freqs + idx); }     // idx % 4 == 0: 16-byte aligned
-template <int NS>
-DEV void pe3_frag_x(Frag<NS>& f, const float xi, const f32x4 fr) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        float s, co;
-        ts_sincos<NS>(xi * fr[q], s, co);
-        frag_set2<NS>(f, q, s, co);
-    }
-}
-template <int NS>
-DEV void pe6_frag_x(Frag<NS>& f, const float v, const f32x4 fr, const float g = 1.0f) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        float s, co;
-        ts_sincos<NS>(v * fr[q], s, co);
-        frag_set2<NS>(f, q, g * s, g * co);
-    }
-}
-template <int NS>
-DEV void pe6_frag_dot_x(Frag<NS>& f, const float v, const f32x4 fr, const float* bv8, float& dot) {      // bv8: the fragment's eight entries of the 192-vector (LDS)
-    const f32x4* b4 = reinterpret_cast<const f32x4*>(bv8);
-    const f32x4 b0 = b4[0], b1 = b4[1];
-    const float bb[8] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        float s, co;
-        ts_sincos<NS>(v * fr[q], s, co);
-        frag_set2<NS>(f, q, s, co);
-        dot = fmaf(s, bb[2 * q], dot);
-        dot = fmaf(co, bb[2 * q + 1], dot);
-    }
-}
-template <int NS>
-DEV void z0_frag_x(Frag<NS>& f, const float xi, const f32x4 fr4, const float g, const float gjc) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float fr = fr4[q];
-        float s, co;
-        ts_sincos<NS>(xi * fr, s, co);
-        const float gf = gjc * fr;
-        frag_set2<NS>(f, q, fmaf(g, s, gf * co), fmaf(g, co, -gf * s));
-    }
-}
-// Jacobian contraction of one gpe tile pair (t = 0, 1) of column tile p with d pe3 / d xi_c: jc += sum_r acc[t][r] * d[r], r ascending, t outer -- the order
-// of dpe_tile + the caller's loop.  fr[kq] = the four frequencies 8 kq + 4 h .. + 3 of the coordinate's k-step kq
-template <int NS>
-DEV void jac_contract_x(float& jc, const f32x16 (&acc_t)[2], const float xi, const f32x4 (&fr)[4]) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        float d[16];
-#pragma unroll
-        for (int rp = 0; rp < 8; ++rp) {
-            const float f = fr[(2 * t + (rp >> 2)) & 3][rp & 3];
-            float s, co;
-            ts_sincos<NS>(xi * f, s, co);
-            d[2 * rp] = f * co;
-            d[2 * rp + 1] = -f * s;
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) jc = fmaf(acc_t[t][r], d[r], jc);
-    }
-}
 }  // namespace ts
 
 // Experiment build (-DDPN_TIMELINE -DTS_TIMELINE, tools/tiles_timeline.py): lane 0 of every wave writes the shader clock at the phase
@@ -730,10 +651,7 @@ template <int NS>
 __global__ __launch_bounds__(256, 3) void dpn_bwd_tiles_kernel(BwdArgs a) {
     constexpr int kXBytes = 12 * 2 * NS * 1024;
     __shared__ __attribute__((aligned(16))) char lds[kXBytes + 1024];
-    // a.reverse (DPN_BWD_ORDER=reverse, a probe of the memory-side cache: DESIGN.md section 4c): workgroups walk nets and tiles in the opposite order of the
-    // forward launch, so stage 1 begins on the saved state the forward wrote last.  Same values either way (no sum crosses a tile).
-    const int net = a.reverse ? kNets - 1 - (int)blockIdx.y : (int)blockIdx.y;
-    const unsigned bx = a.reverse ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
+    const int net = (int)blockIdx.y;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
     TS_STAMP(0);
@@ -750,7 +668,7 @@ __global__ __launch_bounds__(256, 3) void dpn_bwd_tiles_kernel(BwdArgs a) {
     auto chunk = [&](const int kb) __attribute__((always_inline)) { return pk + (long)kb * 1024 * NS; };
     ts::Head<NS, 2> H;
     ts::gemm_head<NS, 12, 2>(chunk(kS0 + 2 * w * 12), lane, H);
-    const int64_t tile0 = (int64_t)bx * 2;
+    const int64_t tile0 = (int64_t)blockIdx.x * 2;
     const int64_t tiles32 = a.n_pad / 32;
     int64_t pc[2];
     float g[2];                                               // cotangent of the lane's point in column tile p (zero for padding points)

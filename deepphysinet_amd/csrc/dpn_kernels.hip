@@ -1050,10 +1050,6 @@ __global__ __launch_bounds__(256, 1) void dpn_fwd_kernel(FwdArgs a) {
     }
 }
 
-#if DPN_HAS_POINT && defined(DPN_EXPERIMENT_FWD2)
-#include "../../tools/experiments/dpn_fwd2_eight_waves.h"       // shelved eight-wave variant (measured slower; see its header and DESIGN.md)
-#endif
-
 #if DPN_HAS_REST
 // g_pe[n][c] = sum_k g_out[n][k] * gpe[n][k][c]: the cotangent of caller-encoded coordinates (PhysicsNet.forward backward w.r.t. coord_x)
 __global__ __launch_bounds__(192) void dpn_contract_gpe_kernel(const float* g_out, const float* gpe, int64_t n, float* g_pe) {
@@ -1251,7 +1247,6 @@ struct BwdArgs {
     const float* g_scale;    // device scalar multiplied into both cotangent streams as they are read (an upstream cotangent on unit-cotangent streams), or null
     void* saved;
     void* operands;
-    int reverse;             // tile-split kernel: walk nets / tiles in the opposite order (DPN_BWD_ORDER=reverse: a cache-residency probe)
 #ifdef DPN_TIMELINE
     unsigned* timeline;      // experiment build: [net][workgroup][4 waves][48] shader clocks at the phase boundaries of dpn_bwd_tiles_kernel
 #endif
@@ -1334,8 +1329,8 @@ __global__ __launch_bounds__(256, 1) void dpn_bwd_kernel(BwdArgs a) {
 
 #if DPN_HAS_POINT
 #include "dpn_fwd_tiles.h"                                       // tile-split forward / backward kernels (the hi+lo mode's default)
-#include "dpn_fwd_pp.h"                                          // round 6: the ping-pong form of the tile-split forward (one persistent 8-wave workgroup per CU)
-#include "dpn_fwd_tiles_persist.h"                               // round 6: persistent workgroups, the next item's features built by the wave that idles through the last GEMM
+// (round 6's ping-pong and persistent forms of the tile-split forward, dpn_fwd_pp.h / dpn_fwd_tiles_persist.h, and the eight-wave forward of
+//  tools/experiments: measured slower, removed; last present at 3bc40f4)
 #endif
 
 #if DPN_HAS_REST
@@ -1359,7 +1354,6 @@ struct WgradArgs {
     void* saved;
     void* operands;
     float* partials;
-    int reverse;            // every workgroup walks its point range from the end (DPN_WGRAD_ORDER=reverse: a cache-residency probe; the sums' order changes)
 #ifdef DPN_WGRAD_PHASES
     unsigned* phases;       // experiment build: [net][workgroup][8 waves][8]: cycles in wait / barrier / issue / compute, tiles
 #endif
@@ -1460,7 +1454,6 @@ DEV void wgrad_body(const WgradArgs& a, char* lds, const int split, const int ne
     }
     auto issue = [&](int64_t tile, int slot) __attribute__((always_inline)) {
         char* sl = lds + slot * kSlot;
-        if (a.reverse && t1 > t0) tile = t0 + (t1 - 1 - tile);
 #pragma unroll
         for (int j = 0; j < S::kIssue; ++j) {
             // read-once operand streams carry the non-temporal hint; the per-point pe6 table of product 2 is read by six nets' workgroups and should
@@ -2543,33 +2536,6 @@ static inline int64_t pad_points(int64_t n) { return ((n + 127) / 128) * 128; }
 // hi+lo mode: the tile-split kernels (dpn_fwd_tiles.h; 64 points per workgroup, two workgroups per CU).  Caller-encoded coordinates and the
 // single-bf16 mode stay on the ring kernels.  DPN_FWD_KERNEL / DPN_BWD_KERNEL = ring | tiles override (read per call: the tests compare the two
 // decompositions inside one process).
-static inline int order_reversed(const char* knob) {          // read on every launch: a measurement switch (tools set it between runs of one process)
-    const char* e = getenv(knob);
-    return e && e[0] == 'r' ? 1 : 0;                     // "reverse"
-}
-#ifndef DPN_FWD_PP_DEFAULT
-#define DPN_FWD_PP_DEFAULT 0
-#endif
-static inline bool use_pp() {
-    const char* e = getenv("DPN_FWD_PP");
-    return e ? (e[0] == '1') : (DPN_FWD_PP_DEFAULT != 0);
-}
-#ifndef DPN_FWD_PERSIST_DEFAULT
-#define DPN_FWD_PERSIST_DEFAULT 0
-#endif
-static inline bool use_persist() {                      // DPN_FWD_PERSIST=0|1, read per call (A/B and bitwise comparison inside one process)
-    const char* e = getenv("DPN_FWD_PERSIST");
-    return e ? (e[0] == '1') : (DPN_FWD_PERSIST_DEFAULT != 0);
-}
-static inline int cu_count() {                          // compute units of the current device (one persistent workgroup each)
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-        else n = 256;
-    }
-    return n;
-}
 static inline bool use_tiles(const char* knob, int prec, bool has_pe_in) {
     const char* force = getenv(knob);
     return (force ? (force[0] == 't') : (prec == 2)) && !has_pe_in;
@@ -2712,33 +2678,10 @@ static int fwd_launch(const float* x, const float* y, const float* t, const floa
 #endif
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)(a.n_pad / 128), n_nets);
-#ifdef DPN_EXPERIMENT_FWD2
-    if (!pe_in && getenv("DPN_FWD2") != nullptr) {          // experiment build only: the shelved eight-wave kernel
-        if (prec == 1) hipLaunchKernelGGL(dpn_fwd2_kernel<1>, grid, dim3(512), 0, s, a);
-        else hipLaunchKernelGGL(dpn_fwd2_kernel<2>, grid, dim3(512), 0, s, a);
-        return ck(hipGetLastError());
-    }
-#endif
     // hi+lo mode: the tile-split kernel (dpn_fwd_tiles.h; 64 points per workgroup, two workgroups per CU).  Caller-encoded coordinates
     // and the single-bf16 mode stay on the ring kernel (one bf16 product per fragment pair cannot pay for the doubled weight stream).
     // DPN_FWD_KERNEL=ring|tiles overrides (A/B measurements, bitwise comparison of the two kernels in the tests).
     if (use_tiles("DPN_FWD_KERNEL", prec, pe_in != nullptr)) {    // (expects the FUSED packed form: dpn_fwd_form)
-        // Training shape (saved state AND Jacobian wanted) in the hi+lo mode: the ping-pong form (dpn_fwd_pp.h), bit-identical results.  DPN_FWD_PP=0|1
-        // overrides (read per call, like DPN_FWD_KERNEL: the tests compare the two forms inside one process).
-        if (prec == 2 && saved && jac_n && use_persist() && a.n_pad / 64 * n_nets < (1ll << 31)) {
-            const int64_t items = (a.n_pad / 64) * n_nets;
-            const int wgs = 2 * cu_count();                      // two workgroups per CU (72 KB of LDS, <= 256 registers each)
-            const dim3 gridp((unsigned)(items < wgs ? items : wgs));
-            hipLaunchKernelGGL(dpn_fwd_tiles_persist_kernel<2>, gridp, dim3(256), 0, s, a, n_nets);
-            return ck(hipGetLastError());
-        }
-        if (prec == 2 && saved && jac_n && use_pp()) {
-            const int64_t items = (a.n_pad / 128) * n_nets;
-            const int cus = cu_count();
-            const dim3 gridp((unsigned)(items < cus ? items : cus));
-            hipLaunchKernelGGL(dpn_fwd_pp_kernel<2>, gridp, dim3(512), 0, s, a, n_nets);
-            return ck(hipGetLastError());
-        }
         const dim3 grid64((unsigned)(a.n_pad / 64), n_nets);
         if (prec == 1) hipLaunchKernelGGL(dpn_fwd_tiles_kernel<1>, grid64, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(dpn_fwd_tiles_kernel<2>, grid64, dim3(256), 0, s, a);
@@ -2810,10 +2753,10 @@ static int bwd_points_launch(const float* x, const float* y, const float* t, con
     if (pe_in ? (g_jxi != nullptr) : (!x || !y || !t)) return -1;
 #ifdef DPN_TIMELINE
     BwdArgs a{x, y, t, coord_data, freqs, pe_in, n, pad_points(n), *geo, reinterpret_cast<const char*>(packed), g_out, g_jxi, g_scale,
-              const_cast<void*>(saved), operands, order_reversed("DPN_BWD_ORDER"), g_timeline};
+              const_cast<void*>(saved), operands, g_timeline};
 #else
     BwdArgs a{x, y, t, coord_data, freqs, pe_in, n, pad_points(n), *geo, reinterpret_cast<const char*>(packed), g_out, g_jxi, g_scale,
-              const_cast<void*>(saved), operands, order_reversed("DPN_BWD_ORDER")};
+              const_cast<void*>(saved), operands};
 #endif
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)(a.n_pad / 128), kNets);
@@ -2838,7 +2781,7 @@ int dpn_wgrad(int64_t n, int prec, const float* g_out, const void* saved, const 
     if (!g_out || !saved || !operands || !partials || n <= 0 || (prec != 1 && prec != 2)) return -1;
     const SplitPlan plan = choose_plan(pad_points(n), prec);
     WgradArgs a{n, pad_points(n), {plan.s[0], plan.s[1], plan.s[2], plan.s[3]}, const_cast<void*>(saved), const_cast<void*>(operands),
-                reinterpret_cast<float*>(partials), order_reversed("DPN_WGRAD_ORDER")};
+                reinterpret_cast<float*>(partials)};
 #ifdef DPN_WGRAD_PHASES
     a.phases = g_wgrad_phases;
 #endif
@@ -2961,18 +2904,10 @@ static int sgemm_batch_launch(int n_problems, const DpnGemmProblem* problems, in
         hipLaunchKernelGGL((dpn_sgemm_batch_kernel<256, 1, 512>), dim3(gx, gy, gz), dim3(512), 0, reinterpret_cast<hipStream_t>(stream), b);
         return ck(hipGetLastError());
     }
-    // Round 6: 64 x 64 output tiles (four 32 x 32 sub-tiles on eight waves: half the L2 -> LDS bytes per MAC) are in the kernel and OFF:
-    // measured slower on every launch of the step -- token convolution + assemble 27.3 against 25.0 us (captured and replayed, tools/embed_parts_bench.py), the
-    // heads' forward 17.7 against 16.3, their backward 34.6 against 26.9 us (rocprofv3): these GEMMs wait for latency, not for L2 bytes, and a quarter of the
-    // workgroups with four times the serial work each is the wrong trade (profiles/round6_sgemm_tile_ab.txt).  DPN_SGEMM_TILE=64 selects it.
-    const char* force = getenv("DPN_SGEMM_TILE");
-    const bool big = force && force[0] == '6';
-    if (big) {
-        const int gx64 = (gx + 1) / 2, gy64 = (gy + 1) / 2;
-        hipLaunchKernelGGL((dpn_sgemm_batch_kernel<64, 2, 512, 2, 2>), dim3(gx64, gy64, gz), dim3(512), 0, reinterpret_cast<hipStream_t>(stream), b);
-    } else {
-        hipLaunchKernelGGL((dpn_sgemm_batch_kernel<64, 2, 512>), dim3(gx, gy, gz), dim3(512), 0, reinterpret_cast<hipStream_t>(stream), b);
-    }
+    // Round 6: 64 x 64 output tiles (four 32 x 32 sub-tiles on eight waves: half the L2 -> LDS bytes per MAC) measured slower on every
+    // launch of the step -- token convolution + assemble 27.3 against 25.0 us, the heads' forward 17.7 against 16.3, their backward 34.6 against 26.9 us: these
+    // GEMMs wait for latency, not for L2 bytes (profiles/round6_sgemm_tile_ab.txt).  The kernel template keeps the parameters; the launch was removed.
+    hipLaunchKernelGGL((dpn_sgemm_batch_kernel<64, 2, 512>), dim3(gx, gy, gz), dim3(512), 0, reinterpret_cast<hipStream_t>(stream), b);
     return ck(hipGetLastError());
 }
 

@@ -265,9 +265,11 @@ def lead_time_pe(h, freq_bands):
 
 class _DataEmbeddingFn(torch.autograd.Function):
     """DataEmbedding + learnable tokens (model/embed.py:60-64, transformer_net.py:124-126) for B field samples:
-    x0[b] = cat(token, circular_conv3(field[b])) + pos + time_embedding(h[b]).  Four launches forward (im2col, one 19-way split-K MFMA GEMM
-    launch, lead-time PE, assemble + split reduction); backward = one GEMM for the conv weight (already in the parameter's [256][C][3]
-    layout) with its bias sum."""
+    x0[b] = cat(token, circular_conv3(field[b])) + pos + time_embedding(h[b]).  Forward: one 19-way split-K MFMA GEMM launch, behind the im2col
+    rows and lead-time PE (made here, or by dpn_enc_prep on the fused path); the split reduction + assemble is a launch of its own, except for
+    one field on the fused path, where the encoder stack's first launch does it (share.defer_assemble).  Backward: the conv weight's gradient
+    (already in the parameter's [256][C][3] layout) with its bias sum -- for one field on the fused path inside the encoder stack's
+    weight-gradient launch (share.embed), otherwise a launch of its own (dpn_wgrad16; dpn_sgemm_batch with DPN_ENCODER_UNFUSED=1)."""
 
     @staticmethod
     def forward(ctx, field, conv_w, conv_b, token, pos, h, freq_bands, xu=None, te=None, share=None):
@@ -282,45 +284,21 @@ class _DataEmbeddingFn(torch.autograd.Function):
             L.check(lib.dpn_im2col_circ3(_p(x), T, C, B, _p(xu), _s()), 'dpn_im2col_circ3')
         w2 = _c(conv_w).view(D, 3 * C)
         K3 = 3 * C
-        c16 = getattr(share, 'conv16', None) if share is not None else None
-        if c16 is not None and c16[5].data_ptr() == w2.data_ptr():
-            # emb = xu . w2^T on the planes dpn_enc_prep split (f16 hi+lo MFMA, per-row scales): sixteen K-slices, added in order by the assemble
-            xs, xe, ws, we, Kp, _ = c16
-            n_parts = 16
-            emb_parts = torch.empty((n_parts, B * T, D), dtype=torch.float32, device=dev)
-            L.check(L.load_experiments().dpn_conv16(_p(xs), _p(xe), _p(ws), _p(we), B * T, D, Kp, n_parts, _p(emb_parts), _s()), 'dpn_conv16')
-        elif not config.FROZEN.embed_gemm16:
-            # emb = xu . w2^T with K = 3C = 7215: sixteen K-slices as sixteen problems of one exact-fp32 MFMA launch (24 us).  DPN_EMBED_PARTS overrides the
-            # number of slices (at most 26 problems per launch): round 6 sweep in tools/embed_parts_bench.py
-            # (default since round 6: slices of 384 = six whole 64-deep k-tiles -> 19 slices x 12 output tiles = 228 workgroups, one round of the 256 CUs:
-            # GEMM + assemble 24.8 us against 28.5 us for sixteen slices of 451 whose eighth k-tile is 95 % padding; profiles/round6_embed_split_sweep.txt)
-            parts = min(26, config.FROZEN.embed_parts) if config.FROZEN.embed_parts > 0 else 19
-            ks = (K3 + parts - 1) // parts
-            if config.FROZEN.embed_align:                      # slices in whole 64-deep k-tiles of the kernel (no slice ends in a mostly empty tile)
-                ks = (ks + 63) // 64 * 64
-            bounds = [(k0, min(k0 + ks, K3)) for k0 in range(0, K3, ks)]
-            emb_parts = torch.empty((len(bounds), B * T, D), dtype=torch.float32, device=dev)
-            problems = []
-            for i, (k0, k1) in enumerate(bounds):
-                q = _problem(B * T, D, k1 - k0, [(xu, K3, w2, K3)], emb_parts, D, 0, 1)
-                q.A[0], q.B[0], q.C = xu.data_ptr() + k0 * 4, w2.data_ptr() + k0 * 4, emb_parts.data_ptr() + i * B * T * D * 4
-                problems.append(q)
-            _launch(problems)
-            n_parts = len(bounds)
-        else:
-            # (measured experiment, DPN_EMBED_GEMM16=1: the same product on the f16 hi+lo MFMA GEMM dpn_gemm16.  With the kernel's
-            # "k is contiguous" load path (two 16-byte buffer loads per operand and block) 17 us at 38 K-slices + 11.6 us assemble, 20.6 + 6.4 us
-            # at 16 (DPN_EMBED_PARTS) against 23.7 + 6.2 us for the exact-fp32 split-K launch: the kernel spends ~2 300 cycles per 32-k block on
-            # scales and splits for 12 MFMAs, and the tile-level scales make a field's result depend on its batch neighbours at the 1e-7
-            # level; not the product path.  What would pay is operands split ONCE -- by dpn_enc_prep, per-row scales -- and a load-only
-            # kernel; at 64 x 64 tiles that GEMM moves 74 MB through L2 for 1 GFLOP.)
-            tiles = ((B * T + 63) // 64) * ((D + 63) // 64)
-            n_parts = config.FROZEN.embed_parts or max(1, min(38, 456 // tiles))
-            q = L.DpnGemm16Problem()
-            emb_parts = torch.empty((n_parts, B * T, D), dtype=torch.float32, device=dev)
-            q.A, q.B, q.C, q.M, q.N, q.K, q.ldc = _p(xu), _p(w2), _p(emb_parts), B * T, D, K3, D
-            q.a_sm, q.a_sk, q.b_sn, q.b_sk = K3, 1, K3, 1
-            L.check(L.load_experiments().dpn_gemm16(1, ctypes.byref(q), n_parts, _p(emb_parts), 0, _s()), 'dpn_gemm16')
+        # emb = xu . w2^T with K = 3C = 7215: K-slices as problems of one exact-fp32 MFMA launch (at most 26 problems).  Default since round 6:
+        # slices of 384 = six whole 64-deep k-tiles -> 19 slices x 12 output tiles = 228 workgroups, one round of the 256 CUs: GEMM + assemble
+        # 24.8 us against 28.5 us for sixteen slices of 451 whose eighth k-tile is 95 % padding (profiles/round6_embed_split_sweep.txt;
+        # DPN_EMBED_PARTS sets the count: the sweep in tools/embed_parts_bench.py)
+        parts = config.FROZEN.embed_parts or 19
+        ks = ((K3 + parts - 1) // parts + 63) // 64 * 64           # slices in whole 64-deep k-tiles of the kernel (no slice ends in a mostly empty tile)
+        bounds = [(k0, min(k0 + ks, K3)) for k0 in range(0, K3, ks)]
+        emb_parts = torch.empty((len(bounds), B * T, D), dtype=torch.float32, device=dev)
+        problems = []
+        for i, (k0, k1) in enumerate(bounds):
+            q = _problem(B * T, D, k1 - k0, [(xu, K3, w2, K3)], emb_parts, D, 0, 1)
+            q.A[0], q.B[0], q.C = xu.data_ptr() + k0 * 4, w2.data_ptr() + k0 * 4, emb_parts.data_ptr() + i * B * T * D * 4
+            problems.append(q)
+        _launch(problems)
+        n_parts = len(bounds)
         if te is None:
             te = lead_time_pe(h, freq_bands)
         n_tok = token.shape[-2]
@@ -337,7 +315,7 @@ class _DataEmbeddingFn(torch.autograd.Function):
         ctx.n_tok, ctx.w_shape, ctx.tok_shape, ctx.B = n_tok, conv_w.shape, token.shape, B
         ctx.params = (conv_w, conv_b)
         ctx.share = share
-        if share is not None and B == 1 and not config.FROZEN.embed_own_wgrad:
+        if share is not None and B == 1:
             # one field: the encoder stack's backward computes the token convolution's weight gradient inside ITS weight-gradient launch
             # (dW = (d x0 rows of the field tokens)^T xu: both operands exist there) and hands it back through `share`
             share.embed = dict(xu=xu, n_tok=n_tok, conv_w=conv_w, conv_b=conv_b, token=token, grads=None, g_tok=None)
@@ -389,7 +367,7 @@ def embed_wgrad_rides_with_stack(n_fields=1):
     a single field on the fused path) instead of a launch of the embedding's own backward?  Then the data-parallel step has nothing to
     overlap between the encoder's and the embedding's gradient buckets: they complete together and travel as ONE all-reduce
     (interface_physics.StagedPdeStep, InterfacePhysics.training_step)."""
-    return n_fields == 1 and not config.FROZEN.embed_own_wgrad and not config.FROZEN.encoder_unfused
+    return n_fields == 1 and not config.FROZEN.encoder_unfused
 
 
 def _assemble(pd):
@@ -437,12 +415,11 @@ HEADS_COLS = sum(HEAD_WIDTHS)
 
 
 class _HeadsFn(torch.autograd.Function):
-    """The twelve hyper-network heads and the six lead-time embeddings of a PhysicsNet (model/variable_net.py:57-65,75-78), per field
-    sample ONE launch forward (18 GEMM problems reading the encoder output transposed in place) and two launches backward (the input
-    gradient as six 2-term problems joined by dpn_sum_parts, twelve weight gradients with their bias sums, six outer products).
+    """The twelve hyper-network heads and the six lead-time embeddings of a PhysicsNet (model/variable_net.py:57-65,75-78): ONE launch
+    forward (18 GEMM problems reading the encoder output transposed in place) and two launches backward (one field: the input gradient as
+    six 2-term problems joined by dpn_sum_parts, twelve weight gradients with their bias sums, six outer products; B > 1: _backward_batched).
     inputs: meta [B, L, 256] (tokens 0..255 are used), pe_h [B, 192], 12 head weights, 12 head biases, 6 fore_h_fc weights, 6 biases
-    -> heads [B, 256, 2700] = [w1b1 of nets 0..5 | w2b2 of nets 0..5] per hidden channel, evec [B, 6, 256].
-    With B > 1 the parameter gradients of the fields are written side by side and added in a fixed order by one dpn_sum_parts."""
+    -> heads [B, 256, 2700] = [w1b1 of nets 0..5 | w2b2 of nets 0..5] per hidden channel, evec [B, 6, 256]."""
 
     @staticmethod
     def forward(ctx, meta, pe_h, *wb):
@@ -450,15 +427,15 @@ class _HeadsFn(torch.autograd.Function):
         hw, hb, fw, fb = wb[0:12], wb[12:24], wb[24:30], wb[30:36]
         hw = [_c(w) for w in hw]
         fw = [_c(w) for w in fw]
-        B, Lt = meta.shape[0], meta.shape[1]
+        B = meta.shape[0]
         m3 = _c(meta)                                            # [B][L tokens][256 channels]
         pe2 = _c(pe_h.reshape(B, 192))
         dev = m3.device
         heads = torch.empty((B, 256, HEADS_COLS), dtype=torch.float32, device=dev)
         evec = torch.empty((B, 6, 256), dtype=torch.float32, device=dev)
-        mode = config.FROZEN.heads_per_field         # A/B measurements: 1 = the per-field launches of rounds 1-3; fwd / bwd = only that pass per field
-        ctx.per_field_bwd = B > 1 and mode in ('1', 'bwd')
-        if B > 1 and mode not in ('1', 'fwd'):
+        ctx.batched = B > 1
+        ctx.params = (hb, fw, fb)                                # identify the gradient slots (grad_arena); fw: the contiguous weights
+        if B > 1:
             # B fields: ONE launch over all of them (it was one per field: 61 launches of 15 us at configs[2]).  The encoder output of the
             # fields is brought into [field * 256 + channel][token] order once (16 MB at B = 61), so that a head is ONE problem with
             # B * 256 rows; the backward pass reuses the copy as the K-operand of the weight gradients.
@@ -476,41 +453,30 @@ class _HeadsFn(torch.autograd.Function):
                 problems.append(q)
             _launch(problems)
             ctx.save_for_backward(m3, pe2, acat, *hw)
-            ctx.batched = True
-            ctx.has_acat = True
-            ctx.params = (hb, fw, fb)
             return heads, evec
-        ctx.batched = B > 1
-        ctx.has_acat = False
-        for f in range(B):
-            m_ptr, h_ptr = m3.data_ptr() + f * Lt * 256 * 4, heads.data_ptr() + f * 256 * HEADS_COLS * 4
-            problems, off = [], 0
-            for w, b in zip(hw, hb):                             # heads[c][off + j] = sum_tok meta[tok][c] W[j][tok] + b[j]
-                n_k = w.shape[0]
-                q = _problem(256, n_k, 256, [(m3, 256, w, 256)], heads, HEADS_COLS, 1, 1, bias=b)
-                q.A[0], q.C = m_ptr, h_ptr + off * 4
-                problems.append(q)
-                off += n_k
-            for k, (w, b) in enumerate(zip(fw, fb)):             # evec[k] = fore_h_fc_k(pe_h)
-                q = _problem(1, 256, 192, [(pe2, 192, w, 192)], evec, 256, 0, 1, bias=b)
-                q.A[0], q.C = pe2.data_ptr() + f * 192 * 4, evec.data_ptr() + (f * 6 + k) * 256 * 4
-                problems.append(q)
-            _launch(problems)
+        problems, off = [], 0
+        for w, b in zip(hw, hb):                                 # heads[c][off + j] = sum_tok meta[tok][c] W[j][tok] + b[j]
+            n_k = w.shape[0]
+            q = _problem(256, n_k, 256, [(m3, 256, w, 256)], heads, HEADS_COLS, 1, 1, bias=b)
+            q.C = heads.data_ptr() + off * 4
+            problems.append(q)
+            off += n_k
+        for k, (w, b) in enumerate(zip(fw, fb)):                 # evec[k] = fore_h_fc_k(pe_h)
+            q = _problem(1, 256, 192, [(pe2, 192, w, 192)], evec, 256, 0, 1, bias=b)
+            q.C = evec.data_ptr() + k * 256 * 4
+            problems.append(q)
+        _launch(problems)
         ctx.save_for_backward(m3, pe2, *hw)
-        ctx.params = (hb, fw, fb)                                    # identify the gradient slots (grad_arena); fw: the contiguous weights
         return heads, evec
 
     @staticmethod
     def backward(ctx, g_heads, g_evec):
         from .linear import _launch, _problem
-        if ctx.batched and not ctx.per_field_bwd:
+        if ctx.batched:
             return _HeadsFn._backward_batched(ctx, g_heads, g_evec)
-        if ctx.has_acat:
-            m3, pe2, _, *hw = ctx.saved_tensors
-        else:
-            m3, pe2, *hw = ctx.saved_tensors
+        m3, pe2, *hw = ctx.saved_tensors                         # one field
         dev = m3.device
-        B, Lt = m3.shape[0], m3.shape[1]
+        Lt = m3.shape[1]
         lib = L.load()
         gh, ge = _c(g_heads), _c(g_evec)
         d_meta = torch.empty(m3.shape, dtype=torch.float32, device=dev)
@@ -518,55 +484,36 @@ class _HeadsFn(torch.autograd.Function):
         for w in hw:
             offs.append(off)
             off += w.shape[0]
-        # destinations of the 36 parameter gradients (12 head weights, 12 head biases, 6 fore_h_fc weights, 6 fore_h_fc biases).
-        # One field: the parameters' own gradient tensors (slots of the optimiser's flat gradient buffer when one is registered,
-        # grad_arena).  B fields: side by side in [B][flat], added in a fixed order by one dpn_sum_parts.
+        # the 36 parameter gradients (12 head weights, 12 head biases, 6 fore_h_fc weights, 6 fore_h_fc biases) go to the parameters' own
+        # gradient tensors (slots of the optimiser's flat gradient buffer when one is registered, grad_arena)
         hb, fw, fb = ctx.params
         shapes = [(w.shape[0], 256) for w in hw] + [(w.shape[0],) for w in hw] + [(256, 192)] * 6 + [(256,)] * 6
-        if B == 1:
-            dest = [new_grad(t, shp) for t, shp in zip(list(hw) + list(hb) + list(fw) + list(fb), shapes)]
-            ptrs = [[d.data_ptr() for d in dest]]
-        else:
-            starts = [0]
-            for shp in shapes:
-                starts.append(starts[-1] + int(torch.Size(shp).numel()))
-            flat = torch.empty((B, starts[-1]), dtype=torch.float32, device=dev)
-            ptrs = [[flat.data_ptr() + (f * starts[-1] + starts[i]) * 4 for i in range(36)] for f in range(B)]
-        # d meta as NP accumulated-term problems side by side, joined by dpn_sum_parts: 6 two-term problems (with the 12 weight gradients and
-        # the 6 outer products exactly the 24 problems a launch takes).  Same box, 300-step runs, three times each: NP = 2 1.614 ms per
-        # step, 3 1.591, 4 1.614 (rounds 1-3), 6 1.580
-        NP = config.FROZEN.heads_dmeta_parts
-        if NP not in (1, 2, 3, 4, 6, 12):
-            raise ValueError('DPN_HEADS_DMETA_PARTS must divide the twelve heads (1, 2, 3, 4, 6 or 12), got %d' % NP)
+        dest = [new_grad(t, shp) for t, shp in zip(list(hw) + list(hb) + list(fw) + list(fb), shapes)]
+        # d_meta[tok][c] = sum_k sum_j W_k[j][tok] g[c][off_k + j]: a 12-term problem would walk 24 k-tiles in sequence, so NP = 6 two-term
+        # problems run side by side and dpn_sum_parts joins them (with the 12 weight gradients and the 6 outer products exactly the 24
+        # problems a launch takes).  Same box, 300-step runs, three times each: NP = 2 1.614 ms per step, 3 1.591, 4 1.614 (rounds 1-3), 6 1.580
+        NP = 6
         parts = torch.empty((NP, 256, 256), dtype=torch.float32, device=dev)
         n_tail = (Lt - 256) * 256                                # tokens >= 256 feed no VariableNet: their gradient rows are zero
-        for f in range(B):
-            g_ptr, m_ptr = gh.data_ptr() + f * 256 * HEADS_COLS * 4, m3.data_ptr() + f * Lt * 256 * 4
-            # d_meta[tok][c] = sum_k sum_j W_k[j][tok] g[c][off_k + j]: a 12-term problem would walk 24 k-tiles in sequence, so NP
-            # problems of 12 / NP terms run side by side and dpn_sum_parts joins them
-            problems = []
-            for p_ in range(NP):
-                grp = list(range((12 // NP) * p_, (12 // NP) * (p_ + 1)))
-                q0 = _problem(256, 256, 256, [(hw[k], 256, gh, HEADS_COLS, hw[k].shape[0]) for k in grp], parts, 256, 1, 1)
-                q0.C = parts.data_ptr() + p_ * 256 * 256 * 4
-                for i, k in enumerate(grp):
-                    q0.B[i] = g_ptr + offs[k] * 4
-                problems.append(q0)
-            for k, w in enumerate(hw):                           # dW_k[j][tok] = sum_c g[c][off + j] meta[tok][c] ; db_k[j] = sum_c g[c][off + j]
-                n_k = w.shape[0]
-                q = _problem(n_k, 256, 256, [(gh, HEADS_COLS, m3, 256)], parts, 256, 1, 1, asum=parts)
-                q.A[0], q.B[0], q.C, q.asum = g_ptr + offs[k] * 4, m_ptr, ptrs[f][k], ptrs[f][12 + k]
-                problems.append(q)
-            for k in range(6):                                   # d fore_h_fc_k.weight = g_evec[k] (outer) pe_h ; its bias gradient = g_evec[k]
-                q = _problem(256, 192, 1, [(ge, 256, pe2, 192)], parts, 192, 1, 0, asum=parts)       # = the "row sums" over the K = 1 reduction
-                q.A[0], q.B[0], q.C, q.asum = ge.data_ptr() + (f * 6 + k) * 256 * 4, pe2.data_ptr() + f * 192 * 4, ptrs[f][24 + k], ptrs[f][30 + k]
-                problems.append(q)
-            _launch(problems)
-            L.check(lib.dpn_sum_parts(_p(parts), NP, 256 * 256, n_tail, ctypes.c_void_p(d_meta.data_ptr() + f * Lt * 256 * 4), _s()), 'dpn_sum_parts')
-        if B > 1:
-            total = torch.empty(starts[-1], dtype=torch.float32, device=dev)
-            L.check(lib.dpn_sum_parts(_p(flat), B, starts[-1], 0, _p(total), _s()), 'dpn_sum_parts')
-            dest = [total[starts[i]:starts[i + 1]].view(shapes[i]) for i in range(36)]
+        problems = []
+        for p_ in range(NP):
+            grp = list(range((12 // NP) * p_, (12 // NP) * (p_ + 1)))
+            q0 = _problem(256, 256, 256, [(hw[k], 256, gh, HEADS_COLS, hw[k].shape[0]) for k in grp], parts, 256, 1, 1)
+            q0.C = parts.data_ptr() + p_ * 256 * 256 * 4
+            for i, k in enumerate(grp):
+                q0.B[i] = gh.data_ptr() + offs[k] * 4
+            problems.append(q0)
+        for k, w in enumerate(hw):                               # dW_k[j][tok] = sum_c g[c][off + j] meta[tok][c] ; db_k[j] = sum_c g[c][off + j]
+            n_k = w.shape[0]
+            q = _problem(n_k, 256, 256, [(gh, HEADS_COLS, m3, 256)], dest[k], 256, 1, 1, asum=dest[12 + k])
+            q.A[0] = gh.data_ptr() + offs[k] * 4
+            problems.append(q)
+        for k in range(6):                                       # d fore_h_fc_k.weight = g_evec[k] (outer) pe_h ; its bias gradient = g_evec[k]
+            q = _problem(256, 192, 1, [(ge, 256, pe2, 192)], dest[24 + k], 192, 1, 0, asum=dest[30 + k])    # = the "row sums" over the K = 1 reduction
+            q.A[0] = ge.data_ptr() + k * 256 * 4
+            problems.append(q)
+        _launch(problems)
+        L.check(lib.dpn_sum_parts(_p(parts), NP, 256 * 256, n_tail, _p(d_meta), _s()), 'dpn_sum_parts')
         return (d_meta, None, *dest)
 
     @staticmethod
@@ -576,11 +523,7 @@ class _HeadsFn(torch.autograd.Function):
         six fore_h_fc gradients as reductions over all fields at once (K = B * 256 resp. B): the sum over the fields happens inside the
         GEMM's own fixed-order reduction, nothing is written per field and joined afterwards."""
         from .linear import _launch, _problem
-        if ctx.has_acat:
-            m3, pe2, acat, *hw = ctx.saved_tensors
-        else:
-            m3, pe2, *hw = ctx.saved_tensors
-            acat = m3[:, :256, :].transpose(1, 2).contiguous().view(m3.shape[0] * 256, 256)
+        m3, pe2, acat, *hw = ctx.saved_tensors
         dev = m3.device
         B, Lt = m3.shape[0], m3.shape[1]
         gh, ge = _c(g_heads), _c(g_evec)                          # [B, 256, 2700] = [(f, c)][j], [B, 6, 256]
@@ -706,7 +649,7 @@ class _EncoderStackFn(torch.autograd.Function):
         n_mats = 6 * nl + (1 if final else 0)                        # 6 l + (q, k, v, o, c1, c2), then the projection
         if wpack is None:                                            # (encoder_prep has packed them when the whole encoder runs fused)
             wpack = enc_pack(_stack_matrices(lay, fin))
-        rt = config.FROZEN.enc_row_tiles or (1 if n <= 2048 else 2)
+        rt = 1 if n <= 2048 else 2                                   # 16-row tiles per workgroup
         stream = _s()
 
         def fwd(**kw):
@@ -734,8 +677,7 @@ class _EncoderStackFn(torch.autograd.Function):
         for l in range(nl):
             p_ = lay[l]
             o, P = new(n, D), new(B * 8, 288, 288)
-            attn = lib.dpn_attn_fwd if config.FROZEN.attn_fwd_fp32 else lib.dpn_attn16_fwd      # (round 3's exact-fp32 kernel: A/B runs)
-            L.check(attn(_p(q), _p(k), _p(v), Lt, B, _p(o), _p(P), stream), 'dpn_attn_fwd')
+            L.check(lib.dpn_attn16_fwd(_p(q), _p(k), _p(v), Lt, B, _p(o), _p(P), stream), 'dpn_attn16_fwd')
             x1, xhat1, rstd1, pre, act, x2, xhat2, rstd2 = new(n, D), new(n, D), new(n), new(n, D), new(n, D), new(n, D), new(n, D), new(n)
             kw = dict(tail=1, o=o, x=x, m_o=6 * l + 3, m_c1=6 * l + 4, m_c2=6 * l + 5, bo=p_[7], g1=p_[8], be1=p_[9], bc1=p_[11], bc2=p_[13],
                       g2=p_[14], be2=p_[15], x1=x1, xhat1=xhat1, rstd1=rstd1, pre=pre, act=act, x2=x2, xhat2=xhat2, rstd2=rstd2)
@@ -932,7 +874,7 @@ def _stack_fits(layers, norm, projection, device=None):
 
 class EncoderPrep:
     """dpn_enc_prep's outputs for one forward of the whole encoder: weight images, im2col rows, lead-time encodings."""
-    __slots__ = ('wpack', 'xu', 'te', 'pe_extra', 'embed', 'conv16', 'defer_assemble', 'pending')
+    __slots__ = ('wpack', 'xu', 'te', 'pe_extra', 'embed', 'defer_assemble', 'pending')
 
 
 def encoder_prep(field, h, emb_module, extra_freqs, layers, norm, projection):
@@ -958,7 +900,6 @@ def encoder_prep(field, h, emb_module, extra_freqs, layers, norm, projection):
     q.n_mats, q.weights, q.packed, q.status_dev = len(mats), ctypes.cast(arr, ctypes.c_void_p), _p(out.wpack), _p(enc_status(dev))
     q.x, q.T, q.C, q.batch, q.xu = _p(x), T, C, B, _p(out.xu)
     q.h, q.freqs_a, q.n_a, q.out_a = _p(hh), _p(fa), fa.numel(), _p(te)
-    out.conv16 = None
     out.pe_extra = None
     if extra_freqs is not None:
         fb = _c(extra_freqs)
@@ -966,20 +907,6 @@ def encoder_prep(field, h, emb_module, extra_freqs, layers, norm, projection):
         q.freqs_b, q.n_b, q.out_b = _p(fb), fb.numel(), _p(out.pe_extra)
     L.check(lib.dpn_enc_prep(ctypes.byref(q), _s()), 'dpn_enc_prep')
     out.te = te.view(-1) if B == 1 else te
-    conv = emb_module.value_embedding.tokenConv
-    if config.FROZEN.conv16 and conv.weight.is_cuda and conv.weight.dtype == torch.float32 and tuple(conv.weight.shape[1:]) == (C, 3):
-        # EXPERIMENT: the token convolution's operands split into f16 hi / lo fragment images with one power-of-two scale per row (dpn_conv16).
-        # Measured: the GEMM 23.7 -> 11.2 us, the split 12-16 us -- no gain; not the product path.
-        lib = L.load_experiments()
-        Kp, n_out = int(lib.dpn_conv16_kp(3 * C)), conv.weight.shape[0]
-        if (B * T + 16) * Kp * 4 < 2 ** 31 - 8192 and Kp <= 29 * 256:
-            xs = torch.empty(((B * T + 15) // 16 * 16, 2 * Kp), dtype=torch.float16, device=dev)      # fragment images: 16-row strips x (Kp / 32) blocks x 2 KB
-            ws = torch.empty(((n_out + 15) // 16 * 16, 2 * Kp), dtype=torch.float16, device=dev)
-            xe = torch.empty(B * T, dtype=torch.int32, device=dev)
-            we = torch.empty(n_out, dtype=torch.int32, device=dev)
-            cw = _c(conv.weight.detach())
-            L.check(lib.dpn_conv16_split(_p(x), T, C, B, _p(cw), n_out, _p(xs), _p(xe), _p(ws), _p(we), _s()), 'dpn_conv16_split')
-            out.conv16 = (xs, xe, ws, we, Kp, cw)
     return out
 
 

@@ -1,5 +1,5 @@
 """SHA-256 of everything the forward + Jacobian launch and the backward stage-1 launch write (fields, Jacobian, saved state, operand rows), for the library in DPN_LIB
-(default: the product build) -- run it for two builds and compare the lines: a change that must not change a bit.  usage: fwd_dump.py [n ...]   (DPN_FWD_PP / DPN_FWD_KERNEL apply)"""
+(default: the product build) -- run it for two builds and compare the lines: a change that must not change a bit.  usage: fwd_dump.py [n ...]   (DPN_FWD_KERNEL applies)"""
 import os, sys, ctypes, hashlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

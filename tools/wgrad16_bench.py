@@ -1,4 +1,4 @@
-"""dpn_wgrad16 / dpn_gemm16 in isolation: time per launch for n problems of [rows x 256]^T [rows x 256] (events over 200 launches; inputs rewritten
+"""dpn_wgrad16 in isolation: time per launch for n problems of [rows x 256]^T [rows x 256] (events over 200 launches; inputs rewritten
 by a dummy kernel in between so that they are L2-cold like in the step).  usage: wgrad16_bench.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
