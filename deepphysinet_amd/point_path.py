@@ -587,13 +587,16 @@ class _StepLossFn(torch.autograd.Function):
     def forward(ctx, cfg, n_inter, beta, margin_factor, x, y, t, f, coord_data, labels, heads, evec, *statics):
         for nm, v in (('x', x), ('coord_data', coord_data), ('heads', heads), ('labels', labels)):
             _require_gpu(v, nm)
+        n, n_lab = coord_data.shape[0], labels.shape[0]
+        if not (0 < n_inter < n and n_lab == n - n_inter):
+            # every launch below takes its row counts from this split: a bad one reads and writes past the groups
+            raise ValueError('step_losses: n_inter = %d of %d points leaves %d margin points for %d label rows; need 0 < n_inter < %d and one '
+                             'label row per margin point' % (n_inter, n, n - n_inter, n_lab, n))
         lib = L.load()
         x_, y_, t_, f_ = (_f32c(v).reshape(-1) for v in (x, y, t, f))
         cd_, hd_, ev_, lab_ = _f32c(coord_data), _f32c(heads), _f32c(evec), _f32c(labels)
         st = [_f32c(s) for s in statics]
-        n = cd_.shape[0]
         n_m = n - n_inter
-        assert 0 < n_inter < n and lab_.shape[0] == n_m
         dev = cd_.device
         need_grad = any(v.requires_grad for v in (heads, evec) + tuple(statics))
         ws = _Workspace(n, cfg.prec, dev)

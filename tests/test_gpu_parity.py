@@ -376,6 +376,317 @@ def test_training_step_matches_reference_optimiser_step(golden_dir):
     assert checked > 5000 and differing <= 0.005 * checked, (checked, differing)
 
 
+# ------------------------------------------------------------------------------------------------ the fused step loss against the oracle
+# training_step takes its three losses from ONE point pass (point_path._StepLossFn): rows [0, n_inter) are the interior points, the rest
+# the margin points, and the group boundary lives entirely in offsets and counts.  F8 above cannot see it: two equal groups of whole
+# 256-row blocks, one unit cotangent for everything.  These tests use unequal and ragged groups, a different cotangent per output, and
+# the reference's own batch sizes (cfg batch_size_inter 4 096 interior, label_batch_size 20 480 margin points).
+STEP_BETA = 0.1                       # the data loss's SmoothL1 beta (training_step)
+STEP_KEYS = ('data', 'inter_terms', 'inter_total', 'margin_terms', 'margin_total')
+DATA_LOSS_TOL = 5e-5                  # the data loss's bar (test_data_loss_and_reference_forward_surface)
+
+
+def _smooth_l1_flips(m, inp, beta=STEP_BETA):
+    """Points at which some |out - label| lies on different sides of the SmoothL1 beta for the HIP fields and for the fp32 oracle's
+    (the data loss's own switch), bool [N]."""
+    import deepphysinet_amd as dpn
+    g = _gpu(inp)
+    with torch.no_grad():
+        heads, evec, statics = m.physics_net.field_weights(g['field_data'], g['forecast_h'])
+        out_n, _ = dpn.pde_fields_and_jacobian(m.point_config(), g['x'], g['y'], g['t'], g['coord_data'], heads, evec, statics)
+        pe = O.encoding_coord(inp['x'], inp['y'], inp['t'], GEO)
+        ref = torch.cat(O.physics_net_forward(O.make_state(), inp['field_data'], pe, inp['coord_data'], inp['forecast_h']), 1)
+    lab = inp['labels']
+    return ((out_n.cpu() - lab).abs() < beta).ne((ref - lab).abs() < beta).any(dim=1)
+
+
+def _replace_flipped(m, inp, group, data_loss=False):
+    """`inp` with every point whose switch differs from the fp32 oracle arithmetic's (_flipped_points; for the margin group also the
+    data loss's beta switch) REPLACED by a copy of the group's first unflipped point, labels included: the group keeps its size, and
+    the group sizes are what these tests are about.  Returns (inputs, number replaced)."""
+    flipped, _ = _flipped_points(m, inp)
+    if data_loss:
+        flipped = flipped | _smooth_l1_flips(m, inp)
+    idx = torch.nonzero(flipped).flatten().tolist()
+    n = flipped.shape[0]
+    print('%-6s group, %5d points: %d flipped points replaced %s' % (group, n, len(idx), idx[:12]))
+    assert len(idx) <= max(3, n // 100), (group, len(idx))
+    if not idx:
+        return inp, 0
+    keep = torch.nonzero(~flipped).flatten()
+    assert keep.numel() > 0, (group, 'no unflipped point to copy')
+    src = int(keep[0])
+    c = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in inp.items()}
+    for k in ('x', 'y', 't', 'f', 'coord_data', 'labels'):
+        c[k][idx] = c[k][src].clone()
+    return c, len(idx)
+
+
+def _step_scalar(spec, outs):
+    """sum of weight * output over the step's outputs; `spec` maps keys of STEP_KEYS to a weight (one number, or six for the terms).
+    Outputs that a spec leaves out are not in the scalar's graph: their cotangents reach _StepLossFn.backward as None."""
+    s = 0
+    for k, w in spec.items():
+        v = outs[k]
+        s = s + (v * torch.as_tensor(w, dtype=v.dtype, device=v.device)).sum()
+    return s
+
+
+def _oracle_step(sd, inter, margin, specs):
+    """The reference's step body on the oracle (its interface_physics.py:464-503): meta_out once, then data_loss(margin) +
+    place_one_batch(inter) + place_one_batch(margin) in its order of additions.  Returns (fp32 outputs {STEP_KEYS}, fp32 loss,
+    [fp64 gradient dict of each spec's scalar], fp64 state): the losses from the fp32 oracle on the closed-form state (as everywhere in
+    this file), the gradients from an fp64 oracle on `sd`, the model's own weights (a state dict)."""
+    def run(st, dt):
+        field, fh = inter['field_data'].to(dt), inter['forecast_h'].to(dt)
+        meta = O.meta_net_forward(st, field, fh)
+        leaf = lambda b: [b[k].to(dt).clone().requires_grad_(True) for k in ('x', 'y', 't')]
+        xm, ym, tm = leaf(margin)
+        data = O.data_loss(st, xm, ym, tm, field, margin['coord_data'].to(dt), margin['labels'].to(dt), fh, GEO, beta=STEP_BETA, meta_out=meta)
+        xi, yi, ti = leaf(inter)
+        it, ip, _, _ = O.place_one_batch(st, xi, yi, ti, inter['f'].to(dt), field, inter['coord_data'].to(dt), fh, GEO, meta_out=meta,
+                                         return_parts=True)
+        mt, mp, _, _ = O.place_one_batch(st, xm, ym, tm, margin['f'].to(dt), field, margin['coord_data'].to(dt), fh, GEO, meta_out=meta,
+                                         return_parts=True)
+        outs = dict(data=data, inter_terms=torch.stack(ip), inter_total=it, margin_terms=torch.stack(mp), margin_total=mt)
+        return outs, data + it + mt
+    outs32, loss32 = run(O.make_state(), torch.float32)
+    outs32 = {k: v.detach().double().numpy() for k, v in outs32.items()}
+    st64 = {k: v.detach().cpu().to(torch.float64 if v.is_floating_point() else v.dtype).clone().requires_grad_(v.is_floating_point() and not k.endswith('.pe'))
+            for k, v in sd.items()}
+    outs64, _ = run(st64, torch.float64)
+    names = O.param_names(st64)
+    grads = []
+    for i, spec in enumerate(specs):
+        g = torch.autograd.grad(_step_scalar(spec, outs64), [st64[k] for k in names], retain_graph=i + 1 < len(specs))
+        grads.append(dict(zip(names, g)))
+    return outs32, float(loss32.detach()), grads, st64
+
+
+def _hip_step_losses(m, inter, margin):
+    """point_path.step_losses called the way training_step calls it: [interior | margin] rows, one encoder pass, the cfg loss factors."""
+    from deepphysinet_amd.point_path import step_losses
+    gi, gm = _gpu(inter), _gpu(margin)
+    lf = m.train_cfg['losses']['loss_factor']
+    cfg = m.point_config(lf)
+    meta = m.physics_net.encode_field(gi['field_data'], gi['forecast_h'])
+    heads, evec, statics = m.physics_net.field_weights(gi['field_data'], gi['forecast_h'], meta_out=meta)
+    cat = lambda k: torch.cat([gi[k].reshape(gi[k].shape[0], -1), gm[k].reshape(gm[k].shape[0], -1)], dim=0)
+    outs = step_losses(cfg, gi['x'].shape[0], cat('x'), cat('y'), cat('t'), cat('f'), cat('coord_data'), gm['labels'], heads, evec, statics,
+                       beta=STEP_BETA, margin_factor=lf['margin_factor'])
+    li, ti, lm, tm, data = outs
+    return dict(data=data, inter_terms=li, inter_total=ti, margin_terms=lm, margin_total=tm)
+
+
+def _hip_step_grads(m, inter, margin, spec):
+    """d(spec's scalar) / d(every parameter) through a fresh step_losses pass, fp64 on the host."""
+    m.physics_net.zero_grad(set_to_none=True)
+    outs = _hip_step_losses(m, inter, margin)
+    _step_scalar(spec, outs).backward()
+    return outs, {k: p.grad.detach().cpu().double() for k, p in m.physics_net.named_parameters()}
+
+
+def _grad_rows(mine, ref):
+    """[(worst element error / the tensor's max |ref|, L2 error / |ref|, name)] for every tensor but key_projection.bias, worst first."""
+    rows = []
+    for name, g in mine.items():
+        if name.endswith('key_projection.bias'):
+            continue                      # mathematically zero gradient (softmax shift invariance): rounding noise on both sides
+        r = ref[name].double()
+        d = g - r
+        rows.append((float(d.abs().max() / (r.abs().max() + 1e-300)), float(d.norm() / (r.norm() + 1e-300)), name))
+    rows.sort(reverse=True)
+    return rows
+
+
+@pytest.mark.parametrize('n_inter,n_margin', [(1037, 1965), (300, 4096), (1, 700), (700, 1)])
+def test_step_losses_unequal_and_ragged_groups_vs_oracle(n_inter, n_margin):
+    """The fused step loss at group sizes where the boundary matters: (1037, 1965) both ragged, the boundary inside a 256-row block;
+    (300, 4096) a short group in front of a long one; (1, 700) / (700, 1) a one-point group on either side.  Losses against the fp32
+    oracle on their own group (PDE terms and totals 1e-4, data loss 5e-5), against separate pde_loss_terms / data_loss calls on the same
+    weights (bitwise: the forward is per-point arithmetic and each group's block sums start at its own row 0), and the gradients of
+    data + inter total + margin total against the fp64 oracle (every element within 1e-3 of its tensor's maximum).  A one-point group
+    gets the x20 of test_fields_jacobian_losses_gradients_vs_oracle's n == 1: a single point's residual has no averaging of rounding."""
+    tol = TOL['bf16x2']
+    m = _model('bf16x2')
+    inter, _ = _replace_flipped(m, synthetic_inputs(n_inter, tag='inter'), 'inter')
+    margin, _ = _replace_flipped(m, synthetic_inputs(n_margin, tag='margin', margin=True), 'margin', data_loss=True)
+    spec = dict(data=1.0, inter_total=1.0, margin_total=1.0)
+    ref, _, (g64,), _ = _oracle_step(m.physics_net.state_dict(), inter, margin, [spec])
+    outs, grads = _hip_step_grads(m, inter, margin, spec)
+    outs = {k: v.detach() for k, v in outs.items()}
+    gi, gm = _gpu(inter), _gpu(margin)
+    with torch.no_grad():
+        sep_li, sep_ti = m.pde_loss_terms(gi['x'], gi['y'], gi['t'], gi['f'], gi['field_data'], gi['coord_data'], gi['forecast_h'], with_total=True)
+        sep_lm, sep_tm = m.pde_loss_terms(gm['x'], gm['y'], gm['t'], gm['f'], gm['field_data'], gm['coord_data'], gm['forecast_h'], with_total=True)
+        sep_d = m.data_loss(gm['x'], gm['y'], gm['t'], gm['field_data'], gm['coord_data'], gm['labels'], gm['forecast_h'], beta=STEP_BETA)
+    sep = dict(data=sep_d, inter_terms=sep_li, inter_total=sep_ti, margin_terms=sep_lm, margin_total=sep_tm)
+    one = lambda n_: 20.0 if n_ == 1 else 1.0
+    bars = dict(data=DATA_LOSS_TOL * one(n_margin), inter_terms=tol['loss'] * one(n_inter), inter_total=tol['loss'] * one(n_inter),
+                margin_terms=tol['loss'] * one(n_margin), margin_total=tol['loss'] * one(n_margin))
+    errs, equal = {}, {}
+    for k in STEP_KEYS:
+        mine = outs[k].double().cpu().numpy()
+        errs[k] = float(np.max(np.abs(mine - ref[k]) / np.abs(ref[k])))
+        equal[k] = torch.equal(outs[k], sep[k])
+        print('%4d + %4d  %-12s rel. error vs fp32 oracle %.2e (bar %.0e) | bitwise the separate call: %s'
+              % (n_inter, n_margin, k, errs[k], bars[k], equal[k]))
+    gbar = tol['grad'] * max(one(n_inter), one(n_margin))
+    rows = _grad_rows(grads, g64)
+    for err, l2, name in rows[:3]:
+        print('%4d + %4d  gradient %-52s %.2e of the tensor maximum (L2 %.2e), bar %.0e' % (n_inter, n_margin, name, err, l2, gbar))
+    for k in STEP_KEYS:
+        assert errs[k] <= bars[k], (k, errs[k], bars[k])
+        assert equal[k], (k, outs[k], sep[k])
+    assert len(rows) == sum(1 for k, _ in m.physics_net.named_parameters() if not k.endswith('key_projection.bias'))
+    for err, l2, name in rows:
+        assert err < gbar, (name, err, gbar)
+
+
+def test_step_losses_cotangents_reach_their_own_rows():
+    """Backward of _StepLossFn from four scalars, each against the fp64 oracle's gradient of the same scalar (1037 + 1965 points, every
+    element within 1e-3 of its tensor's maximum): the data loss alone (both PDE groups take the zero-cotangent branch), six distinct
+    weights on the inter terms plus the margin total (per-term and total cotangents on different groups), six other weights on the margin
+    terms (the inter group takes the zero-cotangent branch), the inter total alone (no data-loss cotangent on the margin rows)."""
+    n_inter, n_margin = 1037, 1965
+    tol = TOL['bf16x2']
+    m = _model('bf16x2')
+    inter, _ = _replace_flipped(m, synthetic_inputs(n_inter, tag='inter'), 'inter')
+    margin, _ = _replace_flipped(m, synthetic_inputs(n_margin, tag='margin', margin=True), 'margin', data_loss=True)
+    specs = [('data loss alone', dict(data=1.0)),
+             ('w . inter terms + margin total', dict(inter_terms=[0.5, 1.75, 0.25, 1.25, 2.0, 0.75], margin_total=1.0)),
+             ("w' . margin terms", dict(margin_terms=[1.5, 0.375, 2.5, 0.625, 1.125, 3.0])),
+             ('inter total alone', dict(inter_total=1.0))]
+    _, _, g64s, _ = _oracle_step(m.physics_net.state_dict(), inter, margin, [s for _, s in specs])
+    results = []
+    for (what, spec), g64 in zip(specs, g64s):
+        _, grads = _hip_step_grads(m, inter, margin, spec)
+        rows = _grad_rows(grads, g64)
+        err, l2, name = rows[0]
+        print('%-32s worst gradient %-52s %.2e of the tensor maximum (L2 %.2e), bar %.0e' % (what, name, err, l2, tol['grad']))
+        results.append((what, rows))
+    for what, rows in results:
+        for err, l2, name in rows:
+            assert err < tol['grad'], (what, name, err)
+
+
+def test_training_step_at_the_reference_batch_sizes_vs_the_oracle():
+    """training_step at the reference's batch sizes (4 096 interior + 20 480 margin points), parity-grade mode, closed-form weights,
+    against the oracle's step body: the three losses and their sum (fp32 oracle, 1e-4; data loss 5e-5), every pre-step gradient
+    element (fp64 oracle, 1e-3 of its tensor's maximum), gnorm (1e-3 of the fp64 oracle's; the clip is active here: the oracle's gnorm is
+    above 2.5e7), and the step of the fused optimiser against clip_and_adam_step on the fp64 gradients (F13's rule).  Copy A steps with
+    build_optimizer() (FusedClipAdam, bucket layout), copy B with torch.optim.Adam; after each of two steps they agree to the bars of
+    test_fused_clip_adam_equals_torch.  Before the second step B takes A's parameters, so that both optimisers see the same gradients
+    and what is compared is their moment state and step counter (a gradient element at rounding-noise level, e.g. key_projection.bias,
+    is not a function of the parameters' last bits)."""
+    tol = TOL['bf16x2']
+    lr, wd, max_norm = 1e-4, 1e-4, 2.5e7
+    A, B = _model('bf16x2'), _model('bf16x2')
+    opt_a = A.build_optimizer()
+    assert opt_a.param_groups[0]['lr'] == lr and opt_a.param_groups[0]['weight_decay'] == wd
+    opt_b = torch.optim.Adam(B.physics_net.parameters(), lr=lr, weight_decay=wd)
+    inter, n_fi = _replace_flipped(A, synthetic_inputs(4096, tag='inter'), 'inter')
+    margin, n_fm = _replace_flipped(A, synthetic_inputs(20480, tag='margin', margin=True), 'margin', data_loss=True)
+
+    def batch(i_, m_):
+        i_, m_ = _gpu(i_), _gpu(m_)
+        return dict(field_data=i_['field_data'], forecast_h=i_['forecast_h'],
+                    margin_x=m_['x'], margin_y=m_['y'], margin_t=m_['t'], margin_f=m_['f'], margin_data=m_['labels'],
+                    margin_input_data=m_['coord_data'], inter_x=i_['x'], inter_y=i_['y'], inter_t=i_['t'], inter_f=i_['f'],
+                    inter_data=i_['coord_data'])
+    b1 = batch(inter, margin)
+    before = {k: v.detach().clone() for k, v in A.physics_net.state_dict().items()}
+    loss_a, parts_a, gn_a = A.training_step(b1, opt_a, with_pde=True, max_norm=max_norm)
+    loss_b, parts_b, gn_b = B.training_step(b1, opt_b, with_pde=True, max_norm=max_norm)
+    gn_a, gn_b = float(gn_a), float(gn_b)
+    # the pre-step gradients are read from p.grad: neither optimiser may have cleared it (torch's clip scales B's in place, A's is untouched)
+    assert all(p.grad is not None for p in A.physics_net.parameters()) and all(p.grad is not None for p in B.physics_net.parameters())
+    grads = {k: p.grad.detach().cpu().double() for k, p in A.physics_net.named_parameters()}
+
+    ref, ref_loss, (g64,), st64 = _oracle_step(before, inter, margin, [dict(data=1.0, inter_total=1.0, margin_total=1.0)])
+    gn64 = float(torch.sqrt(sum((g ** 2).sum() for g in g64.values())))
+    coef = min(1.0, max_norm / (gn64 + 1e-6))
+    # losses
+    pairs = [('margin_loss', 'data', DATA_LOSS_TOL), ('inter_pde_loss', 'inter_total', tol['loss']), ('margin_pde_loss', 'margin_total', tol['loss'])]
+    lerr = {}
+    for part, key, bar in pairs:
+        lerr[part] = (abs(float(parts_a[part]) - float(ref[key])) / abs(float(ref[key])), bar)
+    lerr['loss'] = (abs(float(loss_a) - ref_loss) / abs(ref_loss), tol['loss'])
+    print('4096 + 20480 points: %d + %d flipped points replaced' % (n_fi, n_fm))
+    for k, (e, bar) in lerr.items():
+        print('  %-16s rel. error vs fp32 oracle %.2e (bar %.0e)' % (k, e, bar))
+    print('  gnorm %.6e vs fp64 oracle %.6e: rel. error %.2e (bar 1e-3); clip coefficient %.4e (max_norm %.1e)'
+          % (gn_a, gn64, abs(gn_a - gn64) / gn64, coef, max_norm))
+    rows = _grad_rows(grads, g64)
+    print('  per-tensor gradient error vs the fp64 oracle (worst element / tensor max, L2), bar %.0e on the element:' % tol['grad'])
+    for err, l2, name in rows:
+        print('    %-58s %.2e  L2 %.2e' % (name, err, l2))
+    # the optimiser step: F13's rule against clip_and_adam_step on the fp64 oracle gradients.  The first Adam step is -lr * sign(g_eff) wherever
+    # the effective gradient coef * g + wd * p is clear of zero: entries above 1e-3 of the tensor's largest must match within 2 % of lr, at most
+    # 0.5 % of them may differ, every step is bounded by 1.05 lr
+    names = [k for k, _ in A.physics_net.named_parameters()]
+    pre = {k: st64[k].detach().clone() for k in names}
+    post = {k: st64[k].detach().clone() for k in names}
+    O.clip_and_adam_step(post, {k: g64[k] for k in names}, {}, lr=lr, weight_decay=wd, max_norm=max_norm)
+    checked = differing = 0
+    too_big = []
+    for name, p in A.physics_net.named_parameters():
+        if name.endswith('key_projection.bias'):
+            continue                      # zero gradient up to rounding noise; Adam turns that noise into +-lr steps of arbitrary sign
+        mine = (p.detach() - before[name]).double().cpu()
+        ref_d = post[name] - pre[name]
+        geff = (coef * g64[name] + wd * pre[name]).abs()
+        big = geff > 1e-3 * geff.max()
+        checked += int(big.sum())
+        differing += int(((mine - ref_d).abs() > 0.02 * lr)[big].sum())
+        if float(mine.abs().max()) > 1.05 * lr:
+            too_big.append((name, float(mine.abs().max())))
+    print('  optimiser step: %d entries with a clear effective gradient, %d differ from the oracle step by more than 2 %% of lr' % (checked, differing))
+    # A against B, step 1
+    agree = [(n_, float((pa - pb).abs().max())) for (n_, pa), pb in zip(A.physics_net.named_parameters(), B.physics_net.parameters())
+             if not torch.allclose(pa, pb, rtol=2e-5, atol=2e-7)]
+    print('  FusedClipAdam vs torch.optim.Adam, step 1: gnorm %.7e vs %.7e; %d tensors outside allclose' % (gn_a, gn_b, len(agree)))
+    for k, (e, bar) in lerr.items():
+        assert e <= bar, (k, e, bar)
+    assert gn64 > max_norm, gn64
+    assert abs(gn_a - gn64) <= 1e-3 * gn64, (gn_a, gn64)
+    assert len(rows) == len(names) - sum(1 for k in names if k.endswith('key_projection.bias'))
+    for err, l2, name in rows:
+        assert err < tol['grad'], (name, err)
+    assert not too_big, too_big
+    assert checked > 5000 and differing <= 0.005 * checked, (checked, differing)
+    assert abs(gn_a - gn_b) <= 1e-5 * gn_b, (gn_a, gn_b)
+    assert not agree, agree
+    # step 2 on another batch: Adam's moments and the device-side step counter at full size
+    with torch.no_grad():
+        for pa, pb in zip(A.physics_net.parameters(), B.physics_net.parameters()):
+            pb.copy_(pa)
+    b2 = batch(synthetic_inputs(4096, tag='inter_b'), synthetic_inputs(20480, tag='margin_b', margin=True))
+    _, _, gn_a = A.training_step(b2, opt_a, with_pde=True, max_norm=max_norm)
+    _, _, gn_b = B.training_step(b2, opt_b, with_pde=True, max_norm=max_norm)
+    gn_a, gn_b = float(gn_a), float(gn_b)
+    agree = [(n_, float((pa - pb).abs().max())) for (n_, pa), pb in zip(A.physics_net.named_parameters(), B.physics_net.parameters())
+             if not torch.allclose(pa, pb, rtol=2e-5, atol=2e-7)]
+    print('  FusedClipAdam vs torch.optim.Adam, step 2: gnorm %.7e vs %.7e; %d tensors outside allclose' % (gn_a, gn_b, len(agree)))
+    assert int(opt_a.step_count) == 2
+    assert abs(gn_a - gn_b) <= 1e-5 * gn_b, (gn_a, gn_b)
+    assert not agree, agree
+
+
+def test_step_losses_rejects_a_bad_split():
+    """_StepLossFn takes every launch's row count from the interior / margin split: a split that leaves a group empty, or a label count
+    that is not the margin group's, raises ValueError (not an assert, which `python -O` removes) before anything is launched."""
+    from deepphysinet_amd.point_path import step_losses
+    m = _model('bf16x2')
+    g = _gpu(synthetic_inputs(64, tag='margin', margin=True))
+    cfg = m.point_config()
+    with torch.no_grad():
+        heads, evec, statics = m.physics_net.field_weights(g['field_data'], g['forecast_h'])
+        for n_inter, n_lab in ((0, 64), (64, 0), (40, 23)):
+            with pytest.raises(ValueError, match='n_inter = %d of 64 points' % n_inter):
+                step_losses(cfg, n_inter, g['x'], g['y'], g['t'], g['f'], g['coord_data'], g['labels'][:n_lab], heads, evec, statics)
+
+
 @pytest.mark.parametrize('prec', ['bf16x2', 'bf16'])
 def test_full_grid_properties(prec):
     """N = 37 265 (BASELINE config[1]): the oracle is too slow there, so check what must hold at any size:
