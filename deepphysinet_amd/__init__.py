@@ -10,6 +10,7 @@ Drop-in surfaces (same names / arguments as the reference, /root/reference/DeepP
 The per-point arithmetic runs in libdpn_hip.so (hand-written HIP for gfx950, C ABI in include/dpn_hip.h).
 """
 from . import _lib
-from .point_path import PointConfig, pde_losses, pde_losses_batch, point_fields, pde_fields_and_jacobian, smooth_l1_data_loss
+from .point_path import PointConfig, pde_losses, pde_losses_batch, point_fields, point_fields_xyt, pde_fields_and_jacobian, \
+    smooth_l1_data_loss
 
-__all__ = ['PointConfig', 'pde_losses', 'pde_losses_batch', 'point_fields', 'pde_fields_and_jacobian', 'smooth_l1_data_loss', '_lib']
+__all__ = ['PointConfig', 'pde_losses', 'pde_losses_batch', 'point_fields', 'point_fields_xyt', 'pde_fields_and_jacobian', 'smooth_l1_data_loss', '_lib']

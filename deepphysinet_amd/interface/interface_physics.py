@@ -244,6 +244,14 @@ class InterfacePhysics(nn.Module):
         fields = self.physics_net.forward_xyt(field_data, x, y, t, input_data, forecast_h, use_cache=use_cache)
         return smooth_l1_data_loss(torch.cat(fields, dim=1), labels, beta=beta, factor=1.0).float() * margin_factor
 
+    def fields_at(self, x, y, t, field_data, input_data, forecast_h, use_cache=False):
+        """The six [N,1] normalised fields (u, v, P, T, q, rho) at raw coordinates, differentiable w.r.t. the weights and w.r.t. x, y, t up to
+        the order a second-order residual needs (PhysicsNet.forward_coords).  The reference's own composition trains on it unchanged:
+        fields_at -> inverse_norm -> the *_equation methods with their gradient() calls -> loss.backward(); so does a residual of one's own,
+        e.g. u_xx = gradient(gradient(u, x), x) (INTEGRATION.md)."""
+        self.point_config()
+        return self.physics_net.forward_coords(field_data, x, y, t, input_data, forecast_h, use_cache=use_cache)
+
     @torch.no_grad()
     def predict_grid(self, field_data, x, y, t, input_data, forecast_h, with_clip=False, use_cache=False):
         """Full-grid evaluation of the visualisation branch (:536-591): the six fields at all lon*lat nodes, given in the

@@ -146,5 +146,14 @@ class PhysicsNet(nn.Module):
         out = point_fields(self._cfg(), coord_data, heads, evec, statics, x=x, y=y, t=t)
         return tuple(out[:, k:k + 1] for k in range(6))
 
+    def forward_coords(self, field_x, x, y, t, coord_data, forecast_h, use_cache=False):
+        """The six [N,1] normalised fields at raw coordinates, attached to x, y, t: `torch.autograd.grad(..., create_graph=True)` of them
+        (the reference's gradient(), interface_physics.py:90-95) gives first and second derivatives whose losses train the weights, through
+        the same point kernels as the fused step (point_path.point_fields_xyt).  Mixed partials are zero; third derivatives are the limit."""
+        from ..point_path import point_fields_xyt
+        heads, evec, statics = self.field_weights(field_x, forecast_h, use_cache=use_cache)
+        out = point_fields_xyt(self._cfg(), x, y, t, coord_data, heads, evec, statics)
+        return tuple(out[:, k:k + 1] for k in range(6))
+
     def forward_single(self, variable_name, field_x, coord_x):
         raise NotImplementedError('dead code in the reference as well (model/physics_net.py:57-60 calls MetaNet with one argument)')

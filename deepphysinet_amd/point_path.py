@@ -229,7 +229,25 @@ def _forward_points(cfg: PointConfig, ws: _Workspace, nets, x, y, t, pe_in, coor
     return out_n, jac_n
 
 
-def _backward_points(cfg: PointConfig, ws: _Workspace, nets, x, y, t, pe_in, coord_data, g_out, g_jxi, statics, into=None, fork=False, keep=(), g_scale=None):
+def _forward_derivs(cfg: PointConfig, ws: _Workspace, nets, x, y, t, coord_data, want_saved):
+    """out_n [N,6] and its first, second and third derivatives along x, y, t [N,6,3] (physical units) in ONE forward launch (dpn_fwd_ref_derivs)."""
+    lib = L.load()
+    n = coord_data.shape[0]
+    dev = coord_data.device
+    if not ws.prepacked:
+        L.check(lib.dpn_pack_weights_form(nets, cfg.prec, lib.dpn_fwd_form(cfg.prec, 0), _ptr(ws.packed), _stream()), 'dpn_pack_weights')
+    out_n = torch.empty((n, 6), dtype=torch.float32, device=dev)
+    jac_n, hess_n, d3_n = (torch.empty((n, 6, 3), dtype=torch.float32, device=dev) for _ in range(3))
+    if want_saved:
+        ws.alloc_saved()
+    geo = cfg.geometry()
+    L.check(lib.dpn_fwd_ref_derivs(_ptr(x), _ptr(y), _ptr(t), None, _ptr(coord_data), None, n, _ptr(_freqs(dev)), ctypes.byref(geo), _ptr(ws.packed),
+                                   cfg.prec, _ptr(out_n), _ptr(jac_n), _ptr(hess_n), _ptr(d3_n), _ptr(ws.saved), _stream()), 'dpn_fwd_ref_derivs')
+    return out_n, jac_n, hess_n, d3_n
+
+
+def _backward_points(cfg: PointConfig, ws: _Workspace, nets, x, y, t, pe_in, coord_data, g_out, g_jxi, statics, into=None, fork=False, keep=(), g_scale=None,
+                     g_hxi=None):
     """Weight gradients from per-point cotangents.  Returns (g_heads [256,2700], g_evec [6,256], [48 static grads]); `into` = the same
     triple preallocated by the caller (a batch of fields writes each field's gradients side by side).
 
@@ -247,9 +265,14 @@ def _backward_points(cfg: PointConfig, ws: _Workspace, nets, x, y, t, pe_in, coo
     # g_scale: a device scalar multiplied into both cotangent streams as stage 1 reads them (they were formed for a unit cotangent of the total)
     if clock is not None:
         clock.stamp('bwd')
-    L.check(lib.dpn_bwd_points_scaled(_ptr(x), _ptr(y), _ptr(t), _ptr(pe_in), _ptr(coord_data), n, _ptr(_freqs(dev)), ctypes.byref(geo),
-                                      _ptr(ws.packed), cfg.prec, _ptr(g_out), _ptr(g_jxi), _ptr(g_scale), _ptr(ws.saved), _ptr(operands), _stream()),
-            'dpn_bwd_points')
+    if g_hxi is not None:           # + the cotangent of the second coordinate derivatives (point_fields_xyt), same launch
+        L.check(lib.dpn_bwd_points_derivs(_ptr(x), _ptr(y), _ptr(t), None, _ptr(coord_data), n, _ptr(_freqs(dev)), ctypes.byref(geo), _ptr(ws.packed),
+                                          cfg.prec, _ptr(g_out), _ptr(g_jxi), _ptr(g_hxi), _ptr(g_scale), _ptr(ws.saved), _ptr(operands), _stream()),
+                'dpn_bwd_points_derivs')
+    else:
+        L.check(lib.dpn_bwd_points_scaled(_ptr(x), _ptr(y), _ptr(t), _ptr(pe_in), _ptr(coord_data), n, _ptr(_freqs(dev)), ctypes.byref(geo),
+                                          _ptr(ws.packed), cfg.prec, _ptr(g_out), _ptr(g_jxi), _ptr(g_scale), _ptr(ws.saved), _ptr(operands), _stream()),
+                'dpn_bwd_points')
     if clock is not None:
         clock.stamp('bwd')
     arena = False
@@ -324,7 +347,7 @@ class _NoSecondOrder(torch.autograd.Function):
     def backward(ctx, g):
         raise RuntimeError('deepphysinet_amd: d(fields)/d(coordinates) of PhysicsNet.forward is first-order only; training through the '
                            'standalone *_equation methods needs its parameter derivative -- use InterfacePhysics.place_one_batch (fused '
-                           'residual kernels) for that')
+                           'residual kernels) for that; InterfacePhysics.fields_at (raw x, y, t) gives fields whose coordinate derivatives train')
 
 
 class _PointFieldsFn(torch.autograd.Function):
@@ -368,6 +391,117 @@ class _PointFieldsFn(torch.autograd.Function):
         nets = _net_ptrs(hd_, ev_, st)
         ghd, gev, gst = _backward_points(ctx.cfg, ctx.ws, nets, x_, y_, t_, pe_, cd_, g, None, st, fork=True, keep=(hd_, ev_))
         return (None, None, None, None, g_pe, None, ghd, gev, *gst)
+
+
+class _PointDerivsFn(torch.autograd.Function):
+    """Core node of point_fields_xyt: (out [N,6], J, H, D3 [N,6,3]) as functions of the WEIGHTS (the coordinates are constants here; _AttachFn
+    makes them functions of x, y, t).  J, H, D3 = first, second, third derivatives of out along x, y, t (physical units), all from one forward
+    launch.  The backward takes the cotangents of out, J and H -- autograd has added up every use of them before this node runs, so one
+    loss.backward() is ONE point backward -- and makes one dpn_bwd_points_derivs call, then the usual weight-gradient and finish launches."""
+
+    @staticmethod
+    def forward(ctx, cfg, x, y, t, coord_data, heads, evec, *statics):
+        for nm, v in (('x', x), ('coord_data', coord_data), ('heads', heads)):
+            _require_gpu(v, nm)
+        x_, y_, t_ = (_f32c(v).reshape(-1) for v in (x, y, t))
+        cd_, hd_, ev_ = _f32c(coord_data), _f32c(heads), _f32c(evec)
+        st = [_f32c(s) for s in statics]
+        need_grad = any(v.requires_grad for v in (heads, evec) + tuple(statics))
+        ws = _Workspace(cd_.shape[0], cfg.prec, cd_.device)
+        out_n, jac_n, hess_n, d3_n = _forward_derivs(cfg, ws, _net_ptrs(hd_, ev_, st), x_, y_, t_, cd_, want_saved=need_grad)
+        ctx.cfg, ctx.ws = cfg, ws
+        ctx.keep = (x_, y_, t_, cd_, hd_, ev_, st)
+        ctx.stamp = _stamp((heads, evec) + tuple(statics))
+        ctx.set_materialize_grads(False)
+        return out_n, jac_n, hess_n, d3_n
+
+    @staticmethod
+    def backward(ctx, g_out, g_jac, g_hess, g_d3):
+        if g_d3 is not None:
+            raise RuntimeError(_ORDER_LIMIT)
+        x_, y_, t_, cd_, hd_, ev_, st = ctx.keep
+        if not any(ctx.needs_input_grad[5:]) or (g_out is None and g_jac is None and g_hess is None):
+            return (None,) * (7 + len(st))
+        _check_stamp(ctx.stamp, 'point_fields_xyt')
+        cfg = ctx.cfg
+        n, dev = cd_.shape[0], cd_.device
+        g = torch.zeros((n, 6), dtype=torch.float32, device=dev) if g_out is None else _f32c(g_out)
+        # the kernels take the derivative cotangents along the NORMALISED coordinates xi = x / dx / (lon - 1), y / dy / (lat - 1), t / span:
+        # d J / d J_xi = 1 / (dx (lon - 1)) per coordinate, squared for the second derivatives
+        s1 = _xi_scale(cfg, dev)
+        g_jxi = None if g_jac is None else (_f32c(g_jac) * s1).contiguous()
+        g_hxi = None if g_hess is None else (_f32c(g_hess) * (s1 * s1)).contiguous()
+        ghd, gev, gst = _backward_points(cfg, ctx.ws, _net_ptrs(hd_, ev_, st), x_, y_, t_, None, cd_, g, g_jxi, st, fork=True, keep=(hd_, ev_),
+                                         g_hxi=g_hxi)
+        return (None,) * 5 + (ghd, gev, *gst)
+
+
+_ORDER_LIMIT = ('deepphysinet_amd point_fields_xyt: the fields are differentiable in (x, y, t) up to third order and train losses that contain '
+                'derivatives up to second order; a third derivative cannot be differentiated again (neither to a fourth derivative nor w.r.t. the '
+                'weights)')
+_xi_scales = {}
+
+
+def _xi_scale(cfg: PointConfig, device):
+    """[3] = 1 / (dx (lon - 1)), 1 / (dy (lat - 1)), 1 / pred_t_span as an fp32 device tensor: d (physical derivative) / d (xi derivative)."""
+    key = (float(cfg.dx), float(cfg.dy), int(cfg.lon_size), int(cfg.lat_size), float(cfg.pred_t_span), str(device))
+    if key not in _xi_scales:
+        v = [1.0 / (cfg.dx * (cfg.lon_size - 1)), 1.0 / (cfg.dy * (cfg.lat_size - 1)), 1.0 / cfg.pred_t_span]
+        _xi_scales[key] = torch.tensor(v, dtype=torch.float64).float().to(device)
+    return _xi_scales[key]
+
+
+class _AttachFn(torch.autograd.Function):
+    """v as a function of the coordinates too: the identity on v, and the coordinate cotangent sum_k g[:, k, c] * nxt[:, k, c], where nxt is the
+    next order's tensor, itself attached: d out / d x_c = J[..., c]; d J[..., c] / d x_c' = delta_cc' H[..., c] (each PE channel depends on one
+    coordinate and the nets are piecewise linear in it: the mixed partials are zero); d H / d x = D3.  The cotangent is a torch expression in
+    nxt, so under create_graph it is differentiable again, by the same rule one order up.  nxt travels in a tuple: it is not an input of this
+    node (v does not depend on it), so a backward pass through v never visits nxt's own node."""
+
+    @staticmethod
+    def forward(ctx, v, x, y, t, nxt):
+        ctx.nxt = nxt[0]
+        ctx.shapes = (x.shape, y.shape, t.shape)
+        ctx.set_materialize_grads(False)
+        return v.view_as(v)
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None, None
+        gx = gy = gt = None
+        if any(ctx.needs_input_grad[1:4]):
+            gc = ((g if g.dim() == 3 else g.unsqueeze(2)) * ctx.nxt).sum(1)          # [N, 3]
+            gx, gy, gt = (gc[:, c].reshape(shape) for c, shape in enumerate(ctx.shapes))
+        return g, gx, gy, gt, None
+
+
+class _OrderLimitFn(torch.autograd.Function):
+    """Identity on the third derivatives (and a function of x, y, t, so that it is part of every coordinate graph); a cotangent that reaches it
+    raises."""
+
+    @staticmethod
+    def forward(ctx, d3, x, y, t):
+        ctx.set_materialize_grads(False)
+        return d3.view_as(d3)
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None
+        raise RuntimeError(_ORDER_LIMIT)
+
+
+def point_fields_xyt(cfg: PointConfig, x, y, t, coord_data, heads, evec, statics):
+    """Normalised fields out_n [N,6] at raw coordinates x, y, t ([N] or [N,1]), differentiable w.r.t. every weight input AND w.r.t. x, y, t: first
+    derivatives with create_graph=True, second derivatives, and the coordinate gradient of a loss that contains second derivatives.  Every
+    derivative comes from ONE forward launch (dpn_fwd_ref_derivs); a backward pass through all of them is ONE point backward (_PointDerivsFn).
+    Mixed partials are zero; a third derivative cannot be differentiated again (RuntimeError)."""
+    out, jac, hess, d3 = _PointDerivsFn.apply(cfg, x.detach(), y.detach(), t.detach(), coord_data, heads, evec, *statics)
+    d3 = _OrderLimitFn.apply(d3, x, y, t)
+    hess = _AttachFn.apply(hess, x, y, t, (d3,))
+    jac = _AttachFn.apply(jac, x, y, t, (hess,))
+    return _AttachFn.apply(out, x, y, t, (jac,))
 
 
 class _PdeLossFn(torch.autograd.Function):

@@ -136,6 +136,14 @@ int dpn_fwd_ref_nets(const float* x, const float* y, const float* t, const float
                      int64_t n_points, const float* freqs, const DpnGeometry* geo, const void* packed, int prec, int n_nets,
                      float* out_n, float* jac_n, void* stream);
 
+/* dpn_fwd_ref with coordinate derivatives of order 2 and 3 from the same launch (raw coordinates only: pe_in must be NULL):
+ *   hess_n [N][6][3] = d2 out_n / dx2, dy2, dt2;  d3_n [N][6][3] = d3 out_n / dx3, dy3, dt3  (either may be NULL; a non-NULL one needs jac_n),
+ *   in physical units like jac_n.  Each PE channel depends on one coordinate and the nets are piecewise linear in the features (ReLU), so
+ *   these are all the non-zero higher derivatives: every mixed partial is zero (almost everywhere).  hess_n = d3_n = NULL: dpn_fwd_ref. */
+int dpn_fwd_ref_derivs(const float* x, const float* y, const float* t, const float* pe_in, const float* coord_data, const float* ref_data,
+                       int64_t n_points, const float* freqs, const DpnGeometry* geo, const void* packed, int prec,
+                       float* out_n, float* jac_n, float* hess_n, float* d3_n, void* saved, void* stream);
+
 /* g_pe[N][192] = sum_k g_out[N][k] * gpe[N][k][192]: backward of PhysicsNet.forward w.r.t. its encoded-coordinate input. */
 int dpn_contract_gpe(const float* g_out, const float* gpe, int64_t n_points, float* g_pe, void* stream);
 
@@ -162,6 +170,13 @@ int dpn_bwd_points(const float* x, const float* y, const float* t, const float* 
 int dpn_bwd_points_scaled(const float* x, const float* y, const float* t, const float* pe_in, const float* coord_data, int64_t n_points,
                           const float* freqs, const DpnGeometry* geo, const void* packed, int prec,
                           const float* g_out, const float* g_jxi, const float* g_scale /* [1] device, or NULL = 1 */, const void* saved, void* operands,
+                          void* stream);
+/* The same with g_hxi [N][6][3] (or NULL), the cotangent of the second derivatives along the NORMALISED coordinates xi (g_jxi's space): the
+ * weight gradients of the Jacobian and of the second derivatives in one pass (raw coordinates only: pe_in must be NULL).  Third derivatives
+ * (dpn_fwd_ref_derivs' d3_n) take no cotangent here.  g_hxi = NULL: dpn_bwd_points_scaled. */
+int dpn_bwd_points_derivs(const float* x, const float* y, const float* t, const float* pe_in, const float* coord_data, int64_t n_points,
+                          const float* freqs, const DpnGeometry* geo, const void* packed, int prec,
+                          const float* g_out, const float* g_jxi, const float* g_hxi, const float* g_scale, const void* saved, void* operands,
                           void* stream);
 
 /* Backward, stage 2: weight-gradient reductions over points (split-K partial sums). */
