@@ -100,6 +100,10 @@ class DpnSampler(Structure):
 SAMPLE_INTERIOR, SAMPLE_MARGIN, SAMPLE_EXPLICIT = 0, 1, 2
 
 
+class DpnLattice(Structure):
+    _fields_ = [(n, c_double) for n in ('x0', 'xstep', 'y0', 'ystep', 't0', 'tstep')] + [(n, c_int32) for n in ('nx', 'ny', 'nt')]
+
+
 class DpnSizes(Structure):
     _fields_ = [('n_pad', c_int64), ('packed', c_int64), ('saved', c_int64), ('operands', c_int64), ('partials', c_int64),
                 ('k_splits', c_int32)]
@@ -166,6 +170,10 @@ EXPORTS = {
     'dpn_sample_points_replay': (c_int, [POINTER(DpnSampler), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_uint64, c_uint64,
                                          c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dpn_grid_maps': (c_int, [c_void_p, c_int, c_int, POINTER(DpnPhysics), c_int, c_void_p, c_void_p]),
+    'dpn_sample_at': (c_int, [POINTER(DpnSampler), c_void_p, c_void_p, c_void_p, c_void_p, POINTER(DpnLattice), c_int64, c_int64,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dpn_fields_out': (c_int, [c_void_p, c_int64, POINTER(DpnPhysics), c_int, c_void_p, c_void_p, POINTER(DpnLattice), c_int64, c_void_p]),
+    'dpn_residual_points': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(DpnGeometry), POINTER(DpnPhysics), c_void_p, c_void_p]),
     'dpn_clip_adam_flat_floats': (c_int64, [c_int, c_void_p]),
     'dpn_clip_adam_flat': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
                                    c_float, c_float, c_void_p, c_void_p]),

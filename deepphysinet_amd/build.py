@@ -12,7 +12,7 @@ SRCS = [os.path.join(HERE, 'csrc', 'dpn_kernels.hip'), os.path.join(HERE, 'csrc'
         os.path.join(HERE, 'csrc', 'dpn_sampler.hip'), os.path.join(HERE, 'csrc', 'dpn_fp8.hip'),
         os.path.join(HERE, 'csrc', 'dpn_encoder_chain.hip')]
 DEPS = SRCS + [os.path.join(HERE, 'csrc', 'dpn_layout.h'), os.path.join(HERE, 'csrc', 'dpn_fwd_tiles.h'), os.path.join(HERE, 'csrc', 'dpn_ring_kernels.inc'),
-               os.path.join(HERE, 'csrc', 'dpn_tiles_kernels.inc'), os.path.join(os.path.dirname(HERE), 'include', 'dpn_hip.h'),
+               os.path.join(HERE, 'csrc', 'dpn_tiles_kernels.inc'), os.path.join(HERE, 'csrc', 'dpn_residual_body.inc'), os.path.join(os.path.dirname(HERE), 'include', 'dpn_hip.h'),
                os.path.join(os.path.dirname(HERE), 'include', 'dpn_hip_experiments.h')]
 LIB = os.path.join(HERE, 'libdpn_hip.so')
 

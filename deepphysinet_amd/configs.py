@@ -1,6 +1,6 @@
 """Constants of the one configuration the reference ships (configs/DeepPhysiNet_NCEP_cfg.py), restated as the
 inputs of this build: model sizes (:11-32), observation normalisation + clip bounds (:64-76), grid (:10,:93-95),
-loss factors (:137-148), optimiser (:151-155)."""
+loss factors (:137-148), optimiser (:151-155), inference (:205-230)."""
 import copy
 
 IMG_SIZE = (145, 257)          # (lat, lon) of the 0.25 degree grid
@@ -30,13 +30,22 @@ _NCEP = dict(
         lr_schedule=dict(name='CosineAnnealingLR', T_max=5, eta_min=5e-6),
     ),
     test_cfg=dict(),
-    inference_cfg=dict(),
+    # cfg:205-230, with paths that can be used as they stand (the reference ships Windows paths and empty strings), the training grid as img_size
+    # and half-hourly output; `refine` (optional, new) = output steps per fine-grid node.  vis_* feed the reference's Basemap plots: not built.
+    inference_cfg=dict(
+        batch_size=1, device='cuda:0', num_epoch=105, num_workers=0, dt=30 * 60, img_size=IMG_SIZE, pred_t_span=-1,
+        start_time=r'2022-03-25_00_00_00', end_time=r'2022-03-31_00_00_00',
+        checkpoints=dict(checkpoints_path='checkpoints/DeepPhysiNet'),
+        log=dict(with_vis=False, vis_path='results/DeepPhysiNet/vis', result_path='results/DeepPhysiNet', write_source=True, export_variable=['T'],
+                 vis_downscale_cfg=dict(coord_file='', project_dict=dict(name='Mercator', stand_lon=110.0, moad_cen_lat=30.0, truelat1=30, truelat2=60.0,
+                                                                        pole_lat=90.0, pole_lon=0.0))),
+    ),
 )
 
 
 def ncep_config(img_size=IMG_SIZE, dx=27000, dy=27000):
     """A fresh copy of the NCEP configuration; img_size=(37,65), dx=dy=108000 gives the 1-degree plumbing case."""
     cfg = copy.deepcopy(_NCEP)
-    cfg['train_cfg']['img_size'] = tuple(img_size)
+    cfg['train_cfg']['img_size'] = cfg['inference_cfg']['img_size'] = tuple(img_size)
     cfg['train_cfg']['dx'], cfg['train_cfg']['dy'] = dx, dy
     return cfg

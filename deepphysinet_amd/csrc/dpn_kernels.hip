@@ -15,6 +15,7 @@
 //   dpn_pack_*          fp32 weights -> MFMA-fragment-ordered bf16 (hi/lo) + permuted vectors
 //   dpn_fwd_kernel      fused PE + MLP chain + reverse sweep + Jacobian contraction (activations never leave registers)
 //   dpn_residual_kernel de-norm, clip, six residuals, wave-shuffle loss reduction, analytic cotangents
+//   dpn_residual_points_kernel the same residual body, written out per point (inference diagnostics)
 //   dpn_bwd_kernel      per-point cotangent streams -> operands of the weight-gradient reductions
 //   dpn_wgrad_kernel    points-reduction GEMMs (split over point ranges)
 //   dpn_finish_*        split reduction, un-permutation, rank-1 fc.2 gradients
@@ -880,42 +881,7 @@ __global__ __launch_bounds__(256) void dpn_residual_kernel(ResArgs a) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool valid = i < a.n;
     const int64_t ic = valid ? i : a.n - 1;
-    constexpr float C_P = 1005.f, L_V = 2.5e6f, R_V = 461.5f, R_D = 287.f, EPS = 1e-6f;
-    float val[6], msk[6], J[6][3];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        float v = a.out_n[ic * 6 + k] * a.ph.std[k] + a.ph.mean[k];       // inverse_norm (interface_physics.py:250)
-        float dv = a.ph.std[k];                                          // d val / d out
-        if (a.ph.sq_on[k]) { dv = 2.f * v * a.ph.std[k]; v = v * v + a.ph.sq_add[k]; }   // three-factor min_max: squared, shifted (:244-247)
-        float m = 1.f;
-        if (a.ph.clip_on[k]) {                                           // torch.clip: gradient passes where lo <= v <= hi
-            m = (v >= a.ph.clip_lo[k] && v <= a.ph.clip_hi[k]) ? 1.f : 0.f;
-            v = fminf(fmaxf(v, a.ph.clip_lo[k]), a.ph.clip_hi[k]);
-        }
-        val[k] = v; msk[k] = m * dv;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) J[k][c] = a.jac_n[(ic * 6 + k) * 3 + c] * msk[k];
-    }
-    const float u = val[0], v = val[1], p = val[2], T = val[3], q = val[4], rho = val[5];
-    const float fc = a.f[ic];
-    const float omega = J[2][2] + u * J[2][0] + v * J[2][1];
-    const float A = J[3][2] + u * J[3][0] + v * J[3][1];
-    const float B = J[4][2] + u * J[4][0] + v * J[4][1];
-    const float tc = T - 273.15f;
-    const float e_s = 6.112f * expf(17.67f * tc / (tc + 243.5f)) * 100.f;                 // get_qs :181-185
-    const float qs_raw = 0.622f * e_s / (p - 0.378f * e_s);
-    const float q_s = (qs_raw != qs_raw) ? qs_raw : fmaxf(qs_raw, 1e-6f);          // torch.maximum propagates NaN (:166)
-    const float delta = (omega < 0.f && q >= q_s) ? 1.f : 0.f;
-    const float R = (1.f + 0.608f * q) * R_D;
-    const float Fv = (L_V * R - C_P * R_V * T) / (C_P * R_V + T * T + L_V * L_V * q_s) * q_s * T;   // precedence as written :161-163
-    const float K = delta * Fv / (p + EPS);
-    float r[6];
-    r[0] = J[0][2] + u * J[0][0] + v * J[0][1] + J[2][0] / rho - fc * v;                   // :97-104
-    r[1] = J[1][2] + u * J[1][0] + v * J[1][1] + J[2][1] / rho + fc * u;                   // :106-114
-    r[2] = J[5][2] + u * J[5][0] + v * J[5][1] + rho * J[0][0] + rho * J[1][1];            // :116-124
-    r[3] = C_P * A - omega / (rho + EPS) + L_V * B;                                        // :126-144
-    r[4] = -omega * K + B;                                                                 // :146-175
-    r[5] = p - rho * (1.f + 0.608f * q) * R_D * T;                                         // :177-179
+#include "dpn_residual_body.inc"
     if (a.loss_sums) {
         // fp64 partial sums (residual^2 spans 1e-20..1e+20 across equations): wave shuffle tree, then the four waves of the block
         // in a fixed order -> one [6] row per block.  No atomics: dpn_residual_finish adds the rows in a fixed order, so the
@@ -975,6 +941,22 @@ __global__ __launch_bounds__(256) void dpn_residual_kernel(ResArgs a) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) a.g_jxi[(i * 6 + k) * 3 + c] = gJ[k][c] * msk[k] * sc[c];
     }
+}
+
+// The six signed residuals of every point, res[n][6] = lhs - rhs (motion-u, motion-v, continuity, energy, vapour, gas), unscaled: the same body as
+// dpn_residual_kernel (dpn_residual_body.inc), no reduction and no cotangents -- where a trained field violates its equations.  One thread per point.
+struct ResPointArgs {
+    const float *out_n, *jac_n, *f;
+    int64_t n;
+    DpnPhysics ph;
+    float* res;
+};
+__global__ __launch_bounds__(256) void dpn_residual_points_kernel(ResPointArgs a) {
+    const int64_t ic = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (ic >= a.n) return;
+#include "dpn_residual_body.inc"
+    float2* dst = reinterpret_cast<float2*>(a.res + ic * 6);               // rows of 24 bytes: 8-byte aligned
+    dst[0] = make_float2(r[0], r[1]); dst[1] = make_float2(r[2], r[3]); dst[2] = make_float2(r[4], r[5]);
 }
 
 __global__ __launch_bounds__(384) void dpn_residual_finish_kernel(const double* partials, int64_t n, DpnPhysics ph, float* losses) {
@@ -2454,6 +2436,14 @@ int dpn_residual(const float* out_n, const float* jac_n, const float* f, int64_t
     if (phys->criterion < DPN_CRIT_MSE || phys->criterion > DPN_CRIT_SMOOTH_L1 || (phys->criterion == DPN_CRIT_SMOOTH_L1 && !(phys->beta > 0.f))) return -1;
     ResArgs a{out_n, jac_n, f, n, *geo, *phys, gl, gtot, loss_sums, g_out, g_jxi};
     hipLaunchKernelGGL(dpn_residual_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+    return ck(hipGetLastError());
+}
+
+int dpn_residual_points(const float* out_n, const float* jac_n, const float* f, int64_t n, const DpnGeometry* geo, const DpnPhysics* phys, float* res,
+                        void* stream) {
+    if (!out_n || !jac_n || !f || !geo || !phys || !res || n <= 0) return -1;
+    ResPointArgs a{out_n, jac_n, f, n, *phys, res};
+    hipLaunchKernelGGL(dpn_residual_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
     return ck(hipGetLastError());
 }
 

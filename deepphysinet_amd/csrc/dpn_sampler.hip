@@ -25,6 +25,36 @@ __device__ inline double u53(uint32_t hi, uint32_t lo) {               // unifor
 }
 __device__ inline uint32_t below(uint32_t w, uint32_t n) { return (uint32_t)(((uint64_t)w * n) >> 32); }   // randint(0, n)
 
+// One point of the sampler at position (xr, yr) in fine-grid index units and tr in hours: fp64 weights in the clamped coarse cell, NaN outside the
+// cube, the Coriolis term, one cast to fp32.  The drawn points (dpn_sample_kernel) and the given ones (dpn_sample_at_kernel) share it.
+__device__ __forceinline__ void sample_point(const DpnSampler& s, const float* cube, const double xr, const double yr, const double tr, const int64_t i,
+                                             float* x, float* y, float* t, float* f, float* coord_data) {
+    // trilinear interpolation of the coarse cube [6][lat_in][lon_in][t_in] at (lat, lon, hour)               (:405-411)
+    const double fx = xr * s.cells_x, fy = yr * s.cells_y, ft = tr / s.t_step_hours;
+    int ix = (int)floor(fx), iy = (int)floor(fy), it = (int)floor(ft);
+    ix = ix < 0 ? 0 : (ix > s.lon_in - 2 ? s.lon_in - 2 : ix);
+    iy = iy < 0 ? 0 : (iy > s.lat_in - 2 ? s.lat_in - 2 : iy);
+    it = it < 0 ? 0 : (it > s.t_in - 2 ? s.t_in - 2 : it);
+    const double wx = fx - ix, wy = fy - iy, wt = ft - it;
+    const bool inside = wx >= 0.0 && wx <= 1.0 && wy >= 0.0 && wy <= 1.0 && wt >= 0.0 && wt <= 1.0;   // outside -> NaN (xarray)
+    const int64_t sy = (int64_t)s.lon_in * s.t_in, sx = s.t_in, sk = (int64_t)s.lat_in * sy;
+    const float* c0 = cube + (int64_t)iy * sy + (int64_t)ix * sx + it;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const float* c = c0 + k * sk;
+        const double v000 = c[0], v001 = c[1], v010 = c[sx], v011 = c[sx + 1];
+        const double v100 = c[sy], v101 = c[sy + 1], v110 = c[sy + sx], v111 = c[sy + sx + 1];
+        const double lo = (v000 * (1 - wt) + v001 * wt) * (1 - wx) + (v010 * (1 - wt) + v011 * wt) * wx;
+        const double hi = (v100 * (1 - wt) + v101 * wt) * (1 - wx) + (v110 * (1 - wt) + v111 * wt) * wx;
+        coord_data[i * 6 + k] = inside ? (float)(lo * (1 - wy) + hi * wy) : __builtin_nanf("");
+    }
+    const double lat_deg = s.begin_lat + yr * s.dlat;
+    x[i] = (float)(xr * (double)s.dx);
+    y[i] = (float)(yr * (double)s.dy);
+    t[i] = (float)(tr * 3600.0);
+    f[i] = (float)(2.0 * 7.29e-5 * sin(lat_deg / 180.0 * 3.141592653589793));                           // get_coriolis (:521-526)
+}
+
 struct SampleArgs {
     DpnSampler s;
     const float* cube;
@@ -60,30 +90,7 @@ __global__ __launch_bounds__(256) void dpn_sample_kernel(SampleArgs a) {
         }
         tr = below(v[0], (uint32_t)(s.t_hours + 1));                    // randint(0, step * nums + 1)       (:338, :446)
     }
-    // trilinear interpolation of the coarse cube [6][lat_in][lon_in][t_in] at (lat, lon, hour)               (:405-411)
-    const double fx = xr * s.cells_x, fy = yr * s.cells_y, ft = tr / s.t_step_hours;
-    int ix = (int)floor(fx), iy = (int)floor(fy), it = (int)floor(ft);
-    ix = ix < 0 ? 0 : (ix > s.lon_in - 2 ? s.lon_in - 2 : ix);
-    iy = iy < 0 ? 0 : (iy > s.lat_in - 2 ? s.lat_in - 2 : iy);
-    it = it < 0 ? 0 : (it > s.t_in - 2 ? s.t_in - 2 : it);
-    const double wx = fx - ix, wy = fy - iy, wt = ft - it;
-    const bool inside = wx >= 0.0 && wx <= 1.0 && wy >= 0.0 && wy <= 1.0 && wt >= 0.0 && wt <= 1.0;   // outside -> NaN (xarray)
-    const int64_t sy = (int64_t)s.lon_in * s.t_in, sx = s.t_in, sk = (int64_t)s.lat_in * sy;
-    const float* c0 = a.cube + (int64_t)iy * sy + (int64_t)ix * sx + it;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const float* c = c0 + k * sk;
-        const double v000 = c[0], v001 = c[1], v010 = c[sx], v011 = c[sx + 1];
-        const double v100 = c[sy], v101 = c[sy + 1], v110 = c[sy + sx], v111 = c[sy + sx + 1];
-        const double lo = (v000 * (1 - wt) + v001 * wt) * (1 - wx) + (v010 * (1 - wt) + v011 * wt) * wx;
-        const double hi = (v100 * (1 - wt) + v101 * wt) * (1 - wx) + (v110 * (1 - wt) + v111 * wt) * wx;
-        a.coord_data[i * 6 + k] = inside ? (float)(lo * (1 - wy) + hi * wy) : __builtin_nanf("");
-    }
-    const double lat_deg = s.begin_lat + yr * s.dlat;
-    a.x[i] = (float)(xr * (double)s.dx);
-    a.y[i] = (float)(yr * (double)s.dy);
-    a.t[i] = (float)(tr * 3600.0);
-    a.f[i] = (float)(2.0 * 7.29e-5 * sin(lat_deg / 180.0 * 3.141592653589793));                           // get_coriolis (:521-526)
+    sample_point(s, a.cube, xr, yr, tr, i, a.x, a.y, a.t, a.f, a.coord_data);
     if (a.raw) { a.raw[i * 3] = xr; a.raw[i * 3 + 1] = yr; a.raw[i * 3 + 2] = tr; }
     if (a.labels && a.label_out) {                                      // read_point of the ERA5 label at (x, y, t)  (:347-365)
         const int X = (int)xr, Y = (int)yr, T = (int)tr;
@@ -91,6 +98,20 @@ __global__ __launch_bounds__(256) void dpn_sample_kernel(SampleArgs a) {
         for (int k = 0; k < 6; ++k)
             a.label_out[i * 6 + k] = a.labels[(((int64_t)T * 6 + k) * s.lat + Y) * s.lon + X];
     }
+}
+
+// inverse_norm (:232-262) of one normalised value of variable k: two roundings (mul, then add) like the reference's `v * std + mean` in torch -- not
+// contracted into one fma --, the three-factor min_max form, and the clip of P, T, q, rho.
+__device__ __forceinline__ float denorm(const float out, const int k, const DpnPhysics& ph, const int with_clip) {
+    float v;
+    {
+#pragma clang fp contract(off)
+        const float prod = out * ph.std[k];
+        v = prod + ph.mean[k];
+        if (ph.sq_on[k]) { const float sq = v * v; v = sq + ph.sq_add[k]; }       // three-factor min_max (interface_physics.py:244-247)
+    }
+    if (with_clip && k >= 2) v = v != v ? v : fminf(fmaxf(v, ph.clip_lo[k]), ph.clip_hi[k]);      // NaN passes through like torch.clip
+    return v;
 }
 
 struct MapArgs {
@@ -109,16 +130,70 @@ __global__ __launch_bounds__(256) void dpn_grid_maps_kernel(MapArgs a) {
     const int k = (int)(j / nodes);
     const int64_t r = j - k * nodes;
     const int yy = (int)(r / a.lon), xx = (int)(r - (int64_t)yy * a.lon);
-    // two roundings (mul, then add) like the reference's `v * std + mean` in torch -- not contracted into one fma
-    float v;
-    {
-#pragma clang fp contract(off)
-        const float prod = a.out_n[((int64_t)xx * a.lat + yy) * 6 + k] * a.ph.std[k];
-        v = prod + a.ph.mean[k];
-        if (a.ph.sq_on[k]) { const float sq = v * v; v = sq + a.ph.sq_add[k]; }       // three-factor min_max (interface_physics.py:244-247)
-    }
-    if (a.with_clip && k >= 2) v = v != v ? v : fminf(fmaxf(v, a.ph.clip_lo[k]), a.ph.clip_hi[k]);      // NaN passes through like torch.clip
+    const float v = denorm(a.out_n[((int64_t)xx * a.lat + yy) * 6 + k], k, a.ph, a.with_clip);
     a.maps[j] = v;
+}
+
+// The point of a lattice with running index g: (it, iy, ix), ix fastest, it slowest.
+__device__ __forceinline__ void lattice_index(const DpnLattice& l, const int64_t g, int& it, int& iy, int& ix) {
+    const int64_t plane = (int64_t)l.nx * l.ny;
+    it = (int)(g / plane);
+    const int64_t r = g - (int64_t)it * plane;
+    iy = (int)(r / l.nx);
+    ix = (int)(r - (int64_t)iy * l.nx);
+}
+
+struct SampleAtArgs {
+    DpnSampler s;
+    const float* cube;
+    const double *xr, *yr, *tr;      // stations (NULL: the lattice)
+    DpnLattice lat;
+    int64_t first, n;
+    float *x, *y, *t, *f, *coord_data;
+};
+// The sampler at given positions: stations (three arrays) or points first .. first + n of a lattice built here (no index arrays).
+__global__ __launch_bounds__(256) void dpn_sample_at_kernel(SampleAtArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    double xr, yr, tr;
+    if (a.xr) {
+        xr = a.xr[i]; yr = a.yr[i]; tr = a.tr[i];
+    } else {
+        int it, iy, ix;
+        lattice_index(a.lat, a.first + i, it, iy, ix);
+        {                                         // origin + index * step in two roundings, as a host forms the same positions
+#pragma clang fp contract(off)
+            xr = a.lat.x0 + (double)ix * a.lat.xstep;
+            yr = a.lat.y0 + (double)iy * a.lat.ystep;
+            tr = a.lat.t0 + (double)it * a.lat.tstep;
+        }
+    }
+    sample_point(a.s, a.cube, xr, yr, tr, i, a.x, a.y, a.t, a.f, a.coord_data);
+}
+
+struct FieldsOutArgs {
+    const float* out_n;
+    int64_t n, first;
+    DpnPhysics ph;
+    int with_clip;
+    float *rows, *maps;
+    DpnLattice lat;
+};
+// out_n [n][6] normalised -> physical values (inverse_norm): rows [n][6], or the places of lattice points first .. first + n in
+// maps [nt][6][ny][nx].  Map mode: thread j = (k, point), points fastest -> stores run along ix (a chunk may begin and end anywhere in a plane).
+__global__ __launch_bounds__(256) void dpn_fields_out_kernel(FieldsOutArgs a) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= a.n * 6) return;
+    if (a.rows) {
+        const int k = (int)(j % 6);
+        a.rows[j] = denorm(a.out_n[j], k, a.ph, a.with_clip);
+        return;
+    }
+    const int k = (int)(j / a.n);
+    const int64_t p = j - (int64_t)k * a.n, g = a.first + p;
+    const int64_t plane = (int64_t)a.lat.nx * a.lat.ny;
+    const int64_t it = g / plane, r = g - it * plane;
+    a.maps[(it * 6 + k) * plane + r] = denorm(a.out_n[p * 6 + k], k, a.ph, a.with_clip);
 }
 
 }  // namespace
@@ -149,6 +224,30 @@ int dpn_grid_maps(const float* out_n, int lon, int lat, const DpnPhysics* phys, 
     MapArgs a{out_n, lon, lat, *phys, with_clip, maps};
     const int64_t total = (int64_t)lon * lat * 6;
     hipLaunchKernelGGL(dpn_grid_maps_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+static bool lattice_ok(const DpnLattice* l, int64_t first, int64_t n) {
+    return l && l->nx >= 1 && l->ny >= 1 && l->nt >= 1 && first >= 0 && first + n <= (int64_t)l->nx * l->ny * l->nt;
+}
+
+int dpn_sample_at(const DpnSampler* s, const float* cube, const double* xr, const double* yr, const double* tr, const DpnLattice* lattice,
+                  int64_t first, int64_t n, float* x, float* y, float* t, float* f, float* coord_data, void* stream) {
+    if (!s || !cube || !x || !y || !t || !f || !coord_data || n <= 0) return -1;
+    if (s->lon_in < 2 || s->lat_in < 2 || s->t_in < 2 || s->lon < 2 || s->lat < 2) return -1;
+    const bool stations = xr || yr || tr;
+    if (stations ? (!xr || !yr || !tr || lattice) : !lattice_ok(lattice, first, n)) return -1;
+    SampleAtArgs a{*s, cube, xr, yr, tr, stations ? DpnLattice{} : *lattice, first, n, x, y, t, f, coord_data};
+    hipLaunchKernelGGL(dpn_sample_at_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int dpn_fields_out(const float* out_n, int64_t n, const DpnPhysics* phys, int with_clip, float* rows, float* maps, const DpnLattice* lattice,
+                   int64_t first, void* stream) {
+    if (!out_n || !phys || n <= 0 || (rows != nullptr) == (maps != nullptr)) return -1;
+    if (maps ? !lattice_ok(lattice, first, n) : lattice != nullptr) return -1;
+    FieldsOutArgs a{out_n, n, first, *phys, with_clip, rows, maps, maps ? *lattice : DpnLattice{}};
+    hipLaunchKernelGGL(dpn_fields_out_kernel, dim3((unsigned)((n * 6 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -272,6 +272,126 @@ class InterfacePhysics(nn.Module):
                                        _stream()), 'dpn_grid_maps')
         return maps
 
+    # ------------------------------------------------------------------ inference at stations and on lattices
+    INFER_BUDGET_BYTES = 256 << 20      # per-point buffers of one chunk of a lattice evaluation (the packed weights and the output maps come on top)
+    FIELD_POINT_BYTES = 4 * (4 + 6 + 6)                 # x, y, t, f | coord_data | out_n
+    RESIDUAL_POINT_BYTES = 4 * (4 + 6 + 6 + 18 + 6)     # ... | Jacobian | residual rows
+
+    @staticmethod
+    def chunk_size(n_points, chunk_points=None, point_bytes=FIELD_POINT_BYTES, prec=L.PREC_BF16X2):
+        """Points per chunk of a lattice evaluation: a multiple of the point kernels' padding unit (dpn_sizes: 128 points), so that a chunked and an
+        unchunked run form identical tiles; a given size is rounded down to it (and up to one unit), the default is what INFER_BUDGET_BYTES of
+        per-point buffers hold.  A lattice that is smaller is one chunk."""
+        import ctypes
+        sizes = L.DpnSizes()
+        L.check(L.load().dpn_sizes(1, int(prec), ctypes.byref(sizes)), 'dpn_sizes')
+        unit = int(sizes.n_pad)
+        want = InterfacePhysics.INFER_BUDGET_BYTES // int(point_bytes) if chunk_points is None else int(chunk_points)
+        if want < 1:
+            raise ValueError('chunk_points must be positive, got %r' % (chunk_points,))
+        chunk = max(unit, want // unit * unit)
+        return int(n_points) if chunk >= n_points else chunk
+
+    def _inference_weights(self, field_data, forecast_h, n_chunk):
+        """encode_field, field_weights and the weight packing, once per call (the field cache is not consulted and not written)."""
+        from ..point_path import _Workspace, _f32c, _net_ptrs, _ptr, _require_gpu, _stream
+        _require_gpu(field_data, 'field_data')
+        cfg = self.point_config()
+        heads, evec, statics = self.physics_net.field_weights(field_data, forecast_h, use_cache=False)
+        keep = (_f32c(heads), _f32c(evec), [_f32c(s_) for s_ in statics])
+        nets = _net_ptrs(*keep)
+        ws = _Workspace(n_chunk, cfg.prec, keep[0].device)
+        lib = L.load()
+        L.check(lib.dpn_pack_weights_form(nets, cfg.prec, lib.dpn_fwd_form(cfg.prec, 0), _ptr(ws.packed), _stream()), 'dpn_pack_weights')
+        ws.prepacked = True
+        return cfg, ws, nets, keep
+
+    def _station_inputs(self, sampler, x_idx, y_idx, hours, lonlat):
+        x, y, t, cd, f = (sampler.at_lonlat if lonlat else sampler.at_positions)(x_idx, y_idx, hours)
+        return x, y, t, cd, f.reshape(-1)
+
+    @torch.no_grad()
+    def predict_points(self, field_data, sampler, x_idx, y_idx, hours, forecast_h, with_clip=False, lonlat=False):
+        """The six physical fields [N, 6] (u, v, P, T, q, rho) at N stations: positions in fine-grid index units (lonlat: degrees east / north)
+        and hours, all fractional (CollocationSampler.at_positions / at_lonlat interpolate the coarse cube there)."""
+        import ctypes
+        from ..point_path import _forward_points, _ptr, _stream
+        x, y, t, cd, _ = self._station_inputs(sampler, x_idx, y_idx, hours, lonlat)
+        n = x.shape[0]
+        cfg, ws, nets, keep = self._inference_weights(field_data, forecast_h, n)
+        out_n, _ = _forward_points(cfg, ws, nets, x, y, t, None, cd, want_jac=False, want_saved=False)
+        rows = torch.empty((n, 6), dtype=torch.float32, device=out_n.device)
+        ph = cfg.physics()
+        L.check(L.load().dpn_fields_out(_ptr(out_n), n, ctypes.byref(ph), int(bool(with_clip)), _ptr(rows), None, None, 0, _stream()), 'dpn_fields_out')
+        return rows
+
+    def _lattice_chunks(self, sampler, lattice, chunk):
+        """(first, n, x, y, t, f, coord_data) for the chunks of a lattice; the five buffers are allocated once and reused."""
+        dev = sampler.cube.device
+        bufs = tuple(torch.empty(chunk, dtype=torch.float32, device=dev) for _ in range(4)) + (torch.empty((chunk, 6), dtype=torch.float32, device=dev),)
+        total = lattice.n_points
+        for first in range(0, total, chunk):
+            n = min(chunk, total - first)
+            yield (first, n) + sampler.sample_at(n, lattice=lattice, first=first, out=bufs)
+
+    @torch.no_grad()
+    def predict_lattice(self, field_data, sampler, lattice, forecast_h, with_clip=False, chunk_points=None):
+        """The six physical fields on a lattice (CollocationSampler.lattice) as maps [nt, 6, ny, nx].  The encoder, the hyper-network heads and the
+        weight packing run once; the lattice is then walked in chunks (chunk_size) of dpn_sample_at -> fields-only forward -> dpn_fields_out, every
+        chunk writing its places of the one preallocated output.  NaN where the lattice leaves the coarse cube."""
+        import ctypes
+        from ..point_path import _forward_points, _ptr, _stream
+        chunk = self.chunk_size(lattice.n_points, chunk_points, self.FIELD_POINT_BYTES, self.precision)
+        cfg, ws, nets, keep = self._inference_weights(field_data, forecast_h, chunk)
+        maps = torch.empty((lattice.nt, 6, lattice.ny, lattice.nx), dtype=torch.float32, device=field_data.device)
+        ph, lat, lib = cfg.physics(), lattice.c_struct(), L.load()
+        for first, n, x, y, t, _, cd in self._lattice_chunks(sampler, lattice, chunk):
+            out_n, _ = _forward_points(cfg, ws, nets, x, y, t, None, cd, want_jac=False, want_saved=False)
+            L.check(lib.dpn_fields_out(_ptr(out_n), n, ctypes.byref(ph), int(bool(with_clip)), None, _ptr(maps), ctypes.byref(lat), first, _stream()),
+                    'dpn_fields_out')
+        return maps
+
+    def _residual_factors(self, residual_factors, device):
+        if not residual_factors:
+            return None
+        lf = self.train_cfg['losses']['loss_factor'] if residual_factors is True else residual_factors
+        return torch.tensor([float(lf[k]) for k in LOSS_ORDER], dtype=torch.float64).float().to(device)
+
+    def _residual_rows(self, cfg, ws, nets, x, y, t, f, cd, res):
+        import ctypes
+        from ..point_path import _forward_points, _ptr, _stream
+        n = x.shape[0]
+        out_n, jac_n = _forward_points(cfg, ws, nets, x, y, t, None, cd, want_jac=True, want_saved=False)       # the Jacobian with no saved state
+        geo, ph = cfg.geometry(), cfg.physics()
+        L.check(L.load().dpn_residual_points(_ptr(out_n), _ptr(jac_n), _ptr(f), n, ctypes.byref(geo), ctypes.byref(ph), _ptr(res), _stream()),
+                'dpn_residual_points')
+
+    @torch.no_grad()
+    def residuals_at(self, field_data, sampler, x_idx, y_idx, hours, forecast_h, lonlat=False, residual_factors=False):
+        """Where the network's output violates its equations: the six signed residuals lhs - rhs [N, 6] (motion-u, motion-v, continuity, energy,
+        vapour, gas) at N stations, de-normalised and clipped as the training loss does it (self.with_clip).  loss_factor_i * mean(res_i ** 2) is the
+        MSE loss term of the same points.  residual_factors: True multiplies column i by the configuration's loss factor, a dict by its own."""
+        x, y, t, cd, f = self._station_inputs(sampler, x_idx, y_idx, hours, lonlat)
+        n = x.shape[0]
+        cfg, ws, nets, keep = self._inference_weights(field_data, forecast_h, n)
+        res = torch.empty((n, 6), dtype=torch.float32, device=x.device)
+        self._residual_rows(cfg, ws, nets, x, y, t, f, cd, res)
+        fac = self._residual_factors(residual_factors, res.device)
+        return res if fac is None else res * fac
+
+    @torch.no_grad()
+    def residual_lattice(self, field_data, sampler, lattice, forecast_h, residual_factors=False, chunk_points=None):
+        """residuals_at on a lattice, as maps [nt, 6, ny, nx]; chunked as predict_lattice is."""
+        chunk = self.chunk_size(lattice.n_points, chunk_points, self.RESIDUAL_POINT_BYTES, self.precision)
+        cfg, ws, nets, keep = self._inference_weights(field_data, forecast_h, chunk)
+        rows = torch.empty((lattice.n_points, 6), dtype=torch.float32, device=field_data.device)
+        for first, n, x, y, t, f, cd in self._lattice_chunks(sampler, lattice, chunk):
+            self._residual_rows(cfg, ws, nets, x, y, t, f, cd, rows[first:first + n])
+        fac = self._residual_factors(residual_factors, rows.device)
+        if fac is not None:
+            rows *= fac
+        return rows.view(lattice.nt, lattice.ny, lattice.nx, 6).permute(0, 3, 1, 2).contiguous()
+
     def training_step(self, batch: dict, optimizer, with_pde=True, max_norm=2.5e7, grad_sync=None):
         """One step body (:443-515 / :990-1065): data loss on the margin points, PDE losses on interior and margin points,
         backward, clip_grad_norm_(2.5e7), optimizer step.  `batch` holds device tensors: field_data [1,159,2405],
@@ -553,6 +673,99 @@ class InterfacePhysics(nn.Module):
         (DistributedSampler, :936), gradients are averaged by distributed.GradientAllReduce on the optimiser's flat gradient buffer
         (replaces the DistributedDataParallel wrap :903-907), rank 0 writes the checkpoints."""
         return self._run_train(True, **kwargs)
+
+    # ------------------------------------------------------------------ inference loop (:1407-1530)
+    @staticmethod
+    def gather_key_from_state(k, state_dict: dict, default):
+        """:1532-1536 -- a checkpoint's own value of `k` when it carries one."""
+        return state_dict[k] if k in state_dict else default
+
+    def _inference_samples(self, kwargs):
+        """The field samples of run_inference_interface, from the source _run_train takes its own from (`samples=` keyword or
+        inference_cfg['samples']; 'synthetic' = infer.py --synthetic).  Each sample: a dict with field_data [1,159,2405], forecast_h [1,1,1] and
+        `sampler`, the CollocationSampler over that sample's coarse cube."""
+        src = kwargs.get('samples', (self.inference_cfg or {}).get('samples'))
+        if src is None:
+            raise RuntimeError("run_inference_interface: no `samples` source (a sequence / callable of dicts with field_data, forecast_h and sampler, as "
+                               "keyword or as inference_cfg['samples']).  samples='synthetic' (infer.py --synthetic) evaluates random field samples -- "
+                               "noise, for smoke runs only")
+        if isinstance(src, str):
+            if src != 'synthetic':
+                raise ValueError("samples=%r: the only named source is 'synthetic'" % src)
+            from ..sampler import SyntheticSamples
+            dev = next(self.physics_net.parameters()).device
+            syn = SyntheticSamples(dev, n_margin=128, n_inter=128, leads=int(kwargs.get('samples_per_epoch', 1)), lat=self.lat_size, lon=self.lon_size)
+            print("run_inference_interface: samples='synthetic' -- random field samples (%d): the maps are noise" % len(syn))
+            return [dict(field_data=b['field_data'], forecast_h=b['forecast_h'], sampler=syn.sampler) for b in (syn[i] for i in range(len(syn)))]
+        return src() if callable(src) else src
+
+    def run_inference_interface(self, **kwargs):
+        """The reference's inference loop (:1407-1530; there it cannot run: it calls the network with one argument, :1483): load `physics_latest.pth`
+        (strictly; obs_norm_cfg and pred_t_span come from the checkpoint when it carries them, :1450-1452), then for every field sample evaluate the
+        lattice `img_size` over the training domain (x `refine`) at every `dt` seconds inside the sample's window in ONE predict_lattice call; with
+        log.write_source one `<time>_<variable>.npy` [lat, lon] per time step and exported variable goes to log.result_path (start_time only labels
+        the files).  Returns the maps [nt, 6, ny, nx] of the last sample (None without samples).  kwargs: checkpoint_path, samples, device, with_clip.
+        Plotting (log.with_vis: Basemap) is not built."""
+        import datetime
+        ic = self.inference_cfg or {}
+        device = torch.device(kwargs.get('device', ic.get('device', 'cuda:0')))
+        img_size = ic.get('img_size', (self.lat_size, self.lon_size))
+        if isinstance(img_size, (int, float)):
+            lat_size, lon_size = int(img_size), int(img_size)
+        elif isinstance(img_size, (list, tuple)) and len(img_size) == 2:
+            lat_size, lon_size = (int(v) for v in img_size)
+        else:
+            raise NotImplementedError
+        refine = int(ic.get('refine', 1))
+        dt = float(ic.get('dt', 3600))
+        checkpoint_path = kwargs.get('checkpoint_path') or ic.get('checkpoints', {}).get('checkpoints_path')
+        log = ic.get('log', {})
+        write_source, result_path = bool(log.get('write_source', False)), log.get('result_path') or ''
+        export_variable = list(log.get('export_variable', ['T']))
+        if log.get('with_vis', False):
+            print('run_inference_interface: with_vis is set, but the Basemap plots of the reference are not built here; continuing without them')
+        if not write_source:
+            print('warning: write_source is False. No result will be saved.')
+        elif not result_path:
+            raise ValueError("run_inference_interface: log.write_source needs log.result_path")
+        names = {'U': 0, 'V': 1, 'P': 2, 'T': 3, 'Q': 4, 'RIO': 5}
+        for v in export_variable:
+            if v.upper() not in names:
+                raise KeyError('export_variable %r: one of %s' % (v, sorted(names)))
+        self.physics_net.to(device)
+        self.pe.to(device)
+        state_dict, current_epoch, global_step = (None, 0, 0) if not checkpoint_path else self.load_model(checkpoint_path, prefix='physics', map_location=device)
+        if state_dict is None:
+            raise NotImplementedError(checkpoint_path)
+        print('resume from epoch %d global_step %d' % (current_epoch, global_step))
+        self.physics_net.load_state_dict(state_dict['model'], strict=True)
+        cfg_span = ic.get('pred_t_span', -1)
+        self.pred_t_span = float(self.gather_key_from_state('pred_t_span', state_dict, cfg_span if cfg_span and cfg_span > 0 else self.pred_t_span))
+        self.obs_norm_cfg = self.gather_key_from_state('obs_norm_cfg', state_dict, self.obs_norm_cfg)
+        self.physics_net.eval()
+        start = datetime.datetime.strptime(ic.get('start_time', '1970-01-01_00_00_00'), '%Y-%m-%d_%H_%M_%S')
+        if write_source:
+            os.makedirs(result_path, exist_ok=True)
+        maps = None
+        for k, smp in enumerate(self._inference_samples(kwargs)):
+            sampler = smp['sampler']
+            c = sampler.cfg
+            if (lat_size, lon_size) != (c.lat_size, c.lon_size):
+                raise ValueError('inference img_size %s is not the fine grid of the sample (%d, %d); finer output: inference_cfg["refine"]'
+                                 % ((lat_size, lon_size), c.lat_size, c.lon_size))
+            window_h = c.input_time_step * c.input_time_step_nums
+            nt = int(window_h * 3600.0 / dt + 1e-9) + 1                   # every dt inside [0, window], both ends
+            lattice = sampler.lattice(refine=refine, hours=(0.0, dt / 3600.0, nt))
+            maps = self.predict_lattice(smp['field_data'].to(device), sampler, lattice, smp['forecast_h'].to(device),
+                                        with_clip=kwargs.get('with_clip', self.with_clip))
+            if write_source:
+                import numpy as np
+                host = maps.cpu().numpy()
+                for it in range(nt):
+                    stamp = (start + datetime.timedelta(seconds=k * window_h * 3600.0 + it * dt)).strftime('%Y-%m-%d_%H_%M_%S')
+                    for v in export_variable:
+                        np.save(os.path.join(result_path, '%s_%s.npy' % (stamp, v)), host[it, names[v.upper()]])
+        return maps
 
 
 class StagedPdeStep:

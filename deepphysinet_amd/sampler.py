@@ -11,6 +11,7 @@ draws is parity-tested against `oracle/sampler_oracle.py`.
 import ctypes
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -31,12 +32,47 @@ class SamplerConfig:
     begin_lat: float = 18.0        # out_lat[0]
     dx: float = 27000.0
     dy: float = 27000.0
+    begin_lon: float = 72.0        # out_lon[0] (host side only: at_lonlat's degrees -> index units)
 
     def c_struct(self) -> L.DpnSampler:
         ratio = self.out_res_deg / self.in_res_deg
         return L.DpnSampler(self.lon_size, self.lat_size, self.in_lon_size, self.in_lat_size, self.input_time_step_nums + 1,
                             self.input_time_step * self.input_time_step_nums, ratio, ratio, float(self.input_time_step),
                             float(self.begin_lat), float(self.out_res_deg), float(self.dx), float(self.dy))
+
+
+@dataclass
+class Lattice:
+    """A regular lattice of nx * ny * nt positions in the sampler's units (fine-grid index units, hours); mirrors DpnLattice.  Point
+    g = (it * ny + iy) * nx + ix (ix fastest, it slowest) lies at (x0 + ix * xstep, y0 + iy * ystep, t0 + it * tstep).  A lattice may reach
+    outside the coarse cube: coord_data, and every field evaluated from it, is NaN there."""
+    x0: float
+    xstep: float
+    y0: float
+    ystep: float
+    t0: float
+    tstep: float
+    nx: int
+    ny: int
+    nt: int
+
+    def __post_init__(self):
+        if min(int(self.nx), int(self.ny), int(self.nt)) < 1:
+            raise ValueError('a lattice needs nx, ny, nt >= 1, got (%s, %s, %s)' % (self.nx, self.ny, self.nt))
+
+    @property
+    def n_points(self) -> int:
+        return int(self.nx) * int(self.ny) * int(self.nt)
+
+    def c_struct(self) -> L.DpnLattice:
+        return L.DpnLattice(float(self.x0), float(self.xstep), float(self.y0), float(self.ystep), float(self.t0), float(self.tstep),
+                            int(self.nx), int(self.ny), int(self.nt))
+
+    def positions(self):
+        """(x_idx, y_idx, hours): three fp64 arrays [n_points] in point order, formed as the kernel forms them (origin + index * step)."""
+        it, iy, ix = np.meshgrid(np.arange(self.nt), np.arange(self.ny), np.arange(self.nx), indexing='ij')
+        return ((self.x0 + ix * float(self.xstep)).reshape(-1), (self.y0 + iy * float(self.ystep)).reshape(-1),
+                (self.t0 + it * float(self.tstep)).reshape(-1))
 
 
 class CollocationSampler:
@@ -127,6 +163,73 @@ class CollocationSampler:
         ys = torch.arange(c.lat_size, dtype=torch.int32, device=dev).repeat(c.lon_size)
         ts = torch.full_like(xs, int(time_id))
         return self.get_margin_grid(xs, ys, ts)
+
+    # ---- given positions (inference): stations and lattices -------------------------------------------------------------------------
+    def lattice(self, refine: int = 1, hours=0, x_range=None, y_range=None) -> Lattice:
+        """A lattice over the training domain with steps of 1 / refine node: nx = (lon - 1) * refine + 1, ny alike.  x_range / y_range = (first,
+        last) in node units cut a window out of it.  hours: a tuple (t0, tstep, nt), one hour, or a sequence of equally spaced hours."""
+        r = int(refine)
+        if r < 1 or r != refine:
+            raise ValueError('refine must be a positive integer, got %r' % (refine,))
+        c = self.cfg
+
+        def axis(rng, size):
+            lo, hi = (0.0, float(size - 1)) if rng is None else (float(rng[0]), float(rng[1]))
+            if hi < lo:
+                raise ValueError('empty range %r' % (rng,))
+            return lo, int(np.floor((hi - lo) * r + 1e-9)) + 1
+        x0, nx = axis(x_range, c.lon_size)
+        y0, ny = axis(y_range, c.lat_size)
+        if isinstance(hours, tuple) and len(hours) == 3:
+            t0, tstep, nt = float(hours[0]), float(hours[1]), int(hours[2])
+        else:
+            h = np.atleast_1d(np.asarray(hours, dtype=np.float64))
+            if h.ndim != 1 or h.size == 0:
+                raise ValueError('hours: a tuple (t0, tstep, nt), one hour or a 1-d sequence of hours')
+            t0, nt = float(h[0]), int(h.size)
+            tstep = float(h[1] - h[0]) if nt > 1 else 1.0
+            if nt > 2 and not np.allclose(np.diff(h), tstep, rtol=0, atol=1e-9 * max(1.0, abs(tstep))):
+                raise ValueError('hours must be equally spaced (evaluate other sets with at_positions)')
+        return Lattice(x0, 1.0 / r, y0, 1.0 / r, t0, tstep, nx, ny, nt)
+
+    def sample_at(self, n, xr=None, yr=None, tr=None, lattice: Lattice = None, first: int = 0, out=None):
+        """dpn_sample_at: n stations (xr, yr, tr fp64 device tensors) or points first .. first + n of a lattice -> x, y, t, f [n], coord_data [n, 6];
+        out = the five buffers of an earlier call with at least n rows (a chunk loop reuses them)."""
+        dev = self.cube.device
+        if out is None:
+            out = tuple(torch.empty(n, dtype=torch.float32, device=dev) for _ in range(4)) + (torch.empty((n, 6), dtype=torch.float32, device=dev),)
+        x, y, t, f, cd = (v[:n] for v in out)
+        lat = None if lattice is None else lattice.c_struct()
+        L.check(L.load().dpn_sample_at(ctypes.byref(self._s), _ptr(self.cube), _ptr(xr), _ptr(yr), _ptr(tr), None if lat is None else ctypes.byref(lat),
+                                       int(first), int(n), _ptr(x), _ptr(y), _ptr(t), _ptr(f), _ptr(cd), _stream()), 'dpn_sample_at')
+        return x, y, t, f, cd
+
+    def at_positions(self, x_idx, y_idx, hours):
+        """-> x, y, t, coord_data, f (as get_margin_grid) at given positions: fractional fine-grid indices and fractional hours, one per station.
+        IndexError outside the fine grid or outside [0, input_time_step * input_time_step_nums] hours."""
+        c = self.cfg
+        pos = [np.ascontiguousarray(np.atleast_1d(v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)), dtype=np.float64).reshape(-1)
+               for v in (x_idx, y_idx, hours)]
+        n = pos[0].size
+        if n == 0 or any(v.size != n for v in pos):
+            raise ValueError('x_idx, y_idx and hours must have the same, non-zero length')
+        hi = (c.lon_size - 1, c.lat_size - 1, c.input_time_step * c.input_time_step_nums)
+        for v, top in zip(pos, hi):
+            if not (np.all(v >= 0.0) and np.all(v <= top)):          # (NaN fails both)
+                raise IndexError('position / hour outside the domain')
+        xr, yr, tr = (torch.from_numpy(v).to(self.cube.device) for v in pos)
+        x, y, t, f, cd = self.sample_at(n, xr, yr, tr)
+        return x, y, t, cd, f.unsqueeze(1)
+
+    def lonlat_to_index(self, lon_deg, lat_deg):
+        """Degrees -> fine-grid index units, in fp64 on the host: (lon - begin_lon) / out_res_deg, (lat - begin_lat) / out_res_deg."""
+        c = self.cfg
+        return ((np.asarray(lon_deg, dtype=np.float64) - c.begin_lon) / c.out_res_deg, (np.asarray(lat_deg, dtype=np.float64) - c.begin_lat) / c.out_res_deg)
+
+    def at_lonlat(self, lon_deg, lat_deg, hours):
+        """at_positions for stations given in degrees east / north."""
+        xi, yi = self.lonlat_to_index(lon_deg, lat_deg)
+        return self.at_positions(xi, yi, hours)
 
     def training_batch(self, field_data, forecast_h, n_margin: int = 20480, n_inter: int = 4096):
         """One sample of PhysicsDataset.__getitem__ (physics_dataset.py:501-519) as the dict InterfacePhysics.training_step takes: the

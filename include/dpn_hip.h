@@ -418,6 +418,29 @@ int dpn_sample_points_replay(const DpnSampler* s, const float* cube, const float
  * out_n[lon*lat][6] -> de-normalised maps[6][lat][lon] (inverse_norm :232-262 + the scatter loop :583-591). */
 int dpn_grid_maps(const float* out_n, int lon, int lat, const DpnPhysics* phys, int with_clip, float* maps, void* stream);
 
+/* ---------------------------------------------------------------- inference: given positions, lattices, output planes
+ * A regular lattice of nx * ny * nt positions in the sampler's units (fine-grid index units, hours).  Point g = (it * ny + iy) * nx + ix (ix fastest,
+ * it slowest) lies at (x0 + ix * xstep, y0 + iy * ystep, t0 + it * tstep), each formed in fp64 with two roundings.  Kernels build the points of a
+ * range first .. first + n themselves, so a host walks a long lattice in chunks without any index array. */
+typedef struct DpnLattice {
+    double x0, xstep, y0, ystep, t0, tstep;
+    int32_t nx, ny, nt;
+} DpnLattice;
+/* The sampler evaluated at GIVEN positions instead of drawn ones: either stations xr, yr, tr [n] (fp64; lattice = NULL, first ignored) or points
+ * first .. first + n of *lattice (xr = yr = tr = NULL).  Outputs and arithmetic are dpn_sample_points': x, y (metres), t (seconds), f,
+ * coord_data[n][6] (NaN outside the coarse cube).  -1: n <= 0, a NULL pointer, both or neither source, nx / ny / nt < 1, first + n > nx * ny * nt. */
+int dpn_sample_at(const DpnSampler* s, const float* cube, const double* xr, const double* yr, const double* tr, const DpnLattice* lattice,
+                  int64_t first, int64_t n, float* x, float* y, float* t, float* f, float* coord_data, void* stream);
+/* Normalised fields out_n[n][6] -> physical values with dpn_grid_maps' arithmetic (multiply, then add; the squared form; the clip of P, T, q, rho that
+ * lets NaN through).  Exactly one destination: rows[n][6] (stations; lattice = NULL), or maps[nt][6][ny][nx] where the n points are points
+ * first .. first + n of *lattice (stores run along ix; a chunk may begin and end anywhere in a plane). */
+int dpn_fields_out(const float* out_n, int64_t n, const DpnPhysics* phys, int with_clip, float* rows, float* maps, const DpnLattice* lattice,
+                   int64_t first, void* stream);
+/* The six signed residuals of every point, res[n][6] = lhs - rhs of (motion-u, motion-v, continuity, energy, vapour, gas), unscaled:
+ * factor_i * mean(res_i ** 2) is dpn_residual's MSE loss term.  Inputs as dpn_residual (phys->clip_on etc. apply; the criterion is not read). */
+int dpn_residual_points(const float* out_n, const float* jac_n, const float* f, int64_t n_points, const DpnGeometry* geo, const DpnPhysics* phys,
+                        float* res, void* stream);
+
 /* The same step with the optimiser state held as ONE flat fp32 buffer per moment: tensor i lives at offset (sum of ceil(numel_j / 2048)
  * over j < i) * 2048, i.e. every tensor is padded to whole 2048-element chunks; dpn_clip_adam_flat_floats gives the buffer length.
  * No per-tensor state pointers travel in the kernel arguments, so up to 160 tensors are ONE launch per pass: three launches for a
