@@ -33,6 +33,7 @@ class DpnPhysics(Structure):
                 ('sq_add', c_float * NETS), ('reduce_sum', c_int)]
 
 
+EVAL_STATS = 25        # DPN_EVAL_STATS: one segment's row of dpn_label_errors (include/dpn_hip.h)
 CRIT_MSE, CRIT_L1, CRIT_SMOOTH_L1 = 0, 1, 2          # DpnPhysics.criterion (include/dpn_hip.h)
 
 
@@ -174,6 +175,9 @@ EXPORTS = {
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dpn_fields_out': (c_int, [c_void_p, c_int64, POINTER(DpnPhysics), c_int, c_void_p, c_void_p, POINTER(DpnLattice), c_int64, c_void_p]),
     'dpn_residual_points': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(DpnGeometry), POINTER(DpnPhysics), c_void_p, c_void_p]),
+    'dpn_label_errors_blocks': (c_int64, [c_int64]),
+    'dpn_label_errors': (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(DpnPhysics), c_float, c_int, c_void_p, c_void_p]),
+    'dpn_label_errors_finish': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     'dpn_clip_adam_flat_floats': (c_int64, [c_int, c_void_p]),
     'dpn_clip_adam_flat': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
                                    c_float, c_float, c_void_p, c_void_p]),

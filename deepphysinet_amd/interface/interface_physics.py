@@ -489,6 +489,146 @@ class InterfacePhysics(nn.Module):
         return train_loss.detach(), {k: v.detach() for k, v in parts.items()}, gnorm
 
 
+    # ------------------------------------------------------------------ validation (:518-530, :629-745)
+    def variable_errors(self, out_n, labels, with_clip=False):
+        """The six per-variable errors of normalised predictions out_n [N, 6] against labels [N, 6] in physical units (:518-530: inverse_norm
+        of both sides, nn.MSELoss per variable), from ONE pass over the data (dpn_label_errors): {v: {mse, rmse, mae, bias, max_abs}} for
+        v in u, v, p, T, q, rio; `mse` is the reference's margin_<v>_loss.  with_clip applies the clip bounds of P, T, q, rho to both sides."""
+        from ..point_path import label_errors
+        from .. import validation as V
+        stats = label_errors(self.point_config(), out_n, labels, beta=0.1, with_clip=with_clip)
+        return V.metrics_from_stats(V.stats_row(stats[0], out_n.shape[0]))['variables']
+
+    def _eval_inputs(self, b, with_pde):
+        """The point tensors of eval_step from a training batch: [interior | margin] rows with the PDE losses, the margin rows alone without."""
+        flat = lambda v: v.reshape(v.shape[0], -1)
+        if not with_pde:
+            return 0, tuple(flat(b[k]) for k in ('margin_x', 'margin_y', 'margin_t', 'margin_f', 'margin_input_data'))
+        cat = lambda a_, b_: torch.cat([flat(a_), flat(b_)], dim=0)
+        return b['inter_x'].shape[0], (cat(b['inter_x'], b['margin_x']), cat(b['inter_y'], b['margin_y']), cat(b['inter_t'], b['margin_t']),
+                                       cat(b['inter_f'], b['margin_f']), cat(b['inter_data'], b['margin_input_data']))
+
+    def _validation_dict(self, losses, stats, n_margin, with_pde, forecast_h=None):
+        """One sample's result from eval_step's outputs (device tensors; nothing is synchronised here except the statistics' copy to the host)."""
+        from .. import validation as V
+        mf = self.train_cfg['losses']['loss_factor']['margin_factor']
+        # the training step's own expression (_StepLossFn.forward / data_loss): one rounding to fp32, then the factor
+        out = {'margin_loss': (stats[0] / (6.0 * n_margin)).float() * mf}
+        if with_pde:
+            out['inter_pde_loss'], out['margin_pde_loss'] = losses[0, 6].float(), losses[1, 6].float()
+            out['terms'] = losses[:, :6]
+        else:
+            out['terms'] = None
+        valid = 0
+        for k in ('margin_loss', 'inter_pde_loss', 'margin_pde_loss'):          # the order training_step adds them in
+            if k in out:
+                valid = valid + out[k]
+        out['valid_loss'] = valid
+        row = V.stats_row(stats, n_margin, {k: out[k] for k in V.LOSS_KEYS if k in out})
+        out['variables'] = V.metrics_from_stats(row)['variables']
+        out['stats'] = row
+        if forecast_h is not None:
+            out['forecast_h'] = float(forecast_h.reshape(-1)[0])
+        return out
+
+    @torch.no_grad()
+    def validation_step(self, batch: dict, with_pde=True, with_clip=False):
+        """The validation branch of the reference's loop (:629-719) on one sample -- the batch dict of training_step --: the three losses of the
+        step body without an update, and the per-variable errors of the margin predictions in physical units.  Returns a dict: valid_loss,
+        margin_loss, (with_pde) inter_pde_loss, margin_pde_loss, terms [2, 6] (interior | margin; None without with_pde) as device tensors;
+        variables {u, v, p, T, q, rio: {mse, rmse, mae, bias, max_abs}} (mse = the reference's margin_<v>_loss); stats (the fp64 row
+        validation.merge_stats pools); forecast_h.  One point pass over [interior | margin] with no saved state (point_path.eval_step); the PDE
+        residuals clip as training_step's do (self.with_clip; the loops set it before every step, :629), the per-variable errors only on request
+        (with_clip).
+        Touches no .grad, no optimiser state and not the field cache."""
+        from ..point_path import _require_gpu, eval_step
+        b = batch
+        _require_gpu(b['field_data'], 'field_data')
+        cfg = self.point_config(self.train_cfg['losses']['loss_factor'])
+        heads, evec, statics = self.physics_net.field_weights(b['field_data'], b['forecast_h'], use_cache=False)
+        n_inter, pts = self._eval_inputs(b, with_pde)
+        losses, stats = eval_step(cfg, n_inter, *pts, b['margin_data'], heads, evec, statics, beta=0.1, with_pde=with_pde, with_clip=with_clip)
+        return self._validation_dict(losses, stats, b['margin_data'].shape[0], with_pde, b['forecast_h'])
+
+    VALID_POINT_BYTES = 4 * (4 + 6 + 6 + 18) + 4 * 6      # x, y, t, f | coord_data | out_n | Jacobian of every point, + the margin labels
+
+    def lead_batch_size(self, n_points, n_samples):
+        """Samples per group of `validate`: as many as INFER_BUDGET_BYTES (256 MiB, the rule of chunk_size) hold of per-point buffers
+        (VALID_POINT_BYTES each) plus one packed weight block per sample; at least 1, at most the number of samples."""
+        import ctypes
+        sizes = L.DpnSizes()
+        L.check(L.load().dpn_sizes(int(n_points), int(self.precision), ctypes.byref(sizes)), 'dpn_sizes')
+        per = int(n_points) * self.VALID_POINT_BYTES + int(sizes.packed)
+        return max(1, min(int(n_samples), self.INFER_BUDGET_BYTES // per))
+
+    @torch.no_grad()
+    def validate(self, samples, with_pde=True, lead_batch=None, with_clip=False):
+        """validation_step over a whole validation set, `lead_batch` samples at a time: the encoder, the hyper-network heads and the weight
+        packing run once per group through the lead-batch launches (point_path.eval_step_batch), the point pass sample after sample.  Samples
+        of a group must have equal point counts (a group is cut where they change).  Returns {'samples': [validation_step's dict per sample,
+        in order], 'pooled': validation.metrics_from_stats of the merged rows (+ 'stats', the merged row)}: pooling adds sums and counts and
+        maximises maxima, it never averages RMSEs.  lead_batch None: lead_batch_size (the 256 MiB rule)."""
+        from ..point_path import _require_gpu, eval_step_batch
+        from .. import validation as V
+        samples = list(samples)
+        if not samples:
+            raise ValueError('validate: no samples')
+        cfg = self.point_config(self.train_cfg['losses']['loss_factor'])
+        dev = next(self.physics_net.parameters()).device
+        shape = lambda b: (b['inter_x'].shape[0], b['margin_x'].shape[0])
+        rows, i = [], 0
+        while i < len(samples):
+            n_i, n_m = shape(samples[i])
+            want = self.lead_batch_size((n_i if with_pde else 0) + n_m, len(samples)) if lead_batch is None else max(1, int(lead_batch))
+            j = i + 1
+            while j < len(samples) and j - i < want and shape(samples[j]) == (n_i, n_m):
+                j += 1
+            group = [{k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in b.items()} for b in samples[i:j]]
+            _require_gpu(group[0]['field_data'], 'field_data')
+            if len(group) == 1:
+                rows.append(self.validation_step(group[0], with_pde=with_pde, with_clip=with_clip))
+            else:
+                field = torch.cat([b['field_data'] for b in group], dim=0)
+                fh = torch.cat([b['forecast_h'] for b in group], dim=0)
+                B = len(group)
+                heads, evec, statics = self.physics_net.field_weights(field, fh, use_cache=False)
+                heads, evec = heads.reshape(B, 256, -1), evec.reshape(B, 6, 256)
+                parts = [self._eval_inputs(b, with_pde) for b in group]
+                pts = tuple(torch.stack([p[1][c] for p in parts], dim=0) for c in range(5))
+                labels = torch.stack([b['margin_data'] for b in group], dim=0)
+                losses, stats = eval_step_batch(cfg, parts[0][0], *pts, labels, heads, evec, statics, beta=0.1, with_pde=with_pde, with_clip=with_clip)
+                for k_, b in enumerate(group):
+                    rows.append(self._validation_dict(None if losses is None else losses[k_], stats[k_], n_m, with_pde, b['forecast_h']))
+            i = j
+        merged = V.merge_stats([r['stats'] for r in rows])
+        pooled = V.metrics_from_stats(merged)
+        pooled['stats'] = merged
+        return {'samples': rows, 'pooled': pooled}
+
+    def _valid_samples(self, kwargs):
+        """The validation source of the training loops, resolved like `samples` (_train_samples): keyword `valid_samples` or
+        train_cfg['valid_data']['samples']; a sequence, a callable valid_samples() -> sequence, or 'synthetic' (a SyntheticSamples drawn from
+        another seed than the training source's).  None configured: None -- the loop then runs without validation, as it always did."""
+        src = kwargs.get('valid_samples', (self.train_cfg.get('valid_data') or {}).get('samples'))
+        if src is None:
+            return None
+        if isinstance(src, str):
+            if src != 'synthetic':
+                raise ValueError("valid_samples=%r: the only named source is 'synthetic'" % src)
+            if getattr(self, '_synthetic_valid', None) is None:
+                from ..sampler import SyntheticSamples
+                td = self.train_cfg.get('train_data', {})
+                dev = next(self.physics_net.parameters()).device
+                # seed 1: other fields, other cubes and other collocation draws than the training source's (seed 0)
+                self._synthetic_valid = SyntheticSamples(dev, n_margin=td.get('label_batch_size', 20480), n_inter=td.get('batch_size_inter', 4096),
+                                                         leads=int(kwargs.get('valid_samples_per_epoch', kwargs.get('samples_per_epoch', 61))),
+                                                         seed=1, lat=self.lat_size, lon=self.lon_size)
+            return self._synthetic_valid
+        src = src() if callable(src) else src
+        if not (hasattr(src, '__len__') and hasattr(src, '__getitem__')):
+            src = list(src)
+        return src
+
     # ------------------------------------------------------------------ training loops (:334-846, :848-1404; step body only)
     def build_optimizer(self, **overrides):
         """Fused clip + Adam over the PhysicsNet with the config's optimiser settings (cfg:151-155; `initial_lr` as :394 sets it), its flat
@@ -629,12 +769,18 @@ class InterfacePhysics(nn.Module):
         lr_schedule = self._build_lr_schedule(optimizer, current_epoch)
         self.physics_net.train()
         last = None
+        # validation (:629-745): only with a source; without one nothing below runs and the loop is what it was
+        valid_src = self._valid_samples(kwargs)
+        vlog = self._ValidationLoop(self, valid_src, kwargs.get('log_path'), rank, world, num_epoch, device) if valid_src is not None else None
         for epoch in range(current_epoch, num_epoch):
-            for batch in self._epoch_samples(kwargs, epoch, rank, world, dist_mode):   # DistributedSampler (:936): one field sample per rank per step
+            for batch_id, batch in enumerate(self._epoch_samples(kwargs, epoch, rank, world, dist_mode)):   # DistributedSampler (:936): one field sample per rank per step
                 with_pde = with_pde_cfg and global_step >= pde_start
                 self.with_clip = True
                 global_step += 1
                 batch = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in batch.items()}
+                log_now = vlog is not None and global_step % log_step == 1
+                if log_now:              # the training batch's six errors (:518-530) from the predictions the step is about to train on
+                    train_vars = self.validation_step(batch, with_pde=False)['variables']
                 loss, parts, gnorm = self.training_step(batch, optimizer, with_pde=with_pde, grad_sync=sync)
                 last = {'loss': loss, 'parts': parts, 'grad_norm': gnorm}
                 if rank == 0 and global_step % log_step == 1:
@@ -643,6 +789,8 @@ class InterfacePhysics(nn.Module):
                 if global_step % log_step == 1:                       # (the loop synchronises here anyway: float(loss))
                     from ..encoder_ops import check_enc_status
                     check_enc_status()                                # an encoder weight outside the f16 hi+lo split's range raises HERE, named
+                if log_now:
+                    vlog.log_step_event(epoch, batch_id, global_step, batch, loss, parts, train_vars, with_pde, kwargs)
                 if max_steps is not None and global_step >= max_steps:
                     break
             if epoch % save_step == 0:
@@ -655,23 +803,102 @@ class InterfacePhysics(nn.Module):
                     self.save_model(checkpoint_path, epoch, global_step, prefix='physics', dx=self.dx, dy=self.dy, dt=self.dt,
                                     pred_x_span=self.dx * self.lon_size, pred_y_span=self.dy * self.lat_size, pred_t_span=self.pred_t_span,
                                     label_time_step=time_step, obs_norm_cfg=self.obs_norm_cfg)
+            if vlog is not None and kwargs.get('validate_every_epoch', False):
+                vlog.epoch_event(epoch, global_step, with_pde_cfg and global_step >= pde_start, kwargs)
             if max_steps is not None and global_step >= max_steps:
                 break
-        return {'epoch': epoch if num_epoch > current_epoch else current_epoch, 'global_step': global_step, 'optimizer': optimizer,
-                'lr': optimizer.param_groups[0]['lr'], 'last': last}
+        out = {'epoch': epoch if num_epoch > current_epoch else current_epoch, 'global_step': global_step, 'optimizer': optimizer,
+               'lr': optimizer.param_groups[0]['lr'], 'last': last}
+        if vlog is not None:
+            out['last_validation'], out['last_epoch_validation'] = vlog.last, vlog.last_epoch
+        return out
+
+    class _ValidationLoop:
+        """What the training loops do at a log step once a validation source is set (:596-745): the training line, one validation sample taken
+        round-robin (the reference's valid_iter, :630-634), the validation line; rank 0 writes, every rank evaluates its own shard."""
+
+        def __init__(self, model, source, log_path, rank, world, num_epoch, device):
+            import time
+            from .. import validation as V
+            self.m, self.src, self.rank, self.world, self.num_epoch, self.device = model, source, rank, world, num_epoch, device
+            self.log = V.TrainLog(log_path) if (log_path and rank == 0) else None
+            self.cursor, self.last, self.last_epoch = 0, None, None
+            self.clock, self.t0, self.step0 = time.perf_counter, time.perf_counter(), 0
+            self.hours = float((model.train_cfg.get('train_data') or {}).get('forecast_time_period', 360))
+
+        def _to_device(self, b):
+            return {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in b.items()}
+
+        def _all_ranks(self, row):
+            """The rows of all ranks merged in rank order: ONE collective on one small fp64 tensor (gathered, so that the maxima travel with it)."""
+            from .. import validation as V
+            if self.world == 1:
+                return row
+            import torch.distributed as dist
+            mine = row.to(self.device)
+            rows = [torch.empty_like(mine) for _ in range(self.world)]
+            dist.all_gather(rows, mine)
+            return V.merge_stats([r.cpu() for r in rows])
+
+        def log_step_event(self, epoch, batch_id, global_step, batch, loss, parts, train_vars, with_pde, kwargs):
+            from .. import validation as V
+            m = self.m
+            now = self.clock()
+            fps = (global_step - self.step0) * self.world / max(now - self.t0, 1e-9)          # samples per second since the last log line
+            src_train = kwargs.get('samples', m.train_cfg.get('train_data', {}).get('samples'))
+            if src_train == 'synthetic':
+                src_train = getattr(m, '_synthetic_samples', None)
+            n_batches = -(-len(src_train) // self.world) if hasattr(src_train, '__len__') else 0
+            vb = self._to_device(self.src[(self.cursor * self.world + self.rank) % len(self.src)])     # round-robin; rank r its own stride
+            self.cursor += 1
+            m.with_clip = True                                                                 # :629
+            was_training = m.physics_net.training
+            m.physics_net.eval()                                                               # :516 (no layer here depends on it)
+            res = m.validation_step(vb, with_pde=with_pde)
+            m.physics_net.train(was_training)
+            res['pooled'] = V.metrics_from_stats(self._all_ranks(res['stats']))
+            res['global_step'] = global_step
+            self.last = res
+            if self.log is not None:
+                f_train = int(round(float(batch['forecast_h'].reshape(-1)[0]) * self.hours))
+                f_valid = int(round(res['forecast_h'] * self.hours))
+                vparts = {k: res[k] for k in ('margin_loss', 'inter_pde_loss', 'margin_pde_loss') if k in res}
+                self.log.line(V.format_train_line(epoch, self.num_epoch, batch_id, n_batches, global_step, loss, parts, f_train, fps))
+                self.log.line(V.format_valid_line(epoch, self.num_epoch, batch_id, n_batches, global_step, res['valid_loss'], vparts, f_valid, fps))
+                self.log.event('training', epoch=epoch, global_step=global_step, train_loss=loss, forecast_hours=f_train, fps=fps, variables=train_vars,
+                               **parts)
+                self.log.event('validation', epoch=epoch, global_step=global_step, forecast_hours=f_valid, fps=fps,
+                               **{k: v for k, v in res.items() if k != 'global_step'})
+            self.t0, self.step0 = self.clock(), global_step
+
+        def epoch_event(self, epoch, global_step, with_pde, kwargs):
+            """validate_every_epoch: the whole source (this rank's shard of it, unshuffled), pooled over the ranks."""
+            from .. import validation as V
+            m = self.m
+            shard = list(m._shard_samples(self.src, self.rank, self.world))
+            m.with_clip = True
+            res = m.validate(shard, with_pde=with_pde, lead_batch=kwargs.get('valid_lead_batch'))
+            pooled = V.metrics_from_stats(self._all_ranks(res['pooled']['stats']))
+            self.last_epoch = {'epoch': epoch, 'global_step': global_step, 'samples': res['samples'], 'pooled': pooled}
+            if self.log is not None:
+                self.log.event('validation_epoch', epoch=epoch, global_step=global_step, pooled=pooled,
+                               samples=[{'forecast_h': r['forecast_h'], 'valid_loss': r['valid_loss'], 'variables': r['variables']} for r in res['samples']])
 
     def run_train_interface(self, **kwargs):
         """The single-GPU training loop (:334-846) reduced to what is on the path: per-step body (:443-515) = training_step, PDE losses on
         from global_step >= 2000, CosineAnnealingLR stepped and a checkpoint written once per epoch (:831-845), resume from
-        `physics_latest.pth` (:389-397).  kwargs of the reference: checkpoint_path, log_path (unused: no tensorboard / JPEG output here);
-        added: samples (see _train_samples), num_epoch, max_steps, pde_start_step, device."""
+        `physics_latest.pth` (:389-397).  kwargs of the reference: checkpoint_path, log_path (written only with a validation source: the
+        reference's two lines per log step in log_<date>.txt and metrics.jsonl; no tensorboard / JPEG output here);
+        added: samples (see _train_samples), valid_samples (see _valid_samples; none: no validation, the loop of before), validate_every_epoch,
+        valid_lead_batch, num_epoch, max_steps, pde_start_step, device.  With a validation source the result carries `last_validation`."""
         return self._run_train(False, **kwargs)
 
     def run_train_interface_dist(self, **kwargs):
         """The data-parallel loop (:848-1404): one process per GPU (start it with torchrun; torch.distributed is initialised from the
         environment, which the reference never does -- SURVEY section 0, defect 2), rank r takes every world-th sample
         (DistributedSampler, :936), gradients are averaged by distributed.GradientAllReduce on the optimiser's flat gradient buffer
-        (replaces the DistributedDataParallel wrap :903-907), rank 0 writes the checkpoints."""
+        (replaces the DistributedDataParallel wrap :903-907), rank 0 writes the checkpoints.  Validation: every rank evaluates its own samples
+        of the source, the statistics rows are gathered once (validation.merge_stats), rank 0 logs."""
         return self._run_train(True, **kwargs)
 
     # ------------------------------------------------------------------ inference loop (:1407-1530)

@@ -886,3 +886,114 @@ class _SmoothL1Fn(torch.autograd.Function):
     def backward(ctx, gl):
         (g,) = ctx.saved_tensors
         return g * gl, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------ validation: no-grad evaluation of the step's losses
+EVAL_VARIABLES = ('u', 'v', 'p', 'T', 'q', 'rio')       # the reference's names of the six outputs in its log lines (interface_physics.py:609-618)
+
+
+def _label_partials(cfg: PointConfig, out_n, labels, n, segments, beta, with_clip, partials):
+    lib = L.load()
+    ph = cfg.physics()
+    L.check(lib.dpn_label_errors(_ptr(out_n), _ptr(labels), n, segments, ctypes.byref(ph), float(beta), int(bool(with_clip)), _ptr(partials),
+                                 _stream()), 'dpn_label_errors')
+
+
+def label_errors(cfg: PointConfig, out_n, labels, beta=0.1, with_clip=False):
+    """Sufficient statistics [S, 25] (fp64) of normalised predictions out_n [S, N, 6] (or [N, 6]: S = 1) against labels of the same shape, one
+    row per segment: [0] sum SmoothL1_beta, then per variable (u, v, P, T, q, rho) sum d^2 [1:7], sum |d| [7:13], sum d [13:19], max |d| [19:25]
+    of d = inverse_norm(pred) - inverse_norm(label) (include/dpn_hip.h: dpn_label_errors).  One pass over the data, bitwise reproducible."""
+    _require_gpu(out_n, 'out_n')
+    _require_gpu(labels, 'labels')
+    o, l = _f32c(out_n), _f32c(labels)
+    if o.shape != l.shape or o.dim() not in (2, 3) or o.shape[-1] != 6 or o.numel() == 0:
+        raise ValueError('label_errors: out_n %s and labels %s must both be [N, 6] or [S, N, 6]' % (tuple(out_n.shape), tuple(labels.shape)))
+    S, n = (1, o.shape[0]) if o.dim() == 2 else (o.shape[0], o.shape[1])
+    lib = L.load()
+    partials = torch.empty((S, int(lib.dpn_label_errors_blocks(n)), L.EVAL_STATS), dtype=torch.float64, device=o.device)
+    stats = torch.empty((S, L.EVAL_STATS), dtype=torch.float64, device=o.device)
+    _label_partials(cfg, o, l, n, S, beta, with_clip, partials)
+    L.check(lib.dpn_label_errors_finish(_ptr(partials), n, S, _ptr(stats), _stream()), 'dpn_label_errors_finish')
+    return stats
+
+
+def _eval_one(cfg, ws, nets, n_inter, x_, y_, t_, f_, cd_, lab_, beta, with_pde, with_clip, losses, partials):
+    """One field sample of eval_step / eval_step_batch: the point forward without saved state, the two groups' residual sums (written to
+    `losses` [2, 7] by the finish launches), and the label statistics' block rows of the margin points (`partials`)."""
+    lib = L.load()
+    n = cd_.shape[0]
+    if not with_pde:                                       # the reference's first 2 000 steps: fields only, no Jacobian
+        out_n, _ = _forward_points(cfg, ws, nets, x_[n_inter:], y_[n_inter:], t_[n_inter:], None, cd_[n_inter:], want_jac=False, want_saved=False)
+        _label_partials(cfg, out_n, lab_, n - n_inter, 1, beta, with_clip, partials)
+        return
+    out_n, jac_n = _forward_points(cfg, ws, nets, x_, y_, t_, None, cd_, want_jac=True, want_saved=False)
+    geo, ph = cfg.geometry(), cfg.physics()
+    for gi, (a0, a1) in enumerate(((0, n_inter), (n_inter, n))):             # the launches of _StepLossFn.forward, group by group
+        sums = torch.empty(((a1 - a0 + 255) // 256) * 6, dtype=torch.float64, device=cd_.device)
+        L.check(lib.dpn_residual(_ptr(out_n[a0:]), _ptr(jac_n[a0:]), _ptr(f_[a0:]), a1 - a0, ctypes.byref(geo), ctypes.byref(ph), None, None,
+                                 _ptr(sums), None, None, _stream()), 'dpn_residual')
+        L.check(lib.dpn_residual_finish(_ptr(sums), a1 - a0, ctypes.byref(ph), _ptr(losses[gi]), _stream()), 'dpn_residual_finish')
+    _label_partials(cfg, out_n[n_inter:], lab_, n - n_inter, 1, beta, with_clip, partials)
+
+
+def _check_eval_split(what, n_inter, n, n_lab, with_pde):
+    if not ((0 < n_inter < n if with_pde else 0 <= n_inter < n) and n_lab == n - n_inter):
+        raise ValueError('%s: n_inter = %d of %d points leaves %d margin points for %d label rows; need 0 < n_inter < %d (0 allowed without the '
+                         'PDE losses) and one label row per margin point' % (what, n_inter, n, n - n_inter, n_lab, n))
+
+
+@torch.no_grad()
+def eval_step(cfg: PointConfig, n_inter, x, y, t, f, coord_data, labels, heads, evec, statics, beta=0.1, with_pde=True, with_clip=False):
+    """The losses of the step body (_StepLossFn.forward: same launches, same tiles, same fixed-order sums) evaluated with nothing kept for a
+    backward pass: no saved state, no operands / partials buffers, no autograd node.  The first n_inter rows of x, y, t, f, coord_data are the
+    interior points, the rest the margin points whose labels are `labels`.  Returns (losses [2, 7] fp32: rows interior | margin, columns the
+    six scaled PDE terms and their total -- None without with_pde, which evaluates the margin rows' fields only, no Jacobian --, stats [25]
+    fp64: label_errors of the margin rows, stats[0] / (6 n_margin) = the unscaled data loss).  The cfg's own with_clip governs the PDE
+    residuals as in training; `with_clip` here is the label statistics' alone (off in the reference, interface_physics.py:706-713)."""
+    for nm, v in (('x', x), ('coord_data', coord_data), ('heads', heads), ('labels', labels)):
+        _require_gpu(v, nm)
+    n, n_inter = coord_data.shape[0], int(n_inter)
+    _check_eval_split('eval_step', n_inter, n, labels.shape[0], with_pde)
+    lib = L.load()
+    x_, y_, t_, f_ = (_f32c(v).reshape(-1) for v in (x, y, t, f))
+    cd_, hd_, ev_, lab_ = _f32c(coord_data), _f32c(heads), _f32c(evec), _f32c(labels)
+    st = [_f32c(s) for s in statics]
+    dev = cd_.device
+    n_m = n - n_inter
+    ws = _Workspace(n if with_pde else n_m, cfg.prec, dev)
+    losses = torch.empty((2, 7), dtype=torch.float32, device=dev) if with_pde else None
+    partials = torch.empty((1, int(lib.dpn_label_errors_blocks(n_m)), L.EVAL_STATS), dtype=torch.float64, device=dev)
+    stats = torch.empty((1, L.EVAL_STATS), dtype=torch.float64, device=dev)
+    _eval_one(cfg, ws, _net_ptrs(hd_, ev_, st), n_inter, x_, y_, t_, f_, cd_, lab_, beta, with_pde, with_clip, losses, partials)
+    L.check(lib.dpn_label_errors_finish(_ptr(partials), n_m, 1, _ptr(stats), _stream()), 'dpn_label_errors_finish')
+    return losses, stats[0]
+
+
+@torch.no_grad()
+def eval_step_batch(cfg: PointConfig, n_inter, x, y, t, f, coord_data, labels, heads, evec, statics, beta=0.1, with_pde=True, with_clip=False):
+    """eval_step for B field samples (distinct field / lead time, so distinct hyper-network weights): point tensors [B, N(, 6)], labels
+    [B, N - n_inter, 6], heads [B, 256, 2700], evec [B, 6, 256], shared statics.  The B weight blocks are packed in one launch (_pack_batch); each
+    sample then takes ONE point pass over its [interior | margin] rows -- the pass of eval_step and of the training step, so that a sample's row
+    equals eval_step's bitwise (two passes, one per group, would form other 128-point tiles at the group boundary) --, and one finish launch
+    adds the label statistics of all B samples.  Returns (losses [B, 2, 7] or None, stats [B, 25])."""
+    for nm, v in (('x', x), ('coord_data', coord_data), ('heads', heads), ('labels', labels)):
+        _require_gpu(v, nm)
+    B, n, n_inter = coord_data.shape[0], coord_data.shape[1], int(n_inter)
+    _check_eval_split('eval_step_batch', n_inter, n, labels.shape[1], with_pde)
+    lib = L.load()
+    x_, y_, t_, f_ = (_f32c(v).reshape(B, n) for v in (x, y, t, f))
+    cd_, hd_, ev_, lab_ = _f32c(coord_data), _f32c(heads), _f32c(evec), _f32c(labels)
+    st = [_f32c(s) for s in statics]
+    dev = cd_.device
+    n_m = n - n_inter
+    n_fwd = n if with_pde else n_m
+    losses = torch.empty((B, 2, 7), dtype=torch.float32, device=dev) if with_pde else None
+    partials = torch.empty((B, int(lib.dpn_label_errors_blocks(n_m)), L.EVAL_STATS), dtype=torch.float64, device=dev)
+    stats = torch.empty((B, L.EVAL_STATS), dtype=torch.float64, device=dev)
+    packed = _pack_batch(cfg, hd_, ev_, st, n_fwd)
+    for b in range(B):
+        ws = _Workspace(n_fwd, cfg.prec, dev, packed=packed[b])
+        _eval_one(cfg, ws, _net_ptrs(hd_[b], ev_[b], st), n_inter, x_[b], y_[b], t_[b], f_[b], cd_[b], lab_[b], beta, with_pde, with_clip,
+                  None if losses is None else losses[b], partials[b:b + 1])
+    L.check(lib.dpn_label_errors_finish(_ptr(partials), n_m, B, _ptr(stats), _stream()), 'dpn_label_errors_finish')
+    return losses, stats

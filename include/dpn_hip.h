@@ -436,6 +436,20 @@ int dpn_sample_at(const DpnSampler* s, const float* cube, const double* xr, cons
  * first .. first + n of *lattice (stores run along ix; a chunk may begin and end anywhere in a plane). */
 int dpn_fields_out(const float* out_n, int64_t n, const DpnPhysics* phys, int with_clip, float* rows, float* maps, const DpnLattice* lattice,
                    int64_t first, void* stream);
+/* Label-side evaluation of a validation pass (interface_physics.py:518-530, :629-745): predictions out_n[S][n][6] and labels[S][n][6] (normalised,
+ * variable order u, v, P, T, q, rho) are read once; per segment s (one field sample) the DPN_EVAL_STATS sufficient statistics are
+ *   [0]        sum SmoothL1_beta(out_n - label) over all 6 n elements (the data loss of weights_loss.py:17-20 is this / (6 n)),
+ *   [1 + k]    sum d^2,   [7 + k] sum |d|,   [13 + k] sum d,   [19 + k] max |d|     with d = inverse_norm(pred)_k - inverse_norm(label)_k:
+ * both sides de-normalised in fp32 with dpn_fields_out's arithmetic (multiply, then add; the squared min_max form), subtracted and squared in
+ * fp32, added in fp64.  with_clip applies the clip bounds of P, T, q, rho to both sides (the reference evaluates these errors without it, :706-713).
+ * dpn_label_errors writes one row per block, partials[S][dpn_label_errors_blocks(n)][DPN_EVAL_STATS] (written, not accumulated; a block never
+ * straddles two segments); dpn_label_errors_finish adds the rows of every segment in a fixed order -> stats[S][DPN_EVAL_STATS].  No atomics: two
+ * runs agree bitwise.  out_n / labels: 8-byte aligned (any row of a contiguous [.., 6] fp32 tensor).  -1: NULL, n <= 0, S <= 0, beta <= 0. */
+#define DPN_EVAL_STATS 25
+int64_t dpn_label_errors_blocks(int64_t n_points);
+int dpn_label_errors(const float* out_n, const float* labels, int64_t n_points, int segments, const DpnPhysics* phys, float beta, int with_clip,
+                     double* partials, void* stream);
+int dpn_label_errors_finish(const double* partials, int64_t n_points, int segments, double* stats, void* stream);
 /* The six signed residuals of every point, res[n][6] = lhs - rhs of (motion-u, motion-v, continuity, energy, vapour, gas), unscaled:
  * factor_i * mean(res_i ** 2) is dpn_residual's MSE loss term.  Inputs as dpn_residual (phys->clip_on etc. apply; the criterion is not read). */
 int dpn_residual_points(const float* out_n, const float* jac_n, const float* f, int64_t n_points, const DpnGeometry* geo, const DpnPhysics* phys,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Launcher with the reference's three flags (reference train.py:17-19, :34-48): --config_file, --checkpoint_path, --log_path.
 
-    python train.py [--config_file cfg.py] [--checkpoint_path DIR] [--log_path DIR] [--dist] [--max_steps N] [--synthetic]
+    python train.py [--config_file cfg.py] [--checkpoint_path DIR] [--log_path DIR] [--dist] [--max_steps N] [--synthetic] [--valid_synthetic]
 
 The reference reads the config with mmcv.Config.fromfile (absent here, and moved to mmengine in the pinned mmcv: SURVEY section 0, defect
 3), builds the interface with `builder_models(**cfg['config'])` and calls `run_train_interface(checkpoint_path=..., log_path=...)`.  The
@@ -29,6 +29,9 @@ parse.add_argument('--max_steps', default=None, type=int)
 parse.add_argument('--synthetic', action='store_true', help="samples='synthetic': random field samples and on-device collocation batches "
                    '(the reference dataset is file I/O that does not exist offline); without it a config with no `samples` source fails, '
                    'as the reference does without its data files')
+parse.add_argument('--valid_synthetic', action='store_true', help="valid_samples='synthetic': a validation source of random field samples drawn from "
+                   'another seed than --synthetic; at every log step the loop then evaluates one of them and writes the training / validation lines '
+                   'to log_<date>.txt and metrics.jsonl under --log_path')
 
 
 def load_config(path):
@@ -56,6 +59,10 @@ if __name__ == '__main__':
         kwargs['max_steps'] = args.max_steps
     if args.synthetic:
         kwargs['samples'] = 'synthetic'
+    if args.valid_synthetic:
+        kwargs['valid_samples'] = 'synthetic'
     run = model.run_train_interface_dist if args.dist else model.run_train_interface
     out = run(**kwargs)
     print('done: epoch %d, global_step %d, lr %.3e' % (out['epoch'], out['global_step'], out['lr']))
+    if out.get('last_validation') is not None:
+        print('last validation: valid loss %.6g at step %d' % (float(out['last_validation']['valid_loss']), out['last_validation']['global_step']))
