@@ -257,20 +257,14 @@ class InterfacePhysics(nn.Module):
         """Full-grid evaluation of the visualisation branch (:536-591): the six fields at all lon*lat nodes, given in the
         reference's node order (x outer, y inner; e.g. CollocationSampler.full_grid), de-normalised (the reference switches
         the clip off there, :533) and scattered into maps [6, lat, lon] (u, v, P, T, q, rho) on the device."""
-        import ctypes
-        from .. import _lib as L
-        from ..point_path import point_fields, _ptr, _stream
+        from ..point_path import grid_maps, point_fields
         cfg = self.point_config()
         n = self.lon_size * self.lat_size
         if x.numel() != n:
             raise ValueError('predict_grid needs all %d x %d nodes (got %d points)' % (self.lon_size, self.lat_size, x.numel()))
         heads, evec, statics = self.physics_net.field_weights(field_data, forecast_h, use_cache=use_cache)
         out_n = point_fields(cfg, input_data, heads, evec, statics, x=x, y=y, t=t)
-        maps = torch.empty((6, self.lat_size, self.lon_size), dtype=torch.float32, device=out_n.device)
-        ph = cfg.physics()
-        L.check(L.load().dpn_grid_maps(_ptr(out_n), self.lon_size, self.lat_size, ctypes.byref(ph), int(bool(with_clip)), _ptr(maps),
-                                       _stream()), 'dpn_grid_maps')
-        return maps
+        return grid_maps(cfg, out_n, self.lon_size, self.lat_size, with_clip)
 
     # ------------------------------------------------------------------ inference at stations and on lattices
     INFER_BUDGET_BYTES = 256 << 20      # per-point buffers of one chunk of a lattice evaluation (the packed weights and the output maps come on top)
@@ -282,29 +276,26 @@ class InterfacePhysics(nn.Module):
         """Points per chunk of a lattice evaluation: a multiple of the point kernels' padding unit (dpn_sizes: 128 points), so that a chunked and an
         unchunked run form identical tiles; a given size is rounded down to it (and up to one unit), the default is what INFER_BUDGET_BYTES of
         per-point buffers hold.  A lattice that is smaller is one chunk."""
-        import ctypes
-        sizes = L.DpnSizes()
-        L.check(L.load().dpn_sizes(1, int(prec), ctypes.byref(sizes)), 'dpn_sizes')
-        unit = int(sizes.n_pad)
-        want = InterfacePhysics.INFER_BUDGET_BYTES // int(point_bytes) if chunk_points is None else int(chunk_points)
+        from ..point_path import point_sizes
+        unit = point_sizes(1, prec)[0]
+        want = InterfacePhysics._within_budget(point_bytes) if chunk_points is None else int(chunk_points)
         if want < 1:
             raise ValueError('chunk_points must be positive, got %r' % (chunk_points,))
         chunk = max(unit, want // unit * unit)
         return int(n_points) if chunk >= n_points else chunk
 
+    @staticmethod
+    def _within_budget(item_bytes):
+        """How many items of item_bytes each INFER_BUDGET_BYTES holds: the rule of chunk_size and lead_batch_size."""
+        return InterfacePhysics.INFER_BUDGET_BYTES // int(item_bytes)
+
     def _inference_weights(self, field_data, forecast_h, n_chunk):
         """encode_field, field_weights and the weight packing, once per call (the field cache is not consulted and not written)."""
-        from ..point_path import _Workspace, _f32c, _net_ptrs, _ptr, _require_gpu, _stream
-        _require_gpu(field_data, 'field_data')
+        from ..point_path import PackedField, require_gpu
+        require_gpu(field_data, 'field_data', 'inference')
         cfg = self.point_config()
         heads, evec, statics = self.physics_net.field_weights(field_data, forecast_h, use_cache=False)
-        keep = (_f32c(heads), _f32c(evec), [_f32c(s_) for s_ in statics])
-        nets = _net_ptrs(*keep)
-        ws = _Workspace(n_chunk, cfg.prec, keep[0].device)
-        lib = L.load()
-        L.check(lib.dpn_pack_weights_form(nets, cfg.prec, lib.dpn_fwd_form(cfg.prec, 0), _ptr(ws.packed), _stream()), 'dpn_pack_weights')
-        ws.prepacked = True
-        return cfg, ws, nets, keep
+        return PackedField(cfg, heads, evec, statics, n_chunk)
 
     def _station_inputs(self, sampler, x_idx, y_idx, hours, lonlat):
         x, y, t, cd, f = (sampler.at_lonlat if lonlat else sampler.at_positions)(x_idx, y_idx, hours)
@@ -314,15 +305,9 @@ class InterfacePhysics(nn.Module):
     def predict_points(self, field_data, sampler, x_idx, y_idx, hours, forecast_h, with_clip=False, lonlat=False):
         """The six physical fields [N, 6] (u, v, P, T, q, rho) at N stations: positions in fine-grid index units (lonlat: degrees east / north)
         and hours, all fractional (CollocationSampler.at_positions / at_lonlat interpolate the coarse cube there)."""
-        import ctypes
-        from ..point_path import _forward_points, _ptr, _stream
         x, y, t, cd, _ = self._station_inputs(sampler, x_idx, y_idx, hours, lonlat)
-        n = x.shape[0]
-        cfg, ws, nets, keep = self._inference_weights(field_data, forecast_h, n)
-        out_n, _ = _forward_points(cfg, ws, nets, x, y, t, None, cd, want_jac=False, want_saved=False)
-        rows = torch.empty((n, 6), dtype=torch.float32, device=out_n.device)
-        ph = cfg.physics()
-        L.check(L.load().dpn_fields_out(_ptr(out_n), n, ctypes.byref(ph), int(bool(with_clip)), _ptr(rows), None, None, 0, _stream()), 'dpn_fields_out')
+        rows = torch.empty((x.shape[0], 6), dtype=torch.float32, device=x.device)
+        self._inference_weights(field_data, forecast_h, x.shape[0]).fields(x, y, t, cd, with_clip, rows=rows)
         return rows
 
     def _lattice_chunks(self, sampler, lattice, chunk):
@@ -339,16 +324,11 @@ class InterfacePhysics(nn.Module):
         """The six physical fields on a lattice (CollocationSampler.lattice) as maps [nt, 6, ny, nx].  The encoder, the hyper-network heads and the
         weight packing run once; the lattice is then walked in chunks (chunk_size) of dpn_sample_at -> fields-only forward -> dpn_fields_out, every
         chunk writing its places of the one preallocated output.  NaN where the lattice leaves the coarse cube."""
-        import ctypes
-        from ..point_path import _forward_points, _ptr, _stream
         chunk = self.chunk_size(lattice.n_points, chunk_points, self.FIELD_POINT_BYTES, self.precision)
-        cfg, ws, nets, keep = self._inference_weights(field_data, forecast_h, chunk)
+        field = self._inference_weights(field_data, forecast_h, chunk)
         maps = torch.empty((lattice.nt, 6, lattice.ny, lattice.nx), dtype=torch.float32, device=field_data.device)
-        ph, lat, lib = cfg.physics(), lattice.c_struct(), L.load()
         for first, n, x, y, t, _, cd in self._lattice_chunks(sampler, lattice, chunk):
-            out_n, _ = _forward_points(cfg, ws, nets, x, y, t, None, cd, want_jac=False, want_saved=False)
-            L.check(lib.dpn_fields_out(_ptr(out_n), n, ctypes.byref(ph), int(bool(with_clip)), None, _ptr(maps), ctypes.byref(lat), first, _stream()),
-                    'dpn_fields_out')
+            field.fields(x, y, t, cd, with_clip, maps=maps, lattice=lattice, first=first)
         return maps
 
     def _residual_factors(self, residual_factors, device):
@@ -357,15 +337,6 @@ class InterfacePhysics(nn.Module):
         lf = self.train_cfg['losses']['loss_factor'] if residual_factors is True else residual_factors
         return torch.tensor([float(lf[k]) for k in LOSS_ORDER], dtype=torch.float64).float().to(device)
 
-    def _residual_rows(self, cfg, ws, nets, x, y, t, f, cd, res):
-        import ctypes
-        from ..point_path import _forward_points, _ptr, _stream
-        n = x.shape[0]
-        out_n, jac_n = _forward_points(cfg, ws, nets, x, y, t, None, cd, want_jac=True, want_saved=False)       # the Jacobian with no saved state
-        geo, ph = cfg.geometry(), cfg.physics()
-        L.check(L.load().dpn_residual_points(_ptr(out_n), _ptr(jac_n), _ptr(f), n, ctypes.byref(geo), ctypes.byref(ph), _ptr(res), _stream()),
-                'dpn_residual_points')
-
     @torch.no_grad()
     def residuals_at(self, field_data, sampler, x_idx, y_idx, hours, forecast_h, lonlat=False, residual_factors=False):
         """Where the network's output violates its equations: the six signed residuals lhs - rhs [N, 6] (motion-u, motion-v, continuity, energy,
@@ -373,9 +344,9 @@ class InterfacePhysics(nn.Module):
         MSE loss term of the same points.  residual_factors: True multiplies column i by the configuration's loss factor, a dict by its own."""
         x, y, t, cd, f = self._station_inputs(sampler, x_idx, y_idx, hours, lonlat)
         n = x.shape[0]
-        cfg, ws, nets, keep = self._inference_weights(field_data, forecast_h, n)
+        field = self._inference_weights(field_data, forecast_h, n)
         res = torch.empty((n, 6), dtype=torch.float32, device=x.device)
-        self._residual_rows(cfg, ws, nets, x, y, t, f, cd, res)
+        field.residuals(x, y, t, f, cd, res)
         fac = self._residual_factors(residual_factors, res.device)
         return res if fac is None else res * fac
 
@@ -383,10 +354,10 @@ class InterfacePhysics(nn.Module):
     def residual_lattice(self, field_data, sampler, lattice, forecast_h, residual_factors=False, chunk_points=None):
         """residuals_at on a lattice, as maps [nt, 6, ny, nx]; chunked as predict_lattice is."""
         chunk = self.chunk_size(lattice.n_points, chunk_points, self.RESIDUAL_POINT_BYTES, self.precision)
-        cfg, ws, nets, keep = self._inference_weights(field_data, forecast_h, chunk)
+        field = self._inference_weights(field_data, forecast_h, chunk)
         rows = torch.empty((lattice.n_points, 6), dtype=torch.float32, device=field_data.device)
         for first, n, x, y, t, f, cd in self._lattice_chunks(sampler, lattice, chunk):
-            self._residual_rows(cfg, ws, nets, x, y, t, f, cd, rows[first:first + n])
+            field.residuals(x, y, t, f, cd, rows[first:first + n])
         fac = self._residual_factors(residual_factors, rows.device)
         if fac is not None:
             rows *= fac
@@ -408,11 +379,9 @@ class InterfacePhysics(nn.Module):
             cfg = self.point_config(lf)
             meta_out = self.physics_net.encode_field(b['field_data'], b['forecast_h'], keep_embedding=grad_sync is not None)
             heads, evec, statics = self.physics_net.field_weights(b['field_data'], b['forecast_h'], meta_out=meta_out)
-            cat = lambda a_, b_: torch.cat([a_.reshape(a_.shape[0], -1), b_.reshape(b_.shape[0], -1)], dim=0)
-            _, inter_total, _, margin_total, data = step_losses(
-                cfg, b['inter_x'].shape[0], cat(b['inter_x'], b['margin_x']), cat(b['inter_y'], b['margin_y']), cat(b['inter_t'], b['margin_t']),
-                cat(b['inter_f'], b['margin_f']), cat(b['inter_data'], b['margin_input_data']), b['margin_data'], heads, evec, statics,
-                beta=0.1, margin_factor=lf['margin_factor'])
+            n_inter, pts = self._eval_inputs(b, True)
+            _, inter_total, _, margin_total, data = step_losses(cfg, n_inter, *pts, b['margin_data'], heads, evec, statics, beta=0.1,
+                                                                margin_factor=lf['margin_factor'])
             parts = {'margin_loss': data, 'inter_pde_loss': inter_total.float(), 'margin_pde_loss': margin_total.float()}
         else:
             loss = self.data_loss(b['margin_x'], b['margin_y'], b['margin_t'], b['field_data'], b['margin_input_data'], b['margin_data'],
@@ -500,7 +469,8 @@ class InterfacePhysics(nn.Module):
         return V.metrics_from_stats(V.stats_row(stats[0], out_n.shape[0]))['variables']
 
     def _eval_inputs(self, b, with_pde):
-        """The point tensors of eval_step from a training batch: [interior | margin] rows with the PDE losses, the margin rows alone without."""
+        """(n_inter, (x, y, t, f, coord_data)) of the step body from a training batch (training_step, eval_step): [interior | margin] rows with
+        the PDE losses, the margin rows alone without."""
         flat = lambda v: v.reshape(v.shape[0], -1)
         if not with_pde:
             return 0, tuple(flat(b[k]) for k in ('margin_x', 'margin_y', 'margin_t', 'margin_f', 'margin_input_data'))
@@ -541,9 +511,9 @@ class InterfacePhysics(nn.Module):
         residuals clip as training_step's do (self.with_clip; the loops set it before every step, :629), the per-variable errors only on request
         (with_clip).
         Touches no .grad, no optimiser state and not the field cache."""
-        from ..point_path import _require_gpu, eval_step
+        from ..point_path import eval_step, require_gpu
         b = batch
-        _require_gpu(b['field_data'], 'field_data')
+        require_gpu(b['field_data'], 'field_data', 'validation_step')
         cfg = self.point_config(self.train_cfg['losses']['loss_factor'])
         heads, evec, statics = self.physics_net.field_weights(b['field_data'], b['forecast_h'], use_cache=False)
         n_inter, pts = self._eval_inputs(b, with_pde)
@@ -555,11 +525,9 @@ class InterfacePhysics(nn.Module):
     def lead_batch_size(self, n_points, n_samples):
         """Samples per group of `validate`: as many as INFER_BUDGET_BYTES (256 MiB, the rule of chunk_size) hold of per-point buffers
         (VALID_POINT_BYTES each) plus one packed weight block per sample; at least 1, at most the number of samples."""
-        import ctypes
-        sizes = L.DpnSizes()
-        L.check(L.load().dpn_sizes(int(n_points), int(self.precision), ctypes.byref(sizes)), 'dpn_sizes')
-        per = int(n_points) * self.VALID_POINT_BYTES + int(sizes.packed)
-        return max(1, min(int(n_samples), self.INFER_BUDGET_BYTES // per))
+        from ..point_path import point_sizes
+        per = int(n_points) * self.VALID_POINT_BYTES + point_sizes(n_points, self.precision)[1]
+        return max(1, min(int(n_samples), self._within_budget(per)))
 
     @torch.no_grad()
     def validate(self, samples, with_pde=True, lead_batch=None, with_clip=False):
@@ -568,7 +536,7 @@ class InterfacePhysics(nn.Module):
         of a group must have equal point counts (a group is cut where they change).  Returns {'samples': [validation_step's dict per sample,
         in order], 'pooled': validation.metrics_from_stats of the merged rows (+ 'stats', the merged row)}: pooling adds sums and counts and
         maximises maxima, it never averages RMSEs.  lead_batch None: lead_batch_size (the 256 MiB rule)."""
-        from ..point_path import _require_gpu, eval_step_batch
+        from ..point_path import eval_step_batch, require_gpu
         from .. import validation as V
         samples = list(samples)
         if not samples:
@@ -584,7 +552,7 @@ class InterfacePhysics(nn.Module):
             while j < len(samples) and j - i < want and shape(samples[j]) == (n_i, n_m):
                 j += 1
             group = [{k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in b.items()} for b in samples[i:j]]
-            _require_gpu(group[0]['field_data'], 'field_data')
+            require_gpu(group[0]['field_data'], 'field_data', 'validate')
             if len(group) == 1:
                 rows.append(self.validation_step(group[0], with_pde=with_pde, with_clip=with_clip))
             else:

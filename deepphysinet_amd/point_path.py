@@ -12,6 +12,7 @@ points happens in libdpn_hip.so (deepphysinet_amd/csrc/dpn_kernels.hip).  There 
 import ctypes
 import os
 from dataclasses import dataclass, field
+from collections import namedtuple
 from typing import Optional, Sequence
 
 import torch
@@ -79,9 +80,9 @@ def _freqs(device):
     return _freq_cache[key]
 
 
-def _require_gpu(t: torch.Tensor, name: str):
+def require_gpu(t: torch.Tensor, name: str, what: str = 'point path'):
     if not t.is_cuda:
-        raise RuntimeError('deepphysinet_amd point path needs HIP device tensors (%s is on %s); there is no CPU fallback' % (name, t.device))
+        raise RuntimeError('deepphysinet_amd %s needs HIP device tensors (%s is on %s); there is no CPU fallback' % (what, name, t.device))
 
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
@@ -141,13 +142,40 @@ class _Workspace:
         self.sizes = L.DpnSizes()
         L.check(lib.dpn_sizes(n, prec, ctypes.byref(self.sizes)), 'dpn_sizes')
         self.n, self.prec, self.device = n, prec, device
-        # packed: this field's block of a batch packed in ONE launch (_pack_batch); the forward call then has no packing launch of its own
+        # packed: this field's block of a batch packed in ONE launch (_FieldBatch); the forward call then has no packing launch of its own
         self.prepacked = packed is not None
         self.packed = packed if packed is not None else torch.empty(self.sizes.packed, dtype=torch.uint8, device=device)
         self.saved = None
 
     def alloc_saved(self):
         self.saved = torch.empty(self.sizes.saved, dtype=torch.uint8, device=self.device)
+
+
+class _Operands(namedtuple('_Operands', 'x y t f pe cd hd ev lab st')):
+    """fp32 contiguous device copies of an entry point's x, y, t, f, pe_in, coord_data, heads, evec, labels and statics (_operands)."""
+
+    def nets(self, b=None):
+        """Pointer table of the field, or of field b of a batch."""
+        return _net_ptrs(self.hd, self.ev, self.st) if b is None else _net_ptrs(self.hd[b], self.ev[b], self.st)
+
+
+def _operands(what, x, y, t, f, coord_data, heads, evec, statics, pe_in=None, labels=None, batch=False, split=None):
+    """The GPU check and the fp32 copies of entry point `what`, before any launch: a host tensor among x, coord_data, heads, labels raises
+    (RuntimeError, in that order), then a bad [interior | margin] split = (n_inter, with_pde) (ValueError: every launch takes its row counts
+    from it; n_inter = 0 only without the PDE losses).  x, y, t, f come back flat: [N] for one field, [B, N] for a batch (coord_data [B, N, 6],
+    heads [B, 256, 2700], evec [B, 6, 256], labels [B, N - n_inter, 6]); absent tensors stay None."""
+    for nm, v in (('x', x), ('coord_data', coord_data), ('heads', heads), ('labels', labels)):
+        if v is not None:
+            require_gpu(v, nm, what)
+    if split is not None:
+        (n_inter, with_pde), n, n_lab = split, coord_data.shape[int(batch)], labels.shape[int(batch)]
+        if not ((0 < n_inter < n if with_pde else 0 <= n_inter < n) and n_lab == n - n_inter):
+            raise ValueError('%s: n_inter = %d of %d points leaves %d margin points for %d label rows; need %s n_inter < %d and one label row '
+                             'per margin point' % (what, n_inter, n, n - n_inter, n_lab, '0 <' if with_pde else '0 <=', n))
+    shape = tuple(coord_data.shape[:2]) if batch else (-1,)
+    x_, y_, t_, f_ = (None if v is None else _f32c(v).reshape(shape) for v in (x, y, t, f))
+    pe_, cd_, hd_, ev_, lab_ = (None if v is None else _f32c(v) for v in (pe_in, coord_data, heads, evec, labels))
+    return _Operands(x_, y_, t_, f_, pe_, cd_, hd_, ev_, lab_, [_f32c(s) for s in statics])
 
 
 class KernelClock:
@@ -308,7 +336,7 @@ def _backward_points(cfg: PointConfig, ws: _Workspace, nets, x, y, t, pe_in, coo
 
 
 def _stamp(tensors):
-    """Version counters of the tensors a backward pass will read again through raw pointers (the point path keeps them in ctx.keep, not in
+    """Version counters of the tensors a backward pass will read again through raw pointers (the point path keeps them in ctx.ops, not in
     save_for_backward: most are detached fp32 views).  _check_stamp raises when one was modified in place between forward and backward
     (e.g. an optimiser step before a delayed backward), which autograd's own check would catch for saved tensors."""
     from . import grad_arena
@@ -358,27 +386,22 @@ class _PointFieldsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cfg, x, y, t, pe_in, coord_data, heads, evec, *statics):
-        for nm, v in (('coord_data', coord_data), ('heads', heads)):
-            _require_gpu(v, nm)
-        tens = [None if v is None else _f32c(v) for v in (x, y, t, pe_in, coord_data, heads, evec)]
-        x_, y_, t_, pe_, cd_, hd_, ev_ = tens
-        st = [_f32c(s) for s in statics]
+        ops = _operands('point_fields', x, y, t, None, coord_data, heads, evec, statics, pe_in=pe_in)
         need_grad = any(v.requires_grad for v in (heads, evec) + tuple(statics)) and int(getattr(cfg, 'n_nets', 6) or 6) == 6
         want_gpe = pe_in is not None and pe_in.requires_grad        # (n_nets < 6: the caller has established that nothing is differentiated)
-        ws = _Workspace(cd_.shape[0], cfg.prec, cd_.device)
-        nets = _net_ptrs(hd_, ev_, st)
+        ws = _Workspace(ops.cd.shape[0], cfg.prec, ops.cd.device)
         ref6 = getattr(cfg, 'ref6', None)                 # VariableNet.forward's own ref_data (a constant: no gradient flows to it here)
-        out_n, gpe = _forward_points(cfg, ws, nets, x_, y_, t_, pe_, cd_, want_jac=want_gpe, want_saved=need_grad,
+        out_n, gpe = _forward_points(cfg, ws, ops.nets(), ops.x, ops.y, ops.t, ops.pe, ops.cd, want_jac=want_gpe, want_saved=need_grad,
                                      ref6=None if ref6 is None else _f32c(ref6.detach()))
-        ctx.cfg, ctx.ws, ctx.gpe = cfg, ws, gpe
-        ctx.keep = (x_, y_, t_, pe_, cd_, hd_, ev_, st)
+        ctx.cfg, ctx.ws, ctx.gpe, ctx.ops = cfg, ws, gpe, ops
         ctx.stamp = _stamp((heads, evec) + tuple(statics))
         return out_n
 
     @staticmethod
     def backward(ctx, g_out):
         _check_stamp(ctx.stamp, 'point_fields')
-        x_, y_, t_, pe_, cd_, hd_, ev_, st = ctx.keep
+        ops = ctx.ops
+        st = ops.st
         g = _f32c(g_out)
         g_pe = None
         if ctx.needs_input_grad[4] and ctx.gpe is not None:
@@ -388,8 +411,8 @@ class _PointFieldsFn(torch.autograd.Function):
                 g_pe = _NoSecondOrder.apply(g_pe.requires_grad_(True))      # derivative must fail loudly, not drop its parameter part
         if not any(ctx.needs_input_grad[6:]):
             return (None, None, None, None, g_pe) + (None,) * (3 + len(st))
-        nets = _net_ptrs(hd_, ev_, st)
-        ghd, gev, gst = _backward_points(ctx.cfg, ctx.ws, nets, x_, y_, t_, pe_, cd_, g, None, st, fork=True, keep=(hd_, ev_))
+        ghd, gev, gst = _backward_points(ctx.cfg, ctx.ws, ops.nets(), ops.x, ops.y, ops.t, ops.pe, ops.cd, g, None, st, fork=True,
+                                         keep=(ops.hd, ops.ev))
         return (None, None, None, None, g_pe, None, ghd, gev, *gst)
 
 
@@ -401,16 +424,11 @@ class _PointDerivsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cfg, x, y, t, coord_data, heads, evec, *statics):
-        for nm, v in (('x', x), ('coord_data', coord_data), ('heads', heads)):
-            _require_gpu(v, nm)
-        x_, y_, t_ = (_f32c(v).reshape(-1) for v in (x, y, t))
-        cd_, hd_, ev_ = _f32c(coord_data), _f32c(heads), _f32c(evec)
-        st = [_f32c(s) for s in statics]
+        ops = _operands('point_fields_xyt', x, y, t, None, coord_data, heads, evec, statics)
         need_grad = any(v.requires_grad for v in (heads, evec) + tuple(statics))
-        ws = _Workspace(cd_.shape[0], cfg.prec, cd_.device)
-        out_n, jac_n, hess_n, d3_n = _forward_derivs(cfg, ws, _net_ptrs(hd_, ev_, st), x_, y_, t_, cd_, want_saved=need_grad)
-        ctx.cfg, ctx.ws = cfg, ws
-        ctx.keep = (x_, y_, t_, cd_, hd_, ev_, st)
+        ws = _Workspace(ops.cd.shape[0], cfg.prec, ops.cd.device)
+        out_n, jac_n, hess_n, d3_n = _forward_derivs(cfg, ws, ops.nets(), ops.x, ops.y, ops.t, ops.cd, want_saved=need_grad)
+        ctx.cfg, ctx.ws, ctx.ops = cfg, ws, ops
         ctx.stamp = _stamp((heads, evec) + tuple(statics))
         ctx.set_materialize_grads(False)
         return out_n, jac_n, hess_n, d3_n
@@ -419,20 +437,20 @@ class _PointDerivsFn(torch.autograd.Function):
     def backward(ctx, g_out, g_jac, g_hess, g_d3):
         if g_d3 is not None:
             raise RuntimeError(_ORDER_LIMIT)
-        x_, y_, t_, cd_, hd_, ev_, st = ctx.keep
+        ops = ctx.ops
         if not any(ctx.needs_input_grad[5:]) or (g_out is None and g_jac is None and g_hess is None):
-            return (None,) * (7 + len(st))
+            return (None,) * (7 + len(ops.st))
         _check_stamp(ctx.stamp, 'point_fields_xyt')
         cfg = ctx.cfg
-        n, dev = cd_.shape[0], cd_.device
+        n, dev = ops.cd.shape[0], ops.cd.device
         g = torch.zeros((n, 6), dtype=torch.float32, device=dev) if g_out is None else _f32c(g_out)
         # the kernels take the derivative cotangents along the NORMALISED coordinates xi = x / dx / (lon - 1), y / dy / (lat - 1), t / span:
         # d J / d J_xi = 1 / (dx (lon - 1)) per coordinate, squared for the second derivatives
         s1 = _xi_scale(cfg, dev)
         g_jxi = None if g_jac is None else (_f32c(g_jac) * s1).contiguous()
         g_hxi = None if g_hess is None else (_f32c(g_hess) * (s1 * s1)).contiguous()
-        ghd, gev, gst = _backward_points(cfg, ctx.ws, _net_ptrs(hd_, ev_, st), x_, y_, t_, None, cd_, g, g_jxi, st, fork=True, keep=(hd_, ev_),
-                                         g_hxi=g_hxi)
+        ghd, gev, gst = _backward_points(cfg, ctx.ws, ops.nets(), ops.x, ops.y, ops.t, None, ops.cd, g, g_jxi, ops.st, fork=True,
+                                         keep=(ops.hd, ops.ev), g_hxi=g_hxi)
         return (None,) * 5 + (ghd, gev, *gst)
 
 
@@ -504,83 +522,126 @@ def point_fields_xyt(cfg: PointConfig, x, y, t, coord_data, heads, evec, statics
     return _AttachFn.apply(out, x, y, t, (jac,))
 
 
+def _residual_losses(cfg, out_n, jac_n, f_, groups, losses, unit=None, sums=None):
+    """The residual-loss sums of row groups (a0, a1) of out_n [n, 6], jac_n [n, 6, 3], f_ [n]: per group one dpn_residual launch into per-block
+    rows and one dpn_residual_finish into its `losses` row [7] (the six scaled terms, their total).  unit = (scale, g_out, g_jxi): the same pass
+    over the points also writes d total / d (out, Jacobian) for the cotangent `scale` (a device 1.0) of the total.  sums: the block rows of one
+    group given by the caller; losses None leaves them to a later finish launch (_residual_finish, or dpn_residual_finish_batch for a batch)."""
+    lib = L.load()
+    geo, ph = cfg.geometry(), cfg.physics()
+    for gi, (a0, a1) in enumerate(groups):
+        m = a1 - a0
+        s_ = torch.empty(((m + 255) // 256) * 6, dtype=torch.float64, device=out_n.device) if sums is None else sums
+        sc, g_out, g_jxi = (None, None, None) if unit is None else (unit[0], unit[1][a0:], unit[2][a0:])
+        L.check(lib.dpn_residual(_ptr(out_n[a0:]), _ptr(jac_n[a0:]), _ptr(f_[a0:]), m, ctypes.byref(geo), ctypes.byref(ph), None, _ptr(sc),
+                                 _ptr(s_), _ptr(g_out), _ptr(g_jxi), _stream()), 'dpn_residual')
+        if losses is not None:
+            _residual_finish(cfg, s_, m, losses[gi])
+
+
+def _residual_finish(cfg, sums, n, losses):
+    ph = cfg.physics()
+    L.check(L.load().dpn_residual_finish(_ptr(sums), n, ctypes.byref(ph), _ptr(losses), _stream()), 'dpn_residual_finish')
+
+
+def _residual_cotangent(cfg, out_n, jac_n, f_, groups, g_out=None, g_jxi=None):
+    """d loss / d (out, Jacobian) of the residual losses (dpn_residual in gradient mode) into g_out [n, 6], g_jxi [n, 6, 3] (allocated when not
+    given), group by group: groups = [(a0, a1, cotangent of the terms [6] or None, cotangent of the total [1] or None)]; a group with neither
+    takes a zero cotangent on its terms (its rows are written all the same).  Returns (g_out, g_jxi)."""
+    lib = L.load()
+    n, dev = out_n.shape[0], out_n.device
+    g_out = torch.empty((n, 6), dtype=torch.float32, device=dev) if g_out is None else g_out
+    g_jxi = torch.empty((n, 6, 3), dtype=torch.float32, device=dev) if g_jxi is None else g_jxi
+    geo, ph = cfg.geometry(), cfg.physics()
+    zero6 = None
+    for a0, a1, gl, gt in groups:
+        if gl is None and gt is None:
+            zero6 = torch.zeros(6, dtype=torch.float32, device=dev) if zero6 is None else zero6
+            gl = zero6
+        L.check(lib.dpn_residual(_ptr(out_n[a0:]), _ptr(jac_n[a0:]), _ptr(f_[a0:]), a1 - a0, ctypes.byref(geo), ctypes.byref(ph),
+                                 None if gl is None else _ptr(_f32c(gl)), None if gt is None else _ptr(_f32c(gt).reshape(1)), None,
+                                 _ptr(g_out[a0:]), _ptr(g_jxi[a0:]), _stream()), 'dpn_residual(grad)')
+    return g_out, g_jxi
+
+
 class _PdeLossFn(torch.autograd.Function):
     """losses [6] = (motion_u, motion_v, continuous, energy, vapor, gas), each already scaled by its factor."""
 
     @staticmethod
     def forward(ctx, cfg, x, y, t, f, coord_data, heads, evec, *statics):
-        for nm, v in (('x', x), ('coord_data', coord_data), ('heads', heads)):
-            _require_gpu(v, nm)
-        lib = L.load()
-        x_, y_, t_, f_, cd_, hd_, ev_ = [_f32c(v).reshape(-1) if i < 4 else _f32c(v) for i, v in
-                                         enumerate((x, y, t, f, coord_data, heads, evec))]
-        st = [_f32c(s) for s in statics]
-        n = cd_.shape[0]
-        dev = cd_.device
+        ops = _operands('pde_losses', x, y, t, f, coord_data, heads, evec, statics)
+        n, dev = ops.cd.shape[0], ops.cd.device
         need_grad = any(v.requires_grad for v in (heads, evec) + tuple(statics))
         ws = _Workspace(n, cfg.prec, dev)
-        nets = _net_ptrs(hd_, ev_, st)
-        out_n, jac_n = _forward_points(cfg, ws, nets, x_, y_, t_, None, cd_, want_jac=True, want_saved=need_grad)
-        sums = torch.empty(((n + 255) // 256) * 6, dtype=torch.float64, device=dev)      # per-block rows, reduced by dpn_residual_finish
-        losses7 = torch.empty(7, dtype=torch.float32, device=dev)
-        geo, ph = cfg.geometry(), cfg.physics()
+        out_n, jac_n = _forward_points(cfg, ws, ops.nets(), ops.x, ops.y, ops.t, None, ops.cd, want_jac=True, want_saved=need_grad)
+        losses = torch.empty((1, 7), dtype=torch.float32, device=dev)
         # With gradients wanted, the SAME pass over the points also writes d total / d (out, Jacobian) for a unit cotangent of the total (the usual
         # backward: loss.backward(seed) on the sum of the six terms): the backward pass then has no residual launch of its own, stage 1 multiplies
         # the cotangent that arrives into the streams as it reads them (dpn_bwd_points_scaled).  A cotangent on the individual terms takes the
         # separate pass, as before.
         ctx.unit = None
         if need_grad:
-            g_out = torch.empty((n, 6), dtype=torch.float32, device=dev)
-            g_jxi = torch.empty((n, 6, 3), dtype=torch.float32, device=dev)
-            ctx.unit = (g_out, g_jxi)
-        L.check(lib.dpn_residual(_ptr(out_n), _ptr(jac_n), _ptr(f_), n, ctypes.byref(geo), ctypes.byref(ph), None, _ptr(_one(dev)) if need_grad else None,
-                                 _ptr(sums), _ptr(g_out) if need_grad else None, _ptr(g_jxi) if need_grad else None, _stream()), 'dpn_residual')
-        L.check(lib.dpn_residual_finish(_ptr(sums), n, ctypes.byref(ph), _ptr(losses7), _stream()), 'dpn_residual_finish')
-        ctx.cfg, ctx.ws = cfg, ws
-        ctx.keep = (x_, y_, t_, f_, cd_, hd_, ev_, st, out_n, jac_n)
+            ctx.unit = (torch.empty((n, 6), dtype=torch.float32, device=dev), torch.empty((n, 6, 3), dtype=torch.float32, device=dev))
+        _residual_losses(cfg, out_n, jac_n, ops.f, ((0, n),), losses, unit=None if ctx.unit is None else (_one(dev),) + ctx.unit)
+        ctx.cfg, ctx.ws, ctx.ops, ctx.fields = cfg, ws, ops, (out_n, jac_n)
         ctx.stamp = _stamp((heads, evec) + tuple(statics))
         ctx.set_materialize_grads(False)
-        return losses7[:6], losses7[6]
+        return losses[0, :6], losses[0, 6]
 
     @staticmethod
     def backward(ctx, g_losses, g_total):
-        lib = L.load()
-        cfg = ctx.cfg
+        cfg, ops = ctx.cfg, ctx.ops
         _check_stamp(ctx.stamp, 'pde_losses')
-        x_, y_, t_, f_, cd_, hd_, ev_, st, out_n, jac_n = ctx.keep
-        n = cd_.shape[0]
-        dev = cd_.device
         gl = None if g_losses is None else _f32c(g_losses)
         gt = None if g_total is None else _f32c(g_total).reshape(1)
         if gl is None and gt is None:
-            return (None,) * (8 + len(st))
-        nets = _net_ptrs(hd_, ev_, st)
+            return (None,) * (8 + len(ops.st))
         if gl is None and ctx.unit is not None:                  # cotangent on the total only: the unit-cotangent streams of the forward pass, scaled on load
             g_out, g_jxi = ctx.unit
-            ghd, gev, gst = _backward_points(cfg, ctx.ws, nets, x_, y_, t_, None, cd_, g_out, g_jxi, st, fork=True, keep=(hd_, ev_), g_scale=gt)
+            ghd, gev, gst = _backward_points(cfg, ctx.ws, ops.nets(), ops.x, ops.y, ops.t, None, ops.cd, g_out, g_jxi, ops.st, fork=True,
+                                             keep=(ops.hd, ops.ev), g_scale=gt)
             return (None, None, None, None, None, None, ghd, gev, *gst)
-        g_out = torch.empty((n, 6), dtype=torch.float32, device=dev)
-        g_jxi = torch.empty((n, 6, 3), dtype=torch.float32, device=dev)
-        geo, ph = cfg.geometry(), cfg.physics()
-        L.check(lib.dpn_residual(_ptr(out_n), _ptr(jac_n), _ptr(f_), n, ctypes.byref(geo), ctypes.byref(ph), _ptr(gl), _ptr(gt), None,
-                                 _ptr(g_out), _ptr(g_jxi), _stream()), 'dpn_residual(grad)')
-        ghd, gev, gst = _backward_points(cfg, ctx.ws, nets, x_, y_, t_, None, cd_, g_out, g_jxi, st, fork=True, keep=(hd_, ev_))
+        out_n, jac_n = ctx.fields
+        g_out, g_jxi = _residual_cotangent(cfg, out_n, jac_n, ops.f, ((0, ops.cd.shape[0], gl, gt),))
+        ghd, gev, gst = _backward_points(cfg, ctx.ws, ops.nets(), ops.x, ops.y, ops.t, None, ops.cd, g_out, g_jxi, ops.st, fork=True,
+                                         keep=(ops.hd, ops.ev))
         return (None, None, None, None, None, None, ghd, gev, *gst)
 
 
-def _pack_batch(cfg, heads, evec, statics, n):
-    """The packed weight blocks of B fields (heads [B, 256, 2700], evec [B, 6, 256], shared statics) in ONE launch -> uint8 [B, stride]; row b is
-    field b's `_Workspace.packed`.  (Per field the launch is 17 us of latency-bound tiles, 61 of them 1 ms of a 51-ms step: DESIGN.md 6a.)"""
-    lib = L.load()
-    sizes = L.DpnSizes()
-    L.check(lib.dpn_sizes(n, cfg.prec, ctypes.byref(sizes)), 'dpn_sizes')
-    B = heads.shape[0]
-    stride = (int(sizes.packed) + 255) // 256 * 256
-    packed = torch.empty((B, stride), dtype=torch.uint8, device=heads.device)
-    nets = _net_ptrs(heads[0], evec[0], statics)
-    form = lib.dpn_fwd_form(cfg.prec, 0)
-    L.check(lib.dpn_pack_weights_batch(nets, B, heads.stride(0), evec.stride(0), cfg.prec, form, _ptr(packed), stride, _stream()), 'dpn_pack_weights_batch')
-    return packed
+_STATIC_STARTS = [0]                    # offsets of the 48 static tensors in a flat gradient row
+for _i in range(48):
+    _STATIC_STARTS.append(_STATIC_STARTS[-1] + int(torch.Size(STATIC_SHAPES[_i % 8]).numel()))
+
+
+def _static_views(flat):
+    """The 48 static-parameter gradients as views of one flat row [_STATIC_STARTS[-1]]."""
+    return [flat[_STATIC_STARTS[i]:_STATIC_STARTS[i + 1]].view(STATIC_SHAPES[i % 8]) for i in range(48)]
+
+
+class _FieldBatch:
+    """B fields of one batch (ops: _operands with batch=True) for n-point forwards: field b's workspace and pointer table, and the weight
+    gradients of all B fields side by side (heads [B, 256, 2700], evec [B, 6, 256], statics flat [B, 48 tensors]).  pack: every field's
+    weight block in ONE launch (dpn_pack_weights_batch), issued here in front of whatever the caller launches next; otherwise each field's forward packs
+    its own."""
+
+    def __init__(self, cfg, ops, n, pack):
+        self.cfg, self.ops, self.n = cfg, ops, n
+        self.packed = None
+        if pack:            # row b of packed [B, stride] is field b's _Workspace.packed (per field the launch is 17 us of latency-bound tiles: DESIGN.md 6a)
+            lib, B = L.load(), ops.hd.shape[0]
+            stride = (point_sizes(n, cfg.prec)[1] + 255) // 256 * 256
+            self.packed = torch.empty((B, stride), dtype=torch.uint8, device=ops.hd.device)
+            L.check(lib.dpn_pack_weights_batch(ops.nets(0), B, ops.hd.stride(0), ops.ev.stride(0), cfg.prec, lib.dpn_fwd_form(cfg.prec, 0),
+                                               _ptr(self.packed), stride, _stream()), 'dpn_pack_weights_batch')
+
+    def field(self, b):
+        ws = _Workspace(self.n, self.cfg.prec, self.ops.cd.device, packed=None if self.packed is None else self.packed[b])
+        return ws, self.ops.nets(b)
+
+    def grads(self):
+        B, dev = self.ops.hd.shape[0], self.ops.cd.device
+        return (torch.empty((B, 256, HEADS_COLS), dtype=torch.float32, device=dev), torch.empty((B, 6, 256), dtype=torch.float32, device=dev),
+                torch.empty((B, _STATIC_STARTS[-1]), dtype=torch.float32, device=dev))
 
 
 class _PdeLossBatchFn(torch.autograd.Function):
@@ -596,79 +657,54 @@ class _PdeLossBatchFn(torch.autograd.Function):
     at 61 this way; the 61-field step 80.5 -> 78.6 ms on the same box.  A
     cotangent on the individual loss terms (not only on the totals) takes the general path: forward again, field by field."""
 
-
-    @staticmethod
-    def _static_layout():
-        numels = [int(torch.Size(STATIC_SHAPES[j]).numel()) for _ in range(6) for j in range(8)]
-        starts = [0]
-        for m_ in numels:
-            starts.append(starts[-1] + m_)
-        return starts
-
     @staticmethod
     def forward(ctx, cfg, grad_enabled, x, y, t, f, coord_data, heads, evec, *statics):
-        for nm, v in (('x', x), ('coord_data', coord_data), ('heads', heads)):
-            _require_gpu(v, nm)
-        lib = L.load()
-        B, n = coord_data.shape[0], coord_data.shape[1]
-        x_, y_, t_, f_ = (_f32c(v).reshape(B, n) for v in (x, y, t, f))
-        cd_, hd_, ev_ = _f32c(coord_data), _f32c(heads), _f32c(evec)
-        st = [_f32c(s) for s in statics]
-        dev = cd_.device
+        ops = _operands('pde_losses_batch', x, y, t, f, coord_data, heads, evec, statics, batch=True)
+        B, n = ops.cd.shape[0], ops.cd.shape[1]
+        dev = ops.cd.device
         # Function.forward always runs with grad mode off: the caller's mode arrives as an argument (pde_losses_batch), so that a no-grad
         # evaluation (validation, place_lead_batch scoring) neither saves state nor runs each field's point backward
         need_grad = bool(grad_enabled) and any(v.requires_grad for v in (heads, evec) + tuple(statics))
         eager = need_grad and config.FROZEN.batch_eager_backward
         losses7 = torch.empty((B, 7), dtype=torch.float32, device=dev)
         sums = torch.empty((B, ((n + 255) // 256) * 6), dtype=torch.float64, device=dev)      # per field: block rows, all reduced by ONE launch behind the loop
-        geo, ph = cfg.geometry(), cfg.physics()
         fields = []
         one_launch = config.FROZEN.batch_pack                     # every field's weight block: one launch in front of the loop
-        packed = _pack_batch(cfg, hd_, ev_, st, n) if one_launch else None
+        batch = _FieldBatch(cfg, ops, n, pack=one_launch)
+        unit = grads = None
         if eager:
-            starts = _PdeLossBatchFn._static_layout()
-            one = torch.ones(1, dtype=torch.float32, device=dev)
-            g_out = torch.empty((n, 6), dtype=torch.float32, device=dev)
-            g_jxi = torch.empty((n, 6, 3), dtype=torch.float32, device=dev)
-            g_heads = torch.empty((B, 256, HEADS_COLS), dtype=torch.float32, device=dev)
-            g_evec = torch.empty((B, 6, 256), dtype=torch.float32, device=dev)
-            flat = torch.empty((B, starts[-1]), dtype=torch.float32, device=dev)
+            unit = (torch.ones(1, dtype=torch.float32, device=dev), torch.empty((n, 6), dtype=torch.float32, device=dev),
+                    torch.empty((n, 6, 3), dtype=torch.float32, device=dev))
+            grads = batch.grads()
         for b in range(B):
-            ws = _Workspace(n, cfg.prec, dev, packed=packed[b] if one_launch else None)
-            nets = _net_ptrs(hd_[b], ev_[b], st)
-            out_n, jac_n = _forward_points(cfg, ws, nets, x_[b], y_[b], t_[b], None, cd_[b], want_jac=True, want_saved=need_grad)
+            ws, nets = batch.field(b)
+            out_n, jac_n = _forward_points(cfg, ws, nets, ops.x[b], ops.y[b], ops.t[b], None, ops.cd[b], want_jac=True, want_saved=need_grad)
             # eager: the block sums of the losses AND d total_b / d (out, Jacobian) for a unit cotangent in ONE pass over the points
-            L.check(lib.dpn_residual(_ptr(out_n), _ptr(jac_n), _ptr(f_[b]), n, ctypes.byref(geo), ctypes.byref(ph), None,
-                                     _ptr(one) if eager else None, _ptr(sums[b]), _ptr(g_out) if eager else None, _ptr(g_jxi) if eager else None,
-                                     _stream()), 'dpn_residual')
+            _residual_losses(cfg, out_n, jac_n, ops.f[b], ((0, n),), None, unit=unit, sums=sums[b])
             if eager:                                             # d total_b / d (this field's weights)
-                g_stat = [flat[b, starts[i]:starts[i + 1]].view(STATIC_SHAPES[i % 8]) for i in range(48)]
-                _backward_points(cfg, ws, nets, x_[b], y_[b], t_[b], None, cd_[b], g_out, g_jxi, st, into=(g_heads[b], g_evec[b], g_stat))
+                _backward_points(cfg, ws, nets, ops.x[b], ops.y[b], ops.t[b], None, ops.cd[b], unit[1], unit[2], ops.st,
+                                 into=(grads[0][b], grads[1][b], _static_views(grads[2][b])))
                 del ws, out_n, jac_n
             elif need_grad:
                 fields.append((ws, out_n, jac_n))
             if not one_launch:
-                L.check(lib.dpn_residual_finish(_ptr(sums[b]), n, ctypes.byref(ph), _ptr(losses7[b]), _stream()), 'dpn_residual_finish')
+                _residual_finish(cfg, sums[b], n, losses7[b])
         if one_launch:
-            L.check(lib.dpn_residual_finish_batch(_ptr(sums), n, B, ctypes.byref(ph), _ptr(losses7), _stream()), 'dpn_residual_finish')
-        ctx.cfg, ctx.fields = cfg, fields
-        ctx.eager = (g_heads, g_evec, flat) if eager else None
-        ctx.keep = (x_, y_, t_, f_, cd_, hd_, ev_, st)
+            ph = cfg.physics()
+            L.check(L.load().dpn_residual_finish_batch(_ptr(sums), n, B, ctypes.byref(ph), _ptr(losses7), _stream()), 'dpn_residual_finish')
+        ctx.cfg, ctx.fields, ctx.eager, ctx.ops = cfg, fields, grads, ops
         ctx.stamp = _stamp((heads, evec) + tuple(statics))
         ctx.set_materialize_grads(False)
         return losses7[:, :6], losses7[:, 6]
 
     @staticmethod
     def backward(ctx, g_losses, g_total):
-        lib = L.load()
-        cfg = ctx.cfg
+        cfg, ops = ctx.cfg, ctx.ops
         _check_stamp(ctx.stamp, 'pde_losses_batch')
-        x_, y_, t_, f_, cd_, hd_, ev_, st = ctx.keep
-        B, n = cd_.shape[0], cd_.shape[1]
-        dev = cd_.device
+        B, n = ops.cd.shape[0], ops.cd.shape[1]
+        dev = ops.cd.device
         if g_losses is None and g_total is None:
-            return (None,) * (9 + len(st))
-        starts = _PdeLossBatchFn._static_layout()
+            return (None,) * (9 + len(ops.st))
         if ctx.eager is not None and g_losses is None:
             # the gradients are there for unit cotangents of the B totals: scale them by the cotangents that arrived
             g_heads, g_evec, flat = ctx.eager
@@ -682,33 +718,37 @@ class _PdeLossBatchFn(torch.autograd.Function):
             gt = None if g_total is None else _f32c(g_total)
             g_out = torch.empty((n, 6), dtype=torch.float32, device=dev)
             g_jxi = torch.empty((n, 6, 3), dtype=torch.float32, device=dev)
-            g_heads = torch.empty((B, 256, HEADS_COLS), dtype=torch.float32, device=dev)
-            g_evec = torch.empty((B, 6, 256), dtype=torch.float32, device=dev)
-            flat = torch.empty((B, starts[-1]), dtype=torch.float32, device=dev)
-            geo, ph = cfg.geometry(), cfg.physics()
             recompute = ctx.eager is not None                      # cotangents on the individual terms: the general path, forward again
             ctx.eager = None
             if not recompute and (len(ctx.fields) != B or any(fld is None for fld in ctx.fields)):
                 raise RuntimeError('deepphysinet_amd pde_losses_batch: the per-field state saved by the forward pass is released as the backward '
                                    'pass consumes it (21 GB at 61 fields); run the forward pass again instead of a second backward')
+            batch = _FieldBatch(cfg, ops, n, pack=False)           # (the recompute packs field by field, in its forward launches)
+            g_heads, g_evec, flat = batch.grads()
             for b in range(B):
-                nets = _net_ptrs(hd_[b], ev_[b], st)
                 if recompute:
-                    ws = _Workspace(n, cfg.prec, dev)
-                    out_n, jac_n = _forward_points(cfg, ws, nets, x_[b], y_[b], t_[b], None, cd_[b], want_jac=True, want_saved=True)
+                    ws, nets = batch.field(b)
+                    out_n, jac_n = _forward_points(cfg, ws, nets, ops.x[b], ops.y[b], ops.t[b], None, ops.cd[b], want_jac=True, want_saved=True)
                 else:
-                    ws, out_n, jac_n = ctx.fields[b]
-                L.check(lib.dpn_residual(_ptr(out_n), _ptr(jac_n), _ptr(f_[b]), n, ctypes.byref(geo), ctypes.byref(ph),
-                                         None if gl is None else _ptr(gl[b]), None if gt is None else _ptr(gt[b:b + 1]), None,
-                                         _ptr(g_out), _ptr(g_jxi), _stream()), 'dpn_residual(grad)')
-                g_stat = [flat[b, starts[i]:starts[i + 1]].view(STATIC_SHAPES[i % 8]) for i in range(48)]
-                _backward_points(cfg, ws, nets, x_[b], y_[b], t_[b], None, cd_[b], g_out, g_jxi, st, into=(g_heads[b], g_evec[b], g_stat))
+                    (ws, out_n, jac_n), nets = ctx.fields[b], ops.nets(b)
+                _residual_cotangent(cfg, out_n, jac_n, ops.f[b], ((0, n, None if gl is None else gl[b], None if gt is None else gt[b:b + 1]),),
+                                    g_out, g_jxi)
+                _backward_points(cfg, ws, nets, ops.x[b], ops.y[b], ops.t[b], None, ops.cd[b], g_out, g_jxi, ops.st,
+                                 into=(g_heads[b], g_evec[b], _static_views(flat[b])))
                 if not recompute:
                     ctx.fields[b] = None                          # this field's saved state is no longer needed
-        total = torch.empty(starts[-1], dtype=torch.float32, device=dev)
-        L.check(lib.dpn_sum_parts(_ptr(flat), B, starts[-1], 0, _ptr(total), _stream()), 'dpn_sum_parts')
-        gst = [total[starts[i]:starts[i + 1]].view(STATIC_SHAPES[i % 8]) for i in range(48)]
-        return (None, None, None, None, None, None, None, g_heads, g_evec, *gst)
+        total = torch.empty(_STATIC_STARTS[-1], dtype=torch.float32, device=dev)
+        L.check(L.load().dpn_sum_parts(_ptr(flat), B, _STATIC_STARTS[-1], 0, _ptr(total), _stream()), 'dpn_sum_parts')
+        return (None, None, None, None, None, None, None, g_heads, g_evec, *_static_views(total))
+
+
+def _step_pass(cfg, ws, nets, n_inter, x_, y_, t_, f_, cd_, losses, want_saved=False):
+    """The step body's point pass over [interior | margin] rows (the first n_inter interior): ONE forward with the Jacobian, then the residual-loss
+    sums of the two groups into losses [2, 7].  _StepLossFn.forward (want_saved, for its backward) and eval_step(_batch) both run exactly this, so
+    their PDE losses are the same bitwise.  Returns (out_n, jac_n)."""
+    out_n, jac_n = _forward_points(cfg, ws, nets, x_, y_, t_, None, cd_, want_jac=True, want_saved=want_saved)
+    _residual_losses(cfg, out_n, jac_n, f_, ((0, n_inter), (n_inter, cd_.shape[0])), losses)
+    return out_n, jac_n
 
 
 class _StepLossFn(torch.autograd.Function):
@@ -719,66 +759,38 @@ class _StepLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cfg, n_inter, beta, margin_factor, x, y, t, f, coord_data, labels, heads, evec, *statics):
-        for nm, v in (('x', x), ('coord_data', coord_data), ('heads', heads), ('labels', labels)):
-            _require_gpu(v, nm)
-        n, n_lab = coord_data.shape[0], labels.shape[0]
-        if not (0 < n_inter < n and n_lab == n - n_inter):
-            # every launch below takes its row counts from this split: a bad one reads and writes past the groups
-            raise ValueError('step_losses: n_inter = %d of %d points leaves %d margin points for %d label rows; need 0 < n_inter < %d and one '
-                             'label row per margin point' % (n_inter, n, n - n_inter, n_lab, n))
-        lib = L.load()
-        x_, y_, t_, f_ = (_f32c(v).reshape(-1) for v in (x, y, t, f))
-        cd_, hd_, ev_, lab_ = _f32c(coord_data), _f32c(heads), _f32c(evec), _f32c(labels)
-        st = [_f32c(s) for s in statics]
+        ops = _operands('step_losses', x, y, t, f, coord_data, heads, evec, statics, labels=labels, split=(n_inter, True))
+        n = ops.cd.shape[0]
         n_m = n - n_inter
-        dev = cd_.device
+        dev = ops.cd.device
         need_grad = any(v.requires_grad for v in (heads, evec) + tuple(statics))
         ws = _Workspace(n, cfg.prec, dev)
-        nets = _net_ptrs(hd_, ev_, st)
-        out_n, jac_n = _forward_points(cfg, ws, nets, x_, y_, t_, None, cd_, want_jac=True, want_saved=need_grad)
-        geo, ph = cfg.geometry(), cfg.physics()
         losses = torch.empty((2, 7), dtype=torch.float32, device=dev)
-        for gi, (a0, a1) in enumerate(((0, n_inter), (n_inter, n))):
-            sums = torch.empty(((a1 - a0 + 255) // 256) * 6, dtype=torch.float64, device=dev)
-            L.check(lib.dpn_residual(_ptr(out_n[a0:]), _ptr(jac_n[a0:]), _ptr(f_[a0:]), a1 - a0, ctypes.byref(geo), ctypes.byref(ph), None, None,
-                                     _ptr(sums), None, None, _stream()), 'dpn_residual')
-            L.check(lib.dpn_residual_finish(_ptr(sums), a1 - a0, ctypes.byref(ph), _ptr(losses[gi]), _stream()), 'dpn_residual_finish')
+        out_n, jac_n = _step_pass(cfg, ws, ops.nets(), n_inter, ops.x, ops.y, ops.t, ops.f, ops.cd, losses, want_saved=need_grad)
         dsum = torch.empty((n_m * 6 + 255) // 256, dtype=torch.float64, device=dev)
-        L.check(lib.dpn_smooth_l1(_ptr(out_n[n_inter:]), _ptr(lab_), n_m, beta, 1.0, _ptr(dsum), None, 0, None, _stream()), 'dpn_smooth_l1')
+        L.check(L.load().dpn_smooth_l1(_ptr(out_n[n_inter:]), _ptr(ops.lab), n_m, beta, 1.0, _ptr(dsum), None, 0, None, _stream()), 'dpn_smooth_l1')
         data = (dsum.sum() / (6.0 * n_m)).float() * margin_factor
         ctx.cfg, ctx.ws, ctx.n_inter, ctx.beta, ctx.margin_factor = cfg, ws, n_inter, beta, margin_factor
-        ctx.keep = (x_, y_, t_, f_, cd_, lab_, hd_, ev_, st, out_n, jac_n)
+        ctx.ops, ctx.fields = ops, (out_n, jac_n)
         ctx.stamp = _stamp((heads, evec) + tuple(statics))
         ctx.set_materialize_grads(False)
         return losses[0, :6], losses[0, 6], losses[1, :6], losses[1, 6], data
 
     @staticmethod
     def backward(ctx, g_la, g_ta, g_lb, g_tb, g_data):
-        lib = L.load()
-        cfg, n_inter = ctx.cfg, ctx.n_inter
+        cfg, n_inter, ops = ctx.cfg, ctx.n_inter, ctx.ops
         _check_stamp(ctx.stamp, 'step_losses')
-        x_, y_, t_, f_, cd_, lab_, hd_, ev_, st, out_n, jac_n = ctx.keep
-        n = cd_.shape[0]
+        out_n, jac_n = ctx.fields
+        n = ops.cd.shape[0]
         n_m = n - n_inter
-        dev = cd_.device
         if all(v is None for v in (g_la, g_ta, g_lb, g_tb, g_data)):
-            return (None,) * (12 + len(st))
-        g_out = torch.empty((n, 6), dtype=torch.float32, device=dev)
-        g_jxi = torch.empty((n, 6, 3), dtype=torch.float32, device=dev)
-        geo, ph = cfg.geometry(), cfg.physics()
-        zero6 = None
-        for (a0, a1), gl, gt in (((0, n_inter), g_la, g_ta), ((n_inter, n), g_lb, g_tb)):
-            if gl is None and gt is None:                     # this group's PDE losses are unused: zero cotangent
-                zero6 = torch.zeros(6, dtype=torch.float32, device=dev) if zero6 is None else zero6
-                gl = zero6
-            L.check(lib.dpn_residual(_ptr(out_n[a0:]), _ptr(jac_n[a0:]), _ptr(f_[a0:]), a1 - a0, ctypes.byref(geo), ctypes.byref(ph),
-                                     None if gl is None else _ptr(_f32c(gl)), None if gt is None else _ptr(_f32c(gt).reshape(1)), None,
-                                     _ptr(g_out[a0:]), _ptr(g_jxi[a0:]), _stream()), 'dpn_residual(grad)')
+            return (None,) * (12 + len(ops.st))
+        g_out, g_jxi = _residual_cotangent(cfg, out_n, jac_n, ops.f, ((0, n_inter, g_la, g_ta), (n_inter, n, g_lb, g_tb)))
         if g_data is not None:                                # + d(data loss)/d out on the margin rows
-            L.check(lib.dpn_smooth_l1(_ptr(out_n[n_inter:]), _ptr(lab_), n_m, ctx.beta, ctx.margin_factor / (6.0 * n_m), None,
-                                      _ptr(g_out[n_inter:]), 1, _ptr(_f32c(g_data).reshape(1)), _stream()), 'dpn_smooth_l1(grad)')
-        nets = _net_ptrs(hd_, ev_, st)
-        ghd, gev, gst = _backward_points(cfg, ctx.ws, nets, x_, y_, t_, None, cd_, g_out, g_jxi, st, fork=True, keep=(hd_, ev_))
+            L.check(L.load().dpn_smooth_l1(_ptr(out_n[n_inter:]), _ptr(ops.lab), n_m, ctx.beta, ctx.margin_factor / (6.0 * n_m), None,
+                                           _ptr(g_out[n_inter:]), 1, _ptr(_f32c(g_data).reshape(1)), _stream()), 'dpn_smooth_l1(grad)')
+        ghd, gev, gst = _backward_points(cfg, ctx.ws, ops.nets(), ops.x, ops.y, ops.t, None, ops.cd, g_out, g_jxi, ops.st, fork=True,
+                                         keep=(ops.hd, ops.ev))
         return (None,) * 10 + (ghd, gev, *gst)
 
 
@@ -812,11 +824,9 @@ def pde_losses(cfg: PointConfig, x, y, t, f, coord_data, heads, evec, statics, w
 def pde_fields_and_jacobian(cfg: PointConfig, x, y, t, coord_data, heads, evec, statics):
     """No-grad helper: normalised fields [N,6] and d(fields_n)/d(x,y,t) [N,6,3] straight from the forward kernel."""
     with torch.no_grad():
-        x_, y_, t_ = (_f32c(v).reshape(-1) for v in (x, y, t))
-        cd_, hd_, ev_ = (_f32c(v) for v in (coord_data, heads, evec))
-        st = [_f32c(s) for s in statics]
-        ws = _Workspace(cd_.shape[0], cfg.prec, cd_.device)
-        return _forward_points(cfg, ws, _net_ptrs(hd_, ev_, st), x_, y_, t_, None, cd_, want_jac=True, want_saved=False)
+        ops = _operands('pde_fields_and_jacobian', x, y, t, None, coord_data, heads, evec, statics)
+        ws = _Workspace(ops.cd.shape[0], cfg.prec, ops.cd.device)
+        return _forward_points(cfg, ws, ops.nets(), ops.x, ops.y, ops.t, None, ops.cd, want_jac=True, want_saved=False)
 
 
 def relu_masks(cfg: PointConfig, x, y, t, coord_data, heads, evec, statics):
@@ -826,13 +836,10 @@ def relu_masks(cfg: PointConfig, x, y, t, coord_data, heads, evec, statics):
     pre-activation lies within rounding distance of zero may carry a different bit than another arithmetic's (the parity tests list those
     points and hold everything else to the tight bounds).  Layouts: csrc/dpn_kernels.hip SavedView, dpn_layout.h."""
     with torch.no_grad():
-        x_, y_, t_ = (_f32c(v).reshape(-1) for v in (x, y, t))
-        cd_, hd_, ev_ = (_f32c(v) for v in (coord_data, heads, evec))
-        st = [_f32c(s) for s in statics]
-        n = cd_.shape[0]
-        dev = cd_.device
+        ops = _operands('relu_masks', x, y, t, None, coord_data, heads, evec, statics)
+        n, dev = ops.cd.shape[0], ops.cd.device
         ws = _Workspace(n, cfg.prec, dev)
-        _forward_points(cfg, ws, _net_ptrs(hd_, ev_, st), x_, y_, t_, None, cd_, want_jac=True, want_saved=True)
+        _forward_points(cfg, ws, ops.nets(), ops.x, ops.y, ops.t, None, ops.cd, want_jac=True, want_saved=True)
         n_pad, ns = int(ws.sizes.n_pad), int(cfg.prec)
         tiles = n_pad // 32
         mat = 6 * ns * n_pad * 512                                                      # T1 (hi, lo planes) | M2 | m1: SavedView
@@ -872,7 +879,7 @@ def smooth_l1_data_loss(out_n, labels, beta=0.1, factor=1.0):
 class _SmoothL1Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, out_n, labels, beta, factor):
-        _require_gpu(out_n, 'out_n')
+        require_gpu(out_n, 'out_n', 'smooth_l1_data_loss')
         lib = L.load()
         o, l = _f32c(out_n), _f32c(labels)
         n = o.shape[0]
@@ -903,8 +910,8 @@ def label_errors(cfg: PointConfig, out_n, labels, beta=0.1, with_clip=False):
     """Sufficient statistics [S, 25] (fp64) of normalised predictions out_n [S, N, 6] (or [N, 6]: S = 1) against labels of the same shape, one
     row per segment: [0] sum SmoothL1_beta, then per variable (u, v, P, T, q, rho) sum d^2 [1:7], sum |d| [7:13], sum d [13:19], max |d| [19:25]
     of d = inverse_norm(pred) - inverse_norm(label) (include/dpn_hip.h: dpn_label_errors).  One pass over the data, bitwise reproducible."""
-    _require_gpu(out_n, 'out_n')
-    _require_gpu(labels, 'labels')
+    require_gpu(out_n, 'out_n', 'label_errors')
+    require_gpu(labels, 'labels', 'label_errors')
     o, l = _f32c(out_n), _f32c(labels)
     if o.shape != l.shape or o.dim() not in (2, 3) or o.shape[-1] != 6 or o.numel() == 0:
         raise ValueError('label_errors: out_n %s and labels %s must both be [N, 6] or [S, N, 6]' % (tuple(out_n.shape), tuple(labels.shape)))
@@ -917,29 +924,33 @@ def label_errors(cfg: PointConfig, out_n, labels, beta=0.1, with_clip=False):
     return stats
 
 
-def _eval_one(cfg, ws, nets, n_inter, x_, y_, t_, f_, cd_, lab_, beta, with_pde, with_clip, losses, partials):
-    """One field sample of eval_step / eval_step_batch: the point forward without saved state, the two groups' residual sums (written to
-    `losses` [2, 7] by the finish launches), and the label statistics' block rows of the margin points (`partials`)."""
+def _eval(what, cfg, n_inter, x, y, t, f, coord_data, labels, heads, evec, statics, beta, with_pde, with_clip, batch):
+    """eval_step (batch False: one field, its forward packs the weights) and eval_step_batch (batch True: B fields packed in one launch).  Per
+    field: with_pde, the step body's point pass (_step_pass, no saved state) and the label statistics' block rows of its margin rows; without,
+    the margin rows' fields only.  One finish launch adds the statistics of all fields.  Returns (losses [B, 2, 7] or None, stats [B, 25])."""
+    n_inter = int(n_inter)
+    ops = _operands(what, x, y, t, f, coord_data, heads, evec, statics, labels=labels, batch=batch, split=(n_inter, with_pde))
     lib = L.load()
-    n = cd_.shape[0]
-    if not with_pde:                                       # the reference's first 2 000 steps: fields only, no Jacobian
-        out_n, _ = _forward_points(cfg, ws, nets, x_[n_inter:], y_[n_inter:], t_[n_inter:], None, cd_[n_inter:], want_jac=False, want_saved=False)
-        _label_partials(cfg, out_n, lab_, n - n_inter, 1, beta, with_clip, partials)
-        return
-    out_n, jac_n = _forward_points(cfg, ws, nets, x_, y_, t_, None, cd_, want_jac=True, want_saved=False)
-    geo, ph = cfg.geometry(), cfg.physics()
-    for gi, (a0, a1) in enumerate(((0, n_inter), (n_inter, n))):             # the launches of _StepLossFn.forward, group by group
-        sums = torch.empty(((a1 - a0 + 255) // 256) * 6, dtype=torch.float64, device=cd_.device)
-        L.check(lib.dpn_residual(_ptr(out_n[a0:]), _ptr(jac_n[a0:]), _ptr(f_[a0:]), a1 - a0, ctypes.byref(geo), ctypes.byref(ph), None, None,
-                                 _ptr(sums), None, None, _stream()), 'dpn_residual')
-        L.check(lib.dpn_residual_finish(_ptr(sums), a1 - a0, ctypes.byref(ph), _ptr(losses[gi]), _stream()), 'dpn_residual_finish')
-    _label_partials(cfg, out_n[n_inter:], lab_, n - n_inter, 1, beta, with_clip, partials)
-
-
-def _check_eval_split(what, n_inter, n, n_lab, with_pde):
-    if not ((0 < n_inter < n if with_pde else 0 <= n_inter < n) and n_lab == n - n_inter):
-        raise ValueError('%s: n_inter = %d of %d points leaves %d margin points for %d label rows; need 0 < n_inter < %d (0 allowed without the '
-                         'PDE losses) and one label row per margin point' % (what, n_inter, n, n - n_inter, n_lab, n))
+    B, n = (ops.cd.shape[0], ops.cd.shape[1]) if batch else (1, ops.cd.shape[0])
+    dev = ops.cd.device
+    n_m = n - n_inter
+    n_fwd = n if with_pde else n_m
+    losses = torch.empty((B, 2, 7), dtype=torch.float32, device=dev) if with_pde else None
+    partials = torch.empty((B, int(lib.dpn_label_errors_blocks(n_m)), L.EVAL_STATS), dtype=torch.float64, device=dev)
+    stats = torch.empty((B, L.EVAL_STATS), dtype=torch.float64, device=dev)
+    fields = _FieldBatch(cfg, ops, n_fwd, pack=True) if batch else None
+    for b in range(B):
+        ws, nets = fields.field(b) if batch else (_Workspace(n_fwd, cfg.prec, dev), ops.nets())
+        x_, y_, t_, f_, cd_, lab_ = (v[b] for v in ops[:4] + (ops.cd, ops.lab)) if batch else ops[:4] + (ops.cd, ops.lab)
+        if with_pde:
+            out_n, _ = _step_pass(cfg, ws, nets, n_inter, x_, y_, t_, f_, cd_, losses[b])
+            out_n = out_n[n_inter:]
+        else:                                              # the reference's first 2 000 steps: fields only, no Jacobian
+            out_n, _ = _forward_points(cfg, ws, nets, x_[n_inter:], y_[n_inter:], t_[n_inter:], None, cd_[n_inter:], want_jac=False,
+                                       want_saved=False)
+        _label_partials(cfg, out_n, lab_, n_m, 1, beta, with_clip, partials[b:b + 1])
+    L.check(lib.dpn_label_errors_finish(_ptr(partials), n_m, B, _ptr(stats), _stream()), 'dpn_label_errors_finish')
+    return losses, stats
 
 
 @torch.no_grad()
@@ -950,50 +961,63 @@ def eval_step(cfg: PointConfig, n_inter, x, y, t, f, coord_data, labels, heads, 
     six scaled PDE terms and their total -- None without with_pde, which evaluates the margin rows' fields only, no Jacobian --, stats [25]
     fp64: label_errors of the margin rows, stats[0] / (6 n_margin) = the unscaled data loss).  The cfg's own with_clip governs the PDE
     residuals as in training; `with_clip` here is the label statistics' alone (off in the reference, interface_physics.py:706-713)."""
-    for nm, v in (('x', x), ('coord_data', coord_data), ('heads', heads), ('labels', labels)):
-        _require_gpu(v, nm)
-    n, n_inter = coord_data.shape[0], int(n_inter)
-    _check_eval_split('eval_step', n_inter, n, labels.shape[0], with_pde)
-    lib = L.load()
-    x_, y_, t_, f_ = (_f32c(v).reshape(-1) for v in (x, y, t, f))
-    cd_, hd_, ev_, lab_ = _f32c(coord_data), _f32c(heads), _f32c(evec), _f32c(labels)
-    st = [_f32c(s) for s in statics]
-    dev = cd_.device
-    n_m = n - n_inter
-    ws = _Workspace(n if with_pde else n_m, cfg.prec, dev)
-    losses = torch.empty((2, 7), dtype=torch.float32, device=dev) if with_pde else None
-    partials = torch.empty((1, int(lib.dpn_label_errors_blocks(n_m)), L.EVAL_STATS), dtype=torch.float64, device=dev)
-    stats = torch.empty((1, L.EVAL_STATS), dtype=torch.float64, device=dev)
-    _eval_one(cfg, ws, _net_ptrs(hd_, ev_, st), n_inter, x_, y_, t_, f_, cd_, lab_, beta, with_pde, with_clip, losses, partials)
-    L.check(lib.dpn_label_errors_finish(_ptr(partials), n_m, 1, _ptr(stats), _stream()), 'dpn_label_errors_finish')
-    return losses, stats[0]
+    losses, stats = _eval('eval_step', cfg, n_inter, x, y, t, f, coord_data, labels, heads, evec, statics, beta, with_pde, with_clip, False)
+    return None if losses is None else losses[0], stats[0]
 
 
 @torch.no_grad()
 def eval_step_batch(cfg: PointConfig, n_inter, x, y, t, f, coord_data, labels, heads, evec, statics, beta=0.1, with_pde=True, with_clip=False):
     """eval_step for B field samples (distinct field / lead time, so distinct hyper-network weights): point tensors [B, N(, 6)], labels
-    [B, N - n_inter, 6], heads [B, 256, 2700], evec [B, 6, 256], shared statics.  The B weight blocks are packed in one launch (_pack_batch); each
+    [B, N - n_inter, 6], heads [B, 256, 2700], evec [B, 6, 256], shared statics.  The B weight blocks are packed in one launch (_FieldBatch); each
     sample then takes ONE point pass over its [interior | margin] rows -- the pass of eval_step and of the training step, so that a sample's row
     equals eval_step's bitwise (two passes, one per group, would form other 128-point tiles at the group boundary) --, and one finish launch
     adds the label statistics of all B samples.  Returns (losses [B, 2, 7] or None, stats [B, 25])."""
-    for nm, v in (('x', x), ('coord_data', coord_data), ('heads', heads), ('labels', labels)):
-        _require_gpu(v, nm)
-    B, n, n_inter = coord_data.shape[0], coord_data.shape[1], int(n_inter)
-    _check_eval_split('eval_step_batch', n_inter, n, labels.shape[1], with_pde)
-    lib = L.load()
-    x_, y_, t_, f_ = (_f32c(v).reshape(B, n) for v in (x, y, t, f))
-    cd_, hd_, ev_, lab_ = _f32c(coord_data), _f32c(heads), _f32c(evec), _f32c(labels)
-    st = [_f32c(s) for s in statics]
-    dev = cd_.device
-    n_m = n - n_inter
-    n_fwd = n if with_pde else n_m
-    losses = torch.empty((B, 2, 7), dtype=torch.float32, device=dev) if with_pde else None
-    partials = torch.empty((B, int(lib.dpn_label_errors_blocks(n_m)), L.EVAL_STATS), dtype=torch.float64, device=dev)
-    stats = torch.empty((B, L.EVAL_STATS), dtype=torch.float64, device=dev)
-    packed = _pack_batch(cfg, hd_, ev_, st, n_fwd)
-    for b in range(B):
-        ws = _Workspace(n_fwd, cfg.prec, dev, packed=packed[b])
-        _eval_one(cfg, ws, _net_ptrs(hd_[b], ev_[b], st), n_inter, x_[b], y_[b], t_[b], f_[b], cd_[b], lab_[b], beta, with_pde, with_clip,
-                  None if losses is None else losses[b], partials[b:b + 1])
-    L.check(lib.dpn_label_errors_finish(_ptr(partials), n_m, B, _ptr(stats), _stream()), 'dpn_label_errors_finish')
-    return losses, stats
+    return _eval('eval_step_batch', cfg, n_inter, x, y, t, f, coord_data, labels, heads, evec, statics, beta, with_pde, with_clip, True)
+
+
+# ------------------------------------------------------------------------------------------------ inference: fields and residuals, no autograd
+def point_sizes(n, prec):
+    """(n_pad, packed) of an n-point forward (dpn_sizes): n rounded up to the point kernels' padding unit (n = 1: the unit itself), and the
+    bytes of one field's packed weight block."""
+    sizes = L.DpnSizes()
+    L.check(L.load().dpn_sizes(int(n), int(prec), ctypes.byref(sizes)), 'dpn_sizes')
+    return int(sizes.n_pad), int(sizes.packed)
+
+
+def grid_maps(cfg: PointConfig, out_n, lon_size, lat_size, with_clip=False):
+    """Normalised fields of all lon x lat nodes (out_n [lon * lat, 6], x outer, y inner) de-normalised and scattered into maps [6, lat, lon]
+    (dpn_grid_maps)."""
+    maps = torch.empty((6, lat_size, lon_size), dtype=torch.float32, device=out_n.device)
+    ph = cfg.physics()
+    L.check(L.load().dpn_grid_maps(_ptr(out_n), lon_size, lat_size, ctypes.byref(ph), int(bool(with_clip)), _ptr(maps), _stream()), 'dpn_grid_maps')
+    return maps
+
+
+class PackedField:
+    """One field's weights (heads [256, 2700], evec [6, 256], the 48 statics) packed once for forwards of up to n_chunk points with no saved
+    state: station rows and lattice chunks (fields), or residual rows.  Nothing here is differentiable."""
+
+    def __init__(self, cfg: PointConfig, heads, evec, statics, n_chunk):
+        self.cfg = cfg
+        self.keep = (_f32c(heads), _f32c(evec), [_f32c(s) for s in statics])        # the pointer table points into these
+        self.nets = _net_ptrs(*self.keep)
+        self.ws = _Workspace(n_chunk, cfg.prec, self.keep[0].device)
+        lib = L.load()
+        L.check(lib.dpn_pack_weights_form(self.nets, cfg.prec, lib.dpn_fwd_form(cfg.prec, 0), _ptr(self.ws.packed), _stream()), 'dpn_pack_weights')
+        self.ws.prepacked = True
+
+    def fields(self, x, y, t, coord_data, with_clip=False, rows=None, maps=None, lattice=None, first=0):
+        """The six physical fields at points x, y, t [n], coord_data [n, 6] (dpn_fields_out): into rows [n, 6], or into the places of points
+        first .. first + n of `lattice` in maps [nt, 6, ny, nx]."""
+        out_n, _ = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=False, want_saved=False)
+        ph = self.cfg.physics()
+        lat = None if lattice is None else ctypes.byref(lattice.c_struct())
+        L.check(L.load().dpn_fields_out(_ptr(out_n), out_n.shape[0], ctypes.byref(ph), int(bool(with_clip)), _ptr(rows), _ptr(maps), lat, first,
+                                        _stream()), 'dpn_fields_out')
+
+    def residuals(self, x, y, t, f, coord_data, res):
+        """The six signed residuals lhs - rhs at points x, y, t, f [n], coord_data [n, 6] into res [n, 6] (dpn_residual_points)."""
+        out_n, jac_n = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=True, want_saved=False)
+        geo, ph = self.cfg.geometry(), self.cfg.physics()
+        L.check(L.load().dpn_residual_points(_ptr(out_n), _ptr(jac_n), _ptr(f), out_n.shape[0], ctypes.byref(geo), ctypes.byref(ph), _ptr(res),
+                                             _stream()), 'dpn_residual_points')

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .point_path import _ptr, _require_gpu, _stream
+from .point_path import _ptr, _stream, require_gpu
 
 
 @dataclass
@@ -80,7 +80,7 @@ class CollocationSampler:
     [y, x, t] arrays of physics_dataset.py:400 stacked); labels (optional): [t_hours + 1, 6, lat, lon] fp32 normalised ERA5."""
 
     def __init__(self, cfg: SamplerConfig, cube: torch.Tensor, labels: torch.Tensor = None, seed: int = 0):
-        _require_gpu(cube, 'cube')
+        require_gpu(cube, 'cube')
         c = cfg
         if tuple(cube.shape) != (6, c.in_lat_size, c.in_lon_size, c.input_time_step_nums + 1):
             raise ValueError('cube must be [6, %d, %d, %d], got %s' % (c.in_lat_size, c.in_lon_size, c.input_time_step_nums + 1, tuple(cube.shape)))
@@ -91,7 +91,7 @@ class CollocationSampler:
         self.cube = cube.detach().float().contiguous()
         self.labels = None
         if labels is not None:
-            _require_gpu(labels, 'labels')
+            require_gpu(labels, 'labels')
             hours = c.input_time_step * c.input_time_step_nums + 1
             if tuple(labels.shape) != (hours, 6, c.lat_size, c.lon_size):
                 raise ValueError('labels must be [%d, 6, %d, %d]' % (hours, c.lat_size, c.lon_size))
@@ -104,7 +104,7 @@ class CollocationSampler:
         step_count * points_per_step, step_count being read by the kernel (FusedClipAdam.step_count: int32[1] on the device, bumped
         once per optimiser step).  A sampler launch captured in a hipGraph then draws fresh points on every replay; host-side state no
         longer advances between steps (begin_step() rewinds the offset inside the step; training_batch() calls it)."""
-        _require_gpu(step_count, 'step_count')
+        require_gpu(step_count, 'step_count')
         if step_count.dtype != torch.int32 or step_count.numel() != 1:
             raise ValueError('step_count must be one int32 on the device')
         self._step_dev, self._stride, self.offset = step_count, int(points_per_step), 0
