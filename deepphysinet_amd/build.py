@@ -10,7 +10,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = [os.path.join(HERE, 'csrc', 'dpn_kernels.hip'), os.path.join(HERE, 'csrc', 'dpn_encoder.hip'),
         os.path.join(HERE, 'csrc', 'dpn_sampler.hip'), os.path.join(HERE, 'csrc', 'dpn_fp8.hip'),
-        os.path.join(HERE, 'csrc', 'dpn_encoder_chain.hip'), os.path.join(HERE, 'csrc', 'dpn_eval.hip')]
+        os.path.join(HERE, 'csrc', 'dpn_encoder_chain.hip'), os.path.join(HERE, 'csrc', 'dpn_eval.hip'),
+        os.path.join(HERE, 'csrc', 'dpn_adaptive.hip')]
 DEPS = SRCS + [os.path.join(HERE, 'csrc', 'dpn_layout.h'), os.path.join(HERE, 'csrc', 'dpn_fwd_tiles.h'), os.path.join(HERE, 'csrc', 'dpn_ring_kernels.inc'),
                os.path.join(HERE, 'csrc', 'dpn_tiles_kernels.inc'), os.path.join(HERE, 'csrc', 'dpn_residual_body.inc'), os.path.join(os.path.dirname(HERE), 'include', 'dpn_hip.h'),
                os.path.join(os.path.dirname(HERE), 'include', 'dpn_hip_experiments.h')]
@@ -33,7 +34,8 @@ UNITS = [(SRCS[0], ['-DDPN_TU=1', '-mllvm', '-amdgpu-mfma-vgpr-form'], 'dpn_poin
          (SRCS[2], [], 'dpn_sampler.o'),
          (SRCS[3], [], 'dpn_fp8.o'),
          (SRCS[4], ['-mllvm', '-amdgpu-mfma-vgpr-form'], 'dpn_encoder_chain.o'),
-         (SRCS[5], [], 'dpn_eval.o')]              # the validation pass's label statistics: a unit of its own, the others' objects are unchanged
+         (SRCS[5], [], 'dpn_eval.o'),              # the validation pass's label statistics: a unit of its own, the others' objects are unchanged
+         (SRCS[6], [], 'dpn_adaptive.o')]          # residual-weighted collocation points (scores, prefix sum, draw): likewise
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC']
 
 

@@ -363,6 +363,58 @@ class InterfacePhysics(nn.Module):
             rows *= fac
         return rows.view(lattice.nt, lattice.ny, lattice.nx, 6).permute(0, 3, 1, 2).contiguous()
 
+    @torch.no_grad()
+    def adaptive_interior(self, batch: dict, sampler, pool_factor=8, k=1.0, c=1.0):
+        """The batch with its interior collocation points redrawn where the current network violates its equations most (residual-based adaptive
+        sampling, Wu et al. 2023): pool_factor * n uniform interior draws of `sampler` are scored by the six residuals of the batch's field
+        (score = sum_e loss_factor_e * res_e ** 2, the summand of the PDE loss), and n of them are drawn with probability ~ score ** k /
+        mean(score ** k) + c (CollocationSampler.get_inter_data_adaptive).  Returns a copy of the dict with inter_x, inter_y, inter_t, inter_f,
+        inter_data replaced (same shapes and dtypes); everything else is the same objects.  One encoder forward and one fields + Jacobian pass over
+        the pool, without autograd; parameters, .grad, optimiser state and the field cache are left alone."""
+        from ..point_path import PackedField, require_gpu
+        require_gpu(batch['field_data'], 'field_data', 'adaptive_interior')
+        n = int(batch['inter_x'].shape[0])
+        pool = int(pool_factor) * n
+        if pool < n or pool < 1:
+            raise ValueError('adaptive_interior: pool_factor must be an integer >= 1, got %r' % (pool_factor,))
+        lf = self.train_cfg['losses']['loss_factor']
+        meta_out = self.physics_net.encode_field(batch['field_data'], batch['forecast_h'])
+        heads, evec, statics = self.physics_net.field_weights(batch['field_data'], batch['forecast_h'], meta_out=meta_out)
+        field = PackedField(self.point_config(lf), heads, evec, statics, pool)
+        x, y, t, cd, f = sampler.get_inter_data_adaptive(field, [float(lf[name]) for name in LOSS_ORDER], n=n, pool=pool, k=k, c=c)
+        self.physics_net.clear_field_cache()
+        out = dict(batch)
+        for key, v in (('inter_x', x), ('inter_y', y), ('inter_t', t), ('inter_f', f), ('inter_data', cd)):
+            out[key] = v.reshape(batch[key].shape).to(batch[key].dtype)
+        return out
+
+    def _adaptive_option(self, kwargs):
+        """The loops' `adaptive_interior` option (keyword, or train_cfg['train_data']['adaptive_interior']): None (off), or a dict of pool_factor, k, c,
+        every (refresh on every every-th step, counted from the first) and sampler."""
+        opt = kwargs.get('adaptive_interior', (self.train_cfg.get('train_data') or {}).get('adaptive_interior'))
+        if opt is None or opt is False:
+            return None
+        if opt is True:
+            opt = {}
+        unknown = set(opt) - {'pool_factor', 'k', 'c', 'every', 'sampler'}
+        if unknown:
+            raise ValueError('adaptive_interior: unknown keys %s (known: pool_factor, k, c, every, sampler)' % sorted(unknown))
+        opt = dict({'pool_factor': 8, 'k': 1.0, 'c': 1.0, 'every': 1, 'sampler': None}, **opt)
+        if int(opt['every']) < 1:
+            raise ValueError('adaptive_interior: every must be >= 1, got %r' % (opt['every'],))
+        return opt
+
+    def _adaptive_sampler(self, opt, batch, kwargs):
+        """The sampler that draws the pool: the option's own, the batch's 'sampler' entry, or the sample source's `.sampler` attribute."""
+        src = kwargs.get('samples', (self.train_cfg.get('train_data') or {}).get('samples'))
+        if src == 'synthetic':
+            src = getattr(self, '_synthetic_samples', None)
+        for s in (opt.get('sampler'), batch.get('sampler'), getattr(src, 'sampler', None)):
+            if s is not None:
+                return s
+        raise RuntimeError("adaptive_interior needs the CollocationSampler that draws the pool: give it as adaptive_interior['sampler'], as the batch's "
+                           "'sampler' entry, or as the `.sampler` attribute of the samples source (SyntheticSamples has one)")
+
     def training_step(self, batch: dict, optimizer, with_pde=True, max_norm=2.5e7, grad_sync=None):
         """One step body (:443-515 / :990-1065): data loss on the margin points, PDE losses on interior and margin points,
         backward, clip_grad_norm_(2.5e7), optimizer step.  `batch` holds device tensors: field_data [1,159,2405],
@@ -740,6 +792,7 @@ class InterfacePhysics(nn.Module):
         # validation (:629-745): only with a source; without one nothing below runs and the loop is what it was
         valid_src = self._valid_samples(kwargs)
         vlog = self._ValidationLoop(self, valid_src, kwargs.get('log_path'), rank, world, num_epoch, device) if valid_src is not None else None
+        adaptive = self._adaptive_option(kwargs)                        # None: not one extra call below
         for epoch in range(current_epoch, num_epoch):
             for batch_id, batch in enumerate(self._epoch_samples(kwargs, epoch, rank, world, dist_mode)):   # DistributedSampler (:936): one field sample per rank per step
                 with_pde = with_pde_cfg and global_step >= pde_start
@@ -749,6 +802,10 @@ class InterfacePhysics(nn.Module):
                 log_now = vlog is not None and global_step % log_step == 1
                 if log_now:              # the training batch's six errors (:518-530) from the predictions the step is about to train on
                     train_vars = self.validation_step(batch, with_pde=False)['variables']
+                if adaptive is not None and with_pde and (global_step - 1) % int(adaptive['every']) == 0:
+                    # the interior points go where this step's network violates its equations most (adaptive_interior)
+                    batch = self.adaptive_interior(batch, self._adaptive_sampler(adaptive, batch, kwargs), pool_factor=adaptive['pool_factor'],
+                                                   k=adaptive['k'], c=adaptive['c'])
                 loss, parts, gnorm = self.training_step(batch, optimizer, with_pde=with_pde, grad_sync=sync)
                 last = {'loss': loss, 'parts': parts, 'grad_norm': gnorm}
                 if rank == 0 and global_step % log_step == 1:
@@ -858,7 +915,9 @@ class InterfacePhysics(nn.Module):
         `physics_latest.pth` (:389-397).  kwargs of the reference: checkpoint_path, log_path (written only with a validation source: the
         reference's two lines per log step in log_<date>.txt and metrics.jsonl; no tensorboard / JPEG output here);
         added: samples (see _train_samples), valid_samples (see _valid_samples; none: no validation, the loop of before), validate_every_epoch,
-        valid_lead_batch, num_epoch, max_steps, pde_start_step, device.  With a validation source the result carries `last_validation`."""
+        valid_lead_batch, num_epoch, max_steps, pde_start_step, device, adaptive_interior (None, or dict(pool_factor, k, c, every, sampler): once
+        the PDE losses are on, every every-th step's interior points are redrawn by adaptive_interior before the step; unset: the loop of before).
+        With a validation source the result carries `last_validation`."""
         return self._run_train(False, **kwargs)
 
     def run_train_interface_dist(self, **kwargs):

@@ -1021,3 +1021,23 @@ class PackedField:
         geo, ph = self.cfg.geometry(), self.cfg.physics()
         L.check(L.load().dpn_residual_points(_ptr(out_n), _ptr(jac_n), _ptr(f), out_n.shape[0], ctypes.byref(geo), ctypes.byref(ph), _ptr(res),
                                              _stream()), 'dpn_residual_points')
+
+    def residual_scores(self, x, y, t, f, coord_data, factors, k=1.0):
+        """Scores of a pool of candidate points for residual-weighted sampling (CollocationSampler.get_inter_data_adaptive): `residuals` on the m
+        points, then dpn_adaptive_scores -- score_i = sum_e factors[e] * res_ie ** 2 in fp64, factors = six floats in LOSS_ORDER.  Returns
+        (score [m] fp64, stats [3] fp64: sum score ** k, the count of non-finite scores (written as 0), max score; res [m, 6] fp32; scratch, the
+        dpn_adaptive_scratch_doubles(m) doubles the selection goes on to use)."""
+        lib = L.load()
+        m, dev = coord_data.shape[0], coord_data.device
+        if m > self.ws.n:
+            raise ValueError('residual_scores: %d points, but this PackedField was packed for chunks of %d' % (m, self.ws.n))
+        size = int(lib.dpn_adaptive_scratch_doubles(m))
+        if size <= 0:
+            raise ValueError('residual_scores: %d candidates; dpn_adaptive_select takes 1 .. 2**20' % m)
+        res = torch.empty((m, 6), dtype=torch.float32, device=dev)
+        self.residuals(x, y, t, f, coord_data, res)
+        score, scratch = torch.empty(m, dtype=torch.float64, device=dev), torch.empty(size, dtype=torch.float64, device=dev)
+        stats = torch.empty(3, dtype=torch.float64, device=dev)
+        fac = (ctypes.c_double * 6)(*[float(v) for v in factors])
+        L.check(lib.dpn_adaptive_scores(_ptr(res), m, fac, float(k), _ptr(score), _ptr(stats), _ptr(scratch), _stream()), 'dpn_adaptive_scores')
+        return score, stats, res, scratch

@@ -138,6 +138,62 @@ class CollocationSampler:
         out = (x, y, t, cd, f.unsqueeze(1))
         return out + (raw,) if with_raw else out
 
+    def select_weighted(self, score, pool_rows, n, k=1.0, c=1.0, offset=0, scratch=None, with_details=False):
+        """dpn_adaptive_select: n rows drawn with replacement from the m candidates pool_rows = (x, y, t, f [m], coord_data [m, 6]) with probability
+        ~ score ** k / mean(score ** k) + c (score [m] fp64 on the device), by the inverse of the weights' fp64 prefix sum at the uniforms of Philox
+        stream 2, counters offset .. offset + n (on top of the bound step counter's share).  Returns (x, y, t, f, coord_data) of the drawn rows, and with
+        with_details also (idx int32 [n], u fp64 [n], picked_score fp64 [n], scratch: its first m doubles are the prefix sum)."""
+        require_gpu(score, 'score', 'select_weighted')
+        if score.dtype != torch.float64 or score.dim() != 1 or not score.is_contiguous():
+            raise ValueError('score must be a contiguous fp64 vector')
+        lib = L.load()
+        m, dev = score.shape[0], score.device
+        size = int(lib.dpn_adaptive_scratch_doubles(m))
+        if size <= 0:
+            raise ValueError('select_weighted: %d candidates; dpn_adaptive_select takes 1 .. 2**20' % m)
+        x, y, t, f, cd = pool_rows
+        if any(v.shape[0] != m or v.dtype != torch.float32 or not v.is_contiguous() for v in pool_rows) or tuple(cd.shape) != (m, 6):
+            raise ValueError('pool_rows: x, y, t, f [m] and coord_data [m, 6], contiguous fp32, one row per score')
+        if int(n) < 1:
+            raise ValueError('n must be positive, got %r' % (n,))
+        if not (k >= 0.0 and c >= 0.0 and np.isfinite(k) and np.isfinite(c)):
+            raise ValueError('k and c must be finite and >= 0, got k = %r, c = %r' % (k, c))
+        if scratch is None:
+            scratch = torch.empty(size, dtype=torch.float64, device=dev)
+        elif scratch.dtype != torch.float64 or scratch.numel() < size:
+            raise ValueError('scratch: at least %d fp64 values' % size)
+        ox, oy, ot, of = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(4))
+        ocd = torch.empty((n, 6), dtype=torch.float32, device=dev)
+        idx = torch.empty(n, dtype=torch.int32, device=dev) if with_details else None
+        u, picked = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(2)) if with_details else (None, None)
+        L.check(lib.dpn_adaptive_select(_ptr(score), m, float(k), float(c), _ptr(x), _ptr(y), _ptr(t), _ptr(f), _ptr(cd), n, self.seed, int(offset),
+                                        _ptr(self._step_dev), self._stride, _ptr(ox), _ptr(oy), _ptr(ot), _ptr(of), _ptr(ocd), _ptr(idx), _ptr(u),
+                                        _ptr(picked), _ptr(scratch), _stream()), 'dpn_adaptive_select')
+        out = (ox, oy, ot, of, ocd)
+        return out + (idx, u, picked, scratch) if with_details else out
+
+    def get_inter_data_adaptive(self, packed_field, factors, n: int = 4096, pool: int = None, k: float = 1.0, c: float = 1.0, with_details: bool = False):
+        """get_inter_data with the n interior points placed where the PDE residuals are large (residual-based adaptive sampling, Wu et al. 2023):
+        `pool` (default 8 n) points are drawn as get_inter_data draws them, scored by packed_field (point_path.PackedField of the field's current
+        weights) with score_i = sum_e factors[e] * residual_ie ** 2 (factors: six floats in LOSS_ORDER), and n of them are drawn with replacement with
+        probability ~ score ** k / mean(score ** k) + c.  k = 0 is uniform sampling again; c = 0 never draws a point of zero residual.
+        -> inter_x, inter_y, inter_t, inter_data, inter_f as get_inter_data; with_details adds a dict: idx [n] (rows of the pool), u [n], picked_score
+        [n], score [pool], nonfinite (device scalar: scores that were not finite and count as 0), stats [3], pool (x, y, t, f, coord_data), res, cdf.
+        The pool advances the Philox offset by `pool` (and counts against bind_step_counter's reservation); the selection's uniforms are stream 2 of
+        the pool's first n counters.  Nothing here allocates outside torch's caching allocator or synchronises."""
+        n, pool = int(n), int(8 * n if pool is None else pool)
+        if n < 1 or pool < 1:
+            raise ValueError('n and pool must be positive, got %d, %d' % (n, pool))
+        first = self.offset
+        x, y, t, f, cd, _, _ = self._run(L.SAMPLE_INTERIOR, pool)
+        score, stats, res, scratch = packed_field.residual_scores(x, y, t, f, cd, factors, k)
+        sel = self.select_weighted(score, (x, y, t, f, cd), n, k, c, offset=first, scratch=scratch, with_details=with_details)
+        out = (sel[0], sel[1], sel[2], sel[4], sel[3].unsqueeze(1))
+        if not with_details:
+            return out
+        return out + ({'idx': sel[5], 'u': sel[6], 'picked_score': sel[7], 'score': score, 'nonfinite': stats[1], 'stats': stats,
+                       'pool': (x, y, t, f, cd), 'res': res, 'cdf': scratch[:pool]},)
+
     def get_item_label_data(self, n: int = 20480, with_raw: bool = False):
         """-> margin_x, margin_y, margin_t, margin_data, margin_f, margin_input_data  (physics_dataset.py:429)."""
         x, y, t, f, cd, lab, raw = self._run(L.SAMPLE_MARGIN, n, want_labels=self.labels is not None, want_raw=with_raw)

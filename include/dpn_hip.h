@@ -483,6 +483,30 @@ int dpn_gemm_fp8_mx(int M, int N, int K, const float* A, int lda, const float* W
 /* Self-test of the MFMA fragment-layout assumptions in dpn_layout.h (A = I against an asymmetric B). Returns 0 if they hold. */
 int dpn_selftest(void* scratch_dev /* >= 64 KiB */, void* stream);
 
+/* Residual-weighted interior collocation points (csrc/dpn_adaptive.hip): m candidates -- a pool of uniform interior draws -- are scored by their PDE
+ * residuals and n points are drawn from them, with replacement, with probability p_i ~ w_i = s_i^k / mean_j(s_j^k) + c  (residual-based adaptive
+ * sampling; k = c = 1 are the usual defaults).  fp64 throughout, no atomics, every sum in one fixed order: two runs agree bitwise.
+ * scratch: dpn_adaptive_scratch_doubles(m) doubles on the device (0 for an m that is not supported: m <= 0 or m > 2^20), shared by both calls;
+ * after dpn_adaptive_select its first m doubles hold the inclusive prefix sum of the weights.
+ *
+ * dpn_adaptive_scores: res[m][6] = dpn_residual_points' rows, factors = six HOST doubles (the loss factors in the order of the residuals);
+ *   score[i] = sum_e factors[e] * res[i][e]^2, every product and sum rounded once in fp64, e ascending; a score that is not finite is written as 0
+ *   and counted.  stats[3] (device): sum_i score_i^k, the count of non-finite scores, max_i score_i.
+ * dpn_adaptive_select: score[m] (negative or non-finite entries count as 0), then
+ *   w_i = score_i^k / mean(score^k) + c; all w_i = 1 when the mean is 0 (or not finite); cdf = inclusive prefix sum of w (block-local scans, a scan of
+ *   the block totals, a final pass), total = cdf[m - 1];
+ *   u_j = the 53-bit uniform of Philox-4x32-10, key = seed, counter = offset + *step_dev * stride + j (step_dev NULL: offset + j), stream id 2 -- the
+ *   same counters as points offset .. of dpn_sample_points_replay, whose own draws use stream ids 0 and 1;
+ *   idx_j = the smallest i with cdf[i] > u_j * total (a product that rounds up to total is taken as the last double below it), so an entry with w_i = 0 is
+ *   never drawn;  out row j = row idx_j of x, y, t, f [m], coord_data [m][6].  idx [n], u [n], picked_score [n] (= score[idx_j]) may be NULL.
+ * -1: m <= 0, m > 2^20, n <= 0, a NULL required pointer, k or c negative or not finite. */
+int64_t dpn_adaptive_scratch_doubles(int64_t m);
+int dpn_adaptive_scores(const float* res, int64_t m, const double* factors, double k, double* score, double* stats, double* scratch, void* stream);
+int dpn_adaptive_select(const double* score, int64_t m, double k, double c, const float* x, const float* y, const float* t, const float* f,
+                        const float* coord_data, int64_t n, uint64_t seed, uint64_t offset, const int32_t* step_dev, uint64_t stride,
+                        float* out_x, float* out_y, float* out_t, float* out_f, float* out_coord_data, int32_t* idx, double* u, double* picked_score,
+                        double* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

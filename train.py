@@ -2,6 +2,7 @@
 """Launcher with the reference's three flags (reference train.py:17-19, :34-48): --config_file, --checkpoint_path, --log_path.
 
     python train.py [--config_file cfg.py] [--checkpoint_path DIR] [--log_path DIR] [--dist] [--max_steps N] [--synthetic] [--valid_synthetic]
+                    [--adaptive_interior]
 
 The reference reads the config with mmcv.Config.fromfile (absent here, and moved to mmengine in the pinned mmcv: SURVEY section 0, defect
 3), builds the interface with `builder_models(**cfg['config'])` and calls `run_train_interface(checkpoint_path=..., log_path=...)`.  The
@@ -32,6 +33,9 @@ parse.add_argument('--synthetic', action='store_true', help="samples='synthetic'
 parse.add_argument('--valid_synthetic', action='store_true', help="valid_samples='synthetic': a validation source of random field samples drawn from "
                    'another seed than --synthetic; at every log step the loop then evaluates one of them and writes the training / validation lines '
                    'to log_<date>.txt and metrics.jsonl under --log_path')
+parse.add_argument('--adaptive_interior', action='store_true', help='once the PDE losses are on, redraw every step\'s interior collocation points where '
+                   'the residuals are large (adaptive_interior=dict(pool_factor=8, k=1, c=1, every=1)); the sampler is the samples source\'s own '
+                   '(--synthetic has one)')
 
 
 def load_config(path):
@@ -61,6 +65,8 @@ if __name__ == '__main__':
         kwargs['samples'] = 'synthetic'
     if args.valid_synthetic:
         kwargs['valid_samples'] = 'synthetic'
+    if args.adaptive_interior:
+        kwargs['adaptive_interior'] = dict(pool_factor=8, k=1.0, c=1.0, every=1)
     run = model.run_train_interface_dist if args.dist else model.run_train_interface
     out = run(**kwargs)
     print('done: epoch %d, global_step %d, lr %.3e' % (out['epoch'], out['global_step'], out['lr']))
