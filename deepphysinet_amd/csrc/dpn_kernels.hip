@@ -2704,6 +2704,8 @@ int dpn_clip_adam(int n_tensors, float* const* params, const float* const* grads
                   const int64_t* numel, double* scratch_dev, int* step_dev, float lr, float beta1, float beta2, float eps, float weight_decay,
                   float max_norm, float* out_norm_dev, void* stream) {
     if (n_tensors <= 0 || !params || !grads || !exp_avg || !exp_avg_sq || !numel || !scratch_dev || !step_dev) return -1;
+    // every size is checked before the first launch: a refusal bumps no step counter and writes no partial, whichever table the bad tensor is in
+    for (int i = 0; i < n_tensors; ++i) if (numel[i] <= 0 || numel[i] > 0x7fffffff) return -1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     double* sumsq = scratch_dev;                 // [0]: sum of squares of all gradients; [1 ..]: one partial per 2048-element chunk
     double* partial = scratch_dev + 1;
@@ -2714,7 +2716,6 @@ int dpn_clip_adam(int n_tensors, float* const* params, const float* const* grads
             t.n = (n_tensors - t0 < kAdamMaxTensors) ? n_tensors - t0 : kAdamMaxTensors;
             int chunks = 0;
             for (int i = 0; i < t.n; ++i) {
-                if (numel[t0 + i] <= 0 || numel[t0 + i] > 0x7fffffff) return -1;
                 t.p[i] = params[t0 + i]; t.g[i] = grads[t0 + i]; t.m[i] = exp_avg[t0 + i]; t.v[i] = exp_avg_sq[t0 + i];
                 t.numel[i] = (int)numel[t0 + i];
                 t.chunk_start[i] = chunks;
@@ -2742,6 +2743,8 @@ static int clip_adam_flat_impl(int n_tensors, float* const* params, const float*
                                float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, float lr, float beta1, float beta2, float eps,
                                float weight_decay, float max_norm, float* out_norm_dev, const float* hyper_dev, void* stream) {
     if (n_tensors <= 0 || !params || !grads || !numel || !exp_avg_flat || !exp_avg_sq_flat || !scratch_dev || !step_dev) return -1;
+    // every size is checked before the first launch: a refusal bumps no step counter and writes no partial, whichever table the bad tensor is in
+    for (int i = 0; i < n_tensors; ++i) if (numel[i] <= 0 || numel[i] > 0x7fffffff) return -1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     double* sumsq = scratch_dev;
     double* partial = scratch_dev + 1;
@@ -2754,7 +2757,6 @@ static int clip_adam_flat_impl(int n_tensors, float* const* params, const float*
             t.v_flat = exp_avg_sq_flat + (int64_t)base_chunk * kAdamChunk;
             int chunks = 0;
             for (int i = 0; i < t.n; ++i) {
-                if (numel[t0 + i] <= 0 || numel[t0 + i] > 0x7fffffff) return -1;
                 t.p[i] = params[t0 + i]; t.g[i] = grads[t0 + i];
                 t.numel[i] = (int)numel[t0 + i];
                 t.chunk_start[i] = chunks;

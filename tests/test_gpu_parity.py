@@ -739,12 +739,14 @@ def test_full_grid_properties(prec):
 
 
 def test_fused_clip_adam_equals_torch():
-    """dpn_clip_adam vs clip_grad_norm_ + torch.optim.Adam(weight_decay) over three steps, with the clip active and inactive."""
+    """FusedClipAdam (dpn_clip_adam_flat_dev on the optimiser's flat buffers) vs clip_grad_norm_ + torch.optim.Adam(weight_decay) over three
+    steps, with the clip active and inactive: parameters and both moments.  The fp64 bounds, the other two entry points and the multi-table
+    launches are tests/test_gpu_optim.py's."""
     from deepphysinet_amd.optim import FusedClipAdam
     dev = _dev()
     for max_norm in (1e9, 0.5):
         torch.manual_seed(0)
-        shapes = [(256, 193), (7,), (1, 128, 256), (300, 17), (1,)] * 20            # 100 tensors: exercises the two-table path
+        shapes = [(256, 193), (7,), (1, 128, 256), (300, 17), (1,)] * 20            # 100 tensors: ONE table of the flat form (160 per launch)
         a = [torch.randn(s, device=dev).requires_grad_(True) for s in shapes]
         b = [t.detach().clone().requires_grad_(True) for t in a]
         ref = torch.optim.Adam(a, lr=1e-3, weight_decay=1e-2)
@@ -757,8 +759,10 @@ def test_fused_clip_adam_equals_torch():
             ref.step()
             n_mine = mine.step()
             assert abs(float(n_mine) - float(n_ref)) <= 1e-5 * float(n_ref)
-            for t, u in zip(a, b):
+            for t, u, m, v in zip(a, b, mine.exp_avg, mine.exp_avg_sq):
                 assert torch.allclose(t, u, rtol=2e-5, atol=2e-7)
+                assert torch.allclose(ref.state[t]['exp_avg'], m, rtol=2e-5, atol=2e-7)
+                assert torch.allclose(ref.state[t]['exp_avg_sq'], v, rtol=2e-5, atol=2e-7)
         assert int(mine.step_count) == 3
 
 
