@@ -8,14 +8,38 @@ import shutil
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRCS = [os.path.join(HERE, 'csrc', 'dpn_kernels.hip'), os.path.join(HERE, 'csrc', 'dpn_encoder.hip'),
-        os.path.join(HERE, 'csrc', 'dpn_sampler.hip'), os.path.join(HERE, 'csrc', 'dpn_fp8.hip'),
-        os.path.join(HERE, 'csrc', 'dpn_encoder_chain.hip'), os.path.join(HERE, 'csrc', 'dpn_eval.hip'),
-        os.path.join(HERE, 'csrc', 'dpn_adaptive.hip')]
-DEPS = SRCS + [os.path.join(HERE, 'csrc', 'dpn_layout.h'), os.path.join(HERE, 'csrc', 'dpn_fwd_tiles.h'), os.path.join(HERE, 'csrc', 'dpn_ring_kernels.inc'),
-               os.path.join(HERE, 'csrc', 'dpn_tiles_kernels.inc'), os.path.join(HERE, 'csrc', 'dpn_residual_body.inc'), os.path.join(os.path.dirname(HERE), 'include', 'dpn_hip.h'),
-               os.path.join(os.path.dirname(HERE), 'include', 'dpn_hip_experiments.h')]
 LIB = os.path.join(HERE, 'libdpn_hip.so')
+
+
+# (source, extra flags, object name).  One unit per kernel family.  Only the point forward / backward kernels are compiled with MFMA results
+# in VGPRs (no v_accvgpr_read per epilogue element: forward kernel -10 %); the weight-gradient kernel, the GEMMs and the optimiser measure
+# better with hipcc's default AGPR accumulators.  tools/variant_build.py --unit=I and EXP_UNITS address units by index: append, never reorder.
+def _src(name):
+    return os.path.join(HERE, 'csrc', name)
+
+
+UNITS = [(_src('dpn_point.hip'), ['-mllvm', '-amdgpu-mfma-vgpr-form'], 'dpn_point.o'),
+         (_src('dpn_wgrad.hip'), [], 'dpn_wgrad.o'),      # weight packing, weight-gradient and finish kernels, sizes, self-test
+         (_src('dpn_encoder.hip'), [], 'dpn_encoder.o'),
+         (_src('dpn_sampler.hip'), [], 'dpn_sampler.o'),
+         (_src('dpn_fp8.hip'), [], 'dpn_fp8.o'),
+         (_src('dpn_encoder_chain.hip'), ['-mllvm', '-amdgpu-mfma-vgpr-form'], 'dpn_encoder_chain.o'),
+         (_src('dpn_eval.hip'), [], 'dpn_eval.o'),        # the validation pass's label statistics
+         (_src('dpn_adaptive.hip'), [], 'dpn_adaptive.o'),  # residual-weighted collocation points (scores, prefix sum, draw)
+         (_src('dpn_residual.hip'), [], 'dpn_residual.o'),  # residual and SmoothL1 losses
+         (_src('dpn_gemm.hip'), [], 'dpn_gemm.o'),        # the exact-fp32 GEMM family
+         (_src('dpn_optim.hip'), [], 'dpn_optim.o')]      # fused clip + Adam
+SRCS = [u[0] for u in UNITS]
+COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC']
+
+
+def _listed(folder, suffixes):
+    return sorted(os.path.join(folder, f) for f in os.listdir(folder) if f.endswith(suffixes))
+
+
+# every source, header and include file, taken from the directories (csrc/_obj is not looked into): a file forgotten in a hand-kept list would
+# leave a stale libdpn_hip.so in place, and the tests would run it
+DEPS = _listed(os.path.join(HERE, 'csrc'), ('.hip', '.h', '.inc')) + _listed(os.path.join(os.path.dirname(HERE), 'include'), ('.h',))
 
 
 def needs_build() -> bool:
@@ -23,20 +47,6 @@ def needs_build() -> bool:
         return True
     t = os.path.getmtime(LIB)
     return any(os.path.getmtime(d) > t for d in DEPS)
-
-
-# (source, extra flags, object name).  dpn_kernels.hip is two translation units: the point forward / backward kernels are compiled with
-# MFMA results in VGPRs (no v_accvgpr_read per epilogue element: forward kernel -10 %), the rest (weight-gradient kernel, GEMMs,
-# optimiser) measures better with hipcc's default AGPR accumulators -- see the DPN_TU comment in the source.
-UNITS = [(SRCS[0], ['-DDPN_TU=1', '-mllvm', '-amdgpu-mfma-vgpr-form'], 'dpn_point.o'),
-         (SRCS[0], ['-DDPN_TU=2'], 'dpn_rest.o'),
-         (SRCS[1], [], 'dpn_encoder.o'),
-         (SRCS[2], [], 'dpn_sampler.o'),
-         (SRCS[3], [], 'dpn_fp8.o'),
-         (SRCS[4], ['-mllvm', '-amdgpu-mfma-vgpr-form'], 'dpn_encoder_chain.o'),
-         (SRCS[5], [], 'dpn_eval.o'),              # the validation pass's label statistics: a unit of its own, the others' objects are unchanged
-         (SRCS[6], [], 'dpn_adaptive.o')]          # residual-weighted collocation points (scores, prefix sum, draw): likewise
-COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC']
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -78,8 +88,7 @@ def build_experiments(force: bool = False) -> str:
     """libdpn_hip_exp.so: the product objects with the unit that holds shelved kernels recompiled -DDPN_EXPERIMENTS (their entry points are
     compiled out of the product library).  Tests of those kernels and the tools under tools/ that measure them load it."""
     build_library()
-    deps = DEPS + [os.path.join(os.path.dirname(HERE), 'include', 'dpn_hip_experiments.h')]
-    if not force and os.path.exists(EXP_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(EXP_LIB) for d in deps):
+    if not force and os.path.exists(EXP_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(EXP_LIB) for d in DEPS):
         return EXP_LIB
     hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
     obj_dir = os.path.join(HERE, 'csrc', '_obj')

@@ -1,4 +1,4 @@
-// Forward + Jacobian kernel of the parity-grade (hi+lo) mode, TILE-SPLIT form.  Included by dpn_kernels.hip (point unit).
+// Forward + Jacobian kernel of the parity-grade (hi+lo) mode, TILE-SPLIT form.  Included by dpn_point.hip.
 //
 // Same arithmetic as dpn_fwd_kernel (reference model/variable_net.py:49-87 restated as in DESIGN.md section 3; same packed weight
 // stream, same fragment algebra of dpn_layout.h, same accumulation order per output tile: saved state and Jacobian are bit-identical),

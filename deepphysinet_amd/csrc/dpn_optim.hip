@@ -1,0 +1,234 @@
+// MI355X (gfx950 / CDNA4): global-norm clip + Adam over lists of tensors or flat moment buffers.  A unit of its own.
+//
+// Kernel inventory
+//   dpn_gradnorm_kernel / dpn_gradnorm_reduce_kernel   one fp64 partial per 2048-element chunk, added in a fixed order
+//   dpn_adam_kernel                                    the clipped update
+// No kernel in this file uses atomics: every reduction is fixed-order, the whole step is bitwise reproducible.
+#include "dpn_device.h"
+
+// ------------------------------------------------------------------------------------------------ fused clip + Adam
+// clip_grad_norm_(max_norm) followed by torch.optim.Adam(lr, betas, eps, weight_decay) (L2-in-gradient, not AdamW), as in
+// interface_physics.py:514-515 / cfg:151-155, for a LIST of tensors per launch (pointer table in the kernel arguments).
+constexpr int kAdamMaxTensors = 72;
+constexpr int kAdamChunk = 2048;                 // elements per block
+struct AdamTable {
+    float* p[kAdamMaxTensors];
+    const float* g[kAdamMaxTensors];
+    float* m[kAdamMaxTensors];
+    float* v[kAdamMaxTensors];
+    int chunk_start[kAdamMaxTensors + 1];        // prefix sum of ceil(numel / kAdamChunk)
+    int numel[kAdamMaxTensors];
+    int n;
+};
+// Optimiser state kept by the caller as ONE flat buffer per moment, tensor i at offset chunk_start[i] * kAdamChunk (each tensor padded to
+// whole chunks): no per-tensor state pointers, so 160 tensors fit in the kernel arguments and a PhysicsNet is one launch per pass.
+constexpr int kAdamFlatMaxTensors = 160;
+struct AdamTableFlat {
+    float* p[kAdamFlatMaxTensors];
+    const float* g[kAdamFlatMaxTensors];
+    int chunk_start[kAdamFlatMaxTensors + 1];
+    int numel[kAdamFlatMaxTensors];
+    float* m_flat;
+    float* v_flat;
+    int n;
+};
+static_assert(sizeof(AdamTableFlat) + 64 <= 4096, "kernel arguments are limited to 4 KB");
+DEV float* table_m(const AdamTable& t, int ti) { return t.m[ti]; }
+DEV float* table_v(const AdamTable& t, int ti) { return t.v[ti]; }
+DEV float* table_m(const AdamTableFlat& t, int ti) { return t.m_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+DEV float* table_v(const AdamTableFlat& t, int ti) { return t.v_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+template <class Table>
+DEV int adam_find(const Table& t, int blk) {
+    int lo = 0, hi = t.n - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (t.chunk_start[mid] <= blk) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+template <class Table>
+__global__ __launch_bounds__(256) void dpn_gradnorm_kernel(Table t, double* partial, int* step, int bump_step) {
+    // one fp64 partial per block (no atomics: 2.7k serialised fp64 atomics on one address cost more than reading the gradients);
+    // dpn_gradnorm_reduce_kernel adds them in a fixed order -> the clip coefficient is run-to-run deterministic
+    if (bump_step && blockIdx.x == 0 && threadIdx.x == 0) *step += 1;       // device-side step counter: graph replays advance it
+    const int ti = adam_find(t, blockIdx.x);
+    const int base = (blockIdx.x - t.chunk_start[ti]) * kAdamChunk;
+    const float* g = t.g[ti];
+    const int end = min(base + kAdamChunk, t.numel[ti]);
+    float s = 0.f;
+    if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {                         // 16-byte loads over the aligned body, scalars for the tail
+        const int end4 = base + ((end - base) & ~3);
+        for (int i = base + 4 * threadIdx.x; i < end4; i += 1024) {
+            const float4 q = *reinterpret_cast<const float4*>(g + i);
+            s = fmaf(q.x, q.x, s); s = fmaf(q.y, q.y, s); s = fmaf(q.z, q.z, s); s = fmaf(q.w, q.w, s);
+        }
+        for (int i = end4 + threadIdx.x; i < end; i += 256) s = fmaf(g[i], g[i], s);
+    } else {
+        for (int i = base + threadIdx.x; i < end; i += 256) s = fmaf(g[i], g[i], s);
+    }
+    double d = (double)s;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o);
+    __shared__ double red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = d;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ __launch_bounds__(256) void dpn_gradnorm_reduce_kernel(const double* partial, int n, double* sumsq) {
+    double d = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) d += partial[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o);
+    __shared__ double red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = d;
+    __syncthreads();
+    if (threadIdx.x == 0) *sumsq = (red[0] + red[1]) + (red[2] + red[3]);
+}
+template <class Table>
+__global__ __launch_bounds__(256) void dpn_adam_kernel(Table t, const double* sumsq, const int* step, float lr, float b1, float b2, float eps,
+                                                       float wd, float max_norm, float* out_norm, const float* hyper) {
+    // hyper (optional, device): [lr, beta1, beta2, eps, weight_decay, max_norm, grad_scale] read at run time, so that a step captured in
+    // a hipGraph follows a learning-rate schedule (a by-value lr is frozen into the graph); grad_scale multiplies every gradient
+    // before the norm and the update (1 / world_size after a SUM all-reduce)
+    float gscale = 1.f;
+    if (hyper) { lr = hyper[0]; b1 = hyper[1]; b2 = hyper[2]; eps = hyper[3]; wd = hyper[4]; max_norm = hyper[5]; gscale = hyper[6]; }
+    const float total = (float)sqrt(*sumsq) * gscale;
+    if (out_norm && blockIdx.x == 0 && threadIdx.x == 0) *out_norm = total;
+    const float coef = fminf(max_norm / (total + 1e-6f), 1.0f) * gscale;    // clip_grad_norm_'s clamp(max_norm / (norm + 1e-6), max=1)
+    const float st = (float)(*step);
+    const float bc1 = 1.f - powf(b1, st), bc2s = sqrtf(1.f - powf(b2, st));
+    const float step_size = lr / bc1;
+    const int ti = adam_find(t, blockIdx.x);
+    const int base = (blockIdx.x - t.chunk_start[ti]) * kAdamChunk;
+    float* p = t.p[ti]; const float* g = t.g[ti]; float* m = table_m(t, ti); float* v = table_v(t, ti);
+    const int end = min(base + kAdamChunk, t.numel[ti]);
+    auto upd = [&](float& pi, const float graw, float& mi, float& vi) __attribute__((always_inline)) {
+        const float gi = fmaf(wd, pi, graw * coef);
+        mi = fmaf(b1, mi, (1.f - b1) * gi);                                  // lerp(m, g, 1-b1)
+        vi = fmaf(b2, vi, (1.f - b2) * gi * gi);
+        pi = pi - step_size * mi / (sqrtf(vi) / bc2s + eps);
+    };
+    int scalar_from = base;
+    if (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) == 0) {
+        const int end4 = base + ((end - base) & ~3);
+        for (int i = base + 4 * threadIdx.x; i < end4; i += 1024) {
+            // the moments and the gradient are touched by nobody else: streamed past the caches (the parameters stay cacheable, the
+            // next step reads them first)
+            typedef __attribute__((ext_vector_type(4))) float f32x4_t;
+            float4 P = *reinterpret_cast<float4*>(p + i);
+            // (round 6 once more, rocprofv3 in the step: the gradient loaded without the hint 27.2, all three loads without 27.6, stores too 28.3 against 25.2 us)
+            const f32x4_t Mv = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(m + i));
+            const f32x4_t Vv = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(v + i));
+            const f32x4_t Gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(g + i));
+            float4 M = make_float4(Mv[0], Mv[1], Mv[2], Mv[3]), V = make_float4(Vv[0], Vv[1], Vv[2], Vv[3]);
+            const float4 G = make_float4(Gv[0], Gv[1], Gv[2], Gv[3]);
+            upd(P.x, G.x, M.x, V.x); upd(P.y, G.y, M.y, V.y); upd(P.z, G.z, M.z, V.z); upd(P.w, G.w, M.w, V.w);
+            *reinterpret_cast<float4*>(p + i) = P;
+            __builtin_nontemporal_store(f32x4_t{M.x, M.y, M.z, M.w}, reinterpret_cast<f32x4_t*>(m + i));
+            __builtin_nontemporal_store(f32x4_t{V.x, V.y, V.z, V.w}, reinterpret_cast<f32x4_t*>(v + i));
+        }
+        scalar_from = end4;
+    }
+    for (int i = scalar_from + threadIdx.x; i < end; i += 256) {
+        float pi = p[i], mi = m[i], vi = v[i];
+        upd(pi, g[i], mi, vi);
+        p[i] = pi; m[i] = mi; v[i] = vi;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ C ABI
+extern "C" {
+
+int64_t dpn_clip_adam_scratch_doubles(int n_tensors, const int64_t* numel) {
+    if (n_tensors <= 0 || !numel) return -1;
+    int64_t chunks = 0;
+    for (int i = 0; i < n_tensors; ++i) chunks += (numel[i] + kAdamChunk - 1) / kAdamChunk;
+    return 1 + chunks;
+}
+
+int dpn_clip_adam(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                  const int64_t* numel, double* scratch_dev, int* step_dev, float lr, float beta1, float beta2, float eps, float weight_decay,
+                  float max_norm, float* out_norm_dev, void* stream) {
+    if (n_tensors <= 0 || !params || !grads || !exp_avg || !exp_avg_sq || !numel || !scratch_dev || !step_dev) return -1;
+    // every size is checked before the first launch: a refusal bumps no step counter and writes no partial, whichever table the bad tensor is in
+    for (int i = 0; i < n_tensors; ++i) if (numel[i] <= 0 || numel[i] > 0x7fffffff) return -1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    double* sumsq = scratch_dev;                 // [0]: sum of squares of all gradients; [1 ..]: one partial per 2048-element chunk
+    double* partial = scratch_dev + 1;
+    for (int pass = 0; pass < 2; ++pass) {
+        int base_chunk = 0;
+        for (int t0 = 0; t0 < n_tensors; t0 += kAdamMaxTensors) {
+            AdamTable t;
+            t.n = (n_tensors - t0 < kAdamMaxTensors) ? n_tensors - t0 : kAdamMaxTensors;
+            int chunks = 0;
+            for (int i = 0; i < t.n; ++i) {
+                t.p[i] = params[t0 + i]; t.g[i] = grads[t0 + i]; t.m[i] = exp_avg[t0 + i]; t.v[i] = exp_avg_sq[t0 + i];
+                t.numel[i] = (int)numel[t0 + i];
+                t.chunk_start[i] = chunks;
+                chunks += (t.numel[i] + kAdamChunk - 1) / kAdamChunk;
+            }
+            t.chunk_start[t.n] = chunks;
+            if (pass == 0) hipLaunchKernelGGL(dpn_gradnorm_kernel<AdamTable>, dim3(chunks), dim3(256), 0, s, t, partial + base_chunk, step_dev, t0 == 0 ? 1 : 0);
+            else hipLaunchKernelGGL(dpn_adam_kernel<AdamTable>, dim3(chunks), dim3(256), 0, s, t, (const double*)sumsq, (const int*)step_dev, lr, beta1,
+                                    beta2, eps, weight_decay, max_norm, out_norm_dev, (const float*)nullptr);
+            base_chunk += chunks;
+        }
+        if (pass == 0) hipLaunchKernelGGL(dpn_gradnorm_reduce_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, base_chunk, sumsq);
+    }
+    return ck(hipGetLastError());
+}
+
+int64_t dpn_clip_adam_flat_floats(int n_tensors, const int64_t* numel) {
+    if (n_tensors <= 0 || !numel) return -1;
+    int64_t chunks = 0;
+    for (int i = 0; i < n_tensors; ++i) chunks += (numel[i] + kAdamChunk - 1) / kAdamChunk;
+    return chunks * kAdamChunk;
+}
+
+static int clip_adam_flat_impl(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
+                               float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, float lr, float beta1, float beta2, float eps,
+                               float weight_decay, float max_norm, float* out_norm_dev, const float* hyper_dev, void* stream) {
+    if (n_tensors <= 0 || !params || !grads || !numel || !exp_avg_flat || !exp_avg_sq_flat || !scratch_dev || !step_dev) return -1;
+    // every size is checked before the first launch: a refusal bumps no step counter and writes no partial, whichever table the bad tensor is in
+    for (int i = 0; i < n_tensors; ++i) if (numel[i] <= 0 || numel[i] > 0x7fffffff) return -1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    double* sumsq = scratch_dev;
+    double* partial = scratch_dev + 1;
+    for (int pass = 0; pass < 2; ++pass) {
+        int base_chunk = 0;
+        for (int t0 = 0; t0 < n_tensors; t0 += kAdamFlatMaxTensors) {
+            AdamTableFlat t;
+            t.n = (n_tensors - t0 < kAdamFlatMaxTensors) ? n_tensors - t0 : kAdamFlatMaxTensors;
+            t.m_flat = exp_avg_flat + (int64_t)base_chunk * kAdamChunk;
+            t.v_flat = exp_avg_sq_flat + (int64_t)base_chunk * kAdamChunk;
+            int chunks = 0;
+            for (int i = 0; i < t.n; ++i) {
+                t.p[i] = params[t0 + i]; t.g[i] = grads[t0 + i];
+                t.numel[i] = (int)numel[t0 + i];
+                t.chunk_start[i] = chunks;
+                chunks += (t.numel[i] + kAdamChunk - 1) / kAdamChunk;
+            }
+            t.chunk_start[t.n] = chunks;
+            if (pass == 0) hipLaunchKernelGGL(dpn_gradnorm_kernel<AdamTableFlat>, dim3(chunks), dim3(256), 0, s, t, partial + base_chunk, step_dev, t0 == 0 ? 1 : 0);
+            else hipLaunchKernelGGL(dpn_adam_kernel<AdamTableFlat>, dim3(chunks), dim3(256), 0, s, t, (const double*)sumsq, (const int*)step_dev, lr,
+                                    beta1, beta2, eps, weight_decay, max_norm, out_norm_dev, hyper_dev);
+            base_chunk += chunks;
+        }
+        if (pass == 0) hipLaunchKernelGGL(dpn_gradnorm_reduce_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, base_chunk, sumsq);
+    }
+    return ck(hipGetLastError());
+}
+
+int dpn_clip_adam_flat(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
+                       float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, float lr, float beta1, float beta2, float eps,
+                       float weight_decay, float max_norm, float* out_norm_dev, void* stream) {
+    return clip_adam_flat_impl(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, lr, beta1, beta2, eps,
+                               weight_decay, max_norm, out_norm_dev, nullptr, stream);
+}
+
+int dpn_clip_adam_flat_dev(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
+                           float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const float* hyper_dev, float* out_norm_dev,
+                           void* stream) {
+    if (!hyper_dev) return -1;
+    return clip_adam_flat_impl(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, 0.f, 0.f, 0.f, 0.f,
+                               0.f, 0.f, out_norm_dev, hyper_dev, stream);
+}
+
+}  // extern "C"

@@ -1,0 +1,224 @@
+// MI355X (gfx950 / CDNA4) point path, the losses on the point kernels' outputs.  A unit of its own.
+//
+// Reference behaviour restated here (paths relative to the reference's DeepPhysiNet tree):
+//   interface/interface_physics.py:97-185   six residual losses
+//   interface/interface_physics.py:232-262  inverse_norm (+clip)
+//
+// Kernel inventory
+//   dpn_contract_gpe_kernel     cotangent of caller-encoded coordinates
+//   dpn_residual_kernel         de-norm, clip, six residuals, wave-shuffle loss reduction, analytic cotangents
+//   dpn_residual_points_kernel  the same residual body, written out per point (inference diagnostics)
+//   dpn_residual_finish_kernel  block rows -> the six scaled losses and their sum
+//   dpn_smooth_l1_kernel        the data loss and its cotangent
+// No kernel in this file uses atomics: every reduction is fixed-order, the whole step is bitwise reproducible.
+#include "dpn_device.h"
+
+// g_pe[n][c] = sum_k g_out[n][k] * gpe[n][k][c]: the cotangent of caller-encoded coordinates (PhysicsNet.forward backward w.r.t. coord_x)
+__global__ __launch_bounds__(192) void dpn_contract_gpe_kernel(const float* g_out, const float* gpe, int64_t n, float* g_pe) {
+    const int64_t pt = blockIdx.x;
+    const int c = threadIdx.x;
+    float s_ = 0.f;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) s_ = fmaf(g_out[pt * 6 + k], gpe[(pt * 6 + k) * kPe + c], s_);
+    g_pe[pt * kPe + c] = s_;
+}
+
+// ------------------------------------------------------------------------------------------------ residuals
+struct ResArgs {
+    const float *out_n, *jac_n, *f;
+    int64_t n;
+    DpnGeometry geo;
+    DpnPhysics ph;
+    const float *gl, *gtot;
+    double* loss_sums;
+    float *g_out, *g_jxi;
+};
+
+// the criterion's per-element value rho(r) and slope rho'(r) (DpnPhysics.criterion): every criterion the reference's builder offers is a function of
+// input - target alone, so `loss(lhs, 0)` (:104) and the gas law's `loss(p, rho R T)` (:179) are both mean(rho(r))
+DEV float crit_value(const float r, const int kind, const float beta) {
+    const float ar = fabsf(r);
+    if (kind == DPN_CRIT_L1) return ar;
+    return ar < beta ? 0.5f * r * r / beta : ar - 0.5f * beta;             // nn.SmoothL1Loss
+}
+DEV float crit_slope(const float r, const int kind, const float beta) {
+    if (kind == DPN_CRIT_MSE) return 2.0f * r;
+    const float sg = r > 0.f ? 1.f : (r < 0.f ? -1.f : 0.f);
+    if (kind == DPN_CRIT_L1) return sg;
+    return fabsf(r) < beta ? r / beta : sg;
+}
+
+DEV float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void dpn_residual_kernel(ResArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool valid = i < a.n;
+    const int64_t ic = valid ? i : a.n - 1;
+#include "dpn_residual_body.inc"
+    if (a.loss_sums) {
+        // fp64 partial sums (residual^2 spans 1e-20..1e+20 across equations): wave shuffle tree, then the four waves of the block
+        // in a fixed order -> one [6] row per block.  No atomics: dpn_residual_finish adds the rows in a fixed order, so the
+        // losses are run-to-run deterministic (and 3.5k serialised fp64 atomics are gone from the step).
+        __shared__ double wsum[4][6];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) {
+            double s = 0.0;
+            if (valid) s = a.ph.criterion == DPN_CRIT_MSE ? (double)r[e] * (double)r[e] : (double)crit_value(r[e], a.ph.criterion, a.ph.beta);
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+            if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6][e] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x < 6)
+            a.loss_sums[(int64_t)blockIdx.x * 6 + threadIdx.x] =
+                ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x];
+    }
+    if (!a.g_out || !valid) return;
+    float g[6];
+    const float inv_n = a.ph.reduce_sum ? 1.0f : 1.0f / (float)a.n;       // reduction "sum": the criterion does not divide by the number of points
+#pragma unroll
+    for (int e = 0; e < 6; ++e) {
+        // upstream weight of loss e: cotangent of losses[e] plus cotangent of the in-kernel total (1 when neither is given)
+        const float w = (a.gl || a.gtot) ? ((a.gl ? a.gl[e] : 0.f) + (a.gtot ? a.gtot[0] : 0.f)) : 1.f;
+        g[e] = a.ph.factor[e] * w * crit_slope(r[e], a.ph.criterion, a.ph.beta) * inv_n;     // d(factor*mean(rho(r)))/dr ; MSE: 2 r
+    }
+    const float ir = 1.f / rho, ire = 1.f / (rho + EPS);
+    float gv[6], gJ[6][3];
+    gv[0] = g[0] * J[0][0] + g[1] * (J[1][0] + fc) + g[2] * J[5][0] + g[3] * (C_P * J[3][0] - J[2][0] * ire + L_V * J[4][0]) + g[4] * (-J[2][0] * K + J[4][0]);
+    gv[1] = g[0] * (J[0][1] - fc) + g[1] * J[1][1] + g[2] * J[5][1] + g[3] * (C_P * J[3][1] - J[2][1] * ire + L_V * J[4][1]) + g[4] * (-J[2][1] * K + J[4][1]);
+    gv[2] = g[4] * omega * delta * Fv / ((p + EPS) * (p + EPS)) + g[5];
+    gv[3] = -g[5] * rho * (1.f + 0.608f * q) * R_D;
+    gv[4] = -g[5] * rho * 0.608f * R_D * T;
+    gv[5] = -g[0] * J[2][0] * ir * ir - g[1] * J[2][1] * ir * ir + g[2] * (J[0][0] + J[1][1]) + g[3] * omega * ire * ire - g[5] * (1.f + 0.608f * q) * R_D * T;
+    gJ[0][0] = g[0] * u + g[2] * rho; gJ[0][1] = g[0] * v;             gJ[0][2] = g[0];
+    gJ[1][0] = g[1] * u;              gJ[1][1] = g[1] * v + g[2] * rho; gJ[1][2] = g[1];
+    gJ[2][0] = g[0] * ir - g[3] * u * ire - g[4] * u * K;
+    gJ[2][1] = g[1] * ir - g[3] * v * ire - g[4] * v * K;
+    gJ[2][2] = -g[3] * ire - g[4] * K;
+    gJ[3][0] = g[3] * C_P * u; gJ[3][1] = g[3] * C_P * v; gJ[3][2] = g[3] * C_P;
+    const float gq = g[3] * L_V + g[4];
+    gJ[4][0] = gq * u; gJ[4][1] = gq * v; gJ[4][2] = gq;
+    gJ[5][0] = g[2] * u; gJ[5][1] = g[2] * v; gJ[5][2] = g[2];
+    const float sc[3] = {1.f / a.geo.lon_m1 / a.geo.dx, 1.f / a.geo.lat_m1 / a.geo.dy, 1.f / a.geo.pred_t_span};
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        float go = gv[k] * msk[k];
+        if (a.ph.sq_on[k] && msk[k] != 0.f) {
+            // the squared form is not affine: J = jac * d val / d out depends on `out` as well -- d J / d out = jac * 2 std^2 (inside the clip bounds)
+            float t = 0.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) t = fmaf(gJ[k][c], a.jac_n[(i * 6 + k) * 3 + c], t);
+            go = fmaf(t, 2.f * a.ph.std[k] * a.ph.std[k], go);
+        }
+        a.g_out[i * 6 + k] = go;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a.g_jxi[(i * 6 + k) * 3 + c] = gJ[k][c] * msk[k] * sc[c];
+    }
+}
+
+// The six signed residuals of every point, res[n][6] = lhs - rhs (motion-u, motion-v, continuity, energy, vapour, gas), unscaled: the same body as
+// dpn_residual_kernel (dpn_residual_body.inc), no reduction and no cotangents -- where a trained field violates its equations.  One thread per point.
+struct ResPointArgs {
+    const float *out_n, *jac_n, *f;
+    int64_t n;
+    DpnPhysics ph;
+    float* res;
+};
+__global__ __launch_bounds__(256) void dpn_residual_points_kernel(ResPointArgs a) {
+    const int64_t ic = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (ic >= a.n) return;
+#include "dpn_residual_body.inc"
+    float2* dst = reinterpret_cast<float2*>(a.res + ic * 6);               // rows of 24 bytes: 8-byte aligned
+    dst[0] = make_float2(r[0], r[1]); dst[1] = make_float2(r[2], r[3]); dst[2] = make_float2(r[4], r[5]);
+}
+
+__global__ __launch_bounds__(384) void dpn_residual_finish_kernel(const double* partials, int64_t n, DpnPhysics ph, float* losses) {
+    // (a batch of fields: one workgroup per field, its block rows and its seven outputs side by side)
+    partials += (int64_t)blockIdx.x * ((n + 255) / 256) * 6;
+    losses += (int64_t)blockIdx.x * 7;
+    // partials: [ceil(n/256)][6] block rows of dpn_residual.  Wave e adds equation e (lane l takes rows l, l+64, ... in order, then a
+    // fixed shuffle tree).  losses[0..5]: the six scaled terms; losses[6]: their sum in the reference's order of additions (:301)
+    __shared__ float l[6];
+    const int e = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t nblk = (n + 255) / 256;
+    double s = 0.0;
+    for (int64_t b = lane; b < nblk; b += 64) s += partials[b * 6 + e];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) { l[e] = (float)((double)(float)(ph.reduce_sum ? s : s / (double)n) * (double)ph.factor[e]); losses[e] = l[e]; }   // .float() * factor (:104)
+    __syncthreads();
+    if (threadIdx.x == 0) losses[6] = ((((l[0] + l[1]) + l[3]) + l[2]) + l[4]) + l[5];   // montion_u + montion_v + energy + continous + vapor + gas
+}
+
+__global__ __launch_bounds__(256) void dpn_smooth_l1_kernel(const float* out_n, const float* labels, int64_t n, float beta, float scale,
+                                                            double* loss_sum, float* g_out, int accumulate, const float* scale_dev) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;     // one element of [N][6]
+    const bool valid = i < n * 6;
+    float l = 0.f;
+    if (valid) {
+        const float d = out_n[i] - labels[i];
+        const float ad = fabsf(d);
+        l = (ad < beta) ? 0.5f * d * d / beta : ad - 0.5f * beta;    // nn.SmoothL1Loss(beta), weights_loss.py:15-19
+        if (g_out) {
+            const float gv = scale * (scale_dev ? scale_dev[0] : 1.f) * ((ad < beta) ? d / beta : (d > 0.f ? 1.f : -1.f));
+            g_out[i] = accumulate ? g_out[i] + gv : gv;             // accumulate: joins the PDE cotangent of the same points
+        }
+    }
+    if (!loss_sum) return;
+    double s = (double)l;                          // one fp64 partial per block, fixed order, no atomics: the caller adds the blocks up
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    __shared__ double red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) loss_sum[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// ------------------------------------------------------------------------------------------------ C ABI
+extern "C" {
+
+int dpn_contract_gpe(const float* g_out, const float* gpe, int64_t n, float* g_pe, void* stream) {
+    if (!g_out || !gpe || !g_pe || n <= 0) return -1;
+    hipLaunchKernelGGL(dpn_contract_gpe_kernel, dim3((unsigned)n), dim3(192), 0, reinterpret_cast<hipStream_t>(stream), g_out, gpe, n, g_pe);
+    return ck(hipGetLastError());
+}
+
+int dpn_residual(const float* out_n, const float* jac_n, const float* f, int64_t n, const DpnGeometry* geo, const DpnPhysics* phys,
+                 const float* gl, const float* gtot, double* loss_sums, float* g_out, float* g_jxi, void* stream) {
+    if (!out_n || !jac_n || !f || !geo || !phys || n <= 0 || (g_out && !g_jxi)) return -1;
+    if (phys->criterion < DPN_CRIT_MSE || phys->criterion > DPN_CRIT_SMOOTH_L1 || (phys->criterion == DPN_CRIT_SMOOTH_L1 && !(phys->beta > 0.f))) return -1;
+    ResArgs a{out_n, jac_n, f, n, *geo, *phys, gl, gtot, loss_sums, g_out, g_jxi};
+    hipLaunchKernelGGL(dpn_residual_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+    return ck(hipGetLastError());
+}
+
+int dpn_residual_points(const float* out_n, const float* jac_n, const float* f, int64_t n, const DpnGeometry* geo, const DpnPhysics* phys, float* res,
+                        void* stream) {
+    if (!out_n || !jac_n || !f || !geo || !phys || !res || n <= 0) return -1;
+    ResPointArgs a{out_n, jac_n, f, n, *phys, res};
+    hipLaunchKernelGGL(dpn_residual_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+    return ck(hipGetLastError());
+}
+
+int dpn_residual_finish_batch(const double* loss_sums, int64_t n, int n_fields, const DpnPhysics* phys, float* losses, void* stream) {
+    if (!loss_sums || !phys || !losses || n <= 0 || n_fields < 1) return -1;
+    hipLaunchKernelGGL(dpn_residual_finish_kernel, dim3(n_fields), dim3(384), 0, reinterpret_cast<hipStream_t>(stream), loss_sums, n, *phys, losses);
+    return ck(hipGetLastError());
+}
+int dpn_residual_finish(const double* loss_sums, int64_t n, const DpnPhysics* phys, float* losses, void* stream) {
+    return dpn_residual_finish_batch(loss_sums, n, 1, phys, losses, stream);
+}
+
+int dpn_smooth_l1(const float* out_n, const float* labels, int64_t n, float beta, float scale, double* loss_sum, float* g_out, int accumulate,
+                  const float* scale_dev, void* stream) {
+    if (!out_n || !labels || n <= 0) return -1;
+    hipLaunchKernelGGL(dpn_smooth_l1_kernel, dim3((unsigned)((n * 6 + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                       out_n, labels, n, beta, scale, loss_sum, g_out, accumulate, scale_dev);
+    return ck(hipGetLastError());
+}
+
+}  // extern "C"

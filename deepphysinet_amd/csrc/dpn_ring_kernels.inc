@@ -1,5 +1,5 @@
 // The point kernels of the ring form (one 512-register wave per SIMD owns 32 points; weight fragments through an LDS-DMA ring), included twice by
-// dpn_kernels.hip:
+// dpn_point.hip:
 //   DPN_DERIV 0:  dpn_fwd_kernel, dpn_bwd_kernel -- what the fused step launches;
 //   DPN_DERIV 1:  dpn_fwd_deriv_kernel (+ second and third coordinate derivatives, dpn_fwd_ref_derivs) and dpn_bwd_deriv_kernel (+ their cotangent g_hxi in
 //                 the Z0 seed, dpn_bwd_points_derivs).

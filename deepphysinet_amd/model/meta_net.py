@@ -3,7 +3,7 @@
 Reference: model/meta_net.py:13-20, model/transformer_net.py:17-44,47-72,95-129, model/embed.py:16-64,
 model/attn.py:43-68,161-196.  Same parameters, same math, different execution: every GEMM (linears, 1x1 convolutions, the
 circular token-embedding convolution), the attention and the layer norms run on the library's own exact-fp32 MFMA kernels
-(csrc/dpn_kernels.hip dpn_sgemm_batch, csrc/dpn_encoder.hip); a whole EncoderLayer is one autograd node with a hand-scheduled
+(csrc/dpn_gemm.hip dpn_sgemm_batch, csrc/dpn_encoder.hip); a whole EncoderLayer is one autograd node with a hand-scheduled
 backward (encoder_ops._EncoderLayerFn).  The encoder output is cached across the calls of one training step (the model has
 no dropout, so the three forwards the reference does per step are identical).
 """

@@ -7,7 +7,7 @@
                   weight gradient without building an autograd graph over the points.
 
 PyTorch is used for device memory, the current HIP stream and autograd bookkeeping only; all arithmetic on
-points happens in libdpn_hip.so (deepphysinet_amd/csrc/dpn_kernels.hip).  There is no CPU path.
+points happens in libdpn_hip.so (deepphysinet_amd/csrc/dpn_point.hip, dpn_wgrad.hip, dpn_residual.hip).  There is no CPU path.
 """
 import ctypes
 import os
@@ -834,7 +834,7 @@ def relu_masks(cfg: PointConfig, x, y, t, coord_data, heads, evec, statics):
     pass: (m1, m2), bool [6, N, 256] in natural channel order -- m1 = (w1 . pe + b1 > 0) (variable_net.py:67-68), m2 = (cat_fc1.fc.0 pre-
     activation > 0) (ResMLP, :13-24).  The Jacobian and every gradient are piecewise constant / linear in these bits, so a point whose
     pre-activation lies within rounding distance of zero may carry a different bit than another arithmetic's (the parity tests list those
-    points and hold everything else to the tight bounds).  Layouts: csrc/dpn_kernels.hip SavedView, dpn_layout.h."""
+    points and hold everything else to the tight bounds).  Layouts: csrc/dpn_point_common.h SavedView, dpn_layout.h."""
     with torch.no_grad():
         ops = _operands('relu_masks', x, y, t, None, coord_data, heads, evec, statics)
         n, dev = ops.cd.shape[0], ops.cd.device

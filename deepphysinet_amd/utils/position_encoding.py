@@ -1,7 +1,7 @@
 """SineCosPE with the reference's constructor and output layout (utils/position_encoding.py:11-50).
 
 Used on the host side for the few per-FIELD encodings (lead time); the per-POINT encodings of the hot path
-are generated inside the HIP kernels (csrc/dpn_kernels.hip: build_pe3 / build_pe6) with the same layout
+are generated inside the HIP kernels (csrc/dpn_point.hip: build_pe3 / build_pe6) with the same layout
 [frequency, (sin, cos), channel].
 """
 import torch

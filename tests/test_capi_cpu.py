@@ -177,10 +177,9 @@ def test_inline_asm_lds_reads_are_waited_for_before_any_use(tmp_path):
         pytest.skip('hipcc not available')
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     from deepphysinet_amd.build import COMMON, UNITS
-    src = os.path.join(root, 'deepphysinet_amd', 'csrc', 'dpn_kernels.hip')
     checked = 0
-    for (usrc, flags, _), kernels in zip(UNITS[:2], (['dpn_fwd_kernel', 'dpn_bwd_kernel'], ['dpn_wgrad_kernel'])):   # as the library builds them
-        assert os.path.samefile(usrc, src)
+    for (src, flags, _), unit, kernels in zip(UNITS[:2], ('dpn_point.hip', 'dpn_wgrad.hip'), (['dpn_fwd_kernel', 'dpn_bwd_kernel'], ['dpn_wgrad_kernel'])):   # as the library builds them
+        assert os.path.samefile(src, os.path.join(root, 'deepphysinet_amd', 'csrc', unit))
         asm = str(tmp_path / ('unit%d.s' % checked))
         subprocess.run([hipcc, *[f for f in COMMON if f != '-fPIC'], *flags, '--cuda-device-only', '-S', '-I' + os.path.join(root, 'include'),
                         src, '-o', asm], check=True, capture_output=True)

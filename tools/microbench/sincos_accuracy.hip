@@ -5,7 +5,7 @@
 #include <cstdio>
 #include <vector>
 
-__device__ __forceinline__ void sincos_precise(float th, float& s, float& c) {      // the kernel's current routine (dpn_kernels.hip)
+__device__ __forceinline__ void sincos_precise(float th, float& s, float& c) {      // the kernel's current routine (csrc/dpn_point.hip)
     const float k = rintf(th * 0.63661977236758134f);
     float r = fmaf(k, -1.5707963705062866f, th);
     r = fmaf(k, 4.371138828673793e-08f, r);
