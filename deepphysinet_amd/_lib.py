@@ -188,7 +188,15 @@ EXPORTS = {
     'dpn_adaptive_scores': (c_int, [c_void_p, c_int64, POINTER(c_double), c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dpn_adaptive_select': (c_int, [c_void_p, c_int64, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_uint64, c_uint64,
                                     c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dpn_causal_rows_doubles': (c_int64, [c_int64, c_int]),
+    'dpn_causal_bins': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, POINTER(DpnGeometry), POINTER(DpnPhysics), POINTER(c_double), c_double,
+                                c_double, c_int, c_void_p, c_void_p, c_void_p]),
+    'dpn_causal_weights': (c_int, [c_void_p, c_int64, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p]),
+    'dpn_residual_weighted': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(DpnGeometry), POINTER(DpnPhysics), c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
+
+CAUSAL_MAX_BINS = 64          # DPN_CAUSAL_MAX_BINS (include/dpn_hip.h)
 
 # Shelved experiments (include/dpn_hip_experiments.h): compiled only into libdpn_hip_exp.so (`python -m deepphysinet_amd.build --experiments`), which also
 # holds every product symbol; reached through load_experiments() by the code paths behind the matching frozen switches (config.py)

@@ -28,7 +28,8 @@ UNITS = [(_src('dpn_point.hip'), ['-mllvm', '-amdgpu-mfma-vgpr-form'], 'dpn_poin
          (_src('dpn_adaptive.hip'), [], 'dpn_adaptive.o'),  # residual-weighted collocation points (scores, prefix sum, draw)
          (_src('dpn_residual.hip'), [], 'dpn_residual.o'),  # residual and SmoothL1 losses
          (_src('dpn_gemm.hip'), [], 'dpn_gemm.o'),        # the exact-fp32 GEMM family
-         (_src('dpn_optim.hip'), [], 'dpn_optim.o')]      # fused clip + Adam
+         (_src('dpn_optim.hip'), [], 'dpn_optim.o'),      # fused clip + Adam
+         (_src('dpn_causal.hip'), [], 'dpn_causal.o')]    # per-point weights and causal time weighting of the PDE losses
 SRCS = [u[0] for u in UNITS]
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC']
 

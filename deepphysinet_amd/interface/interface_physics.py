@@ -200,19 +200,23 @@ class InterfacePhysics(nn.Module):
         raise NotImplementedError('the fused residual kernel implements the PDE criteria of the reference\'s loss builder -- nn.MSELoss (cfg:137), nn.L1Loss, '
                                   'WeightSmoothL1Loss(beta > 0), reduction "mean" or "sum"; got %r' % (criterion,))
 
-    def pde_loss_terms(self, x, y, t, f, field_data, input_data, forecast_h, loss_factor=None, use_cache=False, with_total=False, criterion=None):
-        """The six scaled residual losses as a [6] tensor (motion_u, motion_v, continuous, energy, vapor, gas)."""
+    def pde_loss_terms(self, x, y, t, f, field_data, input_data, forecast_h, loss_factor=None, use_cache=False, with_total=False, criterion=None, *,
+                       point_weights=None, causal=None):
+        """The six scaled residual losses as a [6] tensor (motion_u, motion_v, continuous, energy, vapor, gas).  point_weights [N] or [N, 1]: constant
+        per-point weights (importance weights, a region's down-weighting, a 0/1 mask; the mean stays over all N points); causal: a
+        causal.CausalWeights, causal time weights over the points' t (point_path.pde_losses)."""
         cfg = self.point_config(loss_factor, criterion)
         heads, evec, statics = self.physics_net.field_weights(field_data, forecast_h, use_cache=use_cache)
-        return pde_losses(cfg, x, y, t, f, input_data, heads, evec, statics, with_total=with_total)
+        return pde_losses(cfg, x, y, t, f, input_data, heads, evec, statics, with_total=with_total, point_weights=point_weights, causal=causal)
 
     def place_one_batch(self, x, y, t, f, field_data, input_data, forecast_h, criterion, loss_factor, global_step, local_rank, device,
-                        summary=None, prefix='inter', log_step=100, use_cache=False):
-        """:271-320.  Same arguments and return value; the fields, the Jacobian, the residuals and their backward run in HIP."""
+                        summary=None, prefix='inter', log_step=100, use_cache=False, *, point_weights=None, causal=None):
+        """:271-320.  Same arguments and return value; the fields, the Jacobian, the residuals and their backward run in HIP.  point_weights, causal:
+        as pde_loss_terms."""
         f, x, y, t = f.to(device), x.to(device), y.to(device), t.to(device)
         # train_loss = mu + mv + en + co + va + ga in the reference's order of additions (:301), formed inside the residual kernel
         terms, train_loss = self.pde_loss_terms(x, y, t, f, field_data, input_data, forecast_h, loss_factor, use_cache=use_cache,
-                                                with_total=True, criterion=criterion)
+                                                with_total=True, criterion=criterion, point_weights=point_weights, causal=causal)
         if summary is not None and global_step % log_step == 1 and local_rank == 0:
             names = ('montion_u_loss', 'montion_v_loss', 'continous_loss', 'energy_loss', 'vapor_loss', 'gas_loss')
             vals = terms.detach().cpu().tolist()
@@ -404,6 +408,22 @@ class InterfacePhysics(nn.Module):
             raise ValueError('adaptive_interior: every must be >= 1, got %r' % (opt['every'],))
         return opt
 
+    def _causal_option(self, kwargs):
+        """The loops' `causal_weights` option (keyword, or train_cfg['losses']['causal_weights']): None (off), or a dict of eps, bins, relative ->
+        a causal.CausalWeights."""
+        opt = kwargs.get('causal_weights', (self.train_cfg.get('losses') or {}).get('causal_weights'))
+        if opt is None or opt is False:
+            return None
+        from ..causal import CausalWeights
+        if isinstance(opt, CausalWeights):
+            return opt
+        unknown = set(opt) - {'eps', 'bins', 'relative'}
+        if unknown:
+            raise ValueError('causal_weights: unknown keys %s (known: eps, bins, relative)' % sorted(unknown))
+        if 'eps' not in opt:
+            raise ValueError('causal_weights: eps is required')
+        return CausalWeights(**opt)
+
     def _adaptive_sampler(self, opt, batch, kwargs):
         """The sampler that draws the pool: the option's own, the batch's 'sampler' entry, or the sample source's `.sampler` attribute."""
         src = kwargs.get('samples', (self.train_cfg.get('train_data') or {}).get('samples'))
@@ -415,12 +435,20 @@ class InterfacePhysics(nn.Module):
         raise RuntimeError("adaptive_interior needs the CollocationSampler that draws the pool: give it as adaptive_interior['sampler'], as the batch's "
                            "'sampler' entry, or as the `.sampler` attribute of the samples source (SyntheticSamples has one)")
 
-    def training_step(self, batch: dict, optimizer, with_pde=True, max_norm=2.5e7, grad_sync=None):
+    def training_step(self, batch: dict, optimizer, with_pde=True, max_norm=2.5e7, grad_sync=None, *, causal=None):
         """One step body (:443-515 / :990-1065): data loss on the margin points, PDE losses on interior and margin points,
         backward, clip_grad_norm_(2.5e7), optimizer step.  `batch` holds device tensors: field_data [1,159,2405],
         forecast_h [1,1,1], margin_{x,y,t,f} [N,1], margin_data [N,6], margin_input_data [N,6], inter_{x,y,t,f} [M,1],
-        inter_data [M,6].  The encoder runs once (the reference runs it three times on identical inputs)."""
+        inter_data [M,6].  The encoder runs once (the reference runs it three times on identical inputs).
+        causal (a causal.CausalWeights; with the PDE losses only): causal time weights on the interior and on the margin PDE losses, each group with
+        bins and weights of its own; `self.last_causal` then holds {'inter': diag, 'margin': diag} as device tensors (no synchronisation here), and
+        None after a step without the option.  An optional batch entry inter_w [M] or [M, 1]: constant weights of the interior points' PDE losses.
+        The data loss is never weighted."""
         lf = self.train_cfg['losses']['loss_factor']
+        self.last_causal = None
+        inter_w = batch.get('inter_w') if with_pde else None
+        if not with_pde:
+            causal = None
         self.physics_net.clear_field_cache()
         b = batch
         heads = evec = statics = meta_out = None
@@ -432,8 +460,11 @@ class InterfacePhysics(nn.Module):
             meta_out = self.physics_net.encode_field(b['field_data'], b['forecast_h'], keep_embedding=grad_sync is not None)
             heads, evec, statics = self.physics_net.field_weights(b['field_data'], b['forecast_h'], meta_out=meta_out)
             n_inter, pts = self._eval_inputs(b, True)
+            diag = [] if causal is not None else None
             _, inter_total, _, margin_total, data = step_losses(cfg, n_inter, *pts, b['margin_data'], heads, evec, statics, beta=0.1,
-                                                                margin_factor=lf['margin_factor'])
+                                                                margin_factor=lf['margin_factor'], inter_weights=inter_w, causal=causal, diag=diag)
+            if causal is not None:
+                self.last_causal = {'inter': diag[0], 'margin': diag[1]}
             parts = {'margin_loss': data, 'inter_pde_loss': inter_total.float(), 'margin_pde_loss': margin_total.float()}
         else:
             loss = self.data_loss(b['margin_x'], b['margin_y'], b['margin_t'], b['field_data'], b['margin_input_data'], b['margin_data'],
@@ -443,10 +474,10 @@ class InterfacePhysics(nn.Module):
                 crit = nn.MSELoss()
                 parts['inter_pde_loss'] = self.place_one_batch(b['inter_x'], b['inter_y'], b['inter_t'], b['inter_f'], b['field_data'],
                                                                b['inter_data'], b['forecast_h'], crit, lf, 0, 0, b['field_data'].device,
-                                                               use_cache=True)
+                                                               use_cache=True, point_weights=inter_w, causal=causal)
                 parts['margin_pde_loss'] = self.place_one_batch(b['margin_x'], b['margin_y'], b['margin_t'], b['margin_f'], b['field_data'],
                                                                 b['margin_input_data'], b['forecast_h'], crit, lf, 0, 0,
-                                                                b['field_data'].device, prefix='margin', use_cache=True)
+                                                                b['field_data'].device, prefix='margin', use_cache=True, causal=causal)
         train_loss = 0
         for v in parts.values():
             train_loss = train_loss + v
@@ -793,6 +824,7 @@ class InterfacePhysics(nn.Module):
         valid_src = self._valid_samples(kwargs)
         vlog = self._ValidationLoop(self, valid_src, kwargs.get('log_path'), rank, world, num_epoch, device) if valid_src is not None else None
         adaptive = self._adaptive_option(kwargs)                        # None: not one extra call below
+        causal = self._causal_option(kwargs)                            # None: the step's launches of before
         for epoch in range(current_epoch, num_epoch):
             for batch_id, batch in enumerate(self._epoch_samples(kwargs, epoch, rank, world, dist_mode)):   # DistributedSampler (:936): one field sample per rank per step
                 with_pde = with_pde_cfg and global_step >= pde_start
@@ -806,7 +838,10 @@ class InterfacePhysics(nn.Module):
                     # the interior points go where this step's network violates its equations most (adaptive_interior)
                     batch = self.adaptive_interior(batch, self._adaptive_sampler(adaptive, batch, kwargs), pool_factor=adaptive['pool_factor'],
                                                    k=adaptive['k'], c=adaptive['c'])
-                loss, parts, gnorm = self.training_step(batch, optimizer, with_pde=with_pde, grad_sync=sync)
+                if causal is not None and with_pde:                   # causal time weights: once the PDE losses are on
+                    loss, parts, gnorm = self.training_step(batch, optimizer, with_pde=with_pde, grad_sync=sync, causal=causal)
+                else:
+                    loss, parts, gnorm = self.training_step(batch, optimizer, with_pde=with_pde, grad_sync=sync)
                 last = {'loss': loss, 'parts': parts, 'grad_norm': gnorm}
                 if rank == 0 and global_step % log_step == 1:
                     print('epoch %d step %d loss %.6g %s' % (epoch, global_step, float(loss),
@@ -890,8 +925,13 @@ class InterfacePhysics(nn.Module):
                 vparts = {k: res[k] for k in ('margin_loss', 'inter_pde_loss', 'margin_pde_loss') if k in res}
                 self.log.line(V.format_train_line(epoch, self.num_epoch, batch_id, n_batches, global_step, loss, parts, f_train, fps))
                 self.log.line(V.format_valid_line(epoch, self.num_epoch, batch_id, n_batches, global_step, res['valid_loss'], vparts, f_valid, fps))
+                extra = {}
+                lc = getattr(m, 'last_causal', None)
+                if lc is not None:                           # the interior group's causal weights of this step (the loop synchronises here anyway)
+                    bins = (lc['inter'].numel() - 2) // 3
+                    extra = {'causal_min_w': float(lc['inter'][3 * bins]), 'causal_w': lc['inter'][:bins].tolist()}
                 self.log.event('training', epoch=epoch, global_step=global_step, train_loss=loss, forecast_hours=f_train, fps=fps, variables=train_vars,
-                               **parts)
+                               **parts, **extra)
                 self.log.event('validation', epoch=epoch, global_step=global_step, forecast_hours=f_valid, fps=fps,
                                **{k: v for k, v in res.items() if k != 'global_step'})
             self.t0, self.step0 = self.clock(), global_step
@@ -916,7 +956,9 @@ class InterfacePhysics(nn.Module):
         reference's two lines per log step in log_<date>.txt and metrics.jsonl; no tensorboard / JPEG output here);
         added: samples (see _train_samples), valid_samples (see _valid_samples; none: no validation, the loop of before), validate_every_epoch,
         valid_lead_batch, num_epoch, max_steps, pde_start_step, device, adaptive_interior (None, or dict(pool_factor, k, c, every, sampler): once
-        the PDE losses are on, every every-th step's interior points are redrawn by adaptive_interior before the step; unset: the loop of before).
+        the PDE losses are on, every every-th step's interior points are redrawn by adaptive_interior before the step; unset: the loop of before),
+        causal_weights (None, or dict(eps, bins, relative): once the PDE losses are on, every step's PDE losses carry causal time weights; the
+        log-step row of metrics.jsonl gains causal_min_w and causal_w, the interior group's weights; validation stays unweighted).
         With a validation source the result carries `last_validation`."""
         return self._run_train(False, **kwargs)
 

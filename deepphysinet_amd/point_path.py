@@ -522,19 +522,68 @@ def point_fields_xyt(cfg: PointConfig, x, y, t, coord_data, heads, evec, statics
     return _AttachFn.apply(out, x, y, t, (jac,))
 
 
-def _residual_losses(cfg, out_n, jac_n, f_, groups, losses, unit=None, sums=None):
+def _causal_group(cfg, causal, out_n, jac_n, f_, t_, a0, a1):
+    """Causal time weights of the row group (a0, a1) (causal: a causal.CausalWeights): dpn_causal_bins, then dpn_causal_weights.  Returns
+    (bin [m] int32, W32 [bins] fp32, diag [3 bins + 2] fp64), all on the device; nothing is read back."""
+    lib = L.load()
+    m, bins, dev = a1 - a0, int(causal.bins), out_n.device
+    t_lo, t_hi = causal.bounds(cfg.pred_t_span)
+    geo, ph = cfg.geometry(), cfg.physics()
+    fac = (ctypes.c_double * 6)(*[float(v) for v in cfg.factors])
+    bin_ = torch.empty(m, dtype=torch.int32, device=dev)
+    rows = torch.empty(int(lib.dpn_causal_rows_doubles(m, bins)), dtype=torch.float64, device=dev)
+    w32 = torch.empty(bins, dtype=torch.float32, device=dev)
+    diag = torch.empty(3 * bins + 2, dtype=torch.float64, device=dev)
+    L.check(lib.dpn_causal_bins(_ptr(out_n[a0:]), _ptr(jac_n[a0:]), _ptr(f_[a0:]), _ptr(t_[a0:]), m, ctypes.byref(geo), ctypes.byref(ph), fac,
+                                float(t_lo), float(t_hi), bins, _ptr(bin_), _ptr(rows), _stream()), 'dpn_causal_bins')
+    L.check(lib.dpn_causal_weights(_ptr(rows), m, bins, float(causal.eps), int(causal.relative), _ptr(w32), _ptr(diag), _stream()),
+            'dpn_causal_weights')
+    return bin_, w32, diag
+
+
+def _point_weights(what, w, n, device):
+    """A caller's per-point weights as an fp32 contiguous device tensor [n] (constants: detached)."""
+    require_gpu(w, 'point weights', what)
+    w = _f32c(w).reshape(-1)
+    if w.shape[0] != n:
+        raise ValueError('%s: %d point weights for %d points' % (what, w.shape[0], n))
+    return w
+
+
+def _group_weights(cfg, causal, out_n, jac_n, f_, t_, groups, given):
+    """Per row group (a0, a1) the weight sources of dpn_residual_weighted: (w [m] or None, bin or None, W32 or None), or None for a group with
+    neither (it takes the plain dpn_residual).  given: the caller's weights per group (or None); causal: bins and weights per group, each group
+    its own (_causal_group).  Also returns the groups' diag tensors (None without causal)."""
+    out, diags = [], []
+    for (a0, a1), w in zip(groups, given):
+        bin_ = w32 = diag = None
+        if causal is not None:
+            bin_, w32, diag = _causal_group(cfg, causal, out_n, jac_n, f_, t_, a0, a1)
+        out.append(None if (w is None and bin_ is None) else (w, bin_, w32))
+        diags.append(diag)
+    return out, diags
+
+
+def _residual_losses(cfg, out_n, jac_n, f_, groups, losses, unit=None, sums=None, weights=None):
     """The residual-loss sums of row groups (a0, a1) of out_n [n, 6], jac_n [n, 6, 3], f_ [n]: per group one dpn_residual launch into per-block
     rows and one dpn_residual_finish into its `losses` row [7] (the six scaled terms, their total).  unit = (scale, g_out, g_jxi): the same pass
     over the points also writes d total / d (out, Jacobian) for the cotangent `scale` (a device 1.0) of the total.  sums: the block rows of one
-    group given by the caller; losses None leaves them to a later finish launch (_residual_finish, or dpn_residual_finish_batch for a batch)."""
+    group given by the caller; losses None leaves them to a later finish launch (_residual_finish, or dpn_residual_finish_batch for a batch).
+    weights: per group None or (w, bin, W32) (_group_weights): such a group's launch is dpn_residual_weighted, same rows, same finish."""
     lib = L.load()
     geo, ph = cfg.geometry(), cfg.physics()
     for gi, (a0, a1) in enumerate(groups):
         m = a1 - a0
         s_ = torch.empty(((m + 255) // 256) * 6, dtype=torch.float64, device=out_n.device) if sums is None else sums
         sc, g_out, g_jxi = (None, None, None) if unit is None else (unit[0], unit[1][a0:], unit[2][a0:])
-        L.check(lib.dpn_residual(_ptr(out_n[a0:]), _ptr(jac_n[a0:]), _ptr(f_[a0:]), m, ctypes.byref(geo), ctypes.byref(ph), None, _ptr(sc),
-                                 _ptr(s_), _ptr(g_out), _ptr(g_jxi), _stream()), 'dpn_residual')
+        wt = None if weights is None else weights[gi]
+        if wt is None:
+            L.check(lib.dpn_residual(_ptr(out_n[a0:]), _ptr(jac_n[a0:]), _ptr(f_[a0:]), m, ctypes.byref(geo), ctypes.byref(ph), None, _ptr(sc),
+                                     _ptr(s_), _ptr(g_out), _ptr(g_jxi), _stream()), 'dpn_residual')
+        else:
+            L.check(lib.dpn_residual_weighted(_ptr(out_n[a0:]), _ptr(jac_n[a0:]), _ptr(f_[a0:]), m, ctypes.byref(geo), ctypes.byref(ph), None, _ptr(sc),
+                                              _ptr(s_), _ptr(g_out), _ptr(g_jxi), _ptr(wt[0]), _ptr(wt[1]), _ptr(wt[2]), _stream()),
+                    'dpn_residual_weighted')
         if losses is not None:
             _residual_finish(cfg, s_, m, losses[gi])
 
@@ -544,23 +593,31 @@ def _residual_finish(cfg, sums, n, losses):
     L.check(L.load().dpn_residual_finish(_ptr(sums), n, ctypes.byref(ph), _ptr(losses), _stream()), 'dpn_residual_finish')
 
 
-def _residual_cotangent(cfg, out_n, jac_n, f_, groups, g_out=None, g_jxi=None):
+def _residual_cotangent(cfg, out_n, jac_n, f_, groups, g_out=None, g_jxi=None, weights=None):
     """d loss / d (out, Jacobian) of the residual losses (dpn_residual in gradient mode) into g_out [n, 6], g_jxi [n, 6, 3] (allocated when not
     given), group by group: groups = [(a0, a1, cotangent of the terms [6] or None, cotangent of the total [1] or None)]; a group with neither
-    takes a zero cotangent on its terms (its rows are written all the same).  Returns (g_out, g_jxi)."""
+    takes a zero cotangent on its terms (its rows are written all the same).  weights: per group None or (w, bin, W32), the weight sources the
+    forward pass used (saved, never recomputed): such a group's launch is dpn_residual_weighted.  Returns (g_out, g_jxi)."""
     lib = L.load()
     n, dev = out_n.shape[0], out_n.device
     g_out = torch.empty((n, 6), dtype=torch.float32, device=dev) if g_out is None else g_out
     g_jxi = torch.empty((n, 6, 3), dtype=torch.float32, device=dev) if g_jxi is None else g_jxi
     geo, ph = cfg.geometry(), cfg.physics()
     zero6 = None
-    for a0, a1, gl, gt in groups:
+    for gi, (a0, a1, gl, gt) in enumerate(groups):
         if gl is None and gt is None:
             zero6 = torch.zeros(6, dtype=torch.float32, device=dev) if zero6 is None else zero6
             gl = zero6
-        L.check(lib.dpn_residual(_ptr(out_n[a0:]), _ptr(jac_n[a0:]), _ptr(f_[a0:]), a1 - a0, ctypes.byref(geo), ctypes.byref(ph),
-                                 None if gl is None else _ptr(_f32c(gl)), None if gt is None else _ptr(_f32c(gt).reshape(1)), None,
-                                 _ptr(g_out[a0:]), _ptr(g_jxi[a0:]), _stream()), 'dpn_residual(grad)')
+        wt = None if weights is None else weights[gi]
+        if wt is None:
+            L.check(lib.dpn_residual(_ptr(out_n[a0:]), _ptr(jac_n[a0:]), _ptr(f_[a0:]), a1 - a0, ctypes.byref(geo), ctypes.byref(ph),
+                                     None if gl is None else _ptr(_f32c(gl)), None if gt is None else _ptr(_f32c(gt).reshape(1)), None,
+                                     _ptr(g_out[a0:]), _ptr(g_jxi[a0:]), _stream()), 'dpn_residual(grad)')
+        else:
+            L.check(lib.dpn_residual_weighted(_ptr(out_n[a0:]), _ptr(jac_n[a0:]), _ptr(f_[a0:]), a1 - a0, ctypes.byref(geo), ctypes.byref(ph),
+                                              None if gl is None else _ptr(_f32c(gl)), None if gt is None else _ptr(_f32c(gt).reshape(1)), None,
+                                              _ptr(g_out[a0:]), _ptr(g_jxi[a0:]), _ptr(wt[0]), _ptr(wt[1]), _ptr(wt[2]), _stream()),
+                    'dpn_residual_weighted(grad)')
     return g_out, g_jxi
 
 
@@ -568,7 +625,8 @@ class _PdeLossFn(torch.autograd.Function):
     """losses [6] = (motion_u, motion_v, continuous, energy, vapor, gas), each already scaled by its factor."""
 
     @staticmethod
-    def forward(ctx, cfg, x, y, t, f, coord_data, heads, evec, *statics):
+    def forward(ctx, cfg, extra, x, y, t, f, coord_data, heads, evec, *statics):
+        # extra: None (the launches of before), or (point weights [n] or None, causal.CausalWeights or None, a list that receives the diag tensor)
         ops = _operands('pde_losses', x, y, t, f, coord_data, heads, evec, statics)
         n, dev = ops.cd.shape[0], ops.cd.device
         need_grad = any(v.requires_grad for v in (heads, evec) + tuple(statics))
@@ -582,7 +640,15 @@ class _PdeLossFn(torch.autograd.Function):
         ctx.unit = None
         if need_grad:
             ctx.unit = (torch.empty((n, 6), dtype=torch.float32, device=dev), torch.empty((n, 6, 3), dtype=torch.float32, device=dev))
-        _residual_losses(cfg, out_n, jac_n, ops.f, ((0, n),), losses, unit=None if ctx.unit is None else (_one(dev),) + ctx.unit)
+        ctx.weights = None
+        if extra is not None:
+            # bins, weights, then the weighted residual pass; bin, W32 and the caller's w stay in ctx for the backward pass
+            w = None if extra[0] is None else _point_weights('pde_losses', extra[0], n, dev)
+            ctx.weights, diags = _group_weights(cfg, extra[1], out_n, jac_n, ops.f, ops.t, ((0, n),), (w,))
+            if extra[2] is not None:
+                extra[2][:] = diags
+        _residual_losses(cfg, out_n, jac_n, ops.f, ((0, n),), losses, unit=None if ctx.unit is None else (_one(dev),) + ctx.unit,
+                         weights=ctx.weights)
         ctx.cfg, ctx.ws, ctx.ops, ctx.fields = cfg, ws, ops, (out_n, jac_n)
         ctx.stamp = _stamp((heads, evec) + tuple(statics))
         ctx.set_materialize_grads(False)
@@ -595,17 +661,17 @@ class _PdeLossFn(torch.autograd.Function):
         gl = None if g_losses is None else _f32c(g_losses)
         gt = None if g_total is None else _f32c(g_total).reshape(1)
         if gl is None and gt is None:
-            return (None,) * (8 + len(ops.st))
+            return (None,) * (9 + len(ops.st))
         if gl is None and ctx.unit is not None:                  # cotangent on the total only: the unit-cotangent streams of the forward pass, scaled on load
             g_out, g_jxi = ctx.unit
             ghd, gev, gst = _backward_points(cfg, ctx.ws, ops.nets(), ops.x, ops.y, ops.t, None, ops.cd, g_out, g_jxi, ops.st, fork=True,
                                              keep=(ops.hd, ops.ev), g_scale=gt)
-            return (None, None, None, None, None, None, ghd, gev, *gst)
+            return (None, None, None, None, None, None, None, ghd, gev, *gst)
         out_n, jac_n = ctx.fields
-        g_out, g_jxi = _residual_cotangent(cfg, out_n, jac_n, ops.f, ((0, ops.cd.shape[0], gl, gt),))
+        g_out, g_jxi = _residual_cotangent(cfg, out_n, jac_n, ops.f, ((0, ops.cd.shape[0], gl, gt),), weights=ctx.weights)
         ghd, gev, gst = _backward_points(cfg, ctx.ws, ops.nets(), ops.x, ops.y, ops.t, None, ops.cd, g_out, g_jxi, ops.st, fork=True,
                                          keep=(ops.hd, ops.ev))
-        return (None, None, None, None, None, None, ghd, gev, *gst)
+        return (None, None, None, None, None, None, None, ghd, gev, *gst)
 
 
 _STATIC_STARTS = [0]                    # offsets of the 48 static tensors in a flat gradient row
@@ -758,7 +824,9 @@ class _StepLossFn(torch.autograd.Function):
     forward serves both of their losses, and all 24 576 points share one backward / weight-gradient / finish sequence."""
 
     @staticmethod
-    def forward(ctx, cfg, n_inter, beta, margin_factor, x, y, t, f, coord_data, labels, heads, evec, *statics):
+    def forward(ctx, cfg, extra, n_inter, beta, margin_factor, x, y, t, f, coord_data, labels, heads, evec, *statics):
+        # extra: None (the launches of before), or (interior point weights [n_inter] or None, causal.CausalWeights or None, a list that receives
+        # the diag tensors of the two groups)
         ops = _operands('step_losses', x, y, t, f, coord_data, heads, evec, statics, labels=labels, split=(n_inter, True))
         n = ops.cd.shape[0]
         n_m = n - n_inter
@@ -766,7 +834,19 @@ class _StepLossFn(torch.autograd.Function):
         need_grad = any(v.requires_grad for v in (heads, evec) + tuple(statics))
         ws = _Workspace(n, cfg.prec, dev)
         losses = torch.empty((2, 7), dtype=torch.float32, device=dev)
-        out_n, jac_n = _step_pass(cfg, ws, ops.nets(), n_inter, ops.x, ops.y, ops.t, ops.f, ops.cd, losses, want_saved=need_grad)
+        ctx.weights = None
+        if extra is None:
+            out_n, jac_n = _step_pass(cfg, ws, ops.nets(), n_inter, ops.x, ops.y, ops.t, ops.f, ops.cd, losses, want_saved=need_grad)
+        else:
+            # _step_pass with weights: per group bins, weights, the weighted residual pass, finish; interior and margin each their own bins and
+            # weights.  The data loss below is not weighted.
+            groups = ((0, n_inter), (n_inter, n))
+            out_n, jac_n = _forward_points(cfg, ws, ops.nets(), ops.x, ops.y, ops.t, None, ops.cd, want_jac=True, want_saved=need_grad)
+            w = None if extra[0] is None else _point_weights('step_losses', extra[0], n_inter, dev)
+            ctx.weights, diags = _group_weights(cfg, extra[1], out_n, jac_n, ops.f, ops.t, groups, (w, None))
+            if extra[2] is not None:
+                extra[2][:] = diags
+            _residual_losses(cfg, out_n, jac_n, ops.f, groups, losses, weights=ctx.weights)
         dsum = torch.empty((n_m * 6 + 255) // 256, dtype=torch.float64, device=dev)
         L.check(L.load().dpn_smooth_l1(_ptr(out_n[n_inter:]), _ptr(ops.lab), n_m, beta, 1.0, _ptr(dsum), None, 0, None, _stream()), 'dpn_smooth_l1')
         data = (dsum.sum() / (6.0 * n_m)).float() * margin_factor
@@ -784,24 +864,42 @@ class _StepLossFn(torch.autograd.Function):
         n = ops.cd.shape[0]
         n_m = n - n_inter
         if all(v is None for v in (g_la, g_ta, g_lb, g_tb, g_data)):
-            return (None,) * (12 + len(ops.st))
-        g_out, g_jxi = _residual_cotangent(cfg, out_n, jac_n, ops.f, ((0, n_inter, g_la, g_ta), (n_inter, n, g_lb, g_tb)))
+            return (None,) * (13 + len(ops.st))
+        g_out, g_jxi = _residual_cotangent(cfg, out_n, jac_n, ops.f, ((0, n_inter, g_la, g_ta), (n_inter, n, g_lb, g_tb)), weights=ctx.weights)
         if g_data is not None:                                # + d(data loss)/d out on the margin rows
             L.check(L.load().dpn_smooth_l1(_ptr(out_n[n_inter:]), _ptr(ops.lab), n_m, ctx.beta, ctx.margin_factor / (6.0 * n_m), None,
                                            _ptr(g_out[n_inter:]), 1, _ptr(_f32c(g_data).reshape(1)), _stream()), 'dpn_smooth_l1(grad)')
         ghd, gev, gst = _backward_points(cfg, ctx.ws, ops.nets(), ops.x, ops.y, ops.t, None, ops.cd, g_out, g_jxi, ops.st, fork=True,
                                          keep=(ops.hd, ops.ev))
-        return (None,) * 10 + (ghd, gev, *gst)
+        return (None,) * 11 + (ghd, gev, *gst)
 
 
-def step_losses(cfg: PointConfig, n_inter, x, y, t, f, coord_data, labels, heads, evec, statics, beta=0.1, margin_factor=1.0):
+def _weight_options(what, weights, causal, diag):
+    """The `extra` argument of _PdeLossFn / _StepLossFn: None when neither option is given (the launches of before)."""
+    if weights is None and causal is None:
+        return None
+    if causal is not None and not all(hasattr(causal, k) for k in ('eps', 'bins', 'relative', 'bounds')):
+        raise TypeError('%s: causal must be a deepphysinet_amd.causal.CausalWeights, got %r' % (what, causal))
+    return (None if weights is None else weights.detach(), causal, diag)
+
+
+def step_losses(cfg: PointConfig, n_inter, x, y, t, f, coord_data, labels, heads, evec, statics, beta=0.1, margin_factor=1.0, inter_weights=None,
+                causal=None, diag=None):
     """(inter_terms [6], inter_total, margin_terms [6], margin_total, data_loss) of the reference's step body in one point pass; the first
-    n_inter rows of x, y, t, f, coord_data are the interior points, the rest the margin points whose labels are `labels` (_StepLossFn)."""
-    return _StepLossFn.apply(cfg, int(n_inter), float(beta), float(margin_factor), x, y, t, f, coord_data, labels, heads, evec, *statics)
+    n_inter rows of x, y, t, f, coord_data are the interior points, the rest the margin points whose labels are `labels` (_StepLossFn).
+    inter_weights [n_inter]: constant per-point weights of the interior group's PDE losses; causal (causal.CausalWeights): causal time weights, the
+    interior and the margin group each with bins and weights of its own; a list given as `diag` receives the two groups' diag tensors (device,
+    include/dpn_hip.h: dpn_causal_weights).  The data loss is not weighted.  Neither given: the launches of before."""
+    return _StepLossFn.apply(cfg, _weight_options('step_losses', inter_weights, causal, diag), int(n_inter), float(beta), float(margin_factor), x, y, t, f,
+                             coord_data, labels, heads, evec, *statics)
 
 
-def pde_losses_batch(cfg: PointConfig, x, y, t, f, coord_data, heads, evec, statics):
-    """(losses [B,6], totals [B]) for B field samples with N points each; tensors carry a leading B (see _PdeLossBatchFn)."""
+def pde_losses_batch(cfg: PointConfig, x, y, t, f, coord_data, heads, evec, statics, point_weights=None, causal=None):
+    """(losses [B,6], totals [B]) for B field samples with N points each; tensors carry a leading B (see _PdeLossBatchFn).  Point weights and causal
+    time weights are not implemented for lead batches."""
+    if point_weights is not None or causal is not None:
+        raise NotImplementedError('pde_losses_batch: point_weights / causal are implemented for one field at a time (pde_losses, step_losses), not for '
+                                  'lead batches')
     return _PdeLossBatchFn.apply(cfg, torch.is_grad_enabled(), x, y, t, f, coord_data, heads, evec, *statics)
 
 
@@ -815,9 +913,12 @@ def point_fields(cfg: PointConfig, coord_data, heads, evec, statics, x=None, y=N
     return _PointFieldsFn.apply(cfg, x, y, t, pe_in, coord_data, heads, evec, *statics)
 
 
-def pde_losses(cfg: PointConfig, x, y, t, f, coord_data, heads, evec, statics, with_total=False):
-    """The six scaled residual losses [6] of place_one_batch (and, with_total, their sum in the reference's order as a 0-dim tensor)."""
-    terms, total = _PdeLossFn.apply(cfg, x, y, t, f, coord_data, heads, evec, *statics)
+def pde_losses(cfg: PointConfig, x, y, t, f, coord_data, heads, evec, statics, with_total=False, point_weights=None, causal=None, diag=None):
+    """The six scaled residual losses [6] of place_one_batch (and, with_total, their sum in the reference's order as a 0-dim tensor).
+    point_weights [N] (or [N, 1]): constant per-point weights -- loss_e = factor_e * sum_i w_i rho(r_ie) / N, linear in the weights, no gradient
+    flows into them; causal (causal.CausalWeights): causal time weights W_bin(t_i), multiplied with point_weights when both are given; a list given
+    as `diag` receives the diag tensor (device).  Neither given: the launches of before."""
+    terms, total = _PdeLossFn.apply(cfg, _weight_options('pde_losses', point_weights, causal, diag), x, y, t, f, coord_data, heads, evec, *statics)
     return (terms, total) if with_total else terms
 
 

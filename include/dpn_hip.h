@@ -507,6 +507,40 @@ int dpn_adaptive_select(const double* score, int64_t m, double k, double c, cons
                         float* out_x, float* out_y, float* out_t, float* out_f, float* out_coord_data, int32_t* idx, double* u, double* picked_score,
                         double* scratch, void* stream);
 
+/* Per-point weights and causal time weighting of the PDE losses (csrc/dpn_causal.hip).  A weight per collocation point multiplies the point's
+ * criterion value and its cotangent; causal training (Wang, Sankaran & Perdikaris 2022) derives it from the point's time bin:
+ * W_k = exp(-eps * sum_{j<k} l_j), l_j the mean point loss of bin j.  fp64 wherever a result is defined, no atomics, every sum in one fixed order:
+ * two runs agree bitwise.  Weights are constants of the loss: no cotangent is formed for them.
+ *
+ * dpn_causal_bins: out_n, jac_n, f, geo, phys as dpn_residual; t [n] the points' times (fp32, the forward kernel's t); factors = six HOST doubles
+ *   (the loss factors in the order of the residuals; phys->factor is not read).  Per point
+ *     s_i = sum_e factors[e] * rho(r_ie), e ascending, every product and sum rounded once in fp64; rho = (double)r * (double)r for MSE, else the
+ *           fp32 criterion value cast up (what dpn_residual sums);
+ *     b_i = clamp(floor(((double)t_i - t_lo) * n_bins / (t_hi - t_lo)), 0, n_bins - 1), each operation rounded once in fp64 (t_hi - t_lo formed on the
+ *           host); a NaN goes to bin 0.
+ *   bin [n] int32 = b_i;  rows [ceil(n / 256)][n_bins][2] fp64 (dpn_causal_rows_doubles(n, n_bins) doubles; 0 for unsupported arguments): per block and
+ *   bin the sum of s_i in point order and the count.
+ *   -1: n <= 0, n_bins outside 1..DPN_CAUSAL_MAX_BINS, t_hi <= t_lo, a bound that is not finite, a NULL pointer, a criterion dpn_residual rejects.
+ * dpn_causal_weights (one workgroup): the block rows of bin k are added in a fixed order (blocks q, q + 4, ... for q = 0..3, then ((p0 + p1) + p2) + p3);
+ *   l_k = sum_k / count_k, 0 for an empty bin.  relative != 0: l_k is divided by the mean of l over the non-empty bins (added k ascending); when that
+ *   mean is not finite or not > 0 every W_k = 1.  cum_k = the sequential exclusive prefix sum of l (normalised if relative); W_k = exp(-eps * cum_k).
+ *   W32 [n_bins] fp32 = (float)W_k, what dpn_residual_weighted reads;  diag [3 n_bins + 2] fp64 = W [n_bins] | l [n_bins], un-normalised |
+ *   count [n_bins] | min_k W_k | the normaliser (1 when relative == 0).
+ *   -1: a NULL pointer, n <= 0, n_bins outside 1..DPN_CAUSAL_MAX_BINS, eps negative or not finite.
+ * dpn_residual_weighted: dpn_residual with the point weight wt_i = w[i] * bin_w[bin[i]] (w [n] fp32 or NULL = 1; bin [n] int32 with bin_w, both or
+ *   neither, bin[i] an index into bin_w as dpn_causal_bins writes it; neither w nor bin: -1).  wt_i multiplies the point's criterion value in the fp64
+ *   block sums (as a double, before the wave tree) and the point's cotangents g_out, g_jxi (multiplied into the fp32 factor 1 / n of d loss_e / d r_e).  loss_sums has
+ *   dpn_residual's layout: dpn_residual_finish(_batch) finishes it, dividing by n -- not by the sum of the weights --, so the loss is linear in the
+ *   weights and a weight of 1 is the plain mean.  With every wt_i == 1.0f, loss_sums, g_out and g_jxi are bitwise dpn_residual's. */
+#define DPN_CAUSAL_MAX_BINS 64
+int64_t dpn_causal_rows_doubles(int64_t n, int n_bins);
+int dpn_causal_bins(const float* out_n, const float* jac_n, const float* f, const float* t, int64_t n, const DpnGeometry* geo, const DpnPhysics* phys,
+                    const double* factors, double t_lo, double t_hi, int n_bins, int32_t* bin, double* rows, void* stream);
+int dpn_causal_weights(const double* rows, int64_t n, int n_bins, double eps, int relative, float* W32, double* diag, void* stream);
+int dpn_residual_weighted(const float* out_n, const float* jac_n, const float* f, int64_t n, const DpnGeometry* geo, const DpnPhysics* phys,
+                          const float* gl /*[6] or NULL*/, const float* gtot /*[1] or NULL*/, double* loss_sums, float* g_out, float* g_jxi,
+                          const float* w, const int32_t* bin, const float* bin_w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
