@@ -4,16 +4,13 @@
 //   dpn_causal_bins       : the residual body per point, s_i = sum_e factor_e * rho(r_ie) in fp64, the point's time bin, and per block one row of
 //                           per-bin (sum s, count);
 //   dpn_causal_weights    : one workgroup: the block rows added in a fixed order, l_k, the exclusive prefix sum, W_k;
-//   dpn_residual_weighted : dpn_residual_kernel with the point's weight w_i * bin_w[bin_i] multiplied into its block sums and its cotangents.
 // One thread per point, wave64, 256 threads per block.  No atomics: every sum has one fixed order, so two runs -- eager or replayed from a captured
 // graph -- agree bitwise.  All fp64 arithmetic that defines a result is compiled without contraction (one rounding per operation).  The residual
-// body and the fp32 cotangent chain are dpn_residual.hip's, compiled as that unit compiles them: with every weight 1.0f the weighted kernel's block
-// rows and cotangents are bitwise dpn_residual's.
+// body is dpn_residual.hip's (dpn_residual_body.inc), the criterion dpn_criterion.h's.  The kernel that applies the weights is in dpn_residual.hip:
+// dpn_residual_kernel<ResWArgs>, behind dpn_residual_weighted.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "../../include/dpn_hip.h"
-
-#define DEV __device__ __forceinline__
+#include "dpn_criterion.h"
 
 namespace {
 
@@ -21,24 +18,6 @@ constexpr int THREADS = 256, MAX_BINS = DPN_CAUSAL_MAX_BINS;
 
 inline bool finite_host(double v) { return v >= -1.7976931348623157e308 && v <= 1.7976931348623157e308; }       // false for NaN and +-inf
 DEV bool finite64(double v) { return fabs(v) <= 1.7976931348623157e308; }
-
-// the criterion's per-element value and slope exactly as dpn_residual.hip states them (restated here: that unit's object does not change with this one)
-DEV float crit_value(const float r, const int kind, const float beta) {
-    const float ar = fabsf(r);
-    if (kind == DPN_CRIT_L1) return ar;
-    return ar < beta ? 0.5f * r * r / beta : ar - 0.5f * beta;
-}
-DEV float crit_slope(const float r, const int kind, const float beta) {
-    if (kind == DPN_CRIT_MSE) return 2.0f * r;
-    const float sg = r > 0.f ? 1.f : (r < 0.f ? -1.f : 0.f);
-    if (kind == DPN_CRIT_L1) return sg;
-    return fabsf(r) < beta ? r / beta : sg;
-}
-// rho(r) in fp64: MSE squares in fp64 (exact: two 24-bit significands), the others cast the fp32 value up -- what dpn_residual_kernel sums
-DEV double rho64(const float r, const int kind, const float beta) {
-#pragma clang fp contract(off)
-    return kind == DPN_CRIT_MSE ? (double)r * (double)r : (double)crit_value(r, kind, beta);
-}
 
 // ------------------------------------------------------------------------------------------------ bins
 struct BinArgs {
@@ -137,92 +116,6 @@ __global__ __launch_bounds__(THREADS) void dpn_causal_weights_kernel(const doubl
     diag[3 * n_bins] = w_min; diag[3 * n_bins + 1] = norm;
 }
 
-// ------------------------------------------------------------------------------------------------ the weighted residual kernel
-struct ResWArgs {
-    const float *out_n, *jac_n, *f;
-    int64_t n;
-    DpnGeometry geo;
-    DpnPhysics ph;
-    const float *gl, *gtot;
-    double* loss_sums;
-    float *g_out, *g_jxi;
-    const float* w;
-    const int32_t* bin;
-    const float* bin_w;
-};
-
-// dpn_residual_kernel (dpn_residual.hip) line by line, plus `wt`: in the fp64 block sums and in inv_n, the last factor of g[e], the head of the
-// cotangent chain (everything behind g[e] is linear in it).
-__global__ __launch_bounds__(256) void dpn_residual_weighted_kernel(ResWArgs a) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool valid = i < a.n;
-    const int64_t ic = valid ? i : a.n - 1;
-#include "dpn_residual_body.inc"
-    const float wt = (a.w ? a.w[ic] : 1.f) * (a.bin ? a.bin_w[a.bin[ic]] : 1.f);
-    if (a.loss_sums) {
-        __shared__ double wsum[4][6];
-#pragma unroll
-        for (int e = 0; e < 6; ++e) {
-#pragma clang fp contract(off)
-            double s = 0.0;
-            if (valid) s = (double)wt * rho64(r[e], a.ph.criterion, a.ph.beta);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) s = s + __shfl_xor(s, o);
-            if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6][e] = s;
-        }
-        __syncthreads();
-        if (threadIdx.x < 6) {
-#pragma clang fp contract(off)
-            a.loss_sums[(int64_t)blockIdx.x * 6 + threadIdx.x] =
-                ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x];
-        }
-    }
-    if (!a.g_out || !valid) return;
-    float g[6];
-    // The weight rides on 1 / n (the division is by n, not by the sum of the weights): the expression of g[e] keeps dpn_residual_kernel's shape, its
-    // last factor included -- the compiler contracts that multiply into the sums that read g[e], so a factor appended behind it would move a rounding.
-    const float inv_n = (a.ph.reduce_sum ? 1.0f : 1.0f / (float)a.n) * wt;
-#pragma unroll
-    for (int e = 0; e < 6; ++e) {
-        const float w = (a.gl || a.gtot) ? ((a.gl ? a.gl[e] : 0.f) + (a.gtot ? a.gtot[0] : 0.f)) : 1.f;
-        g[e] = a.ph.factor[e] * w * crit_slope(r[e], a.ph.criterion, a.ph.beta) * inv_n;
-    }
-    const float ir = 1.f / rho, ire = 1.f / (rho + EPS);
-    float gv[6], gJ[6][3];
-    gv[0] = g[0] * J[0][0] + g[1] * (J[1][0] + fc) + g[2] * J[5][0] + g[3] * (C_P * J[3][0] - J[2][0] * ire + L_V * J[4][0]) + g[4] * (-J[2][0] * K + J[4][0]);
-    gv[1] = g[0] * (J[0][1] - fc) + g[1] * J[1][1] + g[2] * J[5][1] + g[3] * (C_P * J[3][1] - J[2][1] * ire + L_V * J[4][1]) + g[4] * (-J[2][1] * K + J[4][1]);
-    gv[2] = g[4] * omega * delta * Fv / ((p + EPS) * (p + EPS)) + g[5];
-    gv[3] = -g[5] * rho * (1.f + 0.608f * q) * R_D;
-    gv[4] = -g[5] * rho * 0.608f * R_D * T;
-    gv[5] = -g[0] * J[2][0] * ir * ir - g[1] * J[2][1] * ir * ir + g[2] * (J[0][0] + J[1][1]) + g[3] * omega * ire * ire - g[5] * (1.f + 0.608f * q) * R_D * T;
-    gJ[0][0] = g[0] * u + g[2] * rho; gJ[0][1] = g[0] * v;             gJ[0][2] = g[0];
-    gJ[1][0] = g[1] * u;              gJ[1][1] = g[1] * v + g[2] * rho; gJ[1][2] = g[1];
-    gJ[2][0] = g[0] * ir - g[3] * u * ire - g[4] * u * K;
-    gJ[2][1] = g[1] * ir - g[3] * v * ire - g[4] * v * K;
-    gJ[2][2] = -g[3] * ire - g[4] * K;
-    gJ[3][0] = g[3] * C_P * u; gJ[3][1] = g[3] * C_P * v; gJ[3][2] = g[3] * C_P;
-    const float gq = g[3] * L_V + g[4];
-    gJ[4][0] = gq * u; gJ[4][1] = gq * v; gJ[4][2] = gq;
-    gJ[5][0] = g[2] * u; gJ[5][1] = g[2] * v; gJ[5][2] = g[2];
-    const float sc[3] = {1.f / a.geo.lon_m1 / a.geo.dx, 1.f / a.geo.lat_m1 / a.geo.dy, 1.f / a.geo.pred_t_span};
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        float go = gv[k] * msk[k];
-        if (a.ph.sq_on[k] && msk[k] != 0.f) {
-            float t = 0.f;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) t = fmaf(gJ[k][c], a.jac_n[(i * 6 + k) * 3 + c], t);
-            go = fmaf(t, 2.f * a.ph.std[k] * a.ph.std[k], go);
-        }
-        a.g_out[i * 6 + k] = go;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) a.g_jxi[(i * 6 + k) * 3 + c] = gJ[k][c] * msk[k] * sc[c];
-    }
-}
-
-inline bool criterion_ok(const DpnPhysics* ph) {
-    return ph->criterion >= DPN_CRIT_MSE && ph->criterion <= DPN_CRIT_SMOOTH_L1 && !(ph->criterion == DPN_CRIT_SMOOTH_L1 && !(ph->beta > 0.f));
-}
 inline int64_t blocks_of(int64_t n) { return (n + THREADS - 1) / THREADS; }
 
 }  // namespace
@@ -247,16 +140,6 @@ int dpn_causal_weights(const double* rows, int64_t n, int n_bins, double eps, in
     if (!rows || !W32 || !diag || n <= 0 || n_bins < 1 || n_bins > MAX_BINS || !(eps >= 0.0) || !finite_host(eps)) return -1;
     hipLaunchKernelGGL(dpn_causal_weights_kernel, dim3(1), dim3(THREADS), 0, (hipStream_t)stream, rows, blocks_of(n), n_bins, eps, relative ? 1 : 0, W32,
                        diag);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-int dpn_residual_weighted(const float* out_n, const float* jac_n, const float* f, int64_t n, const DpnGeometry* geo, const DpnPhysics* phys,
-                          const float* gl, const float* gtot, double* loss_sums, float* g_out, float* g_jxi, const float* w, const int32_t* bin,
-                          const float* bin_w, void* stream) {
-    if (!out_n || !jac_n || !f || !geo || !phys || n <= 0 || (g_out && !g_jxi) || !criterion_ok(phys)) return -1;
-    if ((!w && !bin) || (!bin != !bin_w)) return -1;                       // a weight source is required; bin and bin_w come together
-    ResWArgs a{out_n, jac_n, f, n, *geo, *phys, gl, gtot, loss_sums, g_out, g_jxi, w, bin, bin_w};
-    hipLaunchKernelGGL(dpn_residual_weighted_kernel, dim3((unsigned)blocks_of(n)), dim3(256), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -6,12 +6,14 @@
 //
 // Kernel inventory
 //   dpn_contract_gpe_kernel     cotangent of caller-encoded coordinates
-//   dpn_residual_kernel         de-norm, clip, six residuals, wave-shuffle loss reduction, analytic cotangents
+//   dpn_residual_kernel<Args>   de-norm, clip, six residuals, wave-shuffle loss reduction, analytic cotangents; instantiated for ResArgs
+//                               (dpn_residual) and for ResWArgs (dpn_residual_weighted: a weight per point in the sums and the cotangents)
 //   dpn_residual_points_kernel  the same residual body, written out per point (inference diagnostics)
 //   dpn_residual_finish_kernel  block rows -> the six scaled losses and their sum
 //   dpn_smooth_l1_kernel        the data loss and its cotangent
 // No kernel in this file uses atomics: every reduction is fixed-order, the whole step is bitwise reproducible.
 #include "dpn_device.h"
+#include "dpn_criterion.h"
 
 // g_pe[n][c] = sum_k g_out[n][k] * gpe[n][k][c]: the cotangent of caller-encoded coordinates (PhysicsNet.forward backward w.r.t. coord_x)
 __global__ __launch_bounds__(192) void dpn_contract_gpe_kernel(const float* g_out, const float* gpe, int64_t n, float* g_pe) {
@@ -32,21 +34,15 @@ struct ResArgs {
     const float *gl, *gtot;
     double* loss_sums;
     float *g_out, *g_jxi;
+    static constexpr bool weighted = false;
 };
-
-// the criterion's per-element value rho(r) and slope rho'(r) (DpnPhysics.criterion): every criterion the reference's builder offers is a function of
-// input - target alone, so `loss(lhs, 0)` (:104) and the gas law's `loss(p, rho R T)` (:179) are both mean(rho(r))
-DEV float crit_value(const float r, const int kind, const float beta) {
-    const float ar = fabsf(r);
-    if (kind == DPN_CRIT_L1) return ar;
-    return ar < beta ? 0.5f * r * r / beta : ar - 0.5f * beta;             // nn.SmoothL1Loss
-}
-DEV float crit_slope(const float r, const int kind, const float beta) {
-    if (kind == DPN_CRIT_MSE) return 2.0f * r;
-    const float sg = r > 0.f ? 1.f : (r < 0.f ? -1.f : 0.f);
-    if (kind == DPN_CRIT_L1) return sg;
-    return fabsf(r) < beta ? r / beta : sg;
-}
+// + the point weight wt_i = w[i] * bin_w[bin[i]]; either source may be absent (1.0f)
+struct ResWArgs : ResArgs {
+    const float* w;
+    const int32_t* bin;
+    const float* bin_w;
+    static constexpr bool weighted = true;
+};
 
 DEV float wave_sum(float v) {
 #pragma unroll
@@ -54,11 +50,17 @@ DEV float wave_sum(float v) {
     return v;
 }
 
-__global__ __launch_bounds__(256) void dpn_residual_kernel(ResArgs a) {
+// One kernel, two instantiations.  The weighted one differs in `wt` alone: in the fp64 block sums and in inv_n, the last factor of g[e], the head of
+// the cotangent chain (everything behind g[e] is linear in it); with every weight 1.0f its block rows and cotangents are bitwise the unweighted
+// one's.  The template is on the __global__ function itself: through a shared device function the compiler loads the argument struct wholesale
+// and both instruction streams change.
+template <class Args> __global__ __launch_bounds__(256) void dpn_residual_kernel(Args a) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool valid = i < a.n;
     const int64_t ic = valid ? i : a.n - 1;
 #include "dpn_residual_body.inc"
+    float wt = 1.f;
+    if constexpr (Args::weighted) wt = (a.w ? a.w[ic] : 1.f) * (a.bin ? a.bin_w[a.bin[ic]] : 1.f);
     if (a.loss_sums) {
         // fp64 partial sums (residual^2 spans 1e-20..1e+20 across equations): wave shuffle tree, then the four waves of the block
         // in a fixed order -> one [6] row per block.  No atomics: dpn_residual_finish adds the rows in a fixed order, so the
@@ -66,20 +68,29 @@ __global__ __launch_bounds__(256) void dpn_residual_kernel(ResArgs a) {
         __shared__ double wsum[4][6];
 #pragma unroll
         for (int e = 0; e < 6; ++e) {
+#pragma clang fp contract(off)
             double s = 0.0;
-            if (valid) s = a.ph.criterion == DPN_CRIT_MSE ? (double)r[e] * (double)r[e] : (double)crit_value(r[e], a.ph.criterion, a.ph.beta);
+            if (valid) {
+                s = rho64(r[e], a.ph.criterion, a.ph.beta);
+                if constexpr (Args::weighted) s = (double)wt * s;
+            }
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+            for (int o = 32; o > 0; o >>= 1) s = s + __shfl_xor(s, o);
             if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6][e] = s;
         }
         __syncthreads();
-        if (threadIdx.x < 6)
+        if (threadIdx.x < 6) {
+#pragma clang fp contract(off)
             a.loss_sums[(int64_t)blockIdx.x * 6 + threadIdx.x] =
                 ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x];
+        }
     }
     if (!a.g_out || !valid) return;
     float g[6];
-    const float inv_n = a.ph.reduce_sum ? 1.0f : 1.0f / (float)a.n;       // reduction "sum": the criterion does not divide by the number of points
+    float inv_n = a.ph.reduce_sum ? 1.0f : 1.0f / (float)a.n;             // reduction "sum": the criterion does not divide by the number of points
+    // The weight rides on 1 / n (the division is by n, not by the sum of the weights): g[e] keeps its shape, last factor included -- the compiler
+    // contracts that multiply into the sums that read g[e], so a factor appended behind it would move a rounding.
+    if constexpr (Args::weighted) inv_n = inv_n * wt;
 #pragma unroll
     for (int e = 0; e < 6; ++e) {
         // upstream weight of loss e: cotangent of losses[e] plus cotangent of the in-kernel total (1 when neither is given)
@@ -190,10 +201,20 @@ int dpn_contract_gpe(const float* g_out, const float* gpe, int64_t n, float* g_p
 int dpn_residual(const float* out_n, const float* jac_n, const float* f, int64_t n, const DpnGeometry* geo, const DpnPhysics* phys,
                  const float* gl, const float* gtot, double* loss_sums, float* g_out, float* g_jxi, void* stream) {
     if (!out_n || !jac_n || !f || !geo || !phys || n <= 0 || (g_out && !g_jxi)) return -1;
-    if (phys->criterion < DPN_CRIT_MSE || phys->criterion > DPN_CRIT_SMOOTH_L1 || (phys->criterion == DPN_CRIT_SMOOTH_L1 && !(phys->beta > 0.f))) return -1;
+    if (!criterion_ok(phys)) return -1;
     ResArgs a{out_n, jac_n, f, n, *geo, *phys, gl, gtot, loss_sums, g_out, g_jxi};
-    hipLaunchKernelGGL(dpn_residual_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(dpn_residual_kernel<ResArgs>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
     return ck(hipGetLastError());
+}
+
+int dpn_residual_weighted(const float* out_n, const float* jac_n, const float* f, int64_t n, const DpnGeometry* geo, const DpnPhysics* phys,
+                          const float* gl, const float* gtot, double* loss_sums, float* g_out, float* g_jxi, const float* w, const int32_t* bin,
+                          const float* bin_w, void* stream) {
+    if (!out_n || !jac_n || !f || !geo || !phys || n <= 0 || (g_out && !g_jxi) || !criterion_ok(phys)) return -1;
+    if ((!w && !bin) || (!bin != !bin_w)) return -1;                       // a weight source is required; bin and bin_w come together
+    ResWArgs a{{out_n, jac_n, f, n, *geo, *phys, gl, gtot, loss_sums, g_out, g_jxi}, w, bin, bin_w};
+    hipLaunchKernelGGL(dpn_residual_kernel<ResWArgs>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 int dpn_residual_points(const float* out_n, const float* jac_n, const float* f, int64_t n, const DpnGeometry* geo, const DpnPhysics* phys, float* res,

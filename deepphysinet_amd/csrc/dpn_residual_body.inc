@@ -1,4 +1,4 @@
-// The residual body of dpn_residual_kernel / dpn_residual_points_kernel (included by both, the way dpn_ring_kernels.inc is compiled twice):
+// The residual body of dpn_residual_kernel / dpn_residual_points_kernel (dpn_residual.hip) and dpn_causal_bins_kernel (dpn_causal.hip), included by each:
 // inverse_norm (+ clip), the chained Jacobian J, and the six signed residuals r[e] = lhs - rhs of interface_physics.py:97-185 at point `ic` of
 // the kernel argument `a` (out_n, jac_n, f, ph).  Leaves val, msk, J, the named fields, omega, delta, Fv, K and r in scope.
     constexpr float C_P = 1005.f, L_V = 2.5e6f, R_V = 461.5f, R_D = 287.f, EPS = 1e-6f;

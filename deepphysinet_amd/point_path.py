@@ -550,40 +550,50 @@ def _point_weights(what, w, n, device):
     return w
 
 
-def _group_weights(cfg, causal, out_n, jac_n, f_, t_, groups, given):
+def _group_weights(what, cfg, extra, out_n, jac_n, f_, t_, groups):
     """Per row group (a0, a1) the weight sources of dpn_residual_weighted: (w [m] or None, bin or None, W32 or None), or None for a group with
-    neither (it takes the plain dpn_residual).  given: the caller's weights per group (or None); causal: bins and weights per group, each group
-    its own (_causal_group).  Also returns the groups' diag tensors (None without causal)."""
+    neither (it takes the plain dpn_residual); None for extra None (_weight_options: no option given, nothing is launched or allocated).
+    extra = (the caller's weights of the FIRST group or None, causal or None, a list that receives the groups' diag tensors or None); causal: bins
+    and weights per group, each group its own (_causal_group)."""
+    if extra is None:
+        return None
+    given, causal, diag_out = extra
+    if given is not None:
+        given = _point_weights(what, given, groups[0][1] - groups[0][0], out_n.device)
     out, diags = [], []
-    for (a0, a1), w in zip(groups, given):
+    for gi, (a0, a1) in enumerate(groups):
+        w = given if gi == 0 else None
         bin_ = w32 = diag = None
         if causal is not None:
             bin_, w32, diag = _causal_group(cfg, causal, out_n, jac_n, f_, t_, a0, a1)
         out.append(None if (w is None and bin_ is None) else (w, bin_, w32))
         diags.append(diag)
-    return out, diags
+    if diag_out is not None:
+        diag_out[:] = diags
+    return out
+
+
+def _residual_launch(what, geo, ph, out_n, jac_n, f_, m, gl, gt, sums, g_out, g_jxi, wt):
+    """One residual launch over the m points at the head of out_n, jac_n, f_ (a group's slices; gl [6], gt [1]: fp32 device cotangents; sums,
+    g_out, g_jxi: what the launch writes; each may be None).  wt None: dpn_residual; wt = (w, bin, W32) (_group_weights): dpn_residual_weighted,
+    the same arguments and the three weight sources.  what: '' or '(grad)', for the error message."""
+    name, sources = ('dpn_residual', ()) if wt is None else ('dpn_residual_weighted', tuple(_ptr(v) for v in wt))
+    L.check(getattr(L.load(), name)(_ptr(out_n), _ptr(jac_n), _ptr(f_), m, ctypes.byref(geo), ctypes.byref(ph), _ptr(gl), _ptr(gt), _ptr(sums),
+                                    _ptr(g_out), _ptr(g_jxi), *sources, _stream()), name + what)
 
 
 def _residual_losses(cfg, out_n, jac_n, f_, groups, losses, unit=None, sums=None, weights=None):
-    """The residual-loss sums of row groups (a0, a1) of out_n [n, 6], jac_n [n, 6, 3], f_ [n]: per group one dpn_residual launch into per-block
-    rows and one dpn_residual_finish into its `losses` row [7] (the six scaled terms, their total).  unit = (scale, g_out, g_jxi): the same pass
-    over the points also writes d total / d (out, Jacobian) for the cotangent `scale` (a device 1.0) of the total.  sums: the block rows of one
-    group given by the caller; losses None leaves them to a later finish launch (_residual_finish, or dpn_residual_finish_batch for a batch).
-    weights: per group None or (w, bin, W32) (_group_weights): such a group's launch is dpn_residual_weighted, same rows, same finish."""
-    lib = L.load()
+    """The residual-loss sums of row groups (a0, a1) of out_n [n, 6], jac_n [n, 6, 3], f_ [n]: per group one residual launch (_residual_launch)
+    into per-block rows and one dpn_residual_finish into its `losses` row [7] (the six scaled terms, their total).  unit = (scale, g_out, g_jxi):
+    the same pass over the points also writes d total / d (out, Jacobian) for the cotangent `scale` (a device 1.0) of the total.  sums: the block
+    rows of one group given by the caller; losses None leaves them to a later finish launch (_residual_finish, or dpn_residual_finish_batch for a
+    batch).  weights: per group None or (w, bin, W32) (_group_weights): same rows, same finish."""
     geo, ph = cfg.geometry(), cfg.physics()
     for gi, (a0, a1) in enumerate(groups):
         m = a1 - a0
         s_ = torch.empty(((m + 255) // 256) * 6, dtype=torch.float64, device=out_n.device) if sums is None else sums
         sc, g_out, g_jxi = (None, None, None) if unit is None else (unit[0], unit[1][a0:], unit[2][a0:])
-        wt = None if weights is None else weights[gi]
-        if wt is None:
-            L.check(lib.dpn_residual(_ptr(out_n[a0:]), _ptr(jac_n[a0:]), _ptr(f_[a0:]), m, ctypes.byref(geo), ctypes.byref(ph), None, _ptr(sc),
-                                     _ptr(s_), _ptr(g_out), _ptr(g_jxi), _stream()), 'dpn_residual')
-        else:
-            L.check(lib.dpn_residual_weighted(_ptr(out_n[a0:]), _ptr(jac_n[a0:]), _ptr(f_[a0:]), m, ctypes.byref(geo), ctypes.byref(ph), None, _ptr(sc),
-                                              _ptr(s_), _ptr(g_out), _ptr(g_jxi), _ptr(wt[0]), _ptr(wt[1]), _ptr(wt[2]), _stream()),
-                    'dpn_residual_weighted')
+        _residual_launch('', geo, ph, out_n[a0:], jac_n[a0:], f_[a0:], m, None, sc, s_, g_out, g_jxi, None if weights is None else weights[gi])
         if losses is not None:
             _residual_finish(cfg, s_, m, losses[gi])
 
@@ -594,11 +604,10 @@ def _residual_finish(cfg, sums, n, losses):
 
 
 def _residual_cotangent(cfg, out_n, jac_n, f_, groups, g_out=None, g_jxi=None, weights=None):
-    """d loss / d (out, Jacobian) of the residual losses (dpn_residual in gradient mode) into g_out [n, 6], g_jxi [n, 6, 3] (allocated when not
-    given), group by group: groups = [(a0, a1, cotangent of the terms [6] or None, cotangent of the total [1] or None)]; a group with neither
+    """d loss / d (out, Jacobian) of the residual losses (the residual launch in gradient mode) into g_out [n, 6], g_jxi [n, 6, 3] (allocated when
+    not given), group by group: groups = [(a0, a1, cotangent of the terms [6] or None, cotangent of the total [1] or None)]; a group with neither
     takes a zero cotangent on its terms (its rows are written all the same).  weights: per group None or (w, bin, W32), the weight sources the
-    forward pass used (saved, never recomputed): such a group's launch is dpn_residual_weighted.  Returns (g_out, g_jxi)."""
-    lib = L.load()
+    forward pass used (saved, never recomputed).  Returns (g_out, g_jxi)."""
     n, dev = out_n.shape[0], out_n.device
     g_out = torch.empty((n, 6), dtype=torch.float32, device=dev) if g_out is None else g_out
     g_jxi = torch.empty((n, 6, 3), dtype=torch.float32, device=dev) if g_jxi is None else g_jxi
@@ -608,16 +617,8 @@ def _residual_cotangent(cfg, out_n, jac_n, f_, groups, g_out=None, g_jxi=None, w
         if gl is None and gt is None:
             zero6 = torch.zeros(6, dtype=torch.float32, device=dev) if zero6 is None else zero6
             gl = zero6
-        wt = None if weights is None else weights[gi]
-        if wt is None:
-            L.check(lib.dpn_residual(_ptr(out_n[a0:]), _ptr(jac_n[a0:]), _ptr(f_[a0:]), a1 - a0, ctypes.byref(geo), ctypes.byref(ph),
-                                     None if gl is None else _ptr(_f32c(gl)), None if gt is None else _ptr(_f32c(gt).reshape(1)), None,
-                                     _ptr(g_out[a0:]), _ptr(g_jxi[a0:]), _stream()), 'dpn_residual(grad)')
-        else:
-            L.check(lib.dpn_residual_weighted(_ptr(out_n[a0:]), _ptr(jac_n[a0:]), _ptr(f_[a0:]), a1 - a0, ctypes.byref(geo), ctypes.byref(ph),
-                                              None if gl is None else _ptr(_f32c(gl)), None if gt is None else _ptr(_f32c(gt).reshape(1)), None,
-                                              _ptr(g_out[a0:]), _ptr(g_jxi[a0:]), _ptr(wt[0]), _ptr(wt[1]), _ptr(wt[2]), _stream()),
-                    'dpn_residual_weighted(grad)')
+        _residual_launch('(grad)', geo, ph, out_n[a0:], jac_n[a0:], f_[a0:], a1 - a0, None if gl is None else _f32c(gl),
+                         None if gt is None else _f32c(gt).reshape(1), None, g_out[a0:], g_jxi[a0:], None if weights is None else weights[gi])
     return g_out, g_jxi
 
 
@@ -640,13 +641,8 @@ class _PdeLossFn(torch.autograd.Function):
         ctx.unit = None
         if need_grad:
             ctx.unit = (torch.empty((n, 6), dtype=torch.float32, device=dev), torch.empty((n, 6, 3), dtype=torch.float32, device=dev))
-        ctx.weights = None
-        if extra is not None:
-            # bins, weights, then the weighted residual pass; bin, W32 and the caller's w stay in ctx for the backward pass
-            w = None if extra[0] is None else _point_weights('pde_losses', extra[0], n, dev)
-            ctx.weights, diags = _group_weights(cfg, extra[1], out_n, jac_n, ops.f, ops.t, ((0, n),), (w,))
-            if extra[2] is not None:
-                extra[2][:] = diags
+        # bins, weights, then the weighted residual pass; bin, W32 and the caller's w stay in ctx for the backward pass
+        ctx.weights = _group_weights('pde_losses', cfg, extra, out_n, jac_n, ops.f, ops.t, ((0, n),))
         _residual_losses(cfg, out_n, jac_n, ops.f, ((0, n),), losses, unit=None if ctx.unit is None else (_one(dev),) + ctx.unit,
                          weights=ctx.weights)
         ctx.cfg, ctx.ws, ctx.ops, ctx.fields = cfg, ws, ops, (out_n, jac_n)
@@ -808,13 +804,16 @@ class _PdeLossBatchFn(torch.autograd.Function):
         return (None, None, None, None, None, None, None, g_heads, g_evec, *_static_views(total))
 
 
-def _step_pass(cfg, ws, nets, n_inter, x_, y_, t_, f_, cd_, losses, want_saved=False):
+def _step_pass(what, cfg, ws, nets, n_inter, x_, y_, t_, f_, cd_, losses, want_saved=False, extra=None):
     """The step body's point pass over [interior | margin] rows (the first n_inter interior): ONE forward with the Jacobian, then the residual-loss
     sums of the two groups into losses [2, 7].  _StepLossFn.forward (want_saved, for its backward) and eval_step(_batch) both run exactly this, so
-    their PDE losses are the same bitwise.  Returns (out_n, jac_n)."""
+    their PDE losses are the same bitwise.  extra (_weight_options): per group bins, weights, the weighted residual pass, finish; interior and
+    margin each their own bins and weights.  Returns (out_n, jac_n, the groups' weight sources or None)."""
     out_n, jac_n = _forward_points(cfg, ws, nets, x_, y_, t_, None, cd_, want_jac=True, want_saved=want_saved)
-    _residual_losses(cfg, out_n, jac_n, f_, ((0, n_inter), (n_inter, cd_.shape[0])), losses)
-    return out_n, jac_n
+    groups = ((0, n_inter), (n_inter, cd_.shape[0]))
+    weights = _group_weights(what, cfg, extra, out_n, jac_n, f_, t_, groups)
+    _residual_losses(cfg, out_n, jac_n, f_, groups, losses, weights=weights)
+    return out_n, jac_n, weights
 
 
 class _StepLossFn(torch.autograd.Function):
@@ -834,19 +833,9 @@ class _StepLossFn(torch.autograd.Function):
         need_grad = any(v.requires_grad for v in (heads, evec) + tuple(statics))
         ws = _Workspace(n, cfg.prec, dev)
         losses = torch.empty((2, 7), dtype=torch.float32, device=dev)
-        ctx.weights = None
-        if extra is None:
-            out_n, jac_n = _step_pass(cfg, ws, ops.nets(), n_inter, ops.x, ops.y, ops.t, ops.f, ops.cd, losses, want_saved=need_grad)
-        else:
-            # _step_pass with weights: per group bins, weights, the weighted residual pass, finish; interior and margin each their own bins and
-            # weights.  The data loss below is not weighted.
-            groups = ((0, n_inter), (n_inter, n))
-            out_n, jac_n = _forward_points(cfg, ws, ops.nets(), ops.x, ops.y, ops.t, None, ops.cd, want_jac=True, want_saved=need_grad)
-            w = None if extra[0] is None else _point_weights('step_losses', extra[0], n_inter, dev)
-            ctx.weights, diags = _group_weights(cfg, extra[1], out_n, jac_n, ops.f, ops.t, groups, (w, None))
-            if extra[2] is not None:
-                extra[2][:] = diags
-            _residual_losses(cfg, out_n, jac_n, ops.f, groups, losses, weights=ctx.weights)
+        # the data loss below is not weighted
+        out_n, jac_n, ctx.weights = _step_pass('step_losses', cfg, ws, ops.nets(), n_inter, ops.x, ops.y, ops.t, ops.f, ops.cd, losses,
+                                               want_saved=need_grad, extra=extra)
         dsum = torch.empty((n_m * 6 + 255) // 256, dtype=torch.float64, device=dev)
         L.check(L.load().dpn_smooth_l1(_ptr(out_n[n_inter:]), _ptr(ops.lab), n_m, beta, 1.0, _ptr(dsum), None, 0, None, _stream()), 'dpn_smooth_l1')
         data = (dsum.sum() / (6.0 * n_m)).float() * margin_factor
@@ -1044,8 +1033,7 @@ def _eval(what, cfg, n_inter, x, y, t, f, coord_data, labels, heads, evec, stati
         ws, nets = fields.field(b) if batch else (_Workspace(n_fwd, cfg.prec, dev), ops.nets())
         x_, y_, t_, f_, cd_, lab_ = (v[b] for v in ops[:4] + (ops.cd, ops.lab)) if batch else ops[:4] + (ops.cd, ops.lab)
         if with_pde:
-            out_n, _ = _step_pass(cfg, ws, nets, n_inter, x_, y_, t_, f_, cd_, losses[b])
-            out_n = out_n[n_inter:]
+            out_n = _step_pass(what, cfg, ws, nets, n_inter, x_, y_, t_, f_, cd_, losses[b])[0][n_inter:]
         else:                                              # the reference's first 2 000 steps: fields only, no Jacobian
             out_n, _ = _forward_points(cfg, ws, nets, x_[n_inter:], y_[n_inter:], t_[n_inter:], None, cd_[n_inter:], want_jac=False,
                                        want_saved=False)

@@ -507,7 +507,8 @@ int dpn_adaptive_select(const double* score, int64_t m, double k, double c, cons
                         float* out_x, float* out_y, float* out_t, float* out_f, float* out_coord_data, int32_t* idx, double* u, double* picked_score,
                         double* scratch, void* stream);
 
-/* Per-point weights and causal time weighting of the PDE losses (csrc/dpn_causal.hip).  A weight per collocation point multiplies the point's
+/* Per-point weights and causal time weighting of the PDE losses (bins and weights: csrc/dpn_causal.hip; dpn_residual_weighted: csrc/dpn_residual.hip,
+ * dpn_residual's kernel instantiated with the weights).  A weight per collocation point multiplies the point's
  * criterion value and its cotangent; causal training (Wang, Sankaran & Perdikaris 2022) derives it from the point's time bin:
  * W_k = exp(-eps * sum_{j<k} l_j), l_j the mean point loss of bin j.  fp64 wherever a result is defined, no atomics, every sum in one fixed order:
  * two runs agree bitwise.  Weights are constants of the loss: no cotangent is formed for them.

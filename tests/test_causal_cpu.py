@@ -114,14 +114,18 @@ def test_causal_unit_cross_compiles_without_spills_or_scratch(tmp_path):
     from deepphysinet_amd.build import COMMON, UNITS
     unit = [u for u in UNITS if os.path.basename(u[0]) == 'dpn_causal.hip']
     assert len(unit) == 1 and unit[0][2] == 'dpn_causal.o' and UNITS[-1] is unit[0]            # appended: the other units keep their index
-    src, flags, _ = unit[0]
-    asm = str(tmp_path / 'causal.s')
-    subprocess.run([_hipcc(), *[f for f in COMMON if f != '-fPIC'], *flags, '--cuda-device-only', '-S', '-I' + os.path.join(ROOT, 'include'), src, '-o', asm],
-                   check=True, capture_output=True)
-    text = open(asm).read()
-    names = re.findall(r'\.name:\s+(\S*dpn_(?:causal_bins|causal_weights|residual_weighted)_kernel\S*)', text)
-    assert len(names) == 3, names
-    for name in names:
+    residual = [u for u in UNITS if os.path.basename(u[0]) == 'dpn_residual.hip']             # holds the kernel that applies the weights
+    assert len(residual) == 1
+    texts = []
+    for src, flags, obj in (unit[0], residual[0]):
+        asm = str(tmp_path / (obj + '.s'))
+        subprocess.run([_hipcc(), *[f for f in COMMON if f != '-fPIC'], *flags, '--cuda-device-only', '-S', '-I' + os.path.join(ROOT, 'include'), src,
+                        '-o', asm], check=True, capture_output=True)
+        texts.append(open(asm).read())
+    found = [(re.findall(r'\.name:\s+(\S*dpn_causal_(?:bins|weights)_kernel\S*)', texts[0]), texts[0]),
+             (re.findall(r'\.name:\s+(\S*dpn_residual_kernel\S*ResWArgs\S*)', texts[1]), texts[1])]
+    assert [len(names) for names, _ in found] == [2, 1], found[0][0] + found[1][0]
+    for name, text in ((name, text) for names, text in found for name in names):
         at = text.index('.name:           ' + name)                      # the kernel's metadata entry: from its `- .agpr_count` to the next one
         end = text.find('- .agpr_count', at)
         block = text[text.rindex('- .agpr_count', 0, at):end if end > 0 else len(text)]
@@ -129,8 +133,9 @@ def test_causal_unit_cross_compiles_without_spills_or_scratch(tmp_path):
         assert int(re.search(r'\.sgpr_spill_count:\s+(\d+)', block).group(1)) == 0, name
         assert int(re.search(r'\.private_segment_fixed_size:\s+(\d+)', block).group(1)) == 0, name           # no scratch
         assert int(re.search(r'\.wavefront_size:\s+(\d+)', block).group(1)) == 64, name
-    assert 's_swappc_b64' not in text and 'scratch_' not in text
-    assert not re.search(r'\b(global|flat|buffer|ds)_atomic|\bds_(add|max|min)_', text), 'the unit must not use atomics'
+    for text in texts:
+        assert 's_swappc_b64' not in text and 'scratch_' not in text
+        assert not re.search(r'\b(global|flat|buffer|ds)_atomic|\bds_(add|max|min)_', text), 'the units must not use atomics'
 
 
 def test_causal_entry_points_are_exported_and_match_the_binding():

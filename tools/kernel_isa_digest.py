@@ -3,8 +3,10 @@
     python tools/kernel_isa_digest.py > after.txt          # no GPU needed; the same on the commit to compare with, then diff the tables
 
 Every entry of deepphysinet_amd.build.UNITS is compiled to gfx950 assembly with that unit's flags (minus -fPIC, as the hazard test does).
-Body = the text from the kernel's label to its .Lfunc_end, without `;` comments and with the function index taken out of the local labels
-(.LBB<i>_ -> .LBB_, .Ltmp<i> -> .Ltmp): it does not change when kernels move between units or change their order inside one.
+Body = the text from the kernel's label to its .Lfunc_end, without `;` comments, with the function index taken out of the local labels
+(.LBB<i>_ -> .LBB_, .Ltmp<i> -> .Ltmp), the kernel's own mangled name written $self, and without the directive that returns to the kernel's
+text section (.text, or the comdat .section .text.<name> of a template instantiation): it does not change when kernels move between units,
+change their order inside one, are renamed or become template instantiations.
 Descriptor = the .amdhsa_kernel ... .end_amdhsa_kernel block: register counts, LDS, scratch.  Two tables with equal digests for a kernel mean
 the same code object for it; a name listed under two units is a template instantiated twice (it would link silently as a weak symbol).
 """
@@ -27,7 +29,8 @@ def digest(text):
 def body_text(asm, name):
     start = asm.index('\n%s:' % name) + 1
     lines = (re.sub(r';.*', '', ln).rstrip() for ln in asm[start:asm.index('.Lfunc_end', start)].splitlines())
-    return re.sub(r'\.Ltmp\d+', '.Ltmp', re.sub(r'\.LBB\d+_', '.LBB_', '\n'.join(ln for ln in lines if ln)))
+    text = '\n'.join(ln for ln in lines if ln and not re.match(r'\s*\.(text|section\s+\.text\.\S*)$', ln))
+    return re.sub(r'\.Ltmp\d+', '.Ltmp', re.sub(r'\.LBB\d+_', '.LBB_', text.replace(name, '$self')))
 
 
 def main():
