@@ -194,9 +194,14 @@ EXPORTS = {
     'dpn_causal_weights': (c_int, [c_void_p, c_int64, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p]),
     'dpn_residual_weighted': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(DpnGeometry), POINTER(DpnPhysics), c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dpn_balance_scratch_doubles': (c_int64, [c_int, c_void_p]),
+    'dpn_balance_sumsq': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dpn_balance_update': (c_int, [c_void_p, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p]),
+    'dpn_balance_combine': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 CAUSAL_MAX_BINS = 64          # DPN_CAUSAL_MAX_BINS (include/dpn_hip.h)
+BALANCE_MAX_TERMS, BALANCE_STEP_TERMS = 16, 13          # DPN_BALANCE_MAX_TERMS, DPN_BALANCE_STEP_TERMS (include/dpn_hip.h)
 
 # Shelved experiments (include/dpn_hip_experiments.h): compiled only into libdpn_hip_exp.so (`python -m deepphysinet_amd.build --experiments`), which also
 # holds every product symbol; reached through load_experiments() by the code paths behind the matching frozen switches (config.py)

@@ -12,6 +12,7 @@ gradient for the same parameter inside one accumulation window (the parameter us
 zero_grad) gets an ordinary tensor and is added by autograd as usual -- writing it into the slot would overwrite the first one.  Like
 DistributedDataParallel(gradient_as_bucket_view=True), a gradient tensor kept by the caller across zero_grad is overwritten by the next
 backward pass."""
+import contextlib
 import weakref
 
 import torch
@@ -21,6 +22,7 @@ captured_step = [False]   # a fused optimiser step was captured in a hipGraph: i
                           # so parameter-keyed caches (PhysicsNet.encode_field(use_cache=True)) may only be trusted inside a capture
 _slots = {}          # param data_ptr -> (weakref(owner), weakref(param), offset, numel)
 misses = [0]         # new_grad calls that did NOT get an arena slot (branch.py forks a gradient launch only when every output is a fresh slot)
+_detached = [0]      # > 0 inside detached(): no slot is handed out
 
 
 def register(owner, params, offsets):
@@ -40,6 +42,17 @@ def unregister(owner):
         del _slots[k]
 
 
+@contextlib.contextmanager
+def detached():
+    """Inside, every gradient gets an ordinary tensor and no slot is leased: for gradients that are looked at and dropped (the per-term gradients of
+    the loss-balancing refresh, taken with torch.autograd.grad), which must not land in the optimiser's flat buffer."""
+    _detached[0] += 1
+    try:
+        yield
+    finally:
+        _detached[0] -= 1
+
+
 def slot_of(t, lease=True):
     """The arena view for the parameter whose storage `t` aliases (same data pointer, same numel), or None (no arena / already leased)."""
     e = _slots.get(t.data_ptr())
@@ -49,7 +62,7 @@ def slot_of(t, lease=True):
     if owner is None or pref is None or pref.data_ptr() != t.data_ptr() or n != t.numel() or owner._g_flat.device != t.device:
         return None
     if lease:
-        if off in owner._leased:
+        if _detached[0] or off in owner._leased:
             return None
         owner._leased.add(off)
     return owner._g_flat[off:off + n]

@@ -43,6 +43,7 @@ class InterfacePhysics(nn.Module):
         self.with_clip = True
         self.precision = L.PREC_NAMES[precision]
         self._cfg_cache = None
+        self.loss_balance_state = None          # training_step(balance=...): {'groups', 'lam' (fp32 [K], device), 'step', 'diag' (device or None)}
 
     # ------------------------------------------------------------------ configuration of the HIP path
     def point_config(self, loss_factor=None, criterion=None) -> PointConfig:
@@ -85,6 +86,9 @@ class InterfacePhysics(nn.Module):
         checkpoint_file = os.path.join(checkpoint_path, '%s_%d.pth' % (prefix, epoch))
         state_dict = {'model': self.physics_net.state_dict(), 'epoch': epoch, 'gobal_step': global_step}
         state_dict.update(kwargs)
+        lb = self.loss_balance_state
+        if lb is not None:                                   # the loss-balancing weights and their step counter (training_step(balance=...))
+            state_dict['loss_balance'] = {'groups': lb['groups'], 'lam': lb['lam'].detach().cpu().clone(), 'step': int(lb['step'])}
         torch.save(state_dict, checkpoint_file)
         shutil.copy(checkpoint_file, os.path.join(checkpoint_path, '%s_latest.pth' % prefix))
 
@@ -101,6 +105,9 @@ class InterfacePhysics(nn.Module):
         state_dict = torch.load(model_file, map_location=map_location)
         glob_step = state_dict.pop('gobal_step', 0)
         epoch = state_dict.pop('epoch', 0)
+        lb = state_dict.get('loss_balance')
+        if lb is not None:                                   # (a checkpoint without the key leaves the state as it is)
+            self.loss_balance_state = {'groups': lb['groups'], 'lam': lb['lam'].to(dtype=torch.float32).contiguous(), 'step': int(lb['step']), 'diag': None}
         # checkpoints written under DDP carry a 'module.' prefix (:1397 via :56); accept both
         if 'model' in state_dict and any(k.startswith('module.') for k in state_dict['model']):
             state_dict['model'] = {k[len('module.'):] if k.startswith('module.') else k: v for k, v in state_dict['model'].items()}
@@ -424,6 +431,88 @@ class InterfacePhysics(nn.Module):
             raise ValueError('causal_weights: eps is required')
         return CausalWeights(**opt)
 
+    def _balance_option(self, kwargs):
+        """The loops' `balance_losses` option (keyword, or train_cfg['losses']['balance_losses']): None (off), a balance.LossBalance, or a dict of
+        every, momentum, groups, lam_min, lam_max -> a balance.LossBalance."""
+        opt = kwargs.get('balance_losses', (self.train_cfg.get('losses') or {}).get('balance_losses'))
+        if opt is None or opt is False:
+            return None
+        from ..balance import LossBalance
+        if isinstance(opt, LossBalance):
+            return opt
+        if opt is True:
+            opt = {}
+        unknown = set(opt) - {'every', 'momentum', 'groups', 'lam_min', 'lam_max'}
+        if unknown:
+            raise ValueError('balance_losses: unknown keys %s (known: every, momentum, groups, lam_min, lam_max)' % sorted(unknown))
+        return LossBalance(**opt)
+
+    def _balance_state(self, balance, device):
+        """loss_balance_state for this option on this device: kept while the groups stay the same (a checkpoint's weights arrive on the host),
+        otherwise lambda = 1 and the counter at 0."""
+        st = self.loss_balance_state
+        if st is None or st['groups'] != balance.groups or st['lam'].numel() != balance.n_terms:
+            st = {'groups': balance.groups, 'lam': torch.ones(balance.n_terms, dtype=torch.float32, device=device), 'step': 0, 'diag': None}
+        if st['lam'].device != device:
+            st['lam'] = st['lam'].to(device)
+        self.loss_balance_state = st
+        return st
+
+    def _balance_refresh(self, balance, state, b, lf, inter_w, causal, grad_sync):
+        """One refresh of the balancing weights: for each term k the sum of squares of d (group k's terms) / d (all parameters), unweighted by lambda,
+        then dpn_balance_update.  Every term takes a forward and a backward pass of its own: the encoder stack's backward node hands the token
+        convolution's gradient on through state that one backward pass consumes, so one graph is not walked K times.  The
+        gradients come back from torch.autograd.grad inside grad_arena.detached(): none reaches a .grad or the optimiser's flat buffer."""
+        from .. import grad_arena
+        from ..point_path import balance_sumsq, balance_update, step_losses
+        net = self.physics_net
+        params = [p for p in net.parameters() if p.requires_grad]
+        shapes = [p.shape for p in params]
+        K, dev = balance.n_terms, b['field_data'].device
+        sumsq = torch.empty(K, dtype=torch.float64, device=dev)
+        cfg = self.point_config(lf)
+        n_inter, pts = self._eval_inputs(b, True)
+        with grad_arena.detached():
+            for k in range(K):
+                net.clear_field_cache()
+                meta_out = net.encode_field(b['field_data'], b['forecast_h'])
+                heads, evec, statics = net.field_weights(b['field_data'], b['forecast_h'], meta_out=meta_out)
+                it, _, mt, _, data = step_losses(cfg, n_inter, *pts, b['margin_data'], heads, evec, statics, beta=0.1, margin_factor=lf['margin_factor'],
+                                                 inter_weights=inter_w, causal=causal)
+                if k == 0:
+                    term = data
+                elif balance.groups == 'equations':
+                    term = it[k - 1] + mt[k - 1]
+                else:
+                    term = (it, mt)[k - 1].sum()
+                grads = torch.autograd.grad(term, params, allow_unused=True)
+                balance_sumsq(grads, shapes, sumsq[k:k + 1])
+                del grads, term, it, mt, data, heads, evec, statics, meta_out
+        net.clear_field_cache()
+        if grad_sync is not None and grad_sync.active():
+            # every rank must hold the same lambda: the K sums are averaged over the ranks (one collective of 8 K bytes per refresh)
+            import torch.distributed as dist
+            from ..distributed import _all_reduce_mean
+            _all_reduce_mean(sumsq, dist.get_world_size(grad_sync.group), grad_sync.group, False)
+        if state['diag'] is None or state['diag'].device != dev:
+            state['diag'] = torch.zeros(3 * K + 2, dtype=torch.float64, device=dev)
+        balance_update(sumsq, state['lam'], balance, state['diag'])
+
+    def _balance_log(self, on=True):
+        """{'balance_lambda': [K], 'balance_norm': [K]} of the last balanced step (lambda, and the gradient norms n_k of the last refresh), or {}.
+        Reads device memory: for log steps, where the loop synchronises anyway."""
+        st = self.loss_balance_state
+        if not on or st is None or st['step'] == 0 or st['diag'] is None:
+            return {}
+        K = st['lam'].numel()
+        return {'balance_lambda': st['lam'].tolist(), 'balance_norm': st['diag'][:K].tolist()}
+
+    def _balance_log_text(self, on=True):
+        row = self._balance_log(on)
+        if not row:
+            return ''
+        return ' lambda %s grad_norm %s' % (' '.join('%.4g' % v for v in row['balance_lambda']), ' '.join('%.4g' % v for v in row['balance_norm']))
+
     def _adaptive_sampler(self, opt, batch, kwargs):
         """The sampler that draws the pool: the option's own, the batch's 'sampler' entry, or the sample source's `.sampler` attribute."""
         src = kwargs.get('samples', (self.train_cfg.get('train_data') or {}).get('samples'))
@@ -435,7 +524,7 @@ class InterfacePhysics(nn.Module):
         raise RuntimeError("adaptive_interior needs the CollocationSampler that draws the pool: give it as adaptive_interior['sampler'], as the batch's "
                            "'sampler' entry, or as the `.sampler` attribute of the samples source (SyntheticSamples has one)")
 
-    def training_step(self, batch: dict, optimizer, with_pde=True, max_norm=2.5e7, grad_sync=None, *, causal=None):
+    def training_step(self, batch: dict, optimizer, with_pde=True, max_norm=2.5e7, grad_sync=None, *, causal=None, balance=None):
         """One step body (:443-515 / :990-1065): data loss on the margin points, PDE losses on interior and margin points,
         backward, clip_grad_norm_(2.5e7), optimizer step.  `batch` holds device tensors: field_data [1,159,2405],
         forecast_h [1,1,1], margin_{x,y,t,f} [N,1], margin_data [N,6], margin_input_data [N,6], inter_{x,y,t,f} [M,1],
@@ -443,12 +532,34 @@ class InterfacePhysics(nn.Module):
         causal (a causal.CausalWeights; with the PDE losses only): causal time weights on the interior and on the margin PDE losses, each group with
         bins and weights of its own; `self.last_causal` then holds {'inter': diag, 'margin': diag} as device tensors (no synchronisation here), and
         None after a step without the option.  An optional batch entry inter_w [M] or [M, 1]: constant weights of the interior points' PDE losses.
-        The data loss is never weighted."""
+        The data loss is never weighted.
+        balance (a balance.LossBalance; with the PDE losses and device tensors only): the step minimises sum_k lambda_k * (term k) instead of the plain
+        sum, lambda in `self.loss_balance_state['lam']` (fp32 [K] on the device, ones at first); on every balance.every-th call, counted from the
+        first, lambda is refreshed from the norms of the terms' parameter gradients before the step's own passes (_balance_refresh; `diag` of the
+        state: dpn_balance_update's row, a device tensor).  The returned loss is the balanced total, `parts` stay the unweighted three.  A
+        data-parallel step with the option takes the plain backward + grad_sync(parameters); grad_sync must then be a
+        distributed.GradientAllReduce (TypeError otherwise): the refresh averages the K sums of squares over its process group.  A refresh takes
+        at most 4096 trainable parameter tensors (DPN_BALANCE_MAX_TENSORS; a PhysicsNet has 155)."""
         lf = self.train_cfg['losses']['loss_factor']
         self.last_causal = None
         inter_w = batch.get('inter_w') if with_pde else None
         if not with_pde:
-            causal = None
+            causal = balance = None
+        bal_state = None
+        if balance is not None:
+            from ..balance import LossBalance
+            if not isinstance(balance, LossBalance):
+                raise TypeError('training_step: balance must be a deepphysinet_amd.balance.LossBalance, got %r' % (balance,))
+            if grad_sync is not None and not (hasattr(grad_sync, 'active') and hasattr(grad_sync, 'group')):
+                # a plain callable could average the gradients but not the K sums of squares: the ranks' lambda would drift apart unnoticed
+                raise TypeError('training_step: balance with grad_sync needs a distributed.GradientAllReduce (its process group carries the average '
+                                'of the K sums of squares that keeps lambda equal on every rank), got %r' % (grad_sync,))
+            if not batch['field_data'].is_cuda:
+                raise ValueError('training_step: balance needs the HIP point path (device tensors); field_data is on %s' % batch['field_data'].device)
+            bal_state = self._balance_state(balance, batch['field_data'].device)
+            if bal_state['step'] % balance.every == 0:
+                self._balance_refresh(balance, bal_state, batch, lf, inter_w, causal, grad_sync)
+            bal_state['step'] += 1
         self.physics_net.clear_field_cache()
         b = batch
         heads = evec = statics = meta_out = None
@@ -461,7 +572,7 @@ class InterfacePhysics(nn.Module):
             heads, evec, statics = self.physics_net.field_weights(b['field_data'], b['forecast_h'], meta_out=meta_out)
             n_inter, pts = self._eval_inputs(b, True)
             diag = [] if causal is not None else None
-            _, inter_total, _, margin_total, data = step_losses(cfg, n_inter, *pts, b['margin_data'], heads, evec, statics, beta=0.1,
+            inter_terms, inter_total, margin_terms, margin_total, data = step_losses(cfg, n_inter, *pts, b['margin_data'], heads, evec, statics, beta=0.1,
                                                                 margin_factor=lf['margin_factor'], inter_weights=inter_w, causal=causal, diag=diag)
             if causal is not None:
                 self.last_causal = {'inter': diag[0], 'margin': diag[1]}
@@ -478,15 +589,19 @@ class InterfacePhysics(nn.Module):
                 parts['margin_pde_loss'] = self.place_one_batch(b['margin_x'], b['margin_y'], b['margin_t'], b['margin_f'], b['field_data'],
                                                                 b['margin_input_data'], b['forecast_h'], crit, lf, 0, 0,
                                                                 b['field_data'].device, prefix='margin', use_cache=True, causal=causal)
-        train_loss = 0
-        for v in parts.values():
-            train_loss = train_loss + v
+        if bal_state is not None:
+            from ..point_path import balanced_total
+            train_loss = balanced_total(inter_terms, margin_terms, data, bal_state['lam'], balance.groups)      # one launch; its backward: one
+        else:
+            train_loss = 0
+            for v in parts.values():
+                train_loss = train_loss + v
         optimizer.zero_grad()
         if getattr(self, '_seed', None) is None or self._seed.device != train_loss.device:
             self._seed = torch.ones((), dtype=train_loss.dtype, device=train_loss.device)      # persistent backward seed: no fill per step
         from ..optim import FusedClipAdam
         staged = (grad_sync is not None and hasattr(grad_sync, 'reduce_bucket') and grad_sync.active() and isinstance(optimizer, FusedClipAdam)
-                  and heads is not None)
+                  and heads is not None and bal_state is None)
         if staged:
             # the staged form needs THIS optimiser's flat buffer laid out in the four buckets of gradient_buckets() and every parameter
             # trainable; anything else (an optimiser built without `layout`, a reducer bound to another optimiser or to none, frozen
@@ -825,6 +940,9 @@ class InterfacePhysics(nn.Module):
         vlog = self._ValidationLoop(self, valid_src, kwargs.get('log_path'), rank, world, num_epoch, device) if valid_src is not None else None
         adaptive = self._adaptive_option(kwargs)                        # None: not one extra call below
         causal = self._causal_option(kwargs)                            # None: the step's launches of before
+        balance = self._balance_option(kwargs)                          # None: likewise
+        if balance is None:
+            self.loss_balance_state = None                              # (a checkpoint's weights are not carried into a run without the option)
         for epoch in range(current_epoch, num_epoch):
             for batch_id, batch in enumerate(self._epoch_samples(kwargs, epoch, rank, world, dist_mode)):   # DistributedSampler (:936): one field sample per rank per step
                 with_pde = with_pde_cfg and global_step >= pde_start
@@ -838,14 +956,15 @@ class InterfacePhysics(nn.Module):
                     # the interior points go where this step's network violates its equations most (adaptive_interior)
                     batch = self.adaptive_interior(batch, self._adaptive_sampler(adaptive, batch, kwargs), pool_factor=adaptive['pool_factor'],
                                                    k=adaptive['k'], c=adaptive['c'])
-                if causal is not None and with_pde:                   # causal time weights: once the PDE losses are on
-                    loss, parts, gnorm = self.training_step(batch, optimizer, with_pde=with_pde, grad_sync=sync, causal=causal)
+                if (causal is not None or balance is not None) and with_pde:      # causal time weights, balanced terms: once the PDE losses are on
+                    loss, parts, gnorm = self.training_step(batch, optimizer, with_pde=with_pde, grad_sync=sync, causal=causal, balance=balance)
                 else:
                     loss, parts, gnorm = self.training_step(batch, optimizer, with_pde=with_pde, grad_sync=sync)
                 last = {'loss': loss, 'parts': parts, 'grad_norm': gnorm}
                 if rank == 0 and global_step % log_step == 1:
-                    print('epoch %d step %d loss %.6g %s' % (epoch, global_step, float(loss),
-                                                              ' '.join('%s %.4g' % (k, float(v)) for k, v in parts.items())))
+                    print('epoch %d step %d loss %.6g %s%s' % (epoch, global_step, float(loss),
+                                                                ' '.join('%s %.4g' % (k, float(v)) for k, v in parts.items()),
+                                                                self._balance_log_text(balance is not None and with_pde)))
                 if global_step % log_step == 1:                       # (the loop synchronises here anyway: float(loss))
                     from ..encoder_ops import check_enc_status
                     check_enc_status()                                # an encoder weight outside the f16 hi+lo split's range raises HERE, named
@@ -930,6 +1049,7 @@ class InterfacePhysics(nn.Module):
                 if lc is not None:                           # the interior group's causal weights of this step (the loop synchronises here anyway)
                     bins = (lc['inter'].numel() - 2) // 3
                     extra = {'causal_min_w': float(lc['inter'][3 * bins]), 'causal_w': lc['inter'][:bins].tolist()}
+                extra.update(m._balance_log(with_pde))       # the K balancing weights and gradient norms (likewise read here only)
                 self.log.event('training', epoch=epoch, global_step=global_step, train_loss=loss, forecast_hours=f_train, fps=fps, variables=train_vars,
                                **parts, **extra)
                 self.log.event('validation', epoch=epoch, global_step=global_step, forecast_hours=f_valid, fps=fps,
@@ -958,7 +1078,11 @@ class InterfacePhysics(nn.Module):
         valid_lead_batch, num_epoch, max_steps, pde_start_step, device, adaptive_interior (None, or dict(pool_factor, k, c, every, sampler): once
         the PDE losses are on, every every-th step's interior points are redrawn by adaptive_interior before the step; unset: the loop of before),
         causal_weights (None, or dict(eps, bins, relative): once the PDE losses are on, every step's PDE losses carry causal time weights; the
-        log-step row of metrics.jsonl gains causal_min_w and causal_w, the interior group's weights; validation stays unweighted).
+        log-step row of metrics.jsonl gains causal_min_w and causal_w, the interior group's weights; validation stays unweighted),
+        balance_losses (None, a balance.LossBalance, or dict(every, momentum, groups, lam_min, lam_max): once the PDE losses are on, the step
+        minimises the terms under weights balanced by their gradient norms, refreshed on every every-th such step; the log line and the log-step row
+        of metrics.jsonl gain balance_lambda and balance_norm, K values each; checkpoints carry the weights and the counter under 'loss_balance';
+        validation stays unweighted).
         With a validation source the result carries `last_validation`."""
         return self._run_train(False, **kwargs)
 
@@ -1083,7 +1207,10 @@ class StagedPdeStep:
     batch: place_one_batch's tensors (x, y, t, f, field_data, coord_data, forecast_h); with lead_batch they carry a leading B (field_data
     [B, 159, 2405], x .. f [B, N], coord_data [B, N, 6], forecast_h [B, 1, 1]) and the loss is the mean of the B field totals."""
 
-    def __init__(self, interface, optimizer, batch, loss_factor=None, lead_batch=False):
+    def __init__(self, interface, optimizer, batch, loss_factor=None, lead_batch=False, balance=None):
+        if balance is not None:
+            raise NotImplementedError('StagedPdeStep: loss balancing (balance=) is implemented for InterfacePhysics.training_step only, not for the '
+                                      'staged or captured step, nor for lead batches')
         self.m, self.opt, self.b = interface, optimizer, batch
         self.lf = loss_factor or interface.train_cfg['losses']['loss_factor']
         self.lead_batch = bool(lead_batch)

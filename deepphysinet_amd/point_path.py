@@ -883,6 +883,74 @@ def step_losses(cfg: PointConfig, n_inter, x, y, t, f, coord_data, labels, heads
                              coord_data, labels, heads, evec, *statics)
 
 
+def _term_table(inter_terms, margin_terms, data):
+    """The 13 device scalars of dpn_balance_combine as a host pointer table (and the tensors it points into, to be kept alive by the caller)."""
+    it, mt, d = _f32c(inter_terms.detach()), _f32c(margin_terms.detach()), _f32c(data.detach()).reshape(1)
+    if it.numel() != 6 or mt.numel() != 6:
+        raise ValueError('balanced_total: inter_terms and margin_terms hold six terms each, got %d, %d' % (it.numel(), mt.numel()))
+    ptrs = [it.data_ptr() + 4 * i for i in range(6)] + [mt.data_ptr() + 4 * i for i in range(6)] + [d.data_ptr()]
+    return (ctypes.c_void_p * L.BALANCE_STEP_TERMS)(*ptrs), (it, mt, d)
+
+
+class _BalancedTotalFn(torch.autograd.Function):
+    """total = sum_i lambda_map(i) * term_i over the step's 13 terms (dpn_balance_combine: one launch; its backward one launch for the 13
+    cotangents).  lambda is a constant of the loss, read on the device when the launch runs."""
+
+    @staticmethod
+    def forward(ctx, inter_terms, margin_terms, data, lam, term_map):
+        require_gpu(data, 'data', 'balanced_total')
+        table, keep = _term_table(inter_terms, margin_terms, data)
+        K = lam.numel()
+        cmap = (ctypes.c_int * L.BALANCE_STEP_TERMS)(*term_map)
+        total = torch.empty((), dtype=torch.float32, device=data.device)
+        L.check(L.load().dpn_balance_combine(table, K, cmap, _ptr(lam), None, _ptr(total), None, _stream()), 'dpn_balance_combine')
+        ctx.lam, ctx.K, ctx.cmap, ctx.data_shape = lam, K, cmap, data.shape
+        return total
+
+    @staticmethod
+    def backward(ctx, g):
+        cot = torch.empty(L.BALANCE_STEP_TERMS, dtype=torch.float32, device=g.device)
+        L.check(L.load().dpn_balance_combine(None, ctx.K, ctx.cmap, _ptr(ctx.lam), _ptr(_f32c(g).reshape(1)), None, _ptr(cot), _stream()),
+                'dpn_balance_combine(grad)')
+        return cot[:6], cot[6:12], cot[12].reshape(ctx.data_shape), None, None
+
+
+def balanced_total(inter_terms, margin_terms, data, lam, groups='equations'):
+    """The balanced loss of a step: sum_i lam[k(i)] * term_i over step_losses' interior terms [6], margin terms [6] and
+    data loss, fp32, in the order data, interior 0..5, margin 0..5.  lam: fp32 [K] on the device (a constant: no cotangent is formed for it);
+    groups: 'equations' (K = 7) or 'parts' (K = 3), balance.group_map.  The backward pass hands the 13 cotangents lam[k(i)] * g to the terms' node."""
+    from .balance import GROUPS, group_map
+    term_map = group_map(groups)
+    if lam.dtype != torch.float32 or not lam.is_cuda or not lam.is_contiguous() or lam.numel() != len(GROUPS[groups]):
+        raise ValueError('balanced_total: lam must be a contiguous fp32 device tensor of %d weights for groups=%r' % (len(GROUPS[groups]), groups))
+    return _BalancedTotalFn.apply(inter_terms, margin_terms, data, lam.detach(), term_map)
+
+
+def balance_sumsq(grads, shapes, out):
+    """out (one fp64 device slot) = the sum of squares of the fp32 device tensors `grads` in fp64 (dpn_balance_sumsq); an entry None counts as zeros
+    of shape shapes[i]."""
+    lib = L.load()
+    gs = [None if g is None else _f32c(g) for g in grads]
+    for g in gs:
+        if g is not None:
+            require_gpu(g, 'a gradient', 'balance_sumsq')
+    numel = (ctypes.c_int64 * len(gs))(*[int(torch.Size(s).numel()) for s in shapes])
+    table = (ctypes.c_void_p * len(gs))(*[None if g is None else g.data_ptr() for g in gs])
+    n_scratch = int(lib.dpn_balance_scratch_doubles(len(gs), numel))
+    if n_scratch == 0:
+        raise ValueError('balance_sumsq: a table of %d tensors is not taken (1..4096 non-empty tensors, include/dpn_hip.h)' % len(gs))
+    scratch = torch.empty(n_scratch, dtype=torch.float64, device=out.device)
+    L.check(lib.dpn_balance_sumsq(len(gs), table, numel, _ptr(scratch), _ptr(out), _stream()), 'dpn_balance_sumsq')
+    return out
+
+
+def balance_update(sumsq, lam, balance, diag):
+    """dpn_balance_update: lam [K] (fp32, in place) from the K sums of squares by the rule of balance.update_reference; diag [3 K + 2] fp64."""
+    K = lam.numel()
+    L.check(L.load().dpn_balance_update(_ptr(sumsq), K, float(balance.momentum), float(balance.lam_min), float(balance.lam_max), _ptr(lam), _ptr(diag),
+                                        _stream()), 'dpn_balance_update')
+
+
 def pde_losses_batch(cfg: PointConfig, x, y, t, f, coord_data, heads, evec, statics, point_weights=None, causal=None):
     """(losses [B,6], totals [B]) for B field samples with N points each; tensors carry a leading B (see _PdeLossBatchFn).  Point weights and causal
     time weights are not implemented for lead batches."""

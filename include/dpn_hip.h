@@ -542,6 +542,39 @@ int dpn_residual_weighted(const float* out_n, const float* jac_n, const float* f
                           const float* gl /*[6] or NULL*/, const float* gtot /*[1] or NULL*/, double* loss_sums, float* g_out, float* g_jxi,
                           const float* w, const int32_t* bin, const float* bin_w, void* stream);
 
+/* Loss balancing by gradient norms (csrc/dpn_balance.hip).  Each of K loss terms carries a weight lambda_k (fp32, on
+ * the device, read at run time); every few hundred steps it moves towards mean_j |grad L_j| / |grad L_k| (Wang, Teng & Perdikaris 2021; Wang,
+ * Sankaran, Wang & Perdikaris 2023; the mean form: lambda = 1 when all norms are equal).  fp64 wherever a result is defined, no atomics, every sum in
+ * one fixed order, no contraction: two runs agree bitwise.
+ *
+ * dpn_balance_sumsq: grads = a HOST table of n_tensors (1..DPN_BALANCE_MAX_TENSORS; 160 per launch, a longer table is cut into several) fp32 device pointers, numel their lengths (HOST, each 1 .. 2^31 - 2049); a NULL entry
+ *   counts as zeros.  *sumsq_slot = sum of (double)x * (double)x (exact products): per 2048-element chunk of a tensor one fp64 partial (thread j of
+ *   256 adds elements j, j + 256, ... in that order; wave tree; (w0 + w1) + (w2 + w3)), the partials added the same way by one workgroup.
+ *   scratch: dpn_balance_scratch_doubles(n_tensors, numel) doubles (the number of chunks; 0 for a table that is not taken).  -1: such a table, a NULL
+ *   table, scratch or slot.
+ * dpn_balance_update (one workgroup, one thread; deepphysinet_amd/balance.py: update_reference restates it):
+ *     n_k = sqrt(sumsq_k); term k is active when n_k is finite and > 0;
+ *     fewer than two active terms, or a sumsq_k that is not finite: lambda is left as it is, flag = 1, mean = 0, every lambda-hat = 0;
+ *     otherwise mean = (sum of n_k over the active k, k ascending) / (their number), lambda-hat_k = min(max(mean / n_k, lam_min), lam_max),
+ *     lambda_k <- (float)(momentum * (double)lambda_k + (1 - momentum) * lambda-hat_k), every operation rounded once in fp64; an inactive term keeps
+ *     its lambda (lambda-hat_k = 0 in diag).
+ *   lambda [K] fp32 in / out;  diag [3 K + 2] fp64 = n [K] | lambda-hat [K] | the new lambda [K] | mean | flag.
+ *   -1: a NULL pointer, K outside 1..DPN_BALANCE_MAX_TERMS, momentum outside [0, 1], not (0 < lam_min <= 1 <= lam_max, both finite).
+ * dpn_balance_combine: terms = a HOST table of DPN_BALANCE_STEP_TERMS = 13 fp32 device scalars: the interior PDE terms [6], the margin PDE terms
+ *   [6], the data loss; map = 13 HOST ints, the term's k (0..K - 1).  total (or NULL): *total = lambda_map(12) * data + sum over interior 0..5, then
+ *   margin 0..5, of lambda_map(i) * term_i, fp32, in that order, every product and sum rounded once.  cot_out (or NULL; then cot_in [1] is read):
+ *   cot_out[i] = *cot_in * lambda_map(i), i = 0..12.  One launch.  -1: neither output, cot_out without cot_in, total without terms (or with a NULL
+ *   term), a map entry outside 0..K - 1, K outside 1..DPN_BALANCE_MAX_TERMS, a NULL map or lambda. */
+#define DPN_BALANCE_MAX_TERMS 16
+#define DPN_BALANCE_STEP_TERMS 13
+#define DPN_BALANCE_MAX_TENSORS 4096
+int64_t dpn_balance_scratch_doubles(int n_tensors, const int64_t* numel);
+int dpn_balance_sumsq(int n_tensors, const float* const* grads, const int64_t* numel, double* scratch_dev, double* sumsq_slot_dev, void* stream);
+int dpn_balance_update(const double* sumsq_dev, int K, double momentum, double lam_min, double lam_max, float* lambda_dev, double* diag_dev,
+                       void* stream);
+int dpn_balance_combine(const float* const* terms, int K, const int* map, const float* lambda_dev, const float* cot_in_dev, float* total_dev,
+                        float* cot_out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

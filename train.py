@@ -2,7 +2,7 @@
 """Launcher with the reference's three flags (reference train.py:17-19, :34-48): --config_file, --checkpoint_path, --log_path.
 
     python train.py [--config_file cfg.py] [--checkpoint_path DIR] [--log_path DIR] [--dist] [--max_steps N] [--synthetic] [--valid_synthetic]
-                    [--adaptive_interior] [--causal_weights EPS]
+                    [--adaptive_interior] [--causal_weights EPS] [--balance_losses EVERY]
 
 The reference reads the config with mmcv.Config.fromfile (absent here, and moved to mmengine in the pinned mmcv: SURVEY section 0, defect
 3), builds the interface with `builder_models(**cfg['config'])` and calls `run_train_interface(checkpoint_path=..., log_path=...)`.  The
@@ -39,6 +39,9 @@ parse.add_argument('--adaptive_interior', action='store_true', help='once the PD
 parse.add_argument('--causal_weights', default=None, type=float, metavar='EPS', help='once the PDE losses are on, weight every step\'s PDE losses by causal '
                    'time weights W_k = exp(-EPS * sum of the earlier time bins\' losses, relative to their mean) (causal_weights=dict(eps=EPS, bins=16, '
                    'relative=True)); validation stays unweighted')
+parse.add_argument('--balance_losses', default=None, type=int, metavar='EVERY', help='once the PDE losses are on, weight the data loss and the six equations '
+                   'by weights balanced by the norms of their parameter gradients, refreshed on every EVERY-th step (balance_losses=dict(every=EVERY, '
+                   'momentum=0.9, groups=\'equations\')); validation stays unweighted')
 
 
 def load_config(path):
@@ -72,6 +75,8 @@ if __name__ == '__main__':
         kwargs['adaptive_interior'] = dict(pool_factor=8, k=1.0, c=1.0, every=1)
     if args.causal_weights is not None:
         kwargs['causal_weights'] = dict(eps=args.causal_weights, bins=16, relative=True)
+    if args.balance_losses is not None:
+        kwargs['balance_losses'] = dict(every=args.balance_losses, momentum=0.9, groups='equations')
     run = model.run_train_interface_dist if args.dist else model.run_train_interface
     out = run(**kwargs)
     print('done: epoch %d, global_step %d, lr %.3e' % (out['epoch'], out['global_step'], out['lr']))
