@@ -366,7 +366,7 @@ def embed_wgrad_rides_with_stack(n_fields=1):
     """Does the token convolution's weight gradient come out of the encoder stack's ONE weight-gradient launch (_EncoderStackFn.backward:
     a single field on the fused path) instead of a launch of the embedding's own backward?  Then the data-parallel step has nothing to
     overlap between the encoder's and the embedding's gradient buckets: they complete together and travel as ONE all-reduce
-    (interface_physics.StagedPdeStep, InterfacePhysics.training_step)."""
+    (interface_physics.StagedPdeStep, InterfacePhysics.training_step; the cuts: staged_backward.StagedBackward)."""
     return n_fields == 1 and not config.FROZEN.encoder_unfused
 
 

@@ -8,15 +8,43 @@ reference are out of scope.
 """
 import os
 import shutil
+import types
 
 import torch
 import torch.nn as nn
 
+from ..balance import LossBalance
+from ..causal import CausalWeights
 from ..losses.builder import builder_loss
 from ..model.physics_net import PhysicsNet
-from ..point_path import LOSS_ORDER, OBS_ORDER, PointConfig, pde_losses, smooth_l1_data_loss
+from ..optim import FusedClipAdam
+from ..point_path import (balance_sumsq, balance_update, balanced_total, eval_step, eval_step_batch, grid_maps, label_errors, LOSS_ORDER,
+                          OBS_ORDER, PackedField, pde_losses, pde_losses_batch, point_fields, point_sizes, PointConfig, require_gpu,
+                          smooth_l1_data_loss, step_losses)
+from ..sampler import SyntheticSamples
+from ..staged_backward import StagedBackward
 from ..utils.position_encoding import SineCosPE
-from .. import _lib as L
+from .. import _lib as L, encoder_ops, grad_arena, validation as V
+
+
+def _loop_option(kwargs, train_cfg, name, section, known, true_is_empty, instance_of, build):
+    """An option of the training loops: the keyword `name`, or train_cfg[section][name].  None / False: off (None); an instance of `instance_of`
+    passes through; True: {} where true_is_empty; a dict of `known` keys -> build(dict)."""
+    opt = kwargs.get(name, (train_cfg.get(section) or {}).get(name))
+    if opt is None or opt is False:
+        return None
+    if instance_of is not None and isinstance(opt, instance_of):
+        return opt
+    if opt is True and true_is_empty:
+        opt = {}
+    unknown = set(opt) - set(known)
+    if unknown:
+        raise ValueError('%s: unknown keys %s (known: %s)' % (name, sorted(unknown), ', '.join(known)))
+    return build(opt)
+
+
+def _to_device(batch, device):
+    return {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in batch.items()}
 
 
 class InterfacePhysics(nn.Module):
@@ -188,7 +216,6 @@ class InterfacePhysics(nn.Module):
         """The PDE criterion (`builder_loss(**train_cfg.losses.pde_loss)`, :384; every equation calls it as loss(residual, 0), :104 ... :179) as the
         fused residual kernel's (kind, beta, reduce_sum).  What the reference's losses/builder.py can build for it is implemented: MSELoss (cfg:137),
         L1Loss -- reduction "mean" or "sum" --, WeightSmoothL1Loss(beta); given as a module or as the config's dict."""
-        from .. import _lib as L
         from ..losses import WeightSmoothL1Loss
         red = {'mean': False, 'sum': True}
         if isinstance(criterion, dict):
@@ -238,7 +265,6 @@ class InterfacePhysics(nn.Module):
         field_data [B, 159, 2405]; input_data [B, N, 6]; forecast_h [B, 1, 1].  Equals place_one_batch applied to every sample
         (:271-320), the B totals averaged ('mean') or added ('sum'); the encoder runs once over all B samples and the point kernels
         field after field.  Returns (loss, terms [B, 6])."""
-        from ..point_path import pde_losses_batch
         cfg = self.point_config(loss_factor, criterion)
         heads, evec, statics = self.physics_net.field_weights(field_data, forecast_h)
         B = field_data.shape[0]
@@ -268,7 +294,6 @@ class InterfacePhysics(nn.Module):
         """Full-grid evaluation of the visualisation branch (:536-591): the six fields at all lon*lat nodes, given in the
         reference's node order (x outer, y inner; e.g. CollocationSampler.full_grid), de-normalised (the reference switches
         the clip off there, :533) and scattered into maps [6, lat, lon] (u, v, P, T, q, rho) on the device."""
-        from ..point_path import grid_maps, point_fields
         cfg = self.point_config()
         n = self.lon_size * self.lat_size
         if x.numel() != n:
@@ -287,7 +312,6 @@ class InterfacePhysics(nn.Module):
         """Points per chunk of a lattice evaluation: a multiple of the point kernels' padding unit (dpn_sizes: 128 points), so that a chunked and an
         unchunked run form identical tiles; a given size is rounded down to it (and up to one unit), the default is what INFER_BUDGET_BYTES of
         per-point buffers hold.  A lattice that is smaller is one chunk."""
-        from ..point_path import point_sizes
         unit = point_sizes(1, prec)[0]
         want = InterfacePhysics._within_budget(point_bytes) if chunk_points is None else int(chunk_points)
         if want < 1:
@@ -302,7 +326,6 @@ class InterfacePhysics(nn.Module):
 
     def _inference_weights(self, field_data, forecast_h, n_chunk):
         """encode_field, field_weights and the weight packing, once per call (the field cache is not consulted and not written)."""
-        from ..point_path import PackedField, require_gpu
         require_gpu(field_data, 'field_data', 'inference')
         cfg = self.point_config()
         heads, evec, statics = self.physics_net.field_weights(field_data, forecast_h, use_cache=False)
@@ -382,7 +405,6 @@ class InterfacePhysics(nn.Module):
         mean(score ** k) + c (CollocationSampler.get_inter_data_adaptive).  Returns a copy of the dict with inter_x, inter_y, inter_t, inter_f,
         inter_data replaced (same shapes and dtypes); everything else is the same objects.  One encoder forward and one fields + Jacobian pass over
         the pool, without autograd; parameters, .grad, optimiser state and the field cache are left alone."""
-        from ..point_path import PackedField, require_gpu
         require_gpu(batch['field_data'], 'field_data', 'adaptive_interior')
         n = int(batch['inter_x'].shape[0])
         pool = int(pool_factor) * n
@@ -402,50 +424,27 @@ class InterfacePhysics(nn.Module):
     def _adaptive_option(self, kwargs):
         """The loops' `adaptive_interior` option (keyword, or train_cfg['train_data']['adaptive_interior']): None (off), or a dict of pool_factor, k, c,
         every (refresh on every every-th step, counted from the first) and sampler."""
-        opt = kwargs.get('adaptive_interior', (self.train_cfg.get('train_data') or {}).get('adaptive_interior'))
-        if opt is None or opt is False:
-            return None
-        if opt is True:
-            opt = {}
-        unknown = set(opt) - {'pool_factor', 'k', 'c', 'every', 'sampler'}
-        if unknown:
-            raise ValueError('adaptive_interior: unknown keys %s (known: pool_factor, k, c, every, sampler)' % sorted(unknown))
-        opt = dict({'pool_factor': 8, 'k': 1.0, 'c': 1.0, 'every': 1, 'sampler': None}, **opt)
-        if int(opt['every']) < 1:
-            raise ValueError('adaptive_interior: every must be >= 1, got %r' % (opt['every'],))
-        return opt
+        def build(opt):
+            opt = dict({'pool_factor': 8, 'k': 1.0, 'c': 1.0, 'every': 1, 'sampler': None}, **opt)
+            if int(opt['every']) < 1:
+                raise ValueError('adaptive_interior: every must be >= 1, got %r' % (opt['every'],))
+            return opt
+        return _loop_option(kwargs, self.train_cfg, 'adaptive_interior', 'train_data', ('pool_factor', 'k', 'c', 'every', 'sampler'), True, None, build)
 
     def _causal_option(self, kwargs):
         """The loops' `causal_weights` option (keyword, or train_cfg['losses']['causal_weights']): None (off), or a dict of eps, bins, relative ->
         a causal.CausalWeights."""
-        opt = kwargs.get('causal_weights', (self.train_cfg.get('losses') or {}).get('causal_weights'))
-        if opt is None or opt is False:
-            return None
-        from ..causal import CausalWeights
-        if isinstance(opt, CausalWeights):
-            return opt
-        unknown = set(opt) - {'eps', 'bins', 'relative'}
-        if unknown:
-            raise ValueError('causal_weights: unknown keys %s (known: eps, bins, relative)' % sorted(unknown))
-        if 'eps' not in opt:
-            raise ValueError('causal_weights: eps is required')
-        return CausalWeights(**opt)
+        def build(opt):
+            if 'eps' not in opt:
+                raise ValueError('causal_weights: eps is required')
+            return CausalWeights(**opt)
+        return _loop_option(kwargs, self.train_cfg, 'causal_weights', 'losses', ('eps', 'bins', 'relative'), False, CausalWeights, build)
 
     def _balance_option(self, kwargs):
         """The loops' `balance_losses` option (keyword, or train_cfg['losses']['balance_losses']): None (off), a balance.LossBalance, or a dict of
         every, momentum, groups, lam_min, lam_max -> a balance.LossBalance."""
-        opt = kwargs.get('balance_losses', (self.train_cfg.get('losses') or {}).get('balance_losses'))
-        if opt is None or opt is False:
-            return None
-        from ..balance import LossBalance
-        if isinstance(opt, LossBalance):
-            return opt
-        if opt is True:
-            opt = {}
-        unknown = set(opt) - {'every', 'momentum', 'groups', 'lam_min', 'lam_max'}
-        if unknown:
-            raise ValueError('balance_losses: unknown keys %s (known: every, momentum, groups, lam_min, lam_max)' % sorted(unknown))
-        return LossBalance(**opt)
+        return _loop_option(kwargs, self.train_cfg, 'balance_losses', 'losses', ('every', 'momentum', 'groups', 'lam_min', 'lam_max'), True, LossBalance,
+                            lambda opt: LossBalance(**opt))
 
     def _balance_state(self, balance, device):
         """loss_balance_state for this option on this device: kept while the groups stay the same (a checkpoint's weights arrive on the host),
@@ -463,8 +462,6 @@ class InterfacePhysics(nn.Module):
         then dpn_balance_update.  Every term takes a forward and a backward pass of its own: the encoder stack's backward node hands the token
         convolution's gradient on through state that one backward pass consumes, so one graph is not walked K times.  The
         gradients come back from torch.autograd.grad inside grad_arena.detached(): none reaches a .grad or the optimiser's flat buffer."""
-        from .. import grad_arena
-        from ..point_path import balance_sumsq, balance_update, step_losses
         net = self.physics_net
         params = [p for p in net.parameters() if p.requires_grad]
         shapes = [p.shape for p in params]
@@ -515,10 +512,7 @@ class InterfacePhysics(nn.Module):
 
     def _adaptive_sampler(self, opt, batch, kwargs):
         """The sampler that draws the pool: the option's own, the batch's 'sampler' entry, or the sample source's `.sampler` attribute."""
-        src = kwargs.get('samples', (self.train_cfg.get('train_data') or {}).get('samples'))
-        if src == 'synthetic':
-            src = getattr(self, '_synthetic_samples', None)
-        for s in (opt.get('sampler'), batch.get('sampler'), getattr(src, 'sampler', None)):
+        for s in (opt.get('sampler'), batch.get('sampler'), getattr(self._train_source(kwargs), 'sampler', None)):
             if s is not None:
                 return s
         raise RuntimeError("adaptive_interior needs the CollocationSampler that draws the pool: give it as adaptive_interior['sampler'], as the batch's "
@@ -545,101 +539,32 @@ class InterfacePhysics(nn.Module):
         inter_w = batch.get('inter_w') if with_pde else None
         if not with_pde:
             causal = balance = None
-        bal_state = None
-        if balance is not None:
-            from ..balance import LossBalance
-            if not isinstance(balance, LossBalance):
-                raise TypeError('training_step: balance must be a deepphysinet_amd.balance.LossBalance, got %r' % (balance,))
-            if grad_sync is not None and not (hasattr(grad_sync, 'active') and hasattr(grad_sync, 'group')):
-                # a plain callable could average the gradients but not the K sums of squares: the ranks' lambda would drift apart unnoticed
-                raise TypeError('training_step: balance with grad_sync needs a distributed.GradientAllReduce (its process group carries the average '
-                                'of the K sums of squares that keeps lambda equal on every rank), got %r' % (grad_sync,))
-            if not batch['field_data'].is_cuda:
-                raise ValueError('training_step: balance needs the HIP point path (device tensors); field_data is on %s' % batch['field_data'].device)
-            bal_state = self._balance_state(balance, batch['field_data'].device)
-            if bal_state['step'] % balance.every == 0:
-                self._balance_refresh(balance, bal_state, batch, lf, inter_w, causal, grad_sync)
-            bal_state['step'] += 1
+        bal_state = self._balance_prepare(balance, batch, grad_sync, lf, inter_w, causal)
         self.physics_net.clear_field_cache()
-        b = batch
-        heads = evec = statics = meta_out = None
-        if with_pde and b['field_data'].is_cuda:
-            # one point pass for everything: [interior | margin] points, PDE means per group, SmoothL1 on the margin rows; the margin
-            # forward serves both of its losses and all points share one backward (point_path._StepLossFn)
-            from ..point_path import step_losses
-            cfg = self.point_config(lf)
-            meta_out = self.physics_net.encode_field(b['field_data'], b['forecast_h'], keep_embedding=grad_sync is not None)
-            heads, evec, statics = self.physics_net.field_weights(b['field_data'], b['forecast_h'], meta_out=meta_out)
-            n_inter, pts = self._eval_inputs(b, True)
-            diag = [] if causal is not None else None
-            inter_terms, inter_total, margin_terms, margin_total, data = step_losses(cfg, n_inter, *pts, b['margin_data'], heads, evec, statics, beta=0.1,
-                                                                margin_factor=lf['margin_factor'], inter_weights=inter_w, causal=causal, diag=diag)
-            if causal is not None:
-                self.last_causal = {'inter': diag[0], 'margin': diag[1]}
-            parts = {'margin_loss': data, 'inter_pde_loss': inter_total.float(), 'margin_pde_loss': margin_total.float()}
-        else:
-            loss = self.data_loss(b['margin_x'], b['margin_y'], b['margin_t'], b['field_data'], b['margin_input_data'], b['margin_data'],
-                                  b['forecast_h'], lf['margin_factor'], use_cache=True)
-            parts = {'margin_loss': loss}
-            if with_pde:
-                crit = nn.MSELoss()
-                parts['inter_pde_loss'] = self.place_one_batch(b['inter_x'], b['inter_y'], b['inter_t'], b['inter_f'], b['field_data'],
-                                                               b['inter_data'], b['forecast_h'], crit, lf, 0, 0, b['field_data'].device,
-                                                               use_cache=True, point_weights=inter_w, causal=causal)
-                parts['margin_pde_loss'] = self.place_one_batch(b['margin_x'], b['margin_y'], b['margin_t'], b['margin_f'], b['field_data'],
-                                                                b['margin_input_data'], b['forecast_h'], crit, lf, 0, 0,
-                                                                b['field_data'].device, prefix='margin', use_cache=True, causal=causal)
+        fwd = self._step_forward(batch, with_pde, lf, inter_w, causal, keep_embedding=grad_sync is not None)
         if bal_state is not None:
-            from ..point_path import balanced_total
-            train_loss = balanced_total(inter_terms, margin_terms, data, bal_state['lam'], balance.groups)      # one launch; its backward: one
+            train_loss = balanced_total(fwd.inter_terms, fwd.margin_terms, fwd.data, bal_state['lam'], balance.groups)      # one launch; its backward: one
         else:
             train_loss = 0
-            for v in parts.values():
+            for v in fwd.parts.values():
                 train_loss = train_loss + v
         optimizer.zero_grad()
         if getattr(self, '_seed', None) is None or self._seed.device != train_loss.device:
             self._seed = torch.ones((), dtype=train_loss.dtype, device=train_loss.device)      # persistent backward seed: no fill per step
-        from ..optim import FusedClipAdam
-        staged = (grad_sync is not None and hasattr(grad_sync, 'reduce_bucket') and grad_sync.active() and isinstance(optimizer, FusedClipAdam)
-                  and heads is not None and bal_state is None)
-        if staged:
-            # the staged form needs THIS optimiser's flat buffer laid out in the four buckets of gradient_buckets() and every parameter
-            # trainable; anything else (an optimiser built without `layout`, a reducer bound to another optimiser or to none, frozen
-            # parameters) takes the plain backward + grad_sync(parameters) below
-            buckets = self.physics_net.gradient_buckets()
-            lay = getattr(optimizer, 'layout_ids', None)
-            staged = (getattr(grad_sync, 'opt', None) is optimizer and len(getattr(optimizer, 'bucket_bounds', ())) == 4
-                      and lay == [[id(p) for p in b_] for b_ in buckets]
-                      and all(p.requires_grad for b_ in buckets for p in b_))
-        if staged:
-            # data-parallel step: the backward pass is cut where a bucket of gradients is complete and that bucket's all-reduce is queued at
-            # once, so it travels under the rest of the backward (what DistributedDataParallel's bucket hooks do in the reference, :903-907,
-            # :1056).  Layout buckets (PhysicsNet.gradient_buckets): point statics | hyper-network heads | encoder layers | data embedding;
-            # the first two travel as ONE all-reduce (the heads' backward is two launches: a collective of its own costs more than the 40 us
-            # it could start earlier), the token convolution's 7.4 MB (the last gradient to complete) alone
-            g = torch.autograd.grad(train_loss, [heads, evec] + list(statics), grad_outputs=self._seed)
-            optimizer.place_gradients(list(statics), g[2:])
-            g2 = torch.autograd.grad([heads, evec], [meta_out] + buckets[1], grad_outputs=[g[0], g[1]], allow_unused=True)
-            optimizer.place_gradients(buckets[1], g2[1:])
+        buckets = self._can_stage(optimizer, grad_sync, fwd.heads is not None and bal_state is None)
+        if buckets is not None:
+            # data-parallel step: the backward pass is cut where buckets of gradients are complete (staged_backward) and their all-reduce is queued at
+            # once, so it travels under the rest of the backward (what DistributedDataParallel's bucket hooks do in the reference, :903-907, :1056).
+            # Statics + heads are ONE all-reduce (the heads' backward is two launches: a collective of its own costs more than the 40 us it could start
+            # earlier), encoder + embedding another: the fused stack's weight-gradient launch completes both, any other encoder leaves no x0 to cut at
+            back = StagedBackward(buckets, optimizer)
+            back.points(train_loss, fwd.heads, fwd.evec, fwd.statics, fwd.meta_out, getattr(self.physics_net.meta_net.model, 'last_embedding', None),
+                        self._seed)
+            back.heads_cut()
             grad_sync.reduce_bucket(0, 2)
-            x0 = getattr(self.physics_net.meta_net.model, 'last_embedding', None)
-            if x0 is not None and x0.requires_grad:
-                from .. import encoder_ops
-                together = encoder_ops.embed_wgrad_rides_with_stack(1)     # (the stack's weight-gradient launch also wrote the token convolution's)
-                g3 = torch.autograd.grad([meta_out], [x0] + buckets[2], grad_outputs=[g2[0]], allow_unused=True)
-                optimizer.place_gradients(buckets[2], g3[1:])
-                if not together:
-                    grad_sync.reduce_bucket(2)
-                g4 = torch.autograd.grad([x0], buckets[3], grad_outputs=[g3[0]], allow_unused=True)
-                optimizer.place_gradients(buckets[3], g4)
-                if together:
-                    grad_sync.reduce_bucket(2, 4)
-                else:
-                    grad_sync.reduce_bucket(3)
-            else:
-                g3 = torch.autograd.grad([meta_out], buckets[2] + buckets[3], grad_outputs=[g2[0]], allow_unused=True)
-                optimizer.place_gradients(buckets[2] + buckets[3], g3)
-                grad_sync.reduce_bucket(2, 4)
+            back.encoder()
+            back.embedding()
+            grad_sync.reduce_bucket(2, 4)
             grad_sync.wait()
             self.physics_net.clear_field_cache()
         else:
@@ -653,16 +578,75 @@ class InterfacePhysics(nn.Module):
         else:
             gnorm = torch.nn.utils.clip_grad_norm_(self.physics_net.parameters(), max_norm=max_norm)
             optimizer.step()
-        return train_loss.detach(), {k: v.detach() for k, v in parts.items()}, gnorm
+        return train_loss.detach(), {k: v.detach() for k, v in fwd.parts.items()}, gnorm
 
+    def _balance_prepare(self, balance, batch, grad_sync, lf, inter_w, causal):
+        """training_step's balance option: its checks, the refresh on every balance.every-th call and the counter; the state, or None without."""
+        if balance is None:
+            return None
+        if not isinstance(balance, LossBalance):
+            raise TypeError('training_step: balance must be a deepphysinet_amd.balance.LossBalance, got %r' % (balance,))
+        if grad_sync is not None and not (hasattr(grad_sync, 'active') and hasattr(grad_sync, 'group')):
+            # a plain callable could average the gradients but not the K sums of squares: the ranks' lambda would drift apart unnoticed
+            raise TypeError('training_step: balance with grad_sync needs a distributed.GradientAllReduce (its process group carries the average '
+                            'of the K sums of squares that keeps lambda equal on every rank), got %r' % (grad_sync,))
+        if not batch['field_data'].is_cuda:
+            raise ValueError('training_step: balance needs the HIP point path (device tensors); field_data is on %s' % batch['field_data'].device)
+        state = self._balance_state(balance, batch['field_data'].device)
+        if state['step'] % balance.every == 0:
+            self._balance_refresh(balance, state, batch, lf, inter_w, causal, grad_sync)
+        state['step'] += 1
+        return state
+
+    def _step_forward(self, b, with_pde, lf, inter_w, causal, keep_embedding):
+        """training_step's forward: `parts`, the unweighted losses in the order they are added; from the HIP path also inter_terms, margin_terms,
+        data, and heads, evec, statics, meta_out, where a staged backward cuts (heads None: the per-op path ran)."""
+        out = types.SimpleNamespace(heads=None)
+        if with_pde and b['field_data'].is_cuda:
+            # one point pass for everything: [interior | margin] points, PDE means per group, SmoothL1 on the margin rows; the margin
+            # forward serves both of its losses and all points share one backward (point_path._StepLossFn)
+            cfg = self.point_config(lf)
+            out.meta_out = self.physics_net.encode_field(b['field_data'], b['forecast_h'], keep_embedding=keep_embedding)
+            out.heads, out.evec, out.statics = self.physics_net.field_weights(b['field_data'], b['forecast_h'], meta_out=out.meta_out)
+            n_inter, pts = self._eval_inputs(b, True)
+            diag = [] if causal is not None else None
+            out.inter_terms, inter_total, out.margin_terms, margin_total, out.data = step_losses(
+                cfg, n_inter, *pts, b['margin_data'], out.heads, out.evec, out.statics, beta=0.1, margin_factor=lf['margin_factor'],
+                inter_weights=inter_w, causal=causal, diag=diag)
+            if causal is not None:
+                self.last_causal = {'inter': diag[0], 'margin': diag[1]}
+            out.parts = {'margin_loss': out.data, 'inter_pde_loss': inter_total.float(), 'margin_pde_loss': margin_total.float()}
+            return out
+        loss = self.data_loss(b['margin_x'], b['margin_y'], b['margin_t'], b['field_data'], b['margin_input_data'], b['margin_data'],
+                              b['forecast_h'], lf['margin_factor'], use_cache=True)
+        out.parts = {'margin_loss': loss}
+        if with_pde:
+            crit, dev = nn.MSELoss(), b['field_data'].device
+            out.parts['inter_pde_loss'] = self.place_one_batch(b['inter_x'], b['inter_y'], b['inter_t'], b['inter_f'], b['field_data'], b['inter_data'],
+                                                               b['forecast_h'], crit, lf, 0, 0, dev, use_cache=True, point_weights=inter_w, causal=causal)
+            out.parts['margin_pde_loss'] = self.place_one_batch(b['margin_x'], b['margin_y'], b['margin_t'], b['margin_f'], b['field_data'],
+                                                                b['margin_input_data'], b['forecast_h'], crit, lf, 0, 0, dev, prefix='margin',
+                                                                use_cache=True, causal=causal)
+        return out
+
+    def _can_stage(self, optimizer, grad_sync, hip_unbalanced):
+        """The four gradient buckets if training_step may take the staged backward, else None (the plain backward + grad_sync(parameters)): the HIP
+        forward without balancing, an active bucket reducer bound to THIS optimiser, whose flat buffer is laid out in the four buckets of
+        gradient_buckets(), every parameter trainable (not: an optimiser built without `layout`, a reducer of another or no optimiser, frozen ones)."""
+        if not (hip_unbalanced and grad_sync is not None and hasattr(grad_sync, 'reduce_bucket') and grad_sync.active()
+                and isinstance(optimizer, FusedClipAdam)):
+            return None
+        buckets = self.physics_net.gradient_buckets()
+        ok = (getattr(grad_sync, 'opt', None) is optimizer and len(getattr(optimizer, 'bucket_bounds', ())) == 4
+              and getattr(optimizer, 'layout_ids', None) == [[id(p) for p in b_] for b_ in buckets]
+              and all(p.requires_grad for b_ in buckets for p in b_))
+        return buckets if ok else None
 
     # ------------------------------------------------------------------ validation (:518-530, :629-745)
     def variable_errors(self, out_n, labels, with_clip=False):
         """The six per-variable errors of normalised predictions out_n [N, 6] against labels [N, 6] in physical units (:518-530: inverse_norm
         of both sides, nn.MSELoss per variable), from ONE pass over the data (dpn_label_errors): {v: {mse, rmse, mae, bias, max_abs}} for
         v in u, v, p, T, q, rio; `mse` is the reference's margin_<v>_loss.  with_clip applies the clip bounds of P, T, q, rho to both sides."""
-        from ..point_path import label_errors
-        from .. import validation as V
         stats = label_errors(self.point_config(), out_n, labels, beta=0.1, with_clip=with_clip)
         return V.metrics_from_stats(V.stats_row(stats[0], out_n.shape[0]))['variables']
 
@@ -678,7 +662,6 @@ class InterfacePhysics(nn.Module):
 
     def _validation_dict(self, losses, stats, n_margin, with_pde, forecast_h=None):
         """One sample's result from eval_step's outputs (device tensors; nothing is synchronised here except the statistics' copy to the host)."""
-        from .. import validation as V
         mf = self.train_cfg['losses']['loss_factor']['margin_factor']
         # the training step's own expression (_StepLossFn.forward / data_loss): one rounding to fp32, then the factor
         out = {'margin_loss': (stats[0] / (6.0 * n_margin)).float() * mf}
@@ -709,7 +692,6 @@ class InterfacePhysics(nn.Module):
         residuals clip as training_step's do (self.with_clip; the loops set it before every step, :629), the per-variable errors only on request
         (with_clip).
         Touches no .grad, no optimiser state and not the field cache."""
-        from ..point_path import eval_step, require_gpu
         b = batch
         require_gpu(b['field_data'], 'field_data', 'validation_step')
         cfg = self.point_config(self.train_cfg['losses']['loss_factor'])
@@ -723,7 +705,6 @@ class InterfacePhysics(nn.Module):
     def lead_batch_size(self, n_points, n_samples):
         """Samples per group of `validate`: as many as INFER_BUDGET_BYTES (256 MiB, the rule of chunk_size) hold of per-point buffers
         (VALID_POINT_BYTES each) plus one packed weight block per sample; at least 1, at most the number of samples."""
-        from ..point_path import point_sizes
         per = int(n_points) * self.VALID_POINT_BYTES + point_sizes(n_points, self.precision)[1]
         return max(1, min(int(n_samples), self._within_budget(per)))
 
@@ -734,8 +715,6 @@ class InterfacePhysics(nn.Module):
         of a group must have equal point counts (a group is cut where they change).  Returns {'samples': [validation_step's dict per sample,
         in order], 'pooled': validation.metrics_from_stats of the merged rows (+ 'stats', the merged row)}: pooling adds sums and counts and
         maximises maxima, it never averages RMSEs.  lead_batch None: lead_batch_size (the 256 MiB rule)."""
-        from ..point_path import eval_step_batch, require_gpu
-        from .. import validation as V
         samples = list(samples)
         if not samples:
             raise ValueError('validate: no samples')
@@ -749,7 +728,7 @@ class InterfacePhysics(nn.Module):
             j = i + 1
             while j < len(samples) and j - i < want and shape(samples[j]) == (n_i, n_m):
                 j += 1
-            group = [{k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in b.items()} for b in samples[i:j]]
+            group = [_to_device(b, dev) for b in samples[i:j]]
             require_gpu(group[0]['field_data'], 'field_data', 'validate')
             if len(group) == 1:
                 rows.append(self.validation_step(group[0], with_pde=with_pde, with_clip=with_clip))
@@ -782,7 +761,6 @@ class InterfacePhysics(nn.Module):
             if src != 'synthetic':
                 raise ValueError("valid_samples=%r: the only named source is 'synthetic'" % src)
             if getattr(self, '_synthetic_valid', None) is None:
-                from ..sampler import SyntheticSamples
                 td = self.train_cfg.get('train_data', {})
                 dev = next(self.physics_net.parameters()).device
                 # seed 1: other fields, other cubes and other collocation draws than the training source's (seed 0)
@@ -799,7 +777,6 @@ class InterfacePhysics(nn.Module):
     def build_optimizer(self, **overrides):
         """Fused clip + Adam over the PhysicsNet with the config's optimiser settings (cfg:151-155; `initial_lr` as :394 sets it), its flat
         gradient buffer laid out in backward-completion order (PhysicsNet.gradient_buckets)."""
-        from ..optim import FusedClipAdam
         oc = dict(self.train_cfg.get('optimizer', {}))
         name = oc.pop('name', 'Adam')
         if name != 'Adam':
@@ -817,6 +794,12 @@ class InterfacePhysics(nn.Module):
         sc.pop('verbose', None)                       # cfg:160-165 passes verbose=True, which torch >= 2.7 rejects (defect 4)
         return getattr(torch.optim.lr_scheduler, name)(optimizer, last_epoch=current_epoch - 1, **sc)
 
+    def _train_source(self, kwargs):
+        """The training samples source as given (keyword `samples`, or train_cfg['train_data']['samples']); 'synthetic': the SyntheticSamples
+        _train_samples made for it (None before it did)."""
+        src = kwargs.get('samples', (self.train_cfg.get('train_data') or {}).get('samples'))
+        return getattr(self, '_synthetic_samples', None) if src == 'synthetic' else src
+
     def _train_samples(self, kwargs, epoch):
         src = kwargs.get('samples', self.train_cfg.get('train_data', {}).get('samples'))
         if src is None:
@@ -829,7 +812,6 @@ class InterfacePhysics(nn.Module):
             if src != 'synthetic':
                 raise ValueError("samples=%r: the only named source is 'synthetic'" % src)
             if getattr(self, '_synthetic_samples', None) is None:
-                from ..sampler import SyntheticSamples
                 td = self.train_cfg.get('train_data', {})
                 dev = next(self.physics_net.parameters()).device
                 self._synthetic_samples = SyntheticSamples(dev, n_margin=td.get('label_batch_size', 20480), n_inter=td.get('batch_size_inter', 4096),
@@ -889,7 +871,7 @@ class InterfacePhysics(nn.Module):
         unseeded permutation per epoch: shuffle in the source if wanted).  Iterables that cannot be indexed are consumed in their own order.
         With samples_per_rank=True (keyword, or attribute `samples.per_rank = True`) the callable is samples(epoch, rank, world) -> this rank's
         samples only (nothing is drawn for the other ranks)."""
-        src = kwargs.get('samples', self.train_cfg.get('train_data', {}).get('samples'))
+        src = self._train_source(kwargs)
         per_rank = kwargs.get('samples_per_rank', getattr(src, 'per_rank', False))
         if callable(src) and per_rank:                   # explicit protocol (keyword samples_per_rank=True or attribute samples.per_rank)
             return src(epoch, rank, world)
@@ -948,7 +930,7 @@ class InterfacePhysics(nn.Module):
                 with_pde = with_pde_cfg and global_step >= pde_start
                 self.with_clip = True
                 global_step += 1
-                batch = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in batch.items()}
+                batch = _to_device(batch, device)
                 log_now = vlog is not None and global_step % log_step == 1
                 if log_now:              # the training batch's six errors (:518-530) from the predictions the step is about to train on
                     train_vars = self.validation_step(batch, with_pde=False)['variables']
@@ -956,18 +938,15 @@ class InterfacePhysics(nn.Module):
                     # the interior points go where this step's network violates its equations most (adaptive_interior)
                     batch = self.adaptive_interior(batch, self._adaptive_sampler(adaptive, batch, kwargs), pool_factor=adaptive['pool_factor'],
                                                    k=adaptive['k'], c=adaptive['c'])
-                if (causal is not None or balance is not None) and with_pde:      # causal time weights, balanced terms: once the PDE losses are on
-                    loss, parts, gnorm = self.training_step(batch, optimizer, with_pde=with_pde, grad_sync=sync, causal=causal, balance=balance)
-                else:
-                    loss, parts, gnorm = self.training_step(batch, optimizer, with_pde=with_pde, grad_sync=sync)
+                # (causal time weights, balanced terms: training_step drops both until the PDE losses are on)
+                loss, parts, gnorm = self.training_step(batch, optimizer, with_pde=with_pde, grad_sync=sync, causal=causal, balance=balance)
                 last = {'loss': loss, 'parts': parts, 'grad_norm': gnorm}
                 if rank == 0 and global_step % log_step == 1:
                     print('epoch %d step %d loss %.6g %s%s' % (epoch, global_step, float(loss),
                                                                 ' '.join('%s %.4g' % (k, float(v)) for k, v in parts.items()),
                                                                 self._balance_log_text(balance is not None and with_pde)))
                 if global_step % log_step == 1:                       # (the loop synchronises here anyway: float(loss))
-                    from ..encoder_ops import check_enc_status
-                    check_enc_status()                                # an encoder weight outside the f16 hi+lo split's range raises HERE, named
+                    encoder_ops.check_enc_status()                                # an encoder weight outside the f16 hi+lo split's range raises HERE, named
                 if log_now:
                     vlog.log_step_event(epoch, batch_id, global_step, batch, loss, parts, train_vars, with_pde, kwargs)
                 if max_steps is not None and global_step >= max_steps:
@@ -976,8 +955,7 @@ class InterfacePhysics(nn.Module):
                 if lr_schedule is not None:
                     lr_schedule.step()
                     optimizer.sync_hyper()
-                from ..encoder_ops import check_enc_status
-                check_enc_status()
+                encoder_ops.check_enc_status()
                 if checkpoint_path and rank == 0:
                     self.save_model(checkpoint_path, epoch, global_step, prefix='physics', dx=self.dx, dy=self.dy, dt=self.dt,
                                     pred_x_span=self.dx * self.lon_size, pred_y_span=self.dy * self.lat_size, pred_t_span=self.pred_t_span,
@@ -998,19 +976,14 @@ class InterfacePhysics(nn.Module):
 
         def __init__(self, model, source, log_path, rank, world, num_epoch, device):
             import time
-            from .. import validation as V
             self.m, self.src, self.rank, self.world, self.num_epoch, self.device = model, source, rank, world, num_epoch, device
             self.log = V.TrainLog(log_path) if (log_path and rank == 0) else None
             self.cursor, self.last, self.last_epoch = 0, None, None
             self.clock, self.t0, self.step0 = time.perf_counter, time.perf_counter(), 0
             self.hours = float((model.train_cfg.get('train_data') or {}).get('forecast_time_period', 360))
 
-        def _to_device(self, b):
-            return {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in b.items()}
-
         def _all_ranks(self, row):
             """The rows of all ranks merged in rank order: ONE collective on one small fp64 tensor (gathered, so that the maxima travel with it)."""
-            from .. import validation as V
             if self.world == 1:
                 return row
             import torch.distributed as dist
@@ -1020,15 +993,12 @@ class InterfacePhysics(nn.Module):
             return V.merge_stats([r.cpu() for r in rows])
 
         def log_step_event(self, epoch, batch_id, global_step, batch, loss, parts, train_vars, with_pde, kwargs):
-            from .. import validation as V
             m = self.m
             now = self.clock()
             fps = (global_step - self.step0) * self.world / max(now - self.t0, 1e-9)          # samples per second since the last log line
-            src_train = kwargs.get('samples', m.train_cfg.get('train_data', {}).get('samples'))
-            if src_train == 'synthetic':
-                src_train = getattr(m, '_synthetic_samples', None)
+            src_train = m._train_source(kwargs)
             n_batches = -(-len(src_train) // self.world) if hasattr(src_train, '__len__') else 0
-            vb = self._to_device(self.src[(self.cursor * self.world + self.rank) % len(self.src)])     # round-robin; rank r its own stride
+            vb = _to_device(self.src[(self.cursor * self.world + self.rank) % len(self.src)], self.device)     # round-robin; rank r its own stride
             self.cursor += 1
             m.with_clip = True                                                                 # :629
             was_training = m.physics_net.training
@@ -1058,7 +1028,6 @@ class InterfacePhysics(nn.Module):
 
         def epoch_event(self, epoch, global_step, with_pde, kwargs):
             """validate_every_epoch: the whole source (this rank's shard of it, unshuffled), pooled over the ranks."""
-            from .. import validation as V
             m = self.m
             shard = list(m._shard_samples(self.src, self.rank, self.world))
             m.with_clip = True
@@ -1112,7 +1081,6 @@ class InterfacePhysics(nn.Module):
         if isinstance(src, str):
             if src != 'synthetic':
                 raise ValueError("samples=%r: the only named source is 'synthetic'" % src)
-            from ..sampler import SyntheticSamples
             dev = next(self.physics_net.parameters()).device
             syn = SyntheticSamples(dev, n_margin=128, n_inter=128, leads=int(kwargs.get('samples_per_epoch', 1)), lat=self.lat_size, lon=self.lon_size)
             print("run_inference_interface: samples='synthetic' -- random field samples (%d): the maps are noise" % len(syn))
@@ -1200,6 +1168,7 @@ class StagedPdeStep:
                    other 6.4 MB of the encoder start one launch earlier) -> layout bucket 3: stage_buckets[2] = (3, 4)
     One field on the fused encoder (round 6): stages[1] and stages[2] are ONE stage and buckets 2, 3 one all-reduce -- the token convolution's gradient is
     written by the encoder stack's own weight-gradient launch, so both buckets complete together (encoder_ops.embed_wgrad_rides_with_stack).
+    The cuts are staged_backward.StagedBackward's (training_step takes the same); the forward is this class's.
     Each stage is a plain callable (capturable in a hipGraph of its own, on one capture stream and one memory pool); after stage i the caller
     queues `grad_sync.reduce_bucket(*stage_buckets[i])`.  (Round 2 cut the heads' backward off as a stage of its own: three collectives and
     four graph segments cost 1.80 -> 2.00 ms with a one-rank RCCL group; the heads' backward is two launches, so the statics' all-reduce
@@ -1214,45 +1183,36 @@ class StagedPdeStep:
         self.m, self.opt, self.b = interface, optimizer, batch
         self.lf = loss_factor or interface.train_cfg['losses']['loss_factor']
         self.lead_batch = bool(lead_batch)
-        net = interface.physics_net
-        self.buckets = net.gradient_buckets()
-        self.loss = None
+        self.buckets, self.loss = interface.physics_net.gradient_buckets(), None
         self.stages = (self.stage_points_and_heads, self.stage_encoder, self.stage_embedding)
         self.stage_buckets = ((0, 2), (2, 3), (3, 4))
-        from .. import encoder_ops
         if not self.lead_batch and encoder_ops.embed_wgrad_rides_with_stack(1):
             # Round 6: one field on the fused encoder -- the token convolution's weight gradient is a problem of the stack's ONE weight-gradient launch,
             # the embedding's own backward launches nothing: buckets 2 and 3 complete together.  Two all-reduces behind each other (and a graph
             # segment that is empty) were 73 us of exposed tail on a one-rank RCCL group (gap 21 + 10 + gap 17 + 8 + gap 17); one is gap + 16 + gap.
             self.stages = (self.stage_points_and_heads, self.stage_encoder_and_embedding)
             self.stage_buckets = ((0, 2), (2, 4))
-        self._seed = None
-
-    def _assign(self, params, grads):
-        self.opt.place_gradients(params, grads)          # the rare gradient that did not land in its slot is copied there before the all-reduce
+        self._seed, self.back = None, StagedBackward(self.buckets, optimizer)      # (the cuts themselves: shared with training_step)
 
     def stage_points(self):
         m, b = self.m, self.b
         net = m.physics_net
         self.opt.zero_grad(set_to_none=True)
         cfg = m.point_config(self.lf)
-        self.meta_out = net.encode_field(b['field_data'], b['forecast_h'], keep_embedding=True)
-        self.x0 = getattr(net.meta_net.model, 'last_embedding', None)        # the cut between stages 1 and 2 (None: the encoder ran unfused)
-        object.__setattr__(net.meta_net.model, 'last_embedding', None)       # (this object holds it from here on)
-        self.heads, self.evec, statics = net.field_weights(b['field_data'], b['forecast_h'], meta_out=self.meta_out)
+        meta_out = net.encode_field(b['field_data'], b['forecast_h'], keep_embedding=True)
+        x0 = getattr(net.meta_net.model, 'last_embedding', None)             # the cut between stages 1 and 2 (None: the encoder ran unfused)
+        object.__setattr__(net.meta_net.model, 'last_embedding', None)       # (self.back holds it from here on)
+        heads, evec, statics = net.field_weights(b['field_data'], b['forecast_h'], meta_out=meta_out)
         if self.lead_batch:
-            from ..point_path import pde_losses_batch
             B = b['field_data'].shape[0]
-            self.heads, self.evec = self.heads.reshape(B, 256, -1), self.evec.reshape(B, 6, 256)
-            _, totals = pde_losses_batch(cfg, b['x'], b['y'], b['t'], b['f'], b['coord_data'], self.heads, self.evec, statics)
+            heads, evec = heads.reshape(B, 256, -1), evec.reshape(B, 6, 256)
+            _, totals = pde_losses_batch(cfg, b['x'], b['y'], b['t'], b['f'], b['coord_data'], heads, evec, statics)
             total = totals.mean().float()
         else:
-            _, total = pde_losses(cfg, b['x'], b['y'], b['t'], b['f'], b['coord_data'], self.heads, self.evec, statics, with_total=True)
+            _, total = pde_losses(cfg, b['x'], b['y'], b['t'], b['f'], b['coord_data'], heads, evec, statics, with_total=True)
         if self._seed is None:
             self._seed = torch.ones((), dtype=total.dtype, device=total.device)
-        g = torch.autograd.grad(total, [self.heads, self.evec] + list(statics), grad_outputs=self._seed)
-        self.g_heads, self.g_evec = g[0], g[1]
-        self._assign(statics, g[2:])
+        self.back.points(total, heads, evec, statics, meta_out, x0, self._seed)
         self.loss = total.detach()
         return self.loss
 
@@ -1262,31 +1222,15 @@ class StagedPdeStep:
         return loss
 
     def stage_heads(self):
-        params = self.buckets[1]
-        g = torch.autograd.grad([self.heads, self.evec], [self.meta_out] + params, grad_outputs=[self.g_heads, self.g_evec], allow_unused=True)
-        self.g_meta = g[0]
-        self._assign(params, g[1:])
+        self.back.heads_cut()
 
     def stage_encoder(self):
-        if self.x0 is None or not self.x0.requires_grad:             # no cut available: the whole encoder in this stage, stage 2 is empty
-            params = self.buckets[2] + self.buckets[3]
-            g = torch.autograd.grad([self.meta_out], params, grad_outputs=[self.g_meta], allow_unused=True)
-            self._assign(params, g)
-            self.g_x0 = None
-            return
-        params = self.buckets[2]
-        g = torch.autograd.grad([self.meta_out], [self.x0] + params, grad_outputs=[self.g_meta], allow_unused=True)
-        self.g_x0 = g[0]
-        self._assign(params, g[1:])
+        self.back.encoder()
 
     def stage_encoder_and_embedding(self):
         self.stage_encoder()
         self.stage_embedding()
 
     def stage_embedding(self):
-        if self.g_x0 is not None:
-            params = self.buckets[3]
-            g = torch.autograd.grad([self.x0], params, grad_outputs=[self.g_x0], allow_unused=True)
-            self._assign(params, g)
-        self.meta_out = self.heads = self.evec = self.g_heads = self.g_evec = self.g_meta = self.x0 = self.g_x0 = None
+        self.back.embedding()                    # (the rare gradient that did not land in its slot was copied there: FusedClipAdam.place_gradients)
         self.m.physics_net.clear_field_cache()

@@ -311,7 +311,8 @@ def test_staged_data_parallel_step_is_only_taken_with_the_matching_optimiser_lay
     built without a layout (plain backward + grad_sync(parameters))."""
     import inspect
     from deepphysinet_amd.interface import interface_physics
-    src = inspect.getsource(interface_physics.InterfacePhysics.training_step)
+    assert 'self._can_stage(optimizer, grad_sync,' in inspect.getsource(interface_physics.InterfacePhysics.training_step)
+    src = inspect.getsource(interface_physics.InterfacePhysics._can_stage)             # training_step's test for the staged form
     assert "getattr(grad_sync, 'opt', None) is optimizer" in src and 'layout_ids' in src and 'requires_grad' in src
     from deepphysinet_amd import optim
     assert 'self.layout_ids' in inspect.getsource(optim.FusedClipAdam.__init__)
