@@ -198,7 +198,13 @@ EXPORTS = {
     'dpn_balance_sumsq': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dpn_balance_update': (c_int, [c_void_p, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p]),
     'dpn_balance_combine': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dpn_step_rows_doubles': (c_int64, [c_int64, c_int64]),
+    'dpn_step_residual': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, POINTER(DpnGeometry), POINTER(DpnPhysics), c_float, c_float,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dpn_step_finish_batch': (c_int, [c_void_p, c_int64, c_int64, c_int, POINTER(DpnPhysics), c_float, c_void_p, c_void_p]),
 }
+
+STEP_LOSSES = 16              # one field's row of dpn_step_finish_batch (include/dpn_hip.h)
 
 CAUSAL_MAX_BINS = 64          # DPN_CAUSAL_MAX_BINS (include/dpn_hip.h)
 BALANCE_MAX_TERMS, BALANCE_STEP_TERMS = 16, 13          # DPN_BALANCE_MAX_TERMS, DPN_BALANCE_STEP_TERMS (include/dpn_hip.h)

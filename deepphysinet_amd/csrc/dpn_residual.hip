@@ -7,9 +7,11 @@
 // Kernel inventory
 //   dpn_contract_gpe_kernel     cotangent of caller-encoded coordinates
 //   dpn_residual_kernel<Args>   de-norm, clip, six residuals, wave-shuffle loss reduction, analytic cotangents; instantiated for ResArgs
-//                               (dpn_residual) and for ResWArgs (dpn_residual_weighted: a weight per point in the sums and the cotangents)
+//                               (dpn_residual), for ResWArgs (dpn_residual_weighted: a weight per point in the sums and the cotangents) and for
+//                               ResStepArgs (dpn_step_residual: the [interior | margin] rows of a step in one launch, + the data loss)
 //   dpn_residual_points_kernel  the same residual body, written out per point (inference diagnostics)
 //   dpn_residual_finish_kernel  block rows -> the six scaled losses and their sum
+//   dpn_step_finish_kernel      dpn_step_residual's block rows of B fields -> per field both groups' losses, the data loss, the step's total
 //   dpn_smooth_l1_kernel        the data loss and its cotangent
 // No kernel in this file uses atomics: every reduction is fixed-order, the whole step is bitwise reproducible.
 #include "dpn_device.h"
@@ -34,7 +36,7 @@ struct ResArgs {
     const float *gl, *gtot;
     double* loss_sums;
     float *g_out, *g_jxi;
-    static constexpr bool weighted = false;
+    static constexpr bool weighted = false, step = false;
 };
 // + the point weight wt_i = w[i] * bin_w[bin[i]]; either source may be absent (1.0f)
 struct ResWArgs : ResArgs {
@@ -44,20 +46,42 @@ struct ResWArgs : ResArgs {
     static constexpr bool weighted = true;
 };
 
+// The step body of one field (dpn_step_residual): n = all rows, the first n_inter interior, the rest margin points with labels [n - n_inter][6].
+// Blocks 0 .. nb_inter - 1 hold the interior points, the others the margin points from row n_inter on: no block straddles the boundary.
+struct ResStepArgs : ResArgs {
+    const float* labels;
+    int64_t n_inter, nb_inter;
+    float data_beta, data_scale;
+    static constexpr bool step = true;
+};
+
 DEV float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
 
-// One kernel, two instantiations.  The weighted one differs in `wt` alone: in the fp64 block sums and in inv_n, the last factor of g[e], the head of
+// One kernel, three instantiations.  The weighted one differs in `wt` alone: in the fp64 block sums and in inv_n, the last factor of g[e], the head of
 // the cotangent chain (everything behind g[e] is linear in it); with every weight 1.0f its block rows and cotangents are bitwise the unweighted
 // one's.  The template is on the __global__ function itself: through a shared device function the compiler loads the argument struct wholesale
 // and both instruction streams change.
+// The step one (ResStepArgs) differs in where a block's points lie (first, n_grp: the rows of the block's own group, whose 1 / n the cotangent takes),
+// in a seventh column of the block row (the fp64 sum of SmoothL1(data_beta) over the block's margin points x 6 variables against the labels:
+// elements of a point in order, shuffle tree, waves in order; 0.0 from an interior block), and on margin rows in the data cotangent
+// data_scale * gtot[0] * slope added behind the finished PDE cotangent -- dpn_smooth_l1_kernel's expressions, its accumulate form's one addition.  The
+// six criterion sums and the PDE cotangents are bitwise what dpn_residual writes for each group's slice.
 template <class Args> __global__ __launch_bounds__(256) void dpn_residual_kernel(Args a) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool valid = i < a.n;
-    const int64_t ic = valid ? i : a.n - 1;
+    constexpr int ROW = Args::step ? 7 : 6;
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int64_t n_grp = a.n, end = a.n;                 // the group's point count; one past the group's last row
+    [[maybe_unused]] bool margin = false;
+    if constexpr (Args::step) {
+        margin = (int64_t)blockIdx.x >= a.nb_inter;
+        if (margin) { i = a.n_inter + (((int64_t)blockIdx.x - a.nb_inter) * 256 + threadIdx.x); n_grp = a.n - a.n_inter; }
+        else n_grp = end = a.n_inter;
+    }
+    const bool valid = i < end;
+    const int64_t ic = valid ? i : end - 1;
 #include "dpn_residual_body.inc"
     float wt = 1.f;
     if constexpr (Args::weighted) wt = (a.w ? a.w[ic] : 1.f) * (a.bin ? a.bin_w[a.bin[ic]] : 1.f);
@@ -65,7 +89,7 @@ template <class Args> __global__ __launch_bounds__(256) void dpn_residual_kernel
         // fp64 partial sums (residual^2 spans 1e-20..1e+20 across equations): wave shuffle tree, then the four waves of the block
         // in a fixed order -> one [6] row per block.  No atomics: dpn_residual_finish adds the rows in a fixed order, so the
         // losses are run-to-run deterministic (and 3.5k serialised fp64 atomics are gone from the step).
-        __shared__ double wsum[4][6];
+        __shared__ double wsum[4][ROW];
 #pragma unroll
         for (int e = 0; e < 6; ++e) {
 #pragma clang fp contract(off)
@@ -78,16 +102,31 @@ template <class Args> __global__ __launch_bounds__(256) void dpn_residual_kernel
             for (int o = 32; o > 0; o >>= 1) s = s + __shfl_xor(s, o);
             if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6][e] = s;
         }
-        __syncthreads();
-        if (threadIdx.x < 6) {
+        if constexpr (Args::step) {
 #pragma clang fp contract(off)
-            a.loss_sums[(int64_t)blockIdx.x * 6 + threadIdx.x] =
+            double s = 0.0;
+            if (valid && margin) {
+#pragma unroll
+                for (int k = 0; k < 6; ++k) {
+                    const float d = a.out_n[i * 6 + k] - a.labels[(i - a.n_inter) * 6 + k];
+                    const float ad = fabsf(d);
+                    s = s + (double)((ad < a.data_beta) ? 0.5f * d * d / a.data_beta : ad - 0.5f * a.data_beta);
+                }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) s = s + __shfl_xor(s, o);
+            if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6][6] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x < ROW) {
+#pragma clang fp contract(off)
+            a.loss_sums[(int64_t)blockIdx.x * ROW + threadIdx.x] =
                 ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x];
         }
     }
     if (!a.g_out || !valid) return;
     float g[6];
-    float inv_n = a.ph.reduce_sum ? 1.0f : 1.0f / (float)a.n;             // reduction "sum": the criterion does not divide by the number of points
+    float inv_n = a.ph.reduce_sum ? 1.0f : 1.0f / (float)n_grp;           // reduction "sum": the criterion does not divide by the number of points
     // The weight rides on 1 / n (the division is by n, not by the sum of the weights): g[e] keeps its shape, last factor included -- the compiler
     // contracts that multiply into the sums that read g[e], so a factor appended behind it would move a rounding.
     if constexpr (Args::weighted) inv_n = inv_n * wt;
@@ -124,6 +163,15 @@ template <class Args> __global__ __launch_bounds__(256) void dpn_residual_kernel
 #pragma unroll
             for (int c = 0; c < 3; ++c) t = fmaf(gJ[k][c], a.jac_n[(i * 6 + k) * 3 + c], t);
             go = fmaf(t, 2.f * a.ph.std[k] * a.ph.std[k], go);
+        }
+        if constexpr (Args::step) {
+            if (margin) {                                                // + d (data loss) / d out, one rounded addition behind the PDE cotangent
+#pragma clang fp contract(off)
+                const float d = a.out_n[i * 6 + k] - a.labels[(i - a.n_inter) * 6 + k];
+                const float ad = fabsf(d);
+                const float gd = a.data_scale * a.gtot[0] * ((ad < a.data_beta) ? d / a.data_beta : (d > 0.f ? 1.f : -1.f));
+                go = go + gd;
+            }
         }
         a.g_out[i * 6 + k] = go;
 #pragma unroll
@@ -163,6 +211,45 @@ __global__ __launch_bounds__(384) void dpn_residual_finish_kernel(const double* 
     if (lane == 0) { l[e] = (float)((double)(float)(ph.reduce_sum ? s : s / (double)n) * (double)ph.factor[e]); losses[e] = l[e]; }   // .float() * factor (:104)
     __syncthreads();
     if (threadIdx.x == 0) losses[6] = ((((l[0] + l[1]) + l[3]) + l[2]) + l[4]) + l[5];   // montion_u + montion_v + energy + continous + vapor + gas
+}
+
+// dpn_step_residual's rows of B fields side by side (per field blocks(n_inter) + blocks(n - n_inter) rows of 7) -> losses[field][16]: [0:6] the interior
+// terms, [6] their total, [7:13] the margin terms, [13] their total -- each group as dpn_residual_finish_kernel forms it from that group's rows --,
+// [14] the data loss (float)(S / (6 n_m)) * margin_factor, S = column 6 of the margin rows (wave 6: lane l takes rows l, l + 64, ..., the same tree),
+// [15] the step's total (data + interior) + margin in fp32.  One workgroup per field, wave e < 6 adds equation e of the interior, then of the margin group.
+__global__ __launch_bounds__(448) void dpn_step_finish_kernel(const double* rows, int64_t n_inter, int64_t n, DpnPhysics ph, float margin_factor,
+                                                              float* losses) {
+#pragma clang fp contract(off)
+    const int64_t n_m = n - n_inter, nb_i = (n_inter + 255) / 256, nb_m = (n_m + 255) / 256;
+    rows += (int64_t)blockIdx.x * (nb_i + nb_m) * 7;
+    losses += (int64_t)blockIdx.x * 16;
+    __shared__ float l[2][6];
+    __shared__ float data;
+    const int e = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int g = 0; g < (e < 6 ? 2 : 1); ++g) {
+        // wave 6 takes column 6 of the margin rows; the others column e of group g
+        const bool mrg = g == 1 || e == 6;
+        const double* part = mrg ? rows + nb_i * 7 : rows;
+        const int64_t nblk = mrg ? nb_m : nb_i, ng = mrg ? n_m : n_inter;
+        double s = 0.0;
+        for (int64_t b = lane; b < nblk; b += 64) s += part[b * 7 + e];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        if (lane != 0) continue;
+        if (e == 6) {
+            data = (float)(s / (6.0 * (double)n_m)) * margin_factor;
+            losses[14] = data;
+        } else {
+            l[g][e] = (float)((double)(float)(ph.reduce_sum ? s : s / (double)ng) * (double)ph.factor[e]);                       // .float() * factor (:104)
+            losses[g * 7 + e] = l[g][e];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    float tot[2];
+    for (int g = 0; g < 2; ++g) tot[g] = ((((l[g][0] + l[g][1]) + l[g][3]) + l[g][2]) + l[g][4]) + l[g][5];
+    losses[6] = tot[0]; losses[13] = tot[1];
+    losses[15] = (data + tot[0]) + tot[1];                              // the order in which training_step adds its parts
 }
 
 __global__ __launch_bounds__(256) void dpn_smooth_l1_kernel(const float* out_n, const float* labels, int64_t n, float beta, float scale,
@@ -232,6 +319,30 @@ int dpn_residual_finish_batch(const double* loss_sums, int64_t n, int n_fields, 
 }
 int dpn_residual_finish(const double* loss_sums, int64_t n, const DpnPhysics* phys, float* losses, void* stream) {
     return dpn_residual_finish_batch(loss_sums, n, 1, phys, losses, stream);
+}
+
+int64_t dpn_step_rows_doubles(int64_t n_inter, int64_t n) {
+    if (n_inter < 1 || n_inter >= n) return 0;
+    return 7 * ((n_inter + 255) / 256 + (n - n_inter + 255) / 256);
+}
+
+int dpn_step_residual(const float* out_n, const float* jac_n, const float* f, const float* labels, int64_t n_inter, int64_t n, const DpnGeometry* geo,
+                      const DpnPhysics* phys, float beta, float data_scale, const float* gtot, double* rows, float* g_out, float* g_jxi, void* stream) {
+    if (!out_n || !jac_n || !f || !labels || !geo || !phys || !gtot || !rows || (g_out && !g_jxi)) return -1;
+    if (n_inter < 1 || n_inter >= n || !criterion_ok(phys) || !(beta > 0.f)) return -1;
+    const int64_t nb_inter = (n_inter + 255) / 256, nb = nb_inter + (n - n_inter + 255) / 256;
+    if (nb > 0x7fffffff) return -1;
+    ResStepArgs a{{out_n, jac_n, f, n, *geo, *phys, nullptr, gtot, rows, g_out, g_jxi}, labels, n_inter, nb_inter, beta, data_scale};
+    hipLaunchKernelGGL(dpn_residual_kernel<ResStepArgs>, dim3((unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int dpn_step_finish_batch(const double* rows, int64_t n_inter, int64_t n, int n_fields, const DpnPhysics* phys, float margin_factor, float* losses,
+                          void* stream) {
+    if (!rows || !phys || !losses || n_inter < 1 || n_inter >= n || n_fields < 1) return -1;
+    hipLaunchKernelGGL(dpn_step_finish_kernel, dim3(n_fields), dim3(448), 0, reinterpret_cast<hipStream_t>(stream), rows, n_inter, n, *phys, margin_factor,
+                       losses);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 int dpn_smooth_l1(const float* out_n, const float* labels, int64_t n, float beta, float scale, double* loss_sum, float* g_out, int accumulate,

@@ -18,9 +18,9 @@ from ..causal import CausalWeights
 from ..losses.builder import builder_loss
 from ..model.physics_net import PhysicsNet
 from ..optim import FusedClipAdam
-from ..point_path import (balance_sumsq, balance_update, balanced_total, eval_step, eval_step_batch, grid_maps, label_errors, LOSS_ORDER,
-                          OBS_ORDER, PackedField, pde_losses, pde_losses_batch, point_fields, point_sizes, PointConfig, require_gpu,
-                          smooth_l1_data_loss, step_losses)
+from ..point_path import (balance_sumsq, balance_update, balanced_total, data_losses_batch, eval_step, eval_step_batch, grid_maps, label_errors,
+                          LOSS_ORDER, OBS_ORDER, PackedField, pde_losses, pde_losses_batch, point_fields, point_sizes, PointConfig, require_gpu,
+                          smooth_l1_data_loss, step_losses, step_losses_batch)
 from ..sampler import SyntheticSamples
 from ..staged_backward import StagedBackward
 from ..utils.position_encoding import SineCosPE
@@ -440,6 +440,19 @@ class InterfacePhysics(nn.Module):
             return CausalWeights(**opt)
         return _loop_option(kwargs, self.train_cfg, 'causal_weights', 'losses', ('eps', 'bins', 'relative'), False, CausalWeights, build)
 
+    def _lead_batch_option(self, kwargs):
+        """The loops' `lead_batch` option (keyword, or train_cfg['train_data']['lead_batch']): samples per optimiser step, 1 when unset.  Refused
+        together with a causal_weights / balance_losses option that is set (implemented for one sample per step): the loops ask at their start."""
+        k = kwargs.get('lead_batch', (self.train_cfg.get('train_data') or {}).get('lead_batch'))
+        k = 1 if k is None else int(k)
+        if k < 1:
+            raise ValueError('lead_batch must be >= 1, got %d' % k)
+        on = [n for n in ('causal_weights', 'balance_losses') if kwargs.get(n, (self.train_cfg.get('losses') or {}).get(n)) not in (None, False)]
+        if k > 1 and on:
+            raise NotImplementedError('lead_batch=%d with %s: causal time weights and loss balancing are implemented for one sample per optimiser step '
+                                      '(training_step), not for lead batches' % (k, ' and '.join(on)))
+        return k
+
     def _balance_option(self, kwargs):
         """The loops' `balance_losses` option (keyword, or train_cfg['losses']['balance_losses']): None (off), a balance.LossBalance, or a dict of
         every, momentum, groups, lam_min, lam_max -> a balance.LossBalance."""
@@ -579,6 +592,84 @@ class InterfacePhysics(nn.Module):
             gnorm = torch.nn.utils.clip_grad_norm_(self.physics_net.parameters(), max_norm=max_norm)
             optimizer.step()
         return train_loss.detach(), {k: v.detach() for k, v in fwd.parts.items()}, gnorm
+
+    def training_step_batch(self, batches, optimizer, with_pde=True, max_norm=2.5e7, grad_sync=None):
+        """ONE optimiser step on B samples: `batches` is a list of B training_step batch dicts (device tensors) with equal point counts -- for example B
+        forecast leads.  The encoder, the hyper-network heads and the weight packing run once for all B (the lead-batch launches); the point kernels
+        run sample after sample, each sample's backward right behind its forward (point_path.step_losses_batch).  loss = the mean of the B samples'
+        totals, each total training_step's (data + interior PDE) + margin PDE: the mean keeps the gradient scale of a single-sample step, so max_norm
+        and the learning rate keep their meaning.  Then backward, grad_sync(parameters) when given (the plain backward, as a balanced
+        data-parallel step takes it: there is no staged backward for this step), clip + Adam as training_step ends.  with_pde False: the data loss
+        alone (point_path.data_losses_batch).  Returns (loss, parts, gnorm, per_sample): parts = the means over the samples of margin_loss,
+        inter_pde_loss, margin_pde_loss; per_sample = {'terms' [B, 2, 6], 'parts' [B, 3], 'totals' [B]} on the device (without the PDE losses terms
+        is None, parts [B, 1]); nothing is read back.  Point weights (an `inter_w` entry: NotImplementedError), causal weights and loss balancing are
+        implemented for one sample per step only (training_step).  A list of one sample runs the same path with B = 1."""
+        batches = list(batches)
+        if not batches:
+            raise ValueError('training_step_batch: no samples')
+        if any('inter_w' in b for b in batches):
+            raise NotImplementedError('training_step_batch: per-point weights (inter_w) are implemented for one sample per step (training_step), not '
+                                      'for lead batches')
+        shape = lambda b: (b['inter_x'].shape[0] if with_pde else 0, b['margin_x'].shape[0])
+        if any(shape(b) != shape(batches[0]) for b in batches[1:]):
+            raise ValueError('training_step_batch: the samples of one step must have equal point counts, got (interior, margin) = %s'
+                             % sorted({shape(b) for b in batches}))
+        for b in batches:
+            require_gpu(b['field_data'], 'field_data', 'training_step_batch')
+        lf = self.train_cfg['losses']['loss_factor']
+        self.last_causal = None
+        B = len(batches)
+        net = self.physics_net
+        net.clear_field_cache()
+        cfg = self.point_config(lf)
+        field = torch.cat([b['field_data'] for b in batches], dim=0)
+        fh = torch.cat([b['forecast_h'] for b in batches], dim=0)
+        meta_out = net.encode_field(field, fh)
+        heads, evec, statics = net.field_weights(field, fh, meta_out=meta_out)
+        heads, evec = heads.reshape(B, 256, -1), evec.reshape(B, 6, 256)
+        inputs = [self._eval_inputs(b, with_pde) for b in batches]
+        pts = tuple(torch.stack([p[1][c] for p in inputs], dim=0) for c in range(5))
+        labels = torch.stack([b['margin_data'] for b in batches], dim=0)
+        if with_pde:
+            terms, sample_parts, totals = step_losses_batch(cfg, inputs[0][0], *pts, labels, heads, evec, statics, beta=0.1,
+                                                            margin_factor=lf['margin_factor'])
+        else:
+            totals = data_losses_batch(cfg, pts[0], pts[1], pts[2], pts[4], labels, heads, evec, statics, beta=0.1, margin_factor=lf['margin_factor'])
+            terms, sample_parts = None, totals.detach().reshape(B, 1)
+        train_loss = totals.mean()
+        optimizer.zero_grad()
+        if getattr(self, '_seed', None) is None or self._seed.device != train_loss.device:
+            self._seed = torch.ones((), dtype=train_loss.dtype, device=train_loss.device)
+        train_loss.backward(self._seed)
+        net.clear_field_cache()
+        if grad_sync is not None:
+            grad_sync(net.parameters())
+        if isinstance(optimizer, FusedClipAdam):                  # clip + Adam in one HIP pass
+            optimizer.max_norm = float(max_norm)
+            gnorm = optimizer.step()
+        else:
+            gnorm = torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm=max_norm)
+            optimizer.step()
+        means = sample_parts.mean(dim=0)
+        parts = {k: means[i] for i, k in enumerate(('margin_loss', 'inter_pde_loss', 'margin_pde_loss')[:means.numel()])}
+        return train_loss.detach(), parts, gnorm, {'terms': terms, 'parts': sample_parts, 'totals': totals.detach()}
+
+    @staticmethod
+    def _lead_groups(samples, k):
+        """The loops' lead_batch grouping: consecutive samples of a stream, k at a time; a group is cut early where the point counts (interior, margin)
+        change and at the end of the stream, so a shorter last group is a smaller B.  Yields lists of samples; consumes the stream lazily."""
+        k = int(k)
+        if k < 1:
+            raise ValueError('lead_batch must be >= 1, got %d' % k)
+        shape = lambda b: (b['inter_x'].shape[0], b['margin_x'].shape[0])
+        group = []
+        for smp in samples:
+            if group and (len(group) == k or shape(smp) != shape(group[0])):
+                yield group
+                group = []
+            group.append(smp)
+        if group:
+            yield group
 
     def _balance_prepare(self, balance, batch, grad_sync, lf, inter_w, causal):
         """training_step's balance option: its checks, the refresh on every balance.every-th call and the counter; the state, or None without."""
@@ -880,6 +971,8 @@ class InterfacePhysics(nn.Module):
 
     def _run_train(self, dist_mode, **kwargs):
         tc = self.train_cfg
+        # samples per optimiser step (1: not one call differs below); refused here, before anything is built, together with the single-sample options
+        lead_batch = self._lead_batch_option(kwargs)
         num_epoch = int(kwargs.get('num_epoch', tc['num_epoch']))
         self.dx, self.dy = float(tc['dx']), float(tc['dy'])
         time_step = tc.get('lable_time_step', 1)
@@ -925,21 +1018,36 @@ class InterfacePhysics(nn.Module):
         balance = self._balance_option(kwargs)                          # None: likewise
         if balance is None:
             self.loss_balance_state = None                              # (a checkpoint's weights are not carried into a run without the option)
+        seen = global_step                                              # samples this rank has trained on (the log line's fps)
         for epoch in range(current_epoch, num_epoch):
-            for batch_id, batch in enumerate(self._epoch_samples(kwargs, epoch, rank, world, dist_mode)):   # DistributedSampler (:936): one field sample per rank per step
+            stream = self._epoch_samples(kwargs, epoch, rank, world, dist_mode)   # DistributedSampler (:936): one field sample per rank per step
+            if lead_batch > 1:                                          # ... or lead_batch consecutive ones of the rank's stream
+                stream = self._lead_groups(stream, lead_batch)
+            for batch_id, batch in enumerate(stream):
                 with_pde = with_pde_cfg and global_step >= pde_start
                 self.with_clip = True
                 global_step += 1
-                batch = _to_device(batch, device)
+                if lead_batch > 1:                                      # the log step's forecast_hours and train_vars: the group's first sample
+                    group = [_to_device(b, device) for b in batch]
+                    batch = group[0]
+                else:
+                    group, batch = None, _to_device(batch, device)
+                seen += 1 if group is None else len(group)
                 log_now = vlog is not None and global_step % log_step == 1
                 if log_now:              # the training batch's six errors (:518-530) from the predictions the step is about to train on
                     train_vars = self.validation_step(batch, with_pde=False)['variables']
                 if adaptive is not None and with_pde and (global_step - 1) % int(adaptive['every']) == 0:
                     # the interior points go where this step's network violates its equations most (adaptive_interior)
-                    batch = self.adaptive_interior(batch, self._adaptive_sampler(adaptive, batch, kwargs), pool_factor=adaptive['pool_factor'],
-                                                   k=adaptive['k'], c=adaptive['c'])
+                    redraw = lambda b: self.adaptive_interior(b, self._adaptive_sampler(adaptive, b, kwargs), pool_factor=adaptive['pool_factor'],
+                                                              k=adaptive['k'], c=adaptive['c'])
+                    if group is not None:                               # sample by sample (the point counts, so the grouping, stay)
+                        group = [redraw(b) for b in group]
+                    batch = redraw(batch) if group is None else group[0]
                 # (causal time weights, balanced terms: training_step drops both until the PDE losses are on)
-                loss, parts, gnorm = self.training_step(batch, optimizer, with_pde=with_pde, grad_sync=sync, causal=causal, balance=balance)
+                if group is None:
+                    loss, parts, gnorm = self.training_step(batch, optimizer, with_pde=with_pde, grad_sync=sync, causal=causal, balance=balance)
+                else:
+                    loss, parts, gnorm, _ = self.training_step_batch(group, optimizer, with_pde=with_pde, grad_sync=sync)
                 last = {'loss': loss, 'parts': parts, 'grad_norm': gnorm}
                 if rank == 0 and global_step % log_step == 1:
                     print('epoch %d step %d loss %.6g %s%s' % (epoch, global_step, float(loss),
@@ -948,7 +1056,7 @@ class InterfacePhysics(nn.Module):
                 if global_step % log_step == 1:                       # (the loop synchronises here anyway: float(loss))
                     encoder_ops.check_enc_status()                                # an encoder weight outside the f16 hi+lo split's range raises HERE, named
                 if log_now:
-                    vlog.log_step_event(epoch, batch_id, global_step, batch, loss, parts, train_vars, with_pde, kwargs)
+                    vlog.log_step_event(epoch, batch_id, global_step, batch, loss, parts, train_vars, with_pde, kwargs, seen)
                 if max_steps is not None and global_step >= max_steps:
                     break
             if epoch % save_step == 0:
@@ -992,10 +1100,11 @@ class InterfacePhysics(nn.Module):
             dist.all_gather(rows, mine)
             return V.merge_stats([r.cpu() for r in rows])
 
-        def log_step_event(self, epoch, batch_id, global_step, batch, loss, parts, train_vars, with_pde, kwargs):
+        def log_step_event(self, epoch, batch_id, global_step, batch, loss, parts, train_vars, with_pde, kwargs, seen=None):
             m = self.m
             now = self.clock()
-            fps = (global_step - self.step0) * self.world / max(now - self.t0, 1e-9)          # samples per second since the last log line
+            seen = global_step if seen is None else seen                                       # (lead_batch: several samples per step)
+            fps = (seen - self.step0) * self.world / max(now - self.t0, 1e-9)                 # samples per second since the last log line
             src_train = m._train_source(kwargs)
             n_batches = -(-len(src_train) // self.world) if hasattr(src_train, '__len__') else 0
             vb = _to_device(self.src[(self.cursor * self.world + self.rank) % len(self.src)], self.device)     # round-robin; rank r its own stride
@@ -1024,7 +1133,7 @@ class InterfacePhysics(nn.Module):
                                **parts, **extra)
                 self.log.event('validation', epoch=epoch, global_step=global_step, forecast_hours=f_valid, fps=fps,
                                **{k: v for k, v in res.items() if k != 'global_step'})
-            self.t0, self.step0 = self.clock(), global_step
+            self.t0, self.step0 = self.clock(), seen
 
         def epoch_event(self, epoch, global_step, with_pde, kwargs):
             """validate_every_epoch: the whole source (this rank's shard of it, unshuffled), pooled over the ranks."""
@@ -1051,7 +1160,11 @@ class InterfacePhysics(nn.Module):
         balance_losses (None, a balance.LossBalance, or dict(every, momentum, groups, lam_min, lam_max): once the PDE losses are on, the step
         minimises the terms under weights balanced by their gradient norms, refreshed on every every-th such step; the log line and the log-step row
         of metrics.jsonl gain balance_lambda and balance_norm, K values each; checkpoints carry the weights and the counter under 'loss_balance';
-        validation stays unweighted).
+        validation stays unweighted),
+        lead_batch (k: k consecutive samples of the epoch's -- per-rank -- stream per optimiser step, training_step_batch; a group is cut early where
+        the point counts change and at the end of the epoch; global_step counts optimiser steps, the log line's fps counts samples, its forecast
+        hours and train_vars are the group's first sample's; adaptive_interior redraws sample by sample; together with causal_weights or
+        balance_losses: NotImplementedError at loop start; unset or 1: the loop of before).
         With a validation source the result carries `last_validation`."""
         return self._run_train(False, **kwargs)
 
@@ -1060,7 +1173,11 @@ class InterfacePhysics(nn.Module):
         environment, which the reference never does -- SURVEY section 0, defect 2), rank r takes every world-th sample
         (DistributedSampler, :936), gradients are averaged by distributed.GradientAllReduce on the optimiser's flat gradient buffer
         (replaces the DistributedDataParallel wrap :903-907), rank 0 writes the checkpoints.  Validation: every rank evaluates its own samples
-        of the source, the statistics rows are gathered once (validation.merge_stats), rank 0 logs."""
+        of the source, the statistics rows are gathered once (validation.merge_stats), rank 0 logs.
+        lead_batch: every rank groups its OWN stream, and every optimiser step is a collective -- all ranks must form the same number of groups per
+        epoch.  They do when all samples of the epoch have the same point counts (the sharding hands every rank the same number of samples; groups
+        are then cut by count alone).  A source whose point counts vary from sample to sample can cut the ranks' streams differently, and the
+        rank with more groups would wait in its all-reduce for ever: give such a source to this loop only with lead_batch unset."""
         return self._run_train(True, **kwargs)
 
     # ------------------------------------------------------------------ inference loop (:1407-1530)

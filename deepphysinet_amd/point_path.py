@@ -863,6 +863,129 @@ class _StepLossFn(torch.autograd.Function):
         return (None,) * 11 + (ghd, gev, *gst)
 
 
+class _StepLossBatchFn(torch.autograd.Function):
+    """The step body (_StepLossFn: data loss on the margin rows, PDE means of the interior and of the margin group) for B field samples in ONE
+    optimiser step; tensors carry a leading B (eval_step_batch's shapes).  Built like _PdeLossBatchFn's eager path: the B weight blocks are packed in
+    one launch, then field after field one forward over the [interior | margin] rows (the tiles of step_losses and eval_step), ONE dpn_step_residual
+    (both groups' block rows, the data sums and, with gradients wanted, d total_b / d (out, Jacobian) for a unit cotangent), and right behind it the
+    field's point backward: its saved state is consumed warm and freed, never parked.  One dpn_step_finish_batch behind the loop writes every
+    field's 16 losses.  Returns losses [B, 16] (include/dpn_hip.h) and totals [B]; only the totals carry gradient: the backward pass scales the
+    gradient blocks by the cotangents that arrive and adds the static gradients in a fixed order (dpn_sum_parts)."""
+
+    @staticmethod
+    def forward(ctx, cfg, grad_enabled, n_inter, beta, margin_factor, x, y, t, f, coord_data, labels, heads, evec, *statics):
+        ops = _operands('step_losses_batch', x, y, t, f, coord_data, heads, evec, statics, labels=labels, batch=True, split=(n_inter, True))
+        lib = L.load()
+        B, n = ops.cd.shape[0], ops.cd.shape[1]
+        n_m, dev = n - n_inter, ops.cd.device
+        # (Function.forward runs with grad mode off: the caller's mode arrives as an argument, as in _PdeLossBatchFn)
+        need_grad = bool(grad_enabled) and any(v.requires_grad for v in (heads, evec) + tuple(statics))
+        geo, ph = cfg.geometry(), cfg.physics()
+        losses = torch.empty((B, L.STEP_LOSSES), dtype=torch.float32, device=dev)
+        rows = torch.empty((B, int(lib.dpn_step_rows_doubles(n_inter, n))), dtype=torch.float64, device=dev)
+        batch = _FieldBatch(cfg, ops, n, pack=True)
+        g_out = g_jxi = grads = None
+        if need_grad:
+            g_out, g_jxi = torch.empty((n, 6), dtype=torch.float32, device=dev), torch.empty((n, 6, 3), dtype=torch.float32, device=dev)
+            grads = batch.grads()
+        for b in range(B):
+            ws, nets = batch.field(b)
+            out_n, jac_n = _forward_points(cfg, ws, nets, ops.x[b], ops.y[b], ops.t[b], None, ops.cd[b], want_jac=True, want_saved=need_grad)
+            L.check(lib.dpn_step_residual(_ptr(out_n), _ptr(jac_n), _ptr(ops.f[b]), _ptr(ops.lab[b]), n_inter, n, ctypes.byref(geo), ctypes.byref(ph),
+                                          beta, margin_factor / (6.0 * n_m), _ptr(_one(dev)), _ptr(rows[b]), _ptr(g_out), _ptr(g_jxi), _stream()),
+                    'dpn_step_residual')
+            if need_grad:                                         # d total_b / d (this field's weights)
+                _backward_points(cfg, ws, nets, ops.x[b], ops.y[b], ops.t[b], None, ops.cd[b], g_out, g_jxi, ops.st,
+                                 into=(grads[0][b], grads[1][b], _static_views(grads[2][b])))
+            del ws, out_n, jac_n
+        L.check(lib.dpn_step_finish_batch(_ptr(rows), n_inter, n, B, ctypes.byref(ph), margin_factor, _ptr(losses), _stream()), 'dpn_step_finish_batch')
+        ctx.grads, ctx.n_static = grads, len(statics)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(losses)
+        return losses, losses[:, 15].clone()
+
+    @staticmethod
+    def backward(ctx, _g_losses, g_total):
+        if g_total is None:
+            return (None,) * (13 + ctx.n_static)
+        return (None,) * 11 + _scaled_batch_grads(ctx, 'step_losses_batch', g_total)
+
+
+def _scaled_batch_grads(ctx, what, g_total):
+    """The backward pass of a batch whose forward pass ran every field's point backward for a unit cotangent of its total (ctx.grads: heads
+    [B, 256, 2700], evec [B, 6, 256], statics flat [B, ...]): the blocks times the cotangents that arrived, the static gradients added over the
+    fields in a fixed order (dpn_sum_parts).  -> (g_heads, g_evec, the 48 static gradients)."""
+    if ctx.grads is None:
+        raise RuntimeError('deepphysinet_amd %s: the per-field state saved by the forward pass is released as the backward '
+                           'pass consumes it (21 GB at 61 fields); run the forward pass again instead of a second backward' % what)
+    g_heads, g_evec, flat = ctx.grads
+    ctx.grads = None
+    B = flat.shape[0]
+    gt = _f32c(g_total).reshape(B)
+    g_heads.mul_(gt.view(B, 1, 1))
+    g_evec.mul_(gt.view(B, 1, 1))
+    flat.mul_(gt.view(B, 1))
+    total = torch.empty(_STATIC_STARTS[-1], dtype=torch.float32, device=flat.device)
+    L.check(L.load().dpn_sum_parts(_ptr(flat), B, _STATIC_STARTS[-1], 0, _ptr(total), _stream()), 'dpn_sum_parts')
+    return (g_heads, g_evec, *_static_views(total))
+
+
+class _DataLossBatchFn(torch.autograd.Function):
+    """The data loss alone for B field samples in one step (the reference's first 2 000 steps): the B weight blocks packed in one launch, then per
+    field the margin rows' fields (no Jacobian), dpn_smooth_l1 (block sums and the cotangent of a unit total in one launch) and the point backward
+    right behind it.  Existing kernels only.  totals [B] = mean SmoothL1(beta) * margin_factor, step_losses' expression."""
+
+    @staticmethod
+    def forward(ctx, cfg, grad_enabled, beta, margin_factor, x, y, t, coord_data, labels, heads, evec, *statics):
+        ops = _operands('data_losses_batch', x, y, t, None, coord_data, heads, evec, statics, labels=labels, batch=True, split=(0, False))
+        lib = L.load()
+        B, n = ops.cd.shape[0], ops.cd.shape[1]
+        dev = ops.cd.device
+        need_grad = bool(grad_enabled) and any(v.requires_grad for v in (heads, evec) + tuple(statics))
+        dsum = torch.empty((B, (n * 6 + 255) // 256), dtype=torch.float64, device=dev)
+        batch = _FieldBatch(cfg, ops, n, pack=True)
+        g_out = grads = None
+        if need_grad:
+            g_out, grads = torch.empty((n, 6), dtype=torch.float32, device=dev), batch.grads()
+        for b in range(B):
+            ws, nets = batch.field(b)
+            out_n, _ = _forward_points(cfg, ws, nets, ops.x[b], ops.y[b], ops.t[b], None, ops.cd[b], want_jac=False, want_saved=need_grad)
+            L.check(lib.dpn_smooth_l1(_ptr(out_n), _ptr(ops.lab[b]), n, beta, margin_factor / (6.0 * n), _ptr(dsum[b]), _ptr(g_out), 0, None, _stream()),
+                    'dpn_smooth_l1')
+            if need_grad:
+                _backward_points(cfg, ws, nets, ops.x[b], ops.y[b], ops.t[b], None, ops.cd[b], g_out, None, ops.st,
+                                 into=(grads[0][b], grads[1][b], _static_views(grads[2][b])))
+            del ws, out_n
+        ctx.grads, ctx.n_static = grads, len(statics)
+        ctx.set_materialize_grads(False)
+        return (dsum.sum(dim=1) / (6.0 * n)).float() * margin_factor
+
+    @staticmethod
+    def backward(ctx, g_total):
+        if g_total is None:
+            return (None,) * (11 + ctx.n_static)
+        return (None,) * 9 + _scaled_batch_grads(ctx, 'data_losses_batch', g_total)
+
+
+def data_losses_batch(cfg: PointConfig, x, y, t, coord_data, labels, heads, evec, statics, beta=0.1, margin_factor=1.0):
+    """totals [B]: the data loss (mean SmoothL1(beta) over [N, 6], times margin_factor) of B field samples' labelled rows -- x, y, t [B, N],
+    coord_data and labels [B, N, 6], heads [B, 256, 2700], evec [B, 6, 256], shared statics -- in one step (_DataLossBatchFn)."""
+    return _DataLossBatchFn.apply(cfg, torch.is_grad_enabled(), float(beta), float(margin_factor), x, y, t, coord_data, labels, heads, evec, *statics)
+
+
+def step_losses_batch(cfg: PointConfig, n_inter, x, y, t, f, coord_data, labels, heads, evec, statics, beta=0.1, margin_factor=1.0):
+    """step_losses for B field samples in one step (distinct field / lead time, so distinct hyper-network weights): x, y, t, f [B, N], coord_data
+    [B, N, 6], labels [B, N - n_inter, 6], heads [B, 256, 2700], evec [B, 6, 256], shared statics (eval_step_batch's shapes).  Returns (terms
+    [B, 2, 6]: interior | margin, parts [B, 3]: data loss, interior total, margin total, totals [B] = (data + interior) + margin): the PDE values
+    bitwise step_losses' per field.  Only `totals` carries gradient; terms and parts are detached diagnostics.  Under no_grad nothing is saved and no
+    point backward runs.  One backward pass per forward (_StepLossBatchFn).  Point weights, causal weights and loss balancing are implemented for
+    one field at a time only (step_losses)."""
+    losses, totals = _StepLossBatchFn.apply(cfg, torch.is_grad_enabled(), int(n_inter), float(beta), float(margin_factor), x, y, t, f, coord_data, labels,
+                                            heads, evec, *statics)
+    B = losses.shape[0]
+    return losses[:, :14].view(B, 2, 7)[:, :, :6], torch.stack((losses[:, 14], losses[:, 6], losses[:, 13]), dim=1), totals
+
+
 def _weight_options(what, weights, causal, diag):
     """The `extra` argument of _PdeLossFn / _StepLossFn: None when neither option is given (the launches of before)."""
     if weights is None and causal is None:

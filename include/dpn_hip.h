@@ -575,6 +575,31 @@ int dpn_balance_update(const double* sumsq_dev, int K, double momentum, double l
 int dpn_balance_combine(const float* const* terms, int K, const int* map, const float* lambda_dev, const float* cot_in_dev, float* total_dev,
                         float* cot_out_dev, void* stream);
 
+/* The step body for a lead batch (csrc/dpn_residual.hip): one residual pass per field, one finish launch for all fields.
+ *
+ * dpn_step_residual: out_n [n][6], jac_n [n][6][3], f [n] of ONE field, the first n_inter rows interior, the other n_m = n - n_inter margin points with
+ *   labels [n_m][6].  One launch of blocks(n_inter) + blocks(n_m) workgroups of 256 (blocks(k) = ceil(k / 256)): the first blocks(n_inter) hold the
+ *   interior points, the others the margin points from row n_inter on, so a workgroup holds exactly the points that a block of dpn_residual on that
+ *   group's slice holds.  rows [blocks][7] fp64 (dpn_step_rows_doubles(n_inter, n) doubles; 0 for n_inter < 1 or n_inter >= n), written, not
+ *   accumulated: [0:6] the six criterion sums, bitwise dpn_residual's block rows of the group's slice; [6] the sum of SmoothL1(beta) over the block's
+ *   margin points x 6 variables (the fp32 values of dpn_smooth_l1 cast up; elements of a point in order, wave tree, waves in order), 0.0 from an
+ *   interior block.  With g_out [n][6] and g_jxi [n][6][3] (both or neither) the same pass writes d total / d (out_n, J_xi) for the cotangent gtot[0]
+ *   of the field's total = data loss + interior PDE total + margin PDE total: the PDE part bitwise dpn_residual(gl = NULL, gtot) per group (1 / n of
+ *   the point's own group; phys->reduce_sum honoured), and on margin rows + data_scale * gtot[0] * dSmoothL1, added behind it in one rounded addition
+ *   (what dpn_smooth_l1(scale = data_scale, accumulate = 1, scale_dev = gtot) adds).  No atomics.
+ *   -1 (nothing launched, nothing written): a NULL out_n, jac_n, f, labels, geo, phys, gtot or rows; n_inter < 1; n_inter >= n; g_out without g_jxi; a
+ *   criterion dpn_residual rejects; beta <= 0.
+ * dpn_step_finish_batch: rows of n_fields fields side by side (stride dpn_step_rows_doubles) -> losses [n_fields][16] fp32, one workgroup per field:
+ *   [0:6] the interior terms, [6] their total, [7:13] the margin terms, [13] their total -- bitwise dpn_residual_finish on each group's rows --,
+ *   [14] the data loss (float)(S / (6 n_m)) * margin_factor, S = column 6 of the margin rows added in fp64 in a fixed order, [15] the field's total
+ *   ([14] + [6]) + [13] in fp32.  -1: a NULL pointer, n_inter < 1, n_inter >= n, n_fields < 1. */
+int64_t dpn_step_rows_doubles(int64_t n_inter, int64_t n);
+int dpn_step_residual(const float* out_n, const float* jac_n, const float* f, const float* labels /* [n - n_inter][6] */, int64_t n_inter, int64_t n,
+                      const DpnGeometry* geo, const DpnPhysics* phys, float beta, float data_scale, const float* gtot /* [1] device */, double* rows,
+                      float* g_out, float* g_jxi, void* stream);
+int dpn_step_finish_batch(const double* rows, int64_t n_inter, int64_t n, int n_fields, const DpnPhysics* phys, float margin_factor,
+                          float* losses /* [n_fields][16] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
