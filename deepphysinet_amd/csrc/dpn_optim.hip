@@ -2,7 +2,8 @@
 //
 // Kernel inventory
 //   dpn_gradnorm_kernel / dpn_gradnorm_reduce_kernel   one fp64 partial per 2048-element chunk, added in a fixed order
-//   dpn_adam_kernel                                    the clipped update
+//   dpn_adam_kernel                                    the clipped update; the AdamTableFlatEma instantiation also moves the weight EMA
+//   dpn_ema_swap_kernel                                exchanges the parameters with their EMA shadow
 // No kernel in this file uses atomics: every reduction is fixed-order, the whole step is bitwise reproducible.
 #include "dpn_device.h"
 
@@ -19,6 +20,7 @@ struct AdamTable {
     int chunk_start[kAdamMaxTensors + 1];        // prefix sum of ceil(numel / kAdamChunk)
     int numel[kAdamMaxTensors];
     int n;
+    static constexpr bool ema = false;
 };
 // Optimiser state kept by the caller as ONE flat buffer per moment, tensor i at offset chunk_start[i] * kAdamChunk (each tensor padded to
 // whole chunks): no per-tensor state pointers, so 160 tensors fit in the kernel arguments and a PhysicsNet is one launch per pass.
@@ -31,12 +33,33 @@ struct AdamTableFlat {
     float* m_flat;
     float* v_flat;
     int n;
+    static constexpr bool ema = false;
 };
 static_assert(sizeof(AdamTableFlat) + 64 <= 4096, "kernel arguments are limited to 4 KB");
+// AdamTableFlat plus an exponential moving average of the parameters (the shadow `s_flat`, laid out like the moments), updated by the thread
+// that has just formed the new parameter value.  A type of its own (the pattern of ResArgs::weighted): AdamTableFlat keeps its layout and the
+// instantiations without EMA their code.  The EMA scalars ride in the table, so dpn_adam_kernel keeps its argument list.
+struct AdamTableFlatEma {
+    float* p[kAdamFlatMaxTensors];
+    const float* g[kAdamFlatMaxTensors];
+    int chunk_start[kAdamFlatMaxTensors + 1];
+    int numel[kAdamFlatMaxTensors];
+    float* m_flat;
+    float* v_flat;
+    float* s_flat;
+    const int* ema_base;                         // device, may be null (= 0): EMA updates made before this optimiser was built
+    int n;
+    int ema_warmup;
+    static constexpr bool ema = true;
+};
+static_assert(sizeof(AdamTableFlatEma) + 64 <= 4096, "kernel arguments are limited to 4 KB");
 DEV float* table_m(const AdamTable& t, int ti) { return t.m[ti]; }
 DEV float* table_v(const AdamTable& t, int ti) { return t.v[ti]; }
 DEV float* table_m(const AdamTableFlat& t, int ti) { return t.m_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
 DEV float* table_v(const AdamTableFlat& t, int ti) { return t.v_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+DEV float* table_m(const AdamTableFlatEma& t, int ti) { return t.m_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+DEV float* table_v(const AdamTableFlatEma& t, int ti) { return t.v_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+DEV float* table_s(const AdamTableFlatEma& t, int ti) { return t.s_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
 template <class Table>
 DEV int adam_find(const Table& t, int blk) {
     int lo = 0, hi = t.n - 1;
@@ -86,7 +109,7 @@ __global__ __launch_bounds__(256) void dpn_adam_kernel(Table t, const double* su
                                                        float wd, float max_norm, float* out_norm, const float* hyper) {
     // hyper (optional, device): [lr, beta1, beta2, eps, weight_decay, max_norm, grad_scale] read at run time, so that a step captured in
     // a hipGraph follows a learning-rate schedule (a by-value lr is frozen into the graph); grad_scale multiplies every gradient
-    // before the norm and the update (1 / world_size after a SUM all-reduce)
+    // before the norm and the update (1 / world_size after a SUM all-reduce).  Table::ema: hyper[7] is the EMA decay, hyper is not null
     float gscale = 1.f;
     if (hyper) { lr = hyper[0]; b1 = hyper[1]; b2 = hyper[2]; eps = hyper[3]; wd = hyper[4]; max_norm = hyper[5]; gscale = hyper[6]; }
     const float total = (float)sqrt(*sumsq) * gscale;
@@ -99,6 +122,17 @@ __global__ __launch_bounds__(256) void dpn_adam_kernel(Table t, const double* su
     const int base = (blockIdx.x - t.chunk_start[ti]) * kAdamChunk;
     float* p = t.p[ti]; const float* g = t.g[ti]; float* m = table_m(t, ti); float* v = table_v(t, ti);
     const int end = min(base + kAdamChunk, t.numel[ti]);
+    // Table::ema: s' = d s + (1 - d) p' with the p' this thread stores; d = decay, or min(decay, (1 + te) / (10 + te)) during the warm-up,
+    // te = *step + *ema_base.  One rounding per operation, the one fma written here
+    float* sh = nullptr;
+    float ema_d = 0.f, ema_1md = 0.f;
+    if constexpr (Table::ema) {
+        sh = table_s(t, ti);
+        const float te = (float)(*step + (t.ema_base ? *t.ema_base : 0));
+        ema_d = t.ema_warmup ? fminf(hyper[7], (1.f + te) / (10.f + te)) : hyper[7];
+        ema_1md = 1.f - ema_d;
+    }
+    auto ema_upd = [&](const float si, const float pi) __attribute__((always_inline)) { return fmaf(ema_d, si, ema_1md * pi); };
     auto upd = [&](float& pi, const float graw, float& mi, float& vi) __attribute__((always_inline)) {
         const float gi = fmaf(wd, pi, graw * coef);
         mi = fmaf(b1, mi, (1.f - b1) * gi);                                  // lerp(m, g, 1-b1)
@@ -106,7 +140,8 @@ __global__ __launch_bounds__(256) void dpn_adam_kernel(Table t, const double* su
         pi = pi - step_size * mi / (sqrtf(vi) / bc2s + eps);
     };
     int scalar_from = base;
-    if (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) == 0) {
+    if (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
+          reinterpret_cast<uintptr_t>(sh)) & 15) == 0) {
         const int end4 = base + ((end - base) & ~3);
         for (int i = base + 4 * threadIdx.x; i < end4; i += 1024) {
             // the moments and the gradient are touched by nobody else: streamed past the caches (the parameters stay cacheable, the
@@ -119,10 +154,15 @@ __global__ __launch_bounds__(256) void dpn_adam_kernel(Table t, const double* su
             const f32x4_t Gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(g + i));
             float4 M = make_float4(Mv[0], Mv[1], Mv[2], Mv[3]), V = make_float4(Vv[0], Vv[1], Vv[2], Vv[3]);
             const float4 G = make_float4(Gv[0], Gv[1], Gv[2], Gv[3]);
+            f32x4_t Sv;
+            if constexpr (Table::ema) Sv = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(sh + i));     // the shadow: nobody else's either
             upd(P.x, G.x, M.x, V.x); upd(P.y, G.y, M.y, V.y); upd(P.z, G.z, M.z, V.z); upd(P.w, G.w, M.w, V.w);
             *reinterpret_cast<float4*>(p + i) = P;
             __builtin_nontemporal_store(f32x4_t{M.x, M.y, M.z, M.w}, reinterpret_cast<f32x4_t*>(m + i));
             __builtin_nontemporal_store(f32x4_t{V.x, V.y, V.z, V.w}, reinterpret_cast<f32x4_t*>(v + i));
+            if constexpr (Table::ema)
+                __builtin_nontemporal_store(f32x4_t{ema_upd(Sv[0], P.x), ema_upd(Sv[1], P.y), ema_upd(Sv[2], P.z), ema_upd(Sv[3], P.w)},
+                                            reinterpret_cast<f32x4_t*>(sh + i));
         }
         scalar_from = end4;
     }
@@ -130,7 +170,34 @@ __global__ __launch_bounds__(256) void dpn_adam_kernel(Table t, const double* su
         float pi = p[i], mi = m[i], vi = v[i];
         upd(pi, g[i], mi, vi);
         p[i] = pi; m[i] = mi; v[i] = vi;
+        if constexpr (Table::ema) __builtin_nontemporal_store(ema_upd(__builtin_nontemporal_load(sh + i), pi), sh + i);
     }
+}
+// p <-> shadow, bit for bit (moved as 32-bit words: no float operation touches a NaN payload), over the chunk table of the Adam kernels
+struct EmaSwapTable {
+    float* p[kAdamFlatMaxTensors];
+    int chunk_start[kAdamFlatMaxTensors + 1];
+    int numel[kAdamFlatMaxTensors];
+    float* s_flat;
+    int n;
+};
+__global__ __launch_bounds__(256) void dpn_ema_swap_kernel(EmaSwapTable t) {
+    const int ti = adam_find(t, blockIdx.x);
+    const int base = (blockIdx.x - t.chunk_start[ti]) * kAdamChunk;
+    uint32_t* p = reinterpret_cast<uint32_t*>(t.p[ti]);
+    uint32_t* sh = reinterpret_cast<uint32_t*>(t.s_flat + (int64_t)t.chunk_start[ti] * kAdamChunk);
+    const int end = min(base + kAdamChunk, t.numel[ti]);
+    int scalar_from = base;
+    if (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(sh)) & 15) == 0) {
+        const int end4 = base + ((end - base) & ~3);
+        for (int i = base + 4 * threadIdx.x; i < end4; i += 1024) {
+            const uint4 a = *reinterpret_cast<const uint4*>(p + i), b = *reinterpret_cast<const uint4*>(sh + i);
+            *reinterpret_cast<uint4*>(p + i) = b;
+            *reinterpret_cast<uint4*>(sh + i) = a;
+        }
+        scalar_from = end4;
+    }
+    for (int i = scalar_from + threadIdx.x; i < end; i += 256) { const uint32_t a = p[i]; p[i] = sh[i]; sh[i] = a; }
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI
@@ -182,9 +249,11 @@ int64_t dpn_clip_adam_flat_floats(int n_tensors, const int64_t* numel) {
     return chunks * kAdamChunk;
 }
 
+extern "C++" template <class Table>
 static int clip_adam_flat_impl(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
                                float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, float lr, float beta1, float beta2, float eps,
-                               float weight_decay, float max_norm, float* out_norm_dev, const float* hyper_dev, void* stream) {
+                               float weight_decay, float max_norm, float* out_norm_dev, const float* hyper_dev, void* stream,
+                               float* ema_flat = nullptr, const int* ema_base_dev = nullptr, int ema_warmup = 0) {
     if (n_tensors <= 0 || !params || !grads || !numel || !exp_avg_flat || !exp_avg_sq_flat || !scratch_dev || !step_dev) return -1;
     // every size is checked before the first launch: a refusal bumps no step counter and writes no partial, whichever table the bad tensor is in
     for (int i = 0; i < n_tensors; ++i) if (numel[i] <= 0 || numel[i] > 0x7fffffff) return -1;
@@ -194,10 +263,11 @@ static int clip_adam_flat_impl(int n_tensors, float* const* params, const float*
     for (int pass = 0; pass < 2; ++pass) {
         int base_chunk = 0;
         for (int t0 = 0; t0 < n_tensors; t0 += kAdamFlatMaxTensors) {
-            AdamTableFlat t;
+            Table t;
             t.n = (n_tensors - t0 < kAdamFlatMaxTensors) ? n_tensors - t0 : kAdamFlatMaxTensors;
             t.m_flat = exp_avg_flat + (int64_t)base_chunk * kAdamChunk;
             t.v_flat = exp_avg_sq_flat + (int64_t)base_chunk * kAdamChunk;
+            if constexpr (Table::ema) { t.s_flat = ema_flat + (int64_t)base_chunk * kAdamChunk; t.ema_base = ema_base_dev; t.ema_warmup = ema_warmup; }
             int chunks = 0;
             for (int i = 0; i < t.n; ++i) {
                 t.p[i] = params[t0 + i]; t.g[i] = grads[t0 + i];
@@ -206,8 +276,8 @@ static int clip_adam_flat_impl(int n_tensors, float* const* params, const float*
                 chunks += (t.numel[i] + kAdamChunk - 1) / kAdamChunk;
             }
             t.chunk_start[t.n] = chunks;
-            if (pass == 0) hipLaunchKernelGGL(dpn_gradnorm_kernel<AdamTableFlat>, dim3(chunks), dim3(256), 0, s, t, partial + base_chunk, step_dev, t0 == 0 ? 1 : 0);
-            else hipLaunchKernelGGL(dpn_adam_kernel<AdamTableFlat>, dim3(chunks), dim3(256), 0, s, t, (const double*)sumsq, (const int*)step_dev, lr,
+            if (pass == 0) hipLaunchKernelGGL(dpn_gradnorm_kernel<Table>, dim3(chunks), dim3(256), 0, s, t, partial + base_chunk, step_dev, t0 == 0 ? 1 : 0);
+            else hipLaunchKernelGGL(dpn_adam_kernel<Table>, dim3(chunks), dim3(256), 0, s, t, (const double*)sumsq, (const int*)step_dev, lr,
                                     beta1, beta2, eps, weight_decay, max_norm, out_norm_dev, hyper_dev);
             base_chunk += chunks;
         }
@@ -219,7 +289,7 @@ static int clip_adam_flat_impl(int n_tensors, float* const* params, const float*
 int dpn_clip_adam_flat(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
                        float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, float lr, float beta1, float beta2, float eps,
                        float weight_decay, float max_norm, float* out_norm_dev, void* stream) {
-    return clip_adam_flat_impl(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, lr, beta1, beta2, eps,
+    return clip_adam_flat_impl<AdamTableFlat>(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, lr, beta1, beta2, eps,
                                weight_decay, max_norm, out_norm_dev, nullptr, stream);
 }
 
@@ -227,8 +297,39 @@ int dpn_clip_adam_flat_dev(int n_tensors, float* const* params, const float* con
                            float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const float* hyper_dev, float* out_norm_dev,
                            void* stream) {
     if (!hyper_dev) return -1;
-    return clip_adam_flat_impl(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, 0.f, 0.f, 0.f, 0.f,
+    return clip_adam_flat_impl<AdamTableFlat>(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, 0.f, 0.f, 0.f, 0.f,
                                0.f, 0.f, out_norm_dev, hyper_dev, stream);
+}
+
+int dpn_clip_adam_flat_ema(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
+                           float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const float* hyper_dev, float* out_norm_dev,
+                           float* ema_flat, const int* ema_base_dev, int ema_warmup, void* stream) {
+    if (!hyper_dev || !ema_flat) return -1;
+    return clip_adam_flat_impl<AdamTableFlatEma>(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, 0.f, 0.f,
+                                                 0.f, 0.f, 0.f, 0.f, out_norm_dev, hyper_dev, stream, ema_flat, ema_base_dev, ema_warmup);
+}
+
+int dpn_ema_swap(int n_tensors, float* const* params, const int64_t* numel, float* ema_flat, void* stream) {
+    if (n_tensors <= 0 || !params || !numel || !ema_flat) return -1;
+    for (int i = 0; i < n_tensors; ++i) if (numel[i] <= 0 || numel[i] > 0x7fffffff) return -1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int base_chunk = 0;
+    for (int t0 = 0; t0 < n_tensors; t0 += kAdamFlatMaxTensors) {
+        EmaSwapTable t;
+        t.n = (n_tensors - t0 < kAdamFlatMaxTensors) ? n_tensors - t0 : kAdamFlatMaxTensors;
+        t.s_flat = ema_flat + (int64_t)base_chunk * kAdamChunk;
+        int chunks = 0;
+        for (int i = 0; i < t.n; ++i) {
+            t.p[i] = params[t0 + i];
+            t.numel[i] = (int)numel[t0 + i];
+            t.chunk_start[i] = chunks;
+            chunks += (t.numel[i] + kAdamChunk - 1) / kAdamChunk;
+        }
+        t.chunk_start[t.n] = chunks;
+        hipLaunchKernelGGL(dpn_ema_swap_kernel, dim3(chunks), dim3(256), 0, s, t);
+        base_chunk += chunks;
+    }
+    return ck(hipGetLastError());
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@ Hot methods (`place_one_batch`, `data_loss`, `training_step`) run the fused HIP 
 callers that hold autograd-connected fields of their own.  File I/O, visualisation and the epoch loops of the
 reference are out of scope.
 """
+import contextlib
 import os
 import shutil
 import types
@@ -440,6 +441,18 @@ class InterfacePhysics(nn.Module):
             return CausalWeights(**opt)
         return _loop_option(kwargs, self.train_cfg, 'causal_weights', 'losses', ('eps', 'bins', 'relative'), False, CausalWeights, build)
 
+    def _ema_option(self, kwargs):
+        """The loops' `ema_weights` option (keyword, or train_cfg['optimizer']['ema_weights']): None (off), a decay, or a dict of decay, warmup ->
+        dict(decay, warmup) for FusedClipAdam(ema_decay, ema_warmup)."""
+        opt = kwargs.get('ema_weights', (self.train_cfg.get('optimizer') or {}).get('ema_weights'))
+        if isinstance(opt, (int, float)) and not isinstance(opt, bool):
+            opt = {'decay': opt}
+        def build(o):
+            if 'decay' not in o:
+                raise ValueError('ema_weights: decay is required')
+            return dict(decay=float(o['decay']), warmup=bool(o.get('warmup', True)))
+        return _loop_option({'ema_weights': opt}, {}, 'ema_weights', 'optimizer', ('decay', 'warmup'), False, None, build)
+
     def _lead_batch_option(self, kwargs):
         """The loops' `lead_batch` option (keyword, or train_cfg['train_data']['lead_batch']): samples per optimiser step, 1 when unset.  Refused
         together with a causal_weights / balance_losses option that is set (implemented for one sample per step): the loops ask at their start."""
@@ -867,14 +880,21 @@ class InterfacePhysics(nn.Module):
     # ------------------------------------------------------------------ training loops (:334-846, :848-1404; step body only)
     def build_optimizer(self, **overrides):
         """Fused clip + Adam over the PhysicsNet with the config's optimiser settings (cfg:151-155; `initial_lr` as :394 sets it), its flat
-        gradient buffer laid out in backward-completion order (PhysicsNet.gradient_buckets)."""
+        gradient buffer laid out in backward-completion order (PhysicsNet.gradient_buckets).  The config's `ema_weights` entry is a loop option
+        (_ema_option), not an optimiser keyword: it becomes ema_decay / ema_warmup unless the overrides name those themselves."""
         oc = dict(self.train_cfg.get('optimizer', {}))
         name = oc.pop('name', 'Adam')
         if name != 'Adam':
             raise NotImplementedError('the fused optimiser implements Adam (cfg:151-155); got %r' % name)
+        if oc.pop('ema_weights', None) is not None and 'ema_decay' not in overrides:
+            ema = self._ema_option({})
+            if ema is not None:
+                oc.update(ema_decay=ema['decay'], ema_warmup=ema['warmup'])
         oc.update(overrides)
         opt = FusedClipAdam(self.physics_net.parameters(), layout=self.physics_net.gradient_buckets(), **oc)
         opt.param_groups[0].setdefault('initial_lr', opt.param_groups[0]['lr'])
+        if opt.ema_decay is not None:
+            opt.bind_module(self.physics_net)                            # load_ema / ema_state_dict go by this module's parameter names
         return opt
 
     def _build_lr_schedule(self, optimizer, current_epoch):
@@ -1003,16 +1023,25 @@ class InterfacePhysics(nn.Module):
             if rank == 0:
                 print('resume from epoch %d global_step %d' % (current_epoch, global_step))
             self.physics_net.load_state_dict(state_dict['model'], strict=True)
-        optimizer = self.build_optimizer()
+        ema = self._ema_option(kwargs)                                  # None: the optimiser, the launches, the rows and the checkpoints of before
+        optimizer = self.build_optimizer() if ema is None else self.build_optimizer(ema_decay=ema['decay'], ema_warmup=ema['warmup'])
         if dist_mode:
             D.broadcast_parameters(self.physics_net)                    # DistributedDataParallel does this at wrap time (:903-907)
             sync = D.GradientAllReduce(optimizer)
+        if ema is not None:
+            if state_dict is not None and 'model_ema' in state_dict and 'ema' in state_dict:
+                # a resumed run: the saved average, not the raw weights, and the warm-up goes on where it was
+                optimizer.load_ema(state_dict['model_ema'], int(state_dict['ema']['updates']))
+            elif dist_mode:
+                optimizer.reset_ema()                                   # the shadow was filled before the broadcast
         lr_schedule = self._build_lr_schedule(optimizer, current_epoch)
         self.physics_net.train()
         last = None
         # validation (:629-745): only with a source; without one nothing below runs and the loop is what it was
         valid_src = self._valid_samples(kwargs)
         vlog = self._ValidationLoop(self, valid_src, kwargs.get('log_path'), rank, world, num_epoch, device) if valid_src is not None else None
+        if vlog is not None and ema is not None:
+            vlog.ema_optimizer = optimizer                              # both validation events run on the averaged weights
         adaptive = self._adaptive_option(kwargs)                        # None: not one extra call below
         causal = self._causal_option(kwargs)                            # None: the step's launches of before
         balance = self._balance_option(kwargs)                          # None: likewise
@@ -1065,9 +1094,11 @@ class InterfacePhysics(nn.Module):
                     optimizer.sync_hyper()
                 encoder_ops.check_enc_status()
                 if checkpoint_path and rank == 0:
+                    extra = {} if ema is None else dict(model_ema=optimizer.ema_state_dict(self.physics_net),
+                                                        ema=dict(decay=ema['decay'], warmup=ema['warmup'], updates=optimizer.ema_updates()))
                     self.save_model(checkpoint_path, epoch, global_step, prefix='physics', dx=self.dx, dy=self.dy, dt=self.dt,
                                     pred_x_span=self.dx * self.lon_size, pred_y_span=self.dy * self.lat_size, pred_t_span=self.pred_t_span,
-                                    label_time_step=time_step, obs_norm_cfg=self.obs_norm_cfg)
+                                    label_time_step=time_step, obs_norm_cfg=self.obs_norm_cfg, **extra)
             if vlog is not None and kwargs.get('validate_every_epoch', False):
                 vlog.epoch_event(epoch, global_step, with_pde_cfg and global_step >= pde_start, kwargs)
             if max_steps is not None and global_step >= max_steps:
@@ -1089,6 +1120,13 @@ class InterfacePhysics(nn.Module):
             self.cursor, self.last, self.last_epoch = 0, None, None
             self.clock, self.t0, self.step0 = time.perf_counter, time.perf_counter(), 0
             self.hours = float((model.train_cfg.get('train_data') or {}).get('forecast_time_period', 360))
+            self.ema_optimizer = None                  # the loops' ema_weights option: the optimiser whose averaged weights validation runs on
+
+        def _weights(self):
+            """(context the validation runs in, extra keys of its row): the averaged weights and "weights": "ema", or nothing."""
+            if self.ema_optimizer is None:
+                return contextlib.nullcontext(), {}
+            return self.ema_optimizer.ema_weights(), {'weights': 'ema'}
 
         def _all_ranks(self, row):
             """The rows of all ranks merged in rank order: ONE collective on one small fp64 tensor (gathered, so that the maxima travel with it)."""
@@ -1112,7 +1150,9 @@ class InterfacePhysics(nn.Module):
             m.with_clip = True                                                                 # :629
             was_training = m.physics_net.training
             m.physics_net.eval()                                                               # :516 (no layer here depends on it)
-            res = m.validation_step(vb, with_pde=with_pde)
+            weights, tag = self._weights()
+            with weights:
+                res = m.validation_step(vb, with_pde=with_pde)
             m.physics_net.train(was_training)
             res['pooled'] = V.metrics_from_stats(self._all_ranks(res['stats']))
             res['global_step'] = global_step
@@ -1132,7 +1172,7 @@ class InterfacePhysics(nn.Module):
                 self.log.event('training', epoch=epoch, global_step=global_step, train_loss=loss, forecast_hours=f_train, fps=fps, variables=train_vars,
                                **parts, **extra)
                 self.log.event('validation', epoch=epoch, global_step=global_step, forecast_hours=f_valid, fps=fps,
-                               **{k: v for k, v in res.items() if k != 'global_step'})
+                               **{k: v for k, v in res.items() if k != 'global_step'}, **tag)
             self.t0, self.step0 = self.clock(), seen
 
         def epoch_event(self, epoch, global_step, with_pde, kwargs):
@@ -1140,12 +1180,15 @@ class InterfacePhysics(nn.Module):
             m = self.m
             shard = list(m._shard_samples(self.src, self.rank, self.world))
             m.with_clip = True
-            res = m.validate(shard, with_pde=with_pde, lead_batch=kwargs.get('valid_lead_batch'))
+            weights, tag = self._weights()
+            with weights:
+                res = m.validate(shard, with_pde=with_pde, lead_batch=kwargs.get('valid_lead_batch'))
             pooled = V.metrics_from_stats(self._all_ranks(res['pooled']['stats']))
             self.last_epoch = {'epoch': epoch, 'global_step': global_step, 'samples': res['samples'], 'pooled': pooled}
             if self.log is not None:
                 self.log.event('validation_epoch', epoch=epoch, global_step=global_step, pooled=pooled,
-                               samples=[{'forecast_h': r['forecast_h'], 'valid_loss': r['valid_loss'], 'variables': r['variables']} for r in res['samples']])
+                               samples=[{'forecast_h': r['forecast_h'], 'valid_loss': r['valid_loss'], 'variables': r['variables']} for r in res['samples']],
+                               **tag)
 
     def run_train_interface(self, **kwargs):
         """The single-GPU training loop (:334-846) reduced to what is on the path: per-step body (:443-515) = training_step, PDE losses on
@@ -1164,7 +1207,11 @@ class InterfacePhysics(nn.Module):
         lead_batch (k: k consecutive samples of the epoch's -- per-rank -- stream per optimiser step, training_step_batch; a group is cut early where
         the point counts change and at the end of the epoch; global_step counts optimiser steps, the log line's fps counts samples, its forecast
         hours and train_vars are the group's first sample's; adaptive_interior redraws sample by sample; together with causal_weights or
-        balance_losses: NotImplementedError at loop start; unset or 1: the loop of before).
+        balance_losses: NotImplementedError at loop start; unset or 1: the loop of before),
+        ema_weights (None, a decay, or dict(decay, warmup): the optimiser keeps an exponential moving average of the weights inside its update
+        launch; both validation events run on it and their rows carry "weights": "ema" (train_vars stay on the raw weights), checkpoints gain
+        `model_ema` -- a state dict of the PhysicsNet -- and `ema` = dict(decay, warmup, updates), and a resumed run takes the average and its
+        update count from them; unset: the loop of before).
         With a validation source the result carries `last_validation`."""
         return self._run_train(False, **kwargs)
 
@@ -1209,7 +1256,8 @@ class InterfacePhysics(nn.Module):
         (strictly; obs_norm_cfg and pred_t_span come from the checkpoint when it carries them, :1450-1452), then for every field sample evaluate the
         lattice `img_size` over the training domain (x `refine`) at every `dt` seconds inside the sample's window in ONE predict_lattice call; with
         log.write_source one `<time>_<variable>.npy` [lat, lon] per time step and exported variable goes to log.result_path (start_time only labels
-        the files).  Returns the maps [nt, 6, ny, nx] of the last sample (None without samples).  kwargs: checkpoint_path, samples, device, with_clip.
+        the files).  Returns the maps [nt, 6, ny, nx] of the last sample (None without samples).  kwargs: checkpoint_path, samples, device, with_clip,
+        weights ('ema': the checkpoint's averaged weights `model_ema` in place of `model`; KeyError when it carries none).
         Plotting (log.with_vis: Basemap) is not built."""
         import datetime
         ic = self.inference_cfg or {}
@@ -1243,7 +1291,12 @@ class InterfacePhysics(nn.Module):
         if state_dict is None:
             raise NotImplementedError(checkpoint_path)
         print('resume from epoch %d global_step %d' % (current_epoch, global_step))
-        self.physics_net.load_state_dict(state_dict['model'], strict=True)
+        which = kwargs.get('weights')
+        if which not in (None, 'raw', 'ema'):
+            raise ValueError("weights=%r: 'ema' or None" % (which,))
+        if which == 'ema' and 'model_ema' not in state_dict:
+            raise KeyError("the checkpoint %s carries no 'model_ema' (train with ema_weights / train.py --ema)" % checkpoint_path)
+        self.physics_net.load_state_dict(state_dict['model_ema' if which == 'ema' else 'model'], strict=True)
         cfg_span = ic.get('pred_t_span', -1)
         self.pred_t_span = float(self.gather_key_from_state('pred_t_span', state_dict, cfg_span if cfg_span and cfg_span > 0 else self.pred_t_span))
         self.obs_norm_cfg = self.gather_key_from_state('obs_norm_cfg', state_dict, self.obs_norm_cfg)

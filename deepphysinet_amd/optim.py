@@ -13,8 +13,18 @@ Gradients: the optimiser owns ONE flat fp32 gradient buffer laid out like its fl
 nodes of this package write parameter gradients straight into it, the data-parallel all-reduce (distributed.GradientAllReduce) runs in
 place on its bucket slices, and the kernels read it -- gradients that arrive elsewhere (foreign autograd nodes) are copied in first.
 `layout`: optional list of parameter lists = the buckets in the order their gradients become ready in the backward pass.
+
+Weight EMA (`ema_decay`, off by default): a shadow copy of the parameters, s' = d s + (1 - d) p', moved inside the update launch by the thread
+that has just formed p' (dpn_clip_adam_flat_ema: no extra launch, and a step replayed from a hipGraph moves it too).  With `ema_warmup` the decay
+is min(ema_decay, (1 + n) / (10 + n)), n = the number of EMA updates so far (device step counter + `ema_base`), so a young average is not
+dominated by the initial weights.  `ema_weights()` exchanges parameters and shadow for validation, `ema_state_dict()` writes the shadow out as a
+module state dict.
 """
+import contextlib
 import ctypes
+import math
+import weakref
+from collections import OrderedDict
 
 import torch
 
@@ -25,8 +35,13 @@ _CHUNK = 2048            # dpn_clip_adam_flat: every tensor is padded to whole 2
 
 
 class FusedClipAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=2.5e7, layout=None):
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=2.5e7, layout=None, ema_decay=None, ema_warmup=True):
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, max_norm=float(max_norm))
+        if ema_decay is not None:
+            ema_decay = float(ema_decay)
+            if not (math.isfinite(ema_decay) and 0.0 <= ema_decay < 1.0):
+                raise ValueError('FusedClipAdam: ema_decay must be a finite number in [0, 1), got %r' % (ema_decay,))
+        self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)       # attributes, not param_groups entries: state dicts keep their keys
         super().__init__(params, defaults)
         if len(self.param_groups) != 1:
             raise NotImplementedError('FusedClipAdam takes one parameter group (the reference trains with one, cfg:151-155)')
@@ -76,6 +91,12 @@ class FusedClipAdam(torch.optim.Optimizer):
         self.steps_done = 0                                         # host-side count of step() calls (point_path's forward / backward stamps)
         self._leased = set()                                        # offsets of the slots a live gradient may alias (grad_arena)
         self._ptrs = [p.data_ptr() for p in self.params]            # what the kernels write through: checked against the live tensors every step
+        self._ema_flat, self.ema, self.ema_base, self._ema_swapped, self._module = None, None, None, False, None
+        if ema_decay is not None:
+            self._ema_flat = torch.zeros(total, dtype=torch.float32, device=dev)
+            self.ema = [self._ema_flat[o:o + p.numel()].view_as(p) for o, p in zip(self._offsets, self.params)]
+            self.ema_base = torch.zeros(1, dtype=torch.int32, device=dev)       # EMA updates made before this optimiser was built (load_ema)
+            self.reset_ema()
         self.sync_hyper()
         grad_arena.register(self, self.params, self._offsets)
 
@@ -105,7 +126,7 @@ class FusedClipAdam(torch.optim.Optimizer):
     def _hyper_values(self):
         g = self.param_groups[0]
         return (float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay']), float(g['max_norm']),
-                float(self.grad_scale), 0.0)
+                float(self.grad_scale), 0.0 if self.ema_decay is None else self.ema_decay)
 
     def sync_hyper(self):
         """Upload param_groups[0] (lr after a scheduler step, ...) to the device scalars the kernels read.  step() does it by itself
@@ -167,20 +188,111 @@ class FusedClipAdam(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         self._check_pointers()
+        if self._ema_swapped:
+            raise RuntimeError('FusedClipAdam: step() inside ema_weights(): the parameters hold the averaged weights')
         self.gather_gradients()
         if not torch.cuda.is_current_stream_capturing():
             self.sync_hyper()
         else:
             grad_arena.captured_step[0] = True      # replays of this step rewrite the parameters without passing through here
         lib = L.load()
-        L.check(lib.dpn_clip_adam_flat_dev(len(self.params), self._p, self._g, self._numel, ctypes.c_void_p(self._m_flat.data_ptr()),
-                                           ctypes.c_void_p(self._v_flat.data_ptr()), ctypes.c_void_p(self._sumsq.data_ptr()),
-                                           ctypes.c_void_p(self.step_count.data_ptr()), ctypes.c_void_p(self._hyper.data_ptr()),
-                                           ctypes.c_void_p(self.grad_norm.data_ptr()), torch.cuda.current_stream().cuda_stream),
-                'dpn_clip_adam_flat_dev')
+        if self._ema_flat is None:
+            L.check(lib.dpn_clip_adam_flat_dev(len(self.params), self._p, self._g, self._numel, ctypes.c_void_p(self._m_flat.data_ptr()),
+                                               ctypes.c_void_p(self._v_flat.data_ptr()), ctypes.c_void_p(self._sumsq.data_ptr()),
+                                               ctypes.c_void_p(self.step_count.data_ptr()), ctypes.c_void_p(self._hyper.data_ptr()),
+                                               ctypes.c_void_p(self.grad_norm.data_ptr()), torch.cuda.current_stream().cuda_stream),
+                    'dpn_clip_adam_flat_dev')
+        else:
+            L.check(lib.dpn_clip_adam_flat_ema(len(self.params), self._p, self._g, self._numel, ctypes.c_void_p(self._m_flat.data_ptr()),
+                                               ctypes.c_void_p(self._v_flat.data_ptr()), ctypes.c_void_p(self._sumsq.data_ptr()),
+                                               ctypes.c_void_p(self.step_count.data_ptr()), ctypes.c_void_p(self._hyper.data_ptr()),
+                                               ctypes.c_void_p(self.grad_norm.data_ptr()), ctypes.c_void_p(self._ema_flat.data_ptr()),
+                                               ctypes.c_void_p(self.ema_base.data_ptr()), int(self.ema_warmup),
+                                               torch.cuda.current_stream().cuda_stream),
+                    'dpn_clip_adam_flat_ema')
         grad_arena.param_epoch[0] += 1
         self.steps_done += 1
         return self.grad_norm if closure is None else loss
+
+    # ---- weight EMA ----------------------------------------------------------------------------------------------------
+    def _need_ema(self, what):
+        if self._ema_flat is None:
+            raise RuntimeError('FusedClipAdam.%s: the optimiser was built without ema_decay' % what)
+
+    @torch.no_grad()
+    def reset_ema(self):
+        """The shadow becomes the parameters' current values (the EMA update counters stay)."""
+        self._need_ema('reset_ema')
+        if self._ema_swapped:
+            raise RuntimeError('FusedClipAdam.reset_ema inside ema_weights()')
+        for s, p in zip(self.ema, self.params):
+            s.copy_(p.detach())
+
+    def ema_updates(self):
+        """EMA updates made so far: the device step counter plus `ema_base` (reads the device)."""
+        self._need_ema('ema_updates')
+        return int(self.step_count) + int(self.ema_base)
+
+    def bind_module(self, module):
+        """The module whose parameter names `load_ema` uses (kept as a weak reference)."""
+        self._module = weakref.ref(module)
+
+    def _ema_swap(self):
+        L.check(L.load().dpn_ema_swap(len(self.params), self._p, self._numel, ctypes.c_void_p(self._ema_flat.data_ptr()),
+                                      torch.cuda.current_stream().cuda_stream), 'dpn_ema_swap')
+        grad_arena.param_epoch[0] += 1             # the parameters changed through raw pointers, as in step(): caches keyed on the epoch miss
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the parameters hold the averaged weights and the shadow the raw ones (one in-place exchange each way, no copy of the
+        model): validation and inference on the EMA.  No nesting, no step() inside, not during a graph capture."""
+        self._need_ema('ema_weights')
+        if self._ema_swapped:
+            raise RuntimeError('FusedClipAdam.ema_weights() does not nest')
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('FusedClipAdam.ema_weights() during a graph capture: a replay would exchange the weights again')
+        self._check_pointers()
+        self._ema_swap()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._ema_swap()
+            self._ema_swapped = False
+
+    def ema_state_dict(self, module):
+        """`module.state_dict()` with every optimised parameter replaced by a clone of its shadow: same names, shapes and order; buffers and
+        parameters this optimiser does not hold come from the module."""
+        self._need_ema('ema_state_dict')
+        self.bind_module(module)
+        if self._ema_swapped:
+            raise RuntimeError('FusedClipAdam.ema_state_dict inside ema_weights()')
+        shadow = {id(p): s for p, s in zip(self.params, self.ema)}
+        named = {k: shadow[id(p)] for k, p in module.named_parameters(remove_duplicate=False) if id(p) in shadow}
+        return OrderedDict((k, (named[k] if k in named else v).detach().clone()) for k, v in module.state_dict().items())
+
+    @torch.no_grad()
+    def load_ema(self, state_dict, updates, module=None):
+        """Fill the shadow from an `ema_state_dict` (strict: every optimised parameter's name must be there with its shape) and set `ema_base` so
+        that step counter + base = `updates`: the warm-up of a resumed run does not restart.  The names are those of `module`, or of the module
+        last given to `bind_module` / `ema_state_dict`."""
+        self._need_ema('load_ema')
+        module = self._module() if module is None and self._module is not None else module
+        if module is None:
+            raise RuntimeError('FusedClipAdam.load_ema: no module to take the parameter names from (bind_module)')
+        if self._ema_swapped:
+            raise RuntimeError('FusedClipAdam.load_ema inside ema_weights()')
+        shadow = {id(p): s for p, s in zip(self.params, self.ema)}
+        names = {k: shadow[id(p)] for k, p in module.named_parameters(remove_duplicate=False) if id(p) in shadow}
+        missing = [k for k in names if k not in state_dict]
+        if missing:
+            raise KeyError('FusedClipAdam.load_ema: the state dict lacks %s' % ', '.join(missing[:5]))
+        for k, s in names.items():
+            if tuple(state_dict[k].shape) != tuple(s.shape):
+                raise ValueError('FusedClipAdam.load_ema: %s has shape %s, expected %s' % (k, tuple(state_dict[k].shape), tuple(s.shape)))
+        for k, s in names.items():
+            s.copy_(state_dict[k])
+        self.ema_base.fill_(int(updates) - int(self.step_count))
 
     # ---- checkpoints ---------------------------------------------------------------------------------------------------
     def state_dict(self):
@@ -190,17 +302,34 @@ class FusedClipAdam(torch.optim.Optimizer):
         # torch.optim.Adam stores it
         sd['state'] = {k: {'step': step.clone(), 'exp_avg': st['exp_avg'].detach().clone(), 'exp_avg_sq': st['exp_avg_sq'].detach().clone()}
                        for k, st in sd['state'].items()}
+        if self._ema_flat is not None:
+            # sd['state'] is keyed by the parameter's index in param_groups[0]['params'] (the order they were given in)
+            shadow = {id(p): s for p, s in zip(self.params, self.ema)}
+            for k, p in enumerate(self.param_groups[0]['params']):
+                sd['state'][k]['ema'] = shadow[id(p)].detach().clone()
+            sd['ema_updates'] = self.ema_updates()
         return sd
 
     def load_state_dict(self, state_dict):
         views = {id(p): (m, v) for p, m, v in zip(self.params, self.exp_avg, self.exp_avg_sq)}
+        if self._ema_swapped:
+            raise RuntimeError('FusedClipAdam.load_state_dict inside ema_weights()')
+        ema_updates = state_dict.get('ema_updates')
+        if ema_updates is not None:                 # torch's load_state_dict knows 'state' and 'param_groups' only
+            state_dict = {k: v for k, v in state_dict.items() if k != 'ema_updates'}
         super().load_state_dict(state_dict)
         for k, v in self.defaults.items():          # a torch.optim.Adam state dict has no 'max_norm' (load_state_dict replaces the group wholesale)
             self.param_groups[0].setdefault(k, v)
         step = None
+        shadow = {id(p): s for p, s in zip(self.params, self.ema)} if self._ema_flat is not None else {}
+        have_ema = bool(shadow) and ema_updates is not None
         for p in self.param_groups[0]['params']:
             st = self.state.get(p, {})
             m, v = views[id(p)]
+            if have_ema and 'ema' in st:
+                shadow[id(p)].copy_(st['ema'])
+            elif shadow:                            # a state dict without EMA: the average starts from the current parameters
+                have_ema = False
             if 'exp_avg' in st:
                 m.copy_(st['exp_avg'])
                 v.copy_(st['exp_avg_sq'])
@@ -208,5 +337,11 @@ class FusedClipAdam(torch.optim.Optimizer):
             self.state[p] = {'step': self.step_count, 'exp_avg': m, 'exp_avg_sq': v}
         if step is not None:
             self.step_count.fill_(int(float(step)))
+        if shadow:
+            if have_ema:
+                self.ema_base.fill_(int(ema_updates) - int(self.step_count))
+            else:
+                self.reset_ema()
+                self.ema_base.zero_()
         self._hyper_host = None
         self.sync_hyper()

@@ -472,6 +472,24 @@ int dpn_clip_adam_flat_dev(int n_tensors, float* const* params, const float* con
                            float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const float* hyper_dev, float* out_norm_dev,
                            void* stream);
 
+/* dpn_clip_adam_flat_dev that also moves an exponential moving average (EMA) of the parameters, in the update launch: the thread that has formed
+ * a new parameter value p' updates its shadow element, so the average costs one more read and one more write stream and no launch, and follows a
+ * step replayed from a hipGraph.  ema_flat: the shadow, laid out exactly like exp_avg_flat (tensor i at chunk_start[i] * 2048; the padding is
+ * never touched).  hyper_dev[8]: the seven values above and hyper_dev[7] = the decay.  ema_base_dev: device int, may be NULL (= 0), the number of
+ * EMA updates made before this optimiser state was created (a resumed run).  All fp32, one rounding per operation, one fma:
+ *     t = *step_dev after the bump;  te = t + base
+ *     d  = ema_warmup ? fminf(decay, (1.f + (float)te) / (10.f + (float)te)) : decay
+ *     s' = fmaf(d, s, (1.f - d) * p')
+ * p, m, v, out_norm and *step_dev come out bit-identical to dpn_clip_adam_flat_dev.  -1 (nothing launched, nothing written): ema_flat or
+ * hyper_dev NULL and everything dpn_clip_adam_flat_dev refuses. */
+int dpn_clip_adam_flat_ema(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
+                           float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const float* hyper_dev, float* out_norm_dev,
+                           float* ema_flat, const int* ema_base_dev, int ema_warmup, void* stream);
+/* Exchanges every parameter with its shadow in ema_flat in place, bit for bit (validation and inference on the averaged weights without a second
+ * model): one launch per 160 tensors over the same chunk table; the padding of ema_flat and everything outside the tensors stay untouched; two
+ * calls are the identity.  -1: n_tensors <= 0, a NULL pointer, a numel outside 1 .. 2^31 - 1. */
+int dpn_ema_swap(int n_tensors, float* const* params, const int64_t* numel, float* ema_flat, void* stream);
+
 /* BASELINE configs[4] (OFF by default; `bench.py --encoder-fp8` / DPN_ENCODER_FP8=mx routes the encoder layers' forward GEMMs here): C[M][N] =
  * epilogue(A[M][K] . W[N][K]^T + bias[N]) on the block-scaled (MX) fp8 instruction v_mfma_scale_f32_32x32x64_f8f6f4: OCP e4m3 operands quantised in
  * the kernel, one E8M0 power-of-two scale per 32 consecutive k of a row (OCP MX) applied by the hardware, fp32 accumulate; K % 64 == 0; epi =

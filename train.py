@@ -2,7 +2,7 @@
 """Launcher with the reference's three flags (reference train.py:17-19, :34-48): --config_file, --checkpoint_path, --log_path.
 
     python train.py [--config_file cfg.py] [--checkpoint_path DIR] [--log_path DIR] [--dist] [--max_steps N] [--synthetic] [--valid_synthetic]
-                    [--adaptive_interior] [--causal_weights EPS] [--balance_losses EVERY] [--lead_batch K]
+                    [--adaptive_interior] [--causal_weights EPS] [--balance_losses EVERY] [--lead_batch K] [--ema DECAY]
 
 The reference reads the config with mmcv.Config.fromfile (absent here, and moved to mmengine in the pinned mmcv: SURVEY section 0, defect
 3), builds the interface with `builder_models(**cfg['config'])` and calls `run_train_interface(checkpoint_path=..., log_path=...)`.  The
@@ -45,6 +45,8 @@ parse.add_argument('--balance_losses', default=None, type=int, metavar='EVERY', 
 parse.add_argument('--lead_batch', default=None, type=int, metavar='K', help='K consecutive samples of the epoch (for example forecast leads) per optimiser '
                    'step: one batched encoder pass, the point kernels sample after sample, the loss their mean (lead_batch=K; 1 or unset: one sample '
                    'per step); not together with --causal_weights / --balance_losses')
+parse.add_argument('--ema', default=None, type=float, metavar='DECAY', help='keep an exponential moving average of the weights inside the optimiser step '
+                   '(ema_weights=dict(decay=DECAY, warmup=True)): validation runs on it and the checkpoints carry it as model_ema (infer.py --ema)')
 
 
 def load_config(path):
@@ -82,6 +84,8 @@ if __name__ == '__main__':
         kwargs['balance_losses'] = dict(every=args.balance_losses, momentum=0.9, groups='equations')
     if args.lead_batch is not None:
         kwargs['lead_batch'] = args.lead_batch
+    if args.ema is not None:
+        kwargs['ema_weights'] = dict(decay=args.ema, warmup=True)
     run = model.run_train_interface_dist if args.dist else model.run_train_interface
     out = run(**kwargs)
     print('done: epoch %d, global_step %d, lr %.3e' % (out['epoch'], out['global_step'], out['lr']))
