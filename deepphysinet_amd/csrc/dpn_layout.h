@@ -78,4 +78,17 @@ constexpr int kF0 = kS0, kFA = kS1, kFB = kS1 + 8 * 16, kFAT = kS2, kF5 = kS5;
 static_assert(kFB + 8 * 12 == kS2 && kFAT + 8 * 16 == kS3, "fused form fits the block");
 enum { kVecC2 = kVecCvec, kVecA2 = kVecBf1, kVecBv = kVecB2BdE_unused };
 
+// ------------------------------------------------------------------ dpn_wgrad_kernel, product 2: which wave fetches which 1-KB piece of a tile
+// The slot image of S2 = M2^T G6 is 16 X pieces (the mask) and, per plane s < ns, 12 Y pieces p = (k-step, column tile) of the per-point pe6 table.
+// G6 = g pe6 is formed from the table in LDS, in place, by the wave that fetched the piece, so a wave gets BOTH planes of its column pairs:
+// pair `wave` in its first ns slots, pair 8 + wave in the next ns on waves 0..3; the other slots take the X pieces (waves 4..7 take more of them) and,
+// where 8 * issue > 16 + 12 ns, a pad.  Slot j of `issue` per wave -> -1: pad | 0 .. 15: X piece | 16 + 12 s + p: plane s of pair p.
+DPN_HD bool wgrad_coop_is_y(int ns, int wave, int j) { return j < ns || (j < 2 * ns && wave < 4); }
+DPN_HD int wgrad_coop_piece(int ns, int issue, int wave, int j) {
+    const int xlo = issue - 2 * ns, xhi = (16 - 4 * xlo) / 4;       // X pieces of a wave 0..3 / 4..7 (hi+lo: 1 / 3, plain bf16: 2 / 2)
+    if (j < ns) return 16 + 12 * j + wave;
+    if (wave < 4) return j < 2 * ns ? 16 + 12 * (j - ns) + 8 + wave : xlo * wave + (j - 2 * ns);
+    return j - ns < xhi ? 4 * xlo + xhi * (wave - 4) + (j - ns) : -1;
+}
+
 }  // namespace dpn

@@ -73,11 +73,16 @@ struct OperandView {     // written by dpn_bwd_points
     float* gnet;         // [6][n_pad]      per-net cotangent of the normalised field, zero for padding points
 };
 // Round 5: G6 = g pe6 (the Y operand of S2 = M2^T G6) is no longer written per point AND NET: it is a per-point table times a per-net scalar, so
-// dpn_wgrad_kernel forms it in registers from the table fragment it has just read (seven VALU instructions per element beside the MFMAs) and the table
-// -- 768 B per point in the hi+lo mode, shared by the six nets -- stays in the memory-side cache.  Stage 1 writes 2 560 -> 1 792 B per point and net.
-// (The same was built for Z0 = g pe3 + gJ_c d pe3 / d xi_c -- the partner column of one pe3 table through a DPP move -- and measured: stage 1 91 us
-// instead of 130, but product 3's tile loop no longer fits 256 registers beside its 128 accumulators and two X planes, each reload of a spilled value
-// waits for the LDS-DMA ring as well, and dpn_wgrad_kernel went 198 -> 337 us; profiles/round5_operand_tables.txt.  Z0 stays a per-net operand.)
+// dpn_wgrad_kernel forms it from the table and the table -- 768 B per point in the hi+lo mode, shared by the six nets -- stays in the memory-side cache.
+// Stage 1 writes 2 560 -> 1 792 B per point and net.  The forming was in registers at first, on the fragment each wave had just read (seven VALU
+// instructions per element beside the MFMAs, the same elements on four waves); it is now done once per workgroup, in LDS, in place, by the wave that
+// fetched the piece (dpn_wgrad.hip, form()): bit-identical S2, same range plan, dpn_wgrad_kernel<2> alone 229-234 -> 215-219 us and 219.4 -> 203.4 us
+// in the captured step (rocprofv3), the step 1.157-1.166 -> 1.140-1.144 ms (five alternated rounds each on one box; profiles/wgrad_coop_forming_ab.txt).
+// (Round 5 built the same table form for Z0 = g pe3 + gJ_c d pe3 / d xi_c with IN-REGISTER forming -- the partner column of one pe3 table through a
+// DPP move -- and measured: stage 1 91 us instead of 130, but product 3's tile loop no longer fit 256 registers beside its then 128 accumulators and
+// two X planes, each reload of a spilled value waits for the LDS-DMA ring as well, and dpn_wgrad_kernel went 198 -> 337 us;
+// profiles/round5_operand_tables.txt.  Not measured again with the forming in LDS, which holds no fragments beside the accumulators: Z0 is still a
+// per-net operand, written by stage 1 and read once.)
 DEV OperandView operand_view(void* base, int64_t n_pad, int ns) {
     OperandView o;
     char* b = reinterpret_cast<char*>(base);

@@ -10,6 +10,8 @@
 // is dpn_clock_stamp_kernel's ring cursor, a measurement aid.)
 //
 // Built WITHOUT -amdgpu-mfma-vgpr-form: dpn_wgrad_kernel measures slower with its accumulators in VGPRs (dpn_point.hip).
+#include <type_traits>
+
 #include "dpn_point_common.h"
 
 DEV u16 f2bf(float x) {                       // round-to-nearest-even, finite inputs (pack kernels)
@@ -375,12 +377,21 @@ DEV void wgrad_body(const WgradArgs& a, char* lds, const int split, const int ne
     //  360 us against 364 us in the hi+lo mode.  Not kept.)
     // piece q = wave + 8 j of the slot image: where it comes from (address of tile 0, bytes per tile) and where it goes -- worked out once,
     // so that issuing a tile is straight-line code
+    //
+    // Product 2 (kCoop) deals the pieces differently: its Y image is the per-point pe6 TABLE, and G6 = g pe6 is formed from it in LDS, in place, ONCE per
+    // workgroup (form() below) instead of by each of the four wm waves in registers.  A wave fetches what it forms -- the NS planes of column pair
+    // p = wave, and of p = 8 + wave on waves 0..3 (a pair = one k-step of one column tile, 1 KB per plane) -- so the counted wait that says its own
+    // pieces have landed is all that forming needs, and the tile's one barrier then covers "landed AND formed".  Waves 4..7 take X pieces instead.
+    constexpr bool kCoop = PROD == 2;
+    static_assert(!kCoop || (2 * nct == 12 && nsx == 1 && S::kIssue >= 2 * NS), "product 2: 12 column pairs over 8 waves");
+    const bool two_pairs = wave < 4;                                    // wave-uniform
     const char* pbase[S::kIssue];
     int pstride[S::kIssue], pdst[S::kIssue];
 #pragma unroll
     for (int j = 0; j < S::kIssue; ++j) {
-        const int q = wave + 8 * j;
-        if (S::kPad && q >= S::kPieces) {                               // a cache hit after the first time
+        int q = wave + 8 * j;                                           // the piece of the linear slot image: X planes, then Y planes ...
+        if constexpr (kCoop) q = wgrad_coop_piece(NS, S::kIssue, wave, j);     // ... or the deal of dpn_layout.h (-1: the pad)
+        if (S::kPad && (kCoop ? q < 0 : q >= S::kPieces)) {             // a cache hit after the first time
             pbase[j] = xb + ((int64_t)net * nsx * tiles + (t0 < tiles ? t0 : 0)) * 16384; pstride[j] = 0; pdst[j] = S::kPadOff;
         } else if (q < nsx * 16) {
             pbase[j] = xb + ((int64_t)net * nsx + q / 16) * tiles * 16384 + (q % 16) * 1024; pstride[j] = 16384; pdst[j] = q * 1024;
@@ -395,7 +406,7 @@ DEV void wgrad_body(const WgradArgs& a, char* lds, const int split, const int ne
         for (int j = 0; j < S::kIssue; ++j) {
             // read-once operand streams carry the non-temporal hint; the per-point pe6 table of product 2 is read by six nets' workgroups and should
             // stay in the memory-side cache (PMC, round 5: with the hint on it the table came from HBM six times: 1 052 MB against 890 algorithmic)
-            if (PROD == 2 && wave + 8 * j >= nsx * 16) dma16(pbase[j] + tile * pstride[j] + lane * 16, sl + pdst[j]);
+            if (kCoop && wgrad_coop_is_y(NS, wave, j)) dma16(pbase[j] + tile * pstride[j] + lane * 16, sl + pdst[j]);
             else dma16_nt(pbase[j] + tile * pstride[j] + lane * 16, sl + pdst[j]);
         }
         dma4(reinterpret_cast<const char*>(gnet + tile * 32) + lane * 4, sl + S::kGOff + wave * 256);
@@ -435,8 +446,10 @@ DEV void wgrad_body(const WgradArgs& a, char* lds, const int split, const int ne
             asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(base), "i"(off) : "memory");
         };
         auto issue_reads = [&](const int kk, const int b) __attribute__((always_inline)) {
-            rd128o(gqa[b][0], baseG, 64 * kk);
-            rd128o(gqa[b][1], baseG, 64 * kk + 32);
+            if constexpr (!kCoop) {                                 // (product 2 needs g in form() only)
+                rd128o(gqa[b][0], baseG, 64 * kk);
+                rd128o(gqa[b][1], baseG, 64 * kk + 32);
+            }
 #pragma unroll
             for (int s2 = 0; s2 < nsx; ++s2)
 #pragma unroll
@@ -446,7 +459,7 @@ DEV void wgrad_body(const WgradArgs& a, char* lds, const int split, const int ne
 #pragma unroll
                 for (int n2 = 0; n2 < NT; ++n2) rd128o(fba[b][s2][n2], baseB, s2 * S::kYPlane + (kk * nct + n2) * 1024);
         };
-        constexpr int kReads = 2 + MT * nsx + NT * NS;              // LDS reads per k-step
+        constexpr int kReads = (kCoop ? 0 : 2) + MT * nsx + NT * NS;   // LDS reads per k-step
         if constexpr (NS == 1) { issue_reads(0, 0); issue_reads(1, 1); }
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
@@ -460,7 +473,9 @@ DEV void wgrad_body(const WgradArgs& a, char* lds, const int split, const int ne
             // second k-step's reads still behind, the first k-step is complete at lgkmcnt(kReads))
             if (NS == 1 && kk == 0) asm volatile("s_waitcnt lgkmcnt(%0)" :: "n"(kReads) : "memory");
             else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            asm volatile("" : "+v"(gq0), "+v"(gq1), "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fb[0][0]), "+v"(fb[0][1]));
+            if constexpr (kCoop) gq0 = gq1 = (u32x4)0u;             // (gp below is dead code for product 2)
+            else asm volatile("" : "+v"(gq0), "+v"(gq1));
+            asm volatile("" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fb[0][0]), "+v"(fb[0][1]));
             if constexpr (MT == 4) asm volatile("" : "+v"(fa[0][2]), "+v"(fa[0][3]));
             if constexpr (NT == 3) asm volatile("" : "+v"(fb[0][2]));
             if constexpr (NS == 2) asm volatile("" : "+v"(fb[1][0]), "+v"(fb[1][1]));
@@ -469,21 +484,7 @@ DEV void wgrad_body(const WgradArgs& a, char* lds, const int split, const int ne
             if constexpr (nsx == 2 && MT == 4) asm volatile("" : "+v"(fa[1][2]), "+v"(fa[1][3]));
             const float gp[8] = {__uint_as_float(gq0[0]), __uint_as_float(gq0[1]), __uint_as_float(gq0[2]), __uint_as_float(gq0[3]),
                                  __uint_as_float(gq1[0]), __uint_as_float(gq1[1]), __uint_as_float(gq1[2]), __uint_as_float(gq1[3])};
-            if constexpr (PROD == 2) {
-                // the Y fragments just read are the per-point TABLE pe6 (hi [+ lo]); this net's operand G6 = g pe6 is formed here: element e of a register
-                // pair <-> point e of the lane's eight (gp[e])
-#pragma unroll
-                for (int n2 = 0; n2 < NT; ++n2)
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) {
-                        float v0 = bf_lo(fb[0][n2][p]), v1 = bf_hi(fb[0][n2][p]);
-                        if constexpr (NS == 2) { v0 += bf_lo(fb[1][n2][p]); v1 += bf_hi(fb[1][n2][p]); }
-                        const float z0 = gp[2 * p] * v0, z1 = gp[2 * p + 1] * v1;
-                        const u32 hi = pack2(z0, z1);
-                        fb[0][n2][p] = hi;
-                        if constexpr (NS == 2) fb[1][n2][p] = pack2(z0 - bf_lo(hi), z1 - bf_hi(hi));
-                    }
-            }
+            // (product 2: the Y fragments just read are this net's G6 = g pe6 already, form() has been over the slot)
             if (PROD == 1 && wave == 0 && i == 0) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) gsum += gp[e];
@@ -527,6 +528,43 @@ DEV void wgrad_body(const WgradArgs& a, char* lds, const int split, const int ne
         }
     };
 
+    // Product 2: this wave's column pairs of the slot's pe6 table image (hi [+ lo]) become this net's operand G6 = g pe6, in place: the 16 bytes of a lane
+    // per plane are the eight points of its column, element e <-> point e of the lane's eight (its own copy of g).  The arithmetic is what each wm wave did
+    // on its registers before (S2 and q6 are bit-identical).  Reads and writes are lane-private and touch only pieces this wave fetched itself: the caller
+    // has waited for them (vmcnt) and runs the tile's barrier afterwards -- form() ends with all its LDS writes retired.
+    auto form = [&](const int slot_) __attribute__((always_inline)) {
+        const unsigned buf = lds_base + slot_ * kSlot;
+        const unsigned baseG = buf + S::kGOff + wave * 256 + h * 16, baseY = buf + S::kX + wave * 1024 + lane * 16;
+        auto pair = [&](auto q_) __attribute__((always_inline)) {
+            constexpr int q = decltype(q_)::value;                    // pair p = wave + 8 q: k-step kk = p / nct
+            const unsigned ay = baseY + q * 8192, ag = baseG + ((wave + 8 * q) >= nct ? 64 : 0);
+            u32x4 t[2], gq0, gq1;
+            rd128(gq0, ag);
+            asm volatile("ds_read_b128 %0, %1 offset:32" : "=v"(gq1) : "v"(ag) : "memory");
+            rd128(t[0], ay);
+            if constexpr (NS == 2) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(t[1]) : "v"(ay), "i"(S::kYPlane) : "memory");
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            asm volatile("" : "+v"(gq0), "+v"(gq1), "+v"(t[0]));
+            if constexpr (NS == 2) asm volatile("" : "+v"(t[1]));
+            const float gp[8] = {__uint_as_float(gq0[0]), __uint_as_float(gq0[1]), __uint_as_float(gq0[2]), __uint_as_float(gq0[3]),
+                                 __uint_as_float(gq1[0]), __uint_as_float(gq1[1]), __uint_as_float(gq1[2]), __uint_as_float(gq1[3])};
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                float v0 = bf_lo(t[0][p]), v1 = bf_hi(t[0][p]);
+                if constexpr (NS == 2) { v0 += bf_lo(t[1][p]); v1 += bf_hi(t[1][p]); }
+                const float z0 = gp[2 * p] * v0, z1 = gp[2 * p + 1] * v1;
+                const u32 hi = pack2(z0, z1);
+                t[0][p] = hi;
+                if constexpr (NS == 2) t[1][p] = pack2(z0 - bf_lo(hi), z1 - bf_hi(hi));
+            }
+            asm volatile("ds_write_b128 %0, %1" :: "v"(ay), "v"(t[0]) : "memory");
+            if constexpr (NS == 2) asm volatile("ds_write_b128 %0, %1 offset:%2" :: "v"(ay), "v"(t[1]), "i"(S::kYPlane) : "memory");
+        };
+        pair(std::integral_constant<int, 0>{});
+        if (two_pairs) pair(std::integral_constant<int, 1>{});
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    };
+
     // prologue: RING-1 tiles in flight (out-of-range tiles re-read the last valid one; their data is never used)
     const int64_t tl = t1 > t0 ? t1 - 1 : t0;
 #pragma unroll
@@ -538,8 +576,9 @@ DEV void wgrad_body(const WgradArgs& a, char* lds, const int split, const int ne
     for (int64_t tile = t0; tile < t1; ++tile) {
         DPN_WG_CLOCK(c0);
         wait_vmcnt<(RING - 2) * PER_TILE>();                             // this wave's pieces of `tile` have landed
+        if constexpr (kCoop) form(slot);                                 // (nobody reads this slot before the barrier, nobody else writes these bytes)
         DPN_WG_CLOCK(c1);
-        __builtin_amdgcn_s_barrier();                                    // ... and everybody else's; and compute(tile-1) is finished everywhere
+        __builtin_amdgcn_s_barrier();                                    // ... and everybody else's [and formed]; and compute(tile-1) is finished everywhere
         DPN_WG_CLOCK(c2);
         {
             const int64_t nt = tile + RING - 1;
@@ -911,6 +950,14 @@ struct SplitPlan { int s[4]; int most; };
 // per-point table (OperandView), which makes ITS tiles the slowest: it gets the most ranges per byte.  Sweeps of the 42 ranges per net
 // (tools/wgrad_overlap_probe.py, profiles/round5_wgrad_plans.txt; eager launches back to back): hi+lo 14,12,16 277 us, 15,12,15 244, 14,13,15 234,
 // 13,13,16 228, 15,13,14 233, 13,14,15 224; single bf16 14,13,15 163 us, 15,13,14 136, 14,12,16 137, 13,13,16 129, 15,12,15 133, 16,13,13 132.
+// Since G6 is formed once per workgroup in LDS (wgrad_body, form()) product 2's tiles are no longer the slowest.  Sweeps with the forming in LDS (the same
+// 42 ranges; tools/wgrad_time.py, 3 x 100 launches per plan, two processes per build alternated with the build before; profiles/wgrad_coop_forming_plans.txt):
+// hi+lo 13,14,15 215-219 us (before the change: 229-234), 14,13,15 208-211, 15,12,15 211-212, 14,14,14 208-212, 15,13,14 206-208 (before: 239-241) -- and
+// on a second box 13,14,15 203-205, 15,14,13 200-201, 14,15,13 198-202, 15,13,14 194-196; single bf16 13,13,16 124-128 us (before: 129-131), 14,12,16
+// 124-126, 15,12,15 123-126, 15,11,16 131-132, 14,13,15 121-122.  The plans STAY: 15,13,14 is worth 9 us of the kernel and 15-20 us of the captured step
+// (three alternated bench.py rounds, same file), but another plan is another summation order -- every gradient moves by up to 1.2e-06 of its tensor's
+// largest magnitude (two plans of one build, n = 5197), and 200 optimiser steps of the benchmark turn that into a different trajectory, where today a
+// build can be held to the one before it bit for bit.  (Plain bf16: 14,13,15 also has 15 as its most ranges; k_splits of dpn_sizes is 16 there.)
 static inline SplitPlan choose_plan(int64_t n_pad, int ns) {
     int64_t c = n_pad / 32 / 16;
     if (c < 1) c = 1;
