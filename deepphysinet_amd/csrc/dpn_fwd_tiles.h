@@ -298,7 +298,7 @@ DEV void pe6_frag_dot(Frag<NS>& f, const Args& a, const int ks, const int h, con
 }
 // backward: Z0 = g * pe + gJ_c * d pe / d xi_c for k-step ks (coordinate c = ks >> 2), build_pe3<BWD> of the ring kernels
 template <int NS, class Args>
-DEV void z0_frag(Frag<NS>& f, const Args& a, const int ks, const int h, const int64_t pc, const float g, const float gjc) {
+DEV void z0_frag(Frag<NS>& f, const Args& a, const int ks, const int h, const int64_t pc, const float g, const float gjc, float (&sc)[8]) {   // sc: (s, co) x 4, the table form's features
     const int c = ks >> 2;
     const float* src = (c == 0) ? a.x : (c == 1) ? a.y : a.t;
     const float d1 = (c == 0) ? a.geo.dx : (c == 1) ? a.geo.dy : a.geo.pred_t_span;
@@ -311,6 +311,7 @@ DEV void z0_frag(Frag<NS>& f, const Args& a, const int ks, const int h, const in
         ts_sincos<NS>(xi * fr, s, co);
         const float gf = gjc * fr;
         frag_set2<NS>(f, q, fmaf(g, s, gf * co), fmaf(g, co, -gf * s));
+        sc[2 * q] = s; sc[2 * q + 1] = co;
     }
 }
 // d pe3 / d xi_c for the 16 accumulator registers of gpe tile 2c + t (register pair rp = one angle: k-step 2T + (rp >> 2) of the coordinate PE)

@@ -91,4 +91,25 @@ DPN_HD int wgrad_coop_piece(int ns, int issue, int wave, int j) {
     return j - ns < xhi ? 4 * xlo + xhi * (wave - 4) + (j - ns) : -1;
 }
 
+
+// ------------------------------------------------------------------ dpn_wgrad_kernel, product 3 in the TABLE form of Z0 (dpn_point_common.h, OperandView)
+// The slot image of dw1 = T1^T Z0 is 32 X pieces (T1 hi, lo) and 24 Y pieces: plane s < 2 of pair p = 6 kk + ct holds half s (points e = 4 s .. 4 s + 3 of
+// a lane's eight) of the fp32 table's k-step kk of column tile ct, and after forming plane 0 = hi, plane 1 = lo of this net's Z0.  56 pieces, seven per
+// wave, no pad.  A wave fetches BOTH halves of the pairs it forms, and all its pairs are of ONE column tile -- one coordinate c = ct >> 1 (one gJ_c beside
+// g in its per-tile copy) and one frequency per lane: waves 0..3 both k-steps of column tile `wave`, waves 4..7 one k-step of column tile 4 or 5.  The
+// table pieces come first in the issue order (they are what forming waits for); waves 0..3 take three X pieces each, waves 4..7 five.
+// Slot j of 7 per wave -> 0 .. 31: X piece | 32 + 12 s + p: half s of pair p.
+DPN_HD int wgrad_z0_ct(int wave) { return wave < 4 ? wave : 4 + (wave & 1); }
+DPN_HD int wgrad_z0_pairs(int wave) { return wave < 4 ? 2 : 1; }
+DPN_HD int wgrad_z0_kk(int wave, int q) { return wave < 4 ? q : (wave - 4) >> 1; }             // k-step of the wave's q-th pair
+DPN_HD bool wgrad_z0_is_y(int wave, int j) { return j < 2 * wgrad_z0_pairs(wave); }
+DPN_HD int wgrad_z0_piece(int wave, int j) {
+    if (wgrad_z0_is_y(wave, j)) return 32 + 12 * (j & 1) + 6 * wgrad_z0_kk(wave, j >> 1) + wgrad_z0_ct(wave);
+    return wave < 4 ? 3 * wave + (j - 4) : 12 + 5 * (wave - 4) + (j - 2);
+}
+// Column jj of column tile ct is PE slot (k-step 2 ct + (jj >> 4), h = (jj >> 3) & 1, e = jj & 7): sine for even jj, cosine for odd, of the angle
+// xi_c fr with c = ct >> 1 and fr = freqs[z0_freq_index(ct, jj)].  The partner (cosine of a sine column, sine of a cosine column) is column jj ^ 1:
+// in the K-layout lane ^ 1, the neighbouring 16 bytes of the same 1-KB piece.
+DPN_HD int z0_freq_index(int ct, int jj) { return 16 * (ct & 1) + (jj >> 1); }
+
 }  // namespace dpn

@@ -396,6 +396,40 @@ DEV void store_tile_k(const KMat& m, int net, int64_t tile32, int ct, const Lane
     }
 }
 
+// Table form of Z0 (OperandView): the fp32 features (sin, cos of the four angles of a lane's half, k-steps 2ct and 2ct + 1) of the lane's point -> the
+// per-point table's K-layout, column tile ct.  Exact transposition: x = b0 + b1 + b2 with three bf16 parts (8 mantissa bits each, every remainder exact),
+// each part through the identity MFMAs, the parts summed in the fp32 accumulator largest first (every partial sum is a prefix of x's mantissa).
+DEV void store_table_k(const KMat& z0, const int64_t tile32, const int ct, const int lane, const u32x4& idA, const u32x4& idB, const float (&v0)[8],
+                       const float (&v1)[8]) {
+    u32x4 a0[3], a1[3];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        auto split = [&](const float x, const float y, u32x4 (&a)[3]) __attribute__((always_inline)) {
+            const u32 w0 = pack2(x, y);
+            const float rx = x - bf_lo(w0), ry = y - bf_hi(w0);
+            const u32 w1 = pack2(rx, ry);
+            a[0][p] = w0; a[1][p] = w1; a[2][p] = pack2(rx - bf_lo(w1), ry - bf_hi(w1));
+        };
+        split(v0[2 * p], v0[2 * p + 1], a0);
+        split(v1[2 * p], v1[2 * p + 1], a1);
+    }
+    f32x16 d = (f32x16)0.f;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        d = mfma(as_bf(a0[q]), as_bf(idA), d);
+        d = mfma(as_bf(a1[q]), as_bf(idB), d);
+    }
+    // d[r] = the lane's column at point drow32(r, lane >> 5): registers 8 kk + 4 s + (0..3) are half s of k-step kk.  Streaming stores as store_d_as_k's
+    // (the pe6 table goes out the same way and is served to the six nets from the memory-side cache).
+    typedef __attribute__((ext_vector_type(4))) float f32x4_t;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+            __builtin_nontemporal_store(f32x4_t{d[8 * kk + 4 * s], d[8 * kk + 4 * s + 1], d[8 * kk + 4 * s + 2], d[8 * kk + 4 * s + 3]},
+                                        reinterpret_cast<f32x4_t*>(kmat_ptr(z0, 0, 2, s, tile32, ct, lane, kk)));
+}
+
 // ------------------------------------------------------------------------------------------------ forward + Jacobian
 struct FwdArgs {
     const float *x, *y, *t, *coord_data, *freqs, *pe_in;

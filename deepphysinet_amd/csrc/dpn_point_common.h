@@ -68,21 +68,36 @@ DPN_HD int64_t saved_state_bytes(int64_t n_pad, int ns) { return (int64_t)kNets 
 
 struct OperandView {     // written by dpn_bwd_points
     KMat Z1;             // [6][NS] x 256   (round 5: Z is not an operand any more, dpn_finish_gside_kernel)
-    KMat Z0;             // [6][NS] x 192
+    KMat Z0;             // [6][NS] x 192   stored form; table form: planes 0 / 1 of net 0 hold the two 16-byte halves of the per-point fp32 pe3 table
     KMat PE6;            // [1][NS] x 192   per-POINT table of the data features (sin / cos of coord_data), written once by the net-0 workgroups
     float* gnet;         // [6][n_pad]      per-net cotangent of the normalised field, zero for padding points
+    float* gj;           // [6][3][n_pad]   table form: the coordinate cotangents gJ_c (g_scale included), zero for padding points; in net 1's Z0 space
+    unsigned* hdr;       // [0]: kZ0Stored | kZ0Table, [4 + i]: the 32 coordinate frequencies; in the slack behind gnet, outside every form's Z0
 };
+constexpr unsigned kZ0Stored = 0u, kZ0Table = 1u;
 // Round 5: G6 = g pe6 (the Y operand of S2 = M2^T G6) is no longer written per point AND NET: it is a per-point table times a per-net scalar, so
 // dpn_wgrad_kernel forms it from the table and the table -- 768 B per point in the hi+lo mode, shared by the six nets -- stays in the memory-side cache.
 // Stage 1 writes 2 560 -> 1 792 B per point and net.  The forming was in registers at first, on the fragment each wave had just read (seven VALU
 // instructions per element beside the MFMAs, the same elements on four waves); it is now done once per workgroup, in LDS, in place, by the wave that
 // fetched the piece (dpn_wgrad.hip, form()): bit-identical S2, same range plan, dpn_wgrad_kernel<2> alone 229-234 -> 215-219 us and 219.4 -> 203.4 us
 // in the captured step (rocprofv3), the step 1.157-1.166 -> 1.140-1.144 ms (five alternated rounds each on one box; profiles/wgrad_coop_forming_ab.txt).
-// (Round 5 built the same table form for Z0 = g pe3 + gJ_c d pe3 / d xi_c with IN-REGISTER forming -- the partner column of one pe3 table through a
-// DPP move -- and measured: stage 1 91 us instead of 130, but product 3's tile loop no longer fit 256 registers beside its then 128 accumulators and
-// two X planes, each reload of a spilled value waits for the LDS-DMA ring as well, and dpn_wgrad_kernel went 198 -> 337 us;
-// profiles/round5_operand_tables.txt.  Not measured again with the forming in LDS, which holds no fragments beside the accumulators: Z0 is still a
-// per-net operand, written by stage 1 and read once.)
+//
+// Z0 = g pe3 + gJ_c d pe3 / d xi_c has the same structure -- a per-point table (sin / cos of xi_c fr, no net) and four per-net scalars per point -- and
+// in the hi+lo mode on the raw-coordinate route (prec == 2, no pe_in, no second-derivative cotangent) it is not stored either.  TABLE FORM of the Z0 region, inside the bytes the stored form
+// occupies (operand_bytes and the C ABI are unchanged):
+//   table   fp32, 768 B per point, K-layout: the eight points a lane owns of one column in one k-step are 32 B = two 16-byte halves (points e = 0..3 |
+//           4..7 of drow32); half s sits where plane s (hi | lo) of NET 0 keeps its 1-KB piece of that (k-step, column tile) pair, so that the slot image
+//           in LDS is overwritten in place with hi and lo.  Column tile ct is written by the workgroups of net ct (six nets, six column tiles).
+//   gj      [net][c][n_pad] fp32 behind the table (net 1's space): lanes 32..63 of the weight-gradient kernel's per-tile g copy fetch gJ_c beside g.
+//   hdr     the form word and the frequencies (dpn_wgrad has no freqs argument).  EVERY stage-1 launch of every form writes it: one operand buffer may
+//           alternate between the routes.  Plain bf16, caller-encoded coordinates and the *_deriv kernels write kZ0Stored and Z0 as before.
+// The transposition to the K-layout is exact: a three-way bf16 split (8 + 8 + 8 mantissa bits) through the identity MFMAs of the bf16 planes, summed in
+// the fp32 accumulator.  Limits: normal values only (a bf16 part below 2^-126 may be flushed: features below ~2^-100 in magnitude that are not zero),
+// and -0.0 arrives as +0.0.  dpn_wgrad_kernel<2> forms Z0 from the table exactly as ts::z0_frag / build_pe3<BWD> did: gf = gJ_c fr,
+// z = fmaf(g, own, +-(gf partner)), hi = bf16(z), lo = bf16(z - hi): the same bits the stored form holds.
+// (Round 5 built a table form with IN-REGISTER forming -- the partner column through a DPP move -- and measured stage 1 91 us instead of 130 but the
+// weight-gradient kernel 198 -> 337 us: product 3's tile loop spilled; profiles/round5_operand_tables.txt.  The forming in LDS holds no fragments beside
+// the accumulators.)
 DEV OperandView operand_view(void* base, int64_t n_pad, int ns) {
     OperandView o;
     char* b = reinterpret_cast<char*>(base);
@@ -92,7 +107,15 @@ DEV OperandView operand_view(void* base, int64_t n_pad, int ns) {
     o.Z0 = KMat{b + m256, tiles32, 6};
     o.PE6 = KMat{b + m256 + m192, tiles32, 6};
     o.gnet = reinterpret_cast<float*>(b + m256 + m192 + t192);
+    o.gj = reinterpret_cast<float*>(b + m256 + t192);                                     // 72 B per point of net 1's 768
+    o.hdr = reinterpret_cast<unsigned*>(b + m256 + m192 + t192 + (int64_t)kNets * n_pad * 4 + 256);    // (the last tile's 64-lane g copy reads 128 B of the slack)
     return o;
+}
+// every stage-1 kernel, its first workgroup of net 0: the form word and the frequencies
+DEV void write_operand_header(const OperandView& o, const unsigned form, const float* freqs) {
+    if (blockIdx.x != 0 || blockIdx.y != 0 || threadIdx.x >= 32) return;
+    if (threadIdx.x == 0) o.hdr[0] = form;
+    o.hdr[4 + threadIdx.x] = __float_as_uint(freqs[threadIdx.x]);
 }
 static inline int64_t operand_bytes(int64_t n_pad, int ns) { return (int64_t)kNets * ns * n_pad * 512 + (int64_t)(kNets + 1) * ns * n_pad * 384 + (int64_t)kNets * n_pad * 4 + 1024; }
 

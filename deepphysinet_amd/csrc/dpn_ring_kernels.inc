@@ -311,6 +311,13 @@ __global__ __launch_bounds__(256, 1) void dpn_bwd_kernel(BwdArgs a) {
     const uint4 m1v = sv.m1[((int64_t)net * tiles32 + tile32) * 64 + L.lane];
     const u32 m1w[4] = {m1v.x, m1v.y, m1v.z, m1v.w};
     if (h == 0) ov.gnet[(int64_t)net * a.n_pad + tile32 * 32 + L.j] = g;
+    // Z0 in the table form (OperandView): the hi+lo mode on raw coordinates; the second-derivative cotangent (DPN_DERIV) keeps the stored form
+    const bool z0_table = NS == 2 && !DPN_DERIV && !a.pe_in;
+    write_operand_header(ov, z0_table ? kZ0Table : kZ0Stored, a.freqs);
+    if (z0_table && h == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) ov.gj[((int64_t)net * 3 + c) * a.n_pad + tile32 * 32 + L.j] = gj[c];
+    }
 
     Pipe<NS> pipe;
     __syncthreads();
@@ -344,8 +351,21 @@ __global__ __launch_bounds__(256, 1) void dpn_bwd_kernel(BwdArgs a) {
 #else
         else build_pe3<NS, true>(L, z0, g, gj);
 #endif
+        if (z0_table) {                           // column tile ct of the per-point fp32 table: the workgroups of net ct (features exactly as build_pe3 forms them)
 #pragma unroll
-        for (int ct = 0; ct < 6; ++ct) store_tile_k<NS, NS>(ov.Z0, net, tile32, ct, L, z0[2 * ct], z0[2 * ct + 1], false);
+            for (int ct = 0; ct < 6; ++ct) {
+                if (ct != net) continue;
+                float v[2][8];
+#pragma unroll
+                for (int k2 = 0; k2 < 2; ++k2)
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) sincos_t<NS>(L.xi[ct >> 1] * L.fr32[4 * ((2 * ct + k2) & 3) + p], v[k2][2 * p], v[k2][2 * p + 1]);
+                if constexpr (NS == 2) store_table_k(ov.Z0, tile32, ct, L.lane, L.idA, L.idB, v[0], v[1]);
+            }
+        } else {
+#pragma unroll
+            for (int ct = 0; ct < 6; ++ct) store_tile_k<NS, NS>(ov.Z0, net, tile32, ct, L, z0[2 * ct], z0[2 * ct + 1], false);
+        }
 #pragma unroll
         for (int T = 0; T < 8; ++T) {
             acc_init_vec(acc[T], lds_vec, kVecB1, h, T, g);

@@ -328,7 +328,10 @@ __global__ __launch_bounds__(256, 2) void dpn_fwd_tiles_kernel(FwdArgs a) {
 // Backward, stage 1 (per-point cotangent streams -> operands of the weight-gradient reductions), tile-split form.  Same arithmetic and same operand
 // layout as dpn_bwd_kernel (bit-identical Z0, Z1, pe6 table, gnet); decomposition as dpn_fwd_tiles_kernel: 64 points per workgroup, wave w owns tiles
 // 2w, 2w+1 of both column tiles, the cotangent fragments are shared through LDS, the weights come L2 -> VGPR.
-//   Z0 = g pe + sum_c gJ_c d pe / d xi_c                      -> X, K-layout rows (operand of dw1 = T1^T Z0)
+//   Z0 = g pe + sum_c gJ_c d pe / d xi_c                      -> X; K-layout rows (operand of dw1 = T1^T Z0) in plain bf16 and in the second-derivative
+//                                                                kernel only: in the hi+lo mode the rows are NOT written, dpn_wgrad_kernel forms them from
+//                                                                the per-point fp32 pe3 table (column tile ct by the workgroups of net ct), gJ and the header
+//                                                                that this kernel writes instead (OperandView: 313 instead of 454 MB per launch at 37 265 points)
 //   Z1 = m1 (.) (w1 Z0 + g b1)                                -> K-layout rows (operand of S1 = M2^T Z1)
 //   net 0 only: the per-point table pe6                       -> K-layout rows (from which dpn_wgrad_kernel forms G6 = g pe6 of every net: OperandView)
 // Round 5: Z = w2 Z1 + Wd G6 + g (b2 + bd + e) is no longer formed.  It existed only as the Y operand of G = M2^T Z, and being linear in
@@ -379,9 +382,15 @@ __global__ __launch_bounds__(256, 3) void dpn_bwd_tiles_kernel(BwdArgs a) {
     u32 m1w[2];
 #pragma unroll
     for (int p = 0; p < 2; ++p) m1w[p] = reinterpret_cast<const u32*>(sv.m1 + ((int64_t)net * tiles32 + tile0 + p) * 64 + lane)[w];
+    // Z0 in the table form (OperandView): the hi+lo mode (this kernel never has caller-encoded coordinates); the second-derivative cotangent keeps the stored form
+    constexpr bool kTab = NS == 2 && !DPN_DERIV;
+    write_operand_header(ov, kTab ? kZ0Table : kZ0Stored, a.freqs);
     if (w == 0) {                                             // lane (j, h): point j of column tile h
         const int64_t pt = (tile0 + h) * 32 + j;
         ov.gnet[(int64_t)net * a.n_pad + pt] = (pt < a.n) ? gsc * a.g_out[pt * 6 + net] : 0.f;
+    } else if (kTab) {                                    // waves 1..3: the coordinate cotangent gJ_c, c = w - 1, as the Z0 units below read it
+        const int64_t pt = (tile0 + h) * 32 + j;
+        ov.gj[((int64_t)net * 3 + (w - 1)) * a.n_pad + pt] = (a.g_jxi && pt < a.n) ? gsc * a.g_jxi[(pt * 6 + net) * 3 + (w - 1)] : 0.f;
     }
     // ---------------- Z0 -> X (k-steps 0..11) and K-layout rows: wave w builds the (column tile of Z0, point tile) units 3w .. 3w+2.  The rows go
     // out at once (not deferred into the multiply loop as in the forward kernel): nothing of them stays live, the kernel fits 168 registers and
@@ -400,11 +409,17 @@ __global__ __launch_bounds__(256, 3) void dpn_bwd_tiles_kernel(BwdArgs a) {
         ts::z0_frag_derivs<NS>(f0, a, 2 * ct, h, pcp, gp, gjc, ghc);
         ts::z0_frag_derivs<NS>(f1, a, 2 * ct + 1, h, pcp, gp, gjc, ghc);
 #else
-        ts::z0_frag<NS>(f0, a, 2 * ct, h, pcp, gp, gjc);
-        ts::z0_frag<NS>(f1, a, 2 * ct + 1, h, pcp, gp, gjc);
+        float sc0[8], sc1[8];
+        ts::z0_frag<NS>(f0, a, 2 * ct, h, pcp, gp, gjc, sc0);
+        ts::z0_frag<NS>(f1, a, 2 * ct + 1, h, pcp, gp, gjc, sc1);
 #endif
         ts::x_store<NS>(xl, 2 * ct, p, f0);
         ts::x_store<NS>(xl, 2 * ct + 1, p, f1);
+#if !DPN_DERIV
+        if constexpr (NS == 2) {                              // table form: the Z0 rows are not written; column tile ct of the fp32 table by the workgroups of net ct
+            if (ct == net) store_table_k(ov.Z0, tile0 + p, ct, lane, I.a, I.b, sc0, sc1);
+        } else
+#endif
         ts::save_tile_k<NS, NS>(ov.Z0, net, tile0 + p, ct, lane, I, false, f0, f1);
     }
     TS_STAMP(1);

@@ -339,8 +339,10 @@ constexpr int wgrad_lds_bytes() {
     return m;
 }
 
-template <int NS, int PROD>
+// TAB: product 3 with Z0 in the table form (OperandView): the Y image is the per-point fp32 pe3 table and Z0 is formed from it in LDS, as product 2 forms G6
+template <int NS, int PROD, bool TAB = false>
 DEV void wgrad_body(const WgradArgs& a, char* lds, const int split, const int net) {
+    static_assert(!TAB || (NS == 2 && PROD == 3), "the table form of Z0: hi+lo mode, product 3");
     using S = WgradShape<NS, PROD>;
     constexpr int nct = S::nct, nsx = S::nsx, kSlot = S::kSlot, RING = S::RING, PER_TILE = S::PER_TILE, ncol = nct * 32;
     const int64_t tiles = a.n_pad / 32;
@@ -368,8 +370,18 @@ DEV void wgrad_body(const WgradArgs& a, char* lds, const int split, const int ne
     const char* xb = (PROD == 3) ? sv.T1.base : sv.M2.base;                                      // 8 column tiles
     static_assert(PROD >= 1 && PROD <= 3, "products: 1 = M2^T Z1, 2 = M2^T G6, 3 = T1^T Z0");
     const char* yb = (PROD == 1) ? ov.Z1.base : (PROD == 2) ? ov.PE6.base : ov.Z0.base;   // nct column tiles; product 2: the per-point TABLE (no net index)
-    const int64_t ynet = (PROD == 2) ? 0 : net;
+    const int64_t ynet = (PROD == 2 || TAB) ? 0 : net;
     const float* gnet = ov.gnet + (int64_t)net * a.n_pad;
+    // the per-tile copy of g is a 64-lane, 4-byte DMA of which the tile's 32 points use lanes 0..31; in the table form lanes 32..63 fetch gJ_c, c the
+    // coordinate of this wave's column tile (dpn_layout.h): g at bytes 0..127 of the wave's copy, gJ_c at 128..255
+    const char* gsrc = reinterpret_cast<const char*>(gnet) + lane * 4;
+    float fr = 0.f;                                                     // table form: the frequency of this lane's column (both of the wave's pairs)
+    if constexpr (TAB) {
+        const int ct = wgrad_z0_ct(wave);
+        if (lane >= 32) gsrc = reinterpret_cast<const char*>(ov.gj + ((int64_t)net * 3 + (ct >> 1)) * a.n_pad) + (lane - 32) * 4;
+        fr = __uint_as_float(ov.hdr[4 + z0_freq_index(ct, lane & 31)]);
+        asm volatile("" : "+v"(fr));                                    // the load is waited for HERE, in front of the first DMA (not by a vmcnt(0) in the tile loop)
+    }
 
     // every wave issues PER_TILE DMA instructions per tile: piece q = wave + 8*j of the (X planes, Y planes) image, + its own g copy.
     // (Letting only the four waves with wm == tile & 1 issue a tile -- twice the pieces each, in the shadow of their SIMD partners'
@@ -382,15 +394,19 @@ DEV void wgrad_body(const WgradArgs& a, char* lds, const int split, const int ne
     // workgroup (form() below) instead of by each of the four wm waves in registers.  A wave fetches what it forms -- the NS planes of column pair
     // p = wave, and of p = 8 + wave on waves 0..3 (a pair = one k-step of one column tile, 1 KB per plane) -- so the counted wait that says its own
     // pieces have landed is all that forming needs, and the tile's one barrier then covers "landed AND formed".  Waves 4..7 take X pieces instead.
-    constexpr bool kCoop = PROD == 2;
-    static_assert(!kCoop || (2 * nct == 12 && nsx == 1 && S::kIssue >= 2 * NS), "product 2: 12 column pairs over 8 waves");
+    // Product 3 in the table form (TAB) does the same with the fp32 pe3 table: the two PLANES of a pair are the two halves of its fp32 values, and forming
+    // overwrites them with hi and lo of Z0 = g pe3 + gJ_c d pe3 / d xi_c (form_z0() below; the deal is wgrad_z0_piece of dpn_layout.h).
+    constexpr bool kCoop = PROD == 2 || TAB;
+    static_assert(PROD != 2 || (2 * nct == 12 && nsx == 1 && S::kIssue >= 2 * NS), "product 2: 12 column pairs over 8 waves");
+    static_assert(!TAB || (S::kIssue == 7 && S::kPad == 0 && nsx == 2), "product 3, table form: 56 pieces, seven per wave");
     const bool two_pairs = wave < 4;                                    // wave-uniform
     const char* pbase[S::kIssue];
     int pstride[S::kIssue], pdst[S::kIssue];
 #pragma unroll
     for (int j = 0; j < S::kIssue; ++j) {
         int q = wave + 8 * j;                                           // the piece of the linear slot image: X planes, then Y planes ...
-        if constexpr (kCoop) q = wgrad_coop_piece(NS, S::kIssue, wave, j);     // ... or the deal of dpn_layout.h (-1: the pad)
+        if constexpr (TAB) q = wgrad_z0_piece(wave, j);
+        else if constexpr (kCoop) q = wgrad_coop_piece(NS, S::kIssue, wave, j);     // ... or the deal of dpn_layout.h (-1: the pad)
         if (S::kPad && (kCoop ? q < 0 : q >= S::kPieces)) {             // a cache hit after the first time
             pbase[j] = xb + ((int64_t)net * nsx * tiles + (t0 < tiles ? t0 : 0)) * 16384; pstride[j] = 0; pdst[j] = S::kPadOff;
         } else if (q < nsx * 16) {
@@ -406,10 +422,11 @@ DEV void wgrad_body(const WgradArgs& a, char* lds, const int split, const int ne
         for (int j = 0; j < S::kIssue; ++j) {
             // read-once operand streams carry the non-temporal hint; the per-point pe6 table of product 2 is read by six nets' workgroups and should
             // stay in the memory-side cache (PMC, round 5: with the hint on it the table came from HBM six times: 1 052 MB against 890 algorithmic)
-            if (kCoop && wgrad_coop_is_y(NS, wave, j)) dma16(pbase[j] + tile * pstride[j] + lane * 16, sl + pdst[j]);
+            // (the pe3 table of product 3's table form likewise)
+            if (kCoop && (TAB ? wgrad_z0_is_y(wave, j) : wgrad_coop_is_y(NS, wave, j))) dma16(pbase[j] + tile * pstride[j] + lane * 16, sl + pdst[j]);
             else dma16_nt(pbase[j] + tile * pstride[j] + lane * 16, sl + pdst[j]);
         }
-        dma4(reinterpret_cast<const char*>(gnet + tile * 32) + lane * 4, sl + S::kGOff + wave * 256);
+        dma4(gsrc + tile * 128, sl + S::kGOff + wave * 256);
     };
 
     f32x16 acc[MT][NT];
@@ -446,7 +463,7 @@ DEV void wgrad_body(const WgradArgs& a, char* lds, const int split, const int ne
             asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(base), "i"(off) : "memory");
         };
         auto issue_reads = [&](const int kk, const int b) __attribute__((always_inline)) {
-            if constexpr (!kCoop) {                                 // (product 2 needs g in form() only)
+            if constexpr (PROD != 2) {                              // (product 2 needs g in form() only)
                 rd128o(gqa[b][0], baseG, 64 * kk);
                 rd128o(gqa[b][1], baseG, 64 * kk + 32);
             }
@@ -459,7 +476,7 @@ DEV void wgrad_body(const WgradArgs& a, char* lds, const int split, const int ne
 #pragma unroll
                 for (int n2 = 0; n2 < NT; ++n2) rd128o(fba[b][s2][n2], baseB, s2 * S::kYPlane + (kk * nct + n2) * 1024);
         };
-        constexpr int kReads = (kCoop ? 0 : 2) + MT * nsx + NT * NS;   // LDS reads per k-step
+        constexpr int kReads = (PROD == 2 ? 0 : 2) + MT * nsx + NT * NS;   // LDS reads per k-step
         if constexpr (NS == 1) { issue_reads(0, 0); issue_reads(1, 1); }
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
@@ -473,7 +490,7 @@ DEV void wgrad_body(const WgradArgs& a, char* lds, const int split, const int ne
             // second k-step's reads still behind, the first k-step is complete at lgkmcnt(kReads))
             if (NS == 1 && kk == 0) asm volatile("s_waitcnt lgkmcnt(%0)" :: "n"(kReads) : "memory");
             else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if constexpr (kCoop) gq0 = gq1 = (u32x4)0u;             // (gp below is dead code for product 2)
+            if constexpr (PROD == 2) gq0 = gq1 = (u32x4)0u;         // (gp below is dead code for product 2)
             else asm volatile("" : "+v"(gq0), "+v"(gq1));
             asm volatile("" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fb[0][0]), "+v"(fb[0][1]));
             if constexpr (MT == 4) asm volatile("" : "+v"(fa[0][2]), "+v"(fa[0][3]));
@@ -565,6 +582,50 @@ DEV void wgrad_body(const WgradArgs& a, char* lds, const int split, const int ne
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     };
 
+    // Product 3, table form: this wave's pairs of the slot's fp32 pe3 table image become hi (plane 0) and lo (plane 1) of this net's Z0, in place.  A lane
+    // owns eight points of one column: its 32 bytes are own[e], the neighbouring lane's (lane ^ 1, the same 1-KB piece: sine <-> cosine of the same angle)
+    // partner[e]; with g and gJ_c from the wave's per-tile copy,  gf = gJ_c fr,  z = fmaf(g, own, +-(gf partner))  -- + for a sine column, - for a cosine
+    // column -- in ts::z0_frag's operation order, then hi = bf16(z), lo = bf16(z - hi) as frag_set2<2>: the bits the stored form holds.  All of a pair's
+    // reads (the wave's own pieces: vmcnt) are back before its writes go out, and the writes are retired before the caller's barrier.
+    auto form_z0 = [&](const int slot_) __attribute__((always_inline)) {
+        const unsigned buf = lds_base + slot_ * kSlot;
+        const int ct = wgrad_z0_ct(wave);
+        const unsigned baseG = buf + S::kGOff + wave * 256 + h * 16, baseY = buf + S::kX + ct * 1024;
+        const u32 sgn = (lane & 1) ? 0x80000000u : 0u;
+        auto pair = [&](const int kk) __attribute__((always_inline)) {
+            const unsigned ay = baseY + kk * (nct * 1024) + lane * 16, ap = baseY + kk * (nct * 1024) + (lane ^ 1) * 16, ag = baseG + kk * 64;
+            u32x4 gq[2], jq[2], own[2], par[2];
+            rd128(gq[0], ag);
+            asm volatile("ds_read_b128 %0, %1 offset:32" : "=v"(gq[1]) : "v"(ag) : "memory");
+            asm volatile("ds_read_b128 %0, %1 offset:128" : "=v"(jq[0]) : "v"(ag) : "memory");
+            asm volatile("ds_read_b128 %0, %1 offset:160" : "=v"(jq[1]) : "v"(ag) : "memory");
+            rd128(own[0], ay);
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(own[1]) : "v"(ay), "i"(S::kYPlane) : "memory");
+            rd128(par[0], ap);
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(par[1]) : "v"(ap), "i"(S::kYPlane) : "memory");
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            asm volatile("" : "+v"(gq[0]), "+v"(gq[1]), "+v"(jq[0]), "+v"(jq[1]), "+v"(own[0]), "+v"(own[1]), "+v"(par[0]), "+v"(par[1]));
+            float z[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float gf = __uint_as_float(jq[e >> 2][e & 3]) * fr;
+                const float t = __uint_as_float(__float_as_uint(gf * __uint_as_float(par[e >> 2][e & 3])) ^ sgn);
+                z[e] = fmaf(__uint_as_float(gq[e >> 2][e & 3]), __uint_as_float(own[e >> 2][e & 3]), t);
+            }
+            u32x4 hi, lo;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                hi[p] = pack2(z[2 * p], z[2 * p + 1]);
+                lo[p] = pack2(z[2 * p] - bf_lo(hi[p]), z[2 * p + 1] - bf_hi(hi[p]));
+            }
+            asm volatile("ds_write_b128 %0, %1" :: "v"(ay), "v"(hi) : "memory");
+            asm volatile("ds_write_b128 %0, %1 offset:%2" :: "v"(ay), "v"(lo), "i"(S::kYPlane) : "memory");
+        };
+        pair(wgrad_z0_kk(wave, 0));
+        if (two_pairs) pair(wgrad_z0_kk(wave, 1));
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    };
+
     // prologue: RING-1 tiles in flight (out-of-range tiles re-read the last valid one; their data is never used)
     const int64_t tl = t1 > t0 ? t1 - 1 : t0;
 #pragma unroll
@@ -576,7 +637,8 @@ DEV void wgrad_body(const WgradArgs& a, char* lds, const int split, const int ne
     for (int64_t tile = t0; tile < t1; ++tile) {
         DPN_WG_CLOCK(c0);
         wait_vmcnt<(RING - 2) * PER_TILE>();                             // this wave's pieces of `tile` have landed
-        if constexpr (kCoop) form(slot);                                 // (nobody reads this slot before the barrier, nobody else writes these bytes)
+        if constexpr (TAB) form_z0(slot);
+        else if constexpr (kCoop) form(slot);                            // (nobody reads this slot before the barrier, nobody else writes these bytes)
         DPN_WG_CLOCK(c1);
         __builtin_amdgcn_s_barrier();                                    // ... and everybody else's [and formed]; and compute(tile-1) is finished everywhere
         DPN_WG_CLOCK(c2);
@@ -649,7 +711,15 @@ __global__ __launch_bounds__(512, 2) void dpn_wgrad_kernel(WgradArgs a) {
     while (prod < 3 && split >= a.splits[prod]) { split -= a.splits[prod]; ++prod; }
     if (prod == 1) wgrad_body<NS, 1>(a, lds, split, net);
     else if (prod == 2) wgrad_body<NS, 2>(a, lds, split, net);
-    else wgrad_body<NS, 3>(a, lds, split, net);
+    else {
+        // product 3 has two bodies: Z0 stored per point and net (plain bf16, caller-encoded coordinates, the second-derivative kernels) or formed from the
+        // per-point table (OperandView); the stage-1 launch that filled the operand buffer said which, in the buffer's header -- workgroup-uniform
+        if constexpr (NS == 2) {
+            const unsigned form = __builtin_amdgcn_readfirstlane(operand_view(a.operands, a.n_pad, NS).hdr[0]);
+            if (form == kZ0Table) { wgrad_body<NS, 3, true>(a, lds, split, net); return; }
+        }
+        wgrad_body<NS, 3>(a, lds, split, net);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ backward, stage 3
