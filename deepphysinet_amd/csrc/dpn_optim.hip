@@ -2,7 +2,8 @@
 //
 // Kernel inventory
 //   dpn_gradnorm_kernel / dpn_gradnorm_reduce_kernel   one fp64 partial per 2048-element chunk, added in a fixed order
-//   dpn_adam_kernel                                    the clipped update; the AdamTableFlatEma instantiation also moves the weight EMA
+//   dpn_adam_kernel                                    the clipped update; the AdamTableFlatEma instantiation also moves the weight EMA, the
+//                                                      AdamTableFlatGroups* ones read their hyper-parameters from their tensor's group row
 //   dpn_ema_swap_kernel                                exchanges the parameters with their EMA shadow
 // No kernel in this file uses atomics: every reduction is fixed-order, the whole step is bitwise reproducible.
 #include "dpn_device.h"
@@ -21,6 +22,7 @@ struct AdamTable {
     int numel[kAdamMaxTensors];
     int n;
     static constexpr bool ema = false;
+    static constexpr bool groups = false;
 };
 // Optimiser state kept by the caller as ONE flat buffer per moment, tensor i at offset chunk_start[i] * kAdamChunk (each tensor padded to
 // whole chunks): no per-tensor state pointers, so 160 tensors fit in the kernel arguments and a PhysicsNet is one launch per pass.
@@ -34,6 +36,7 @@ struct AdamTableFlat {
     float* v_flat;
     int n;
     static constexpr bool ema = false;
+    static constexpr bool groups = false;
 };
 static_assert(sizeof(AdamTableFlat) + 64 <= 4096, "kernel arguments are limited to 4 KB");
 // AdamTableFlat plus an exponential moving average of the parameters (the shadow `s_flat`, laid out like the moments), updated by the thread
@@ -51,8 +54,43 @@ struct AdamTableFlatEma {
     int n;
     int ema_warmup;
     static constexpr bool ema = true;
+    static constexpr bool groups = false;
 };
 static_assert(sizeof(AdamTableFlatEma) + 64 <= 4096, "kernel arguments are limited to 4 KB");
+// AdamTableFlat / AdamTableFlatEma plus a parameter group per tensor (fine-tuning: a learning rate, betas, eps and weight decay per group).  How
+// the group ids fit next to the by-value scalars of dpn_adam_kernel: sixteen groups are four bits, so the ids ride as NIBBLES, two tensors per
+// byte (80 bytes, not 160) -- dpn_adam_kernel keeps its argument list for every table and `numel` its 31 bits, no tensor size is refused that the
+// other forms take.  Types of their own once more: the four instantiations without groups keep their code.
+constexpr int kAdamMaxGroups = 16;
+struct AdamTableFlatGroups {
+    float* p[kAdamFlatMaxTensors];
+    const float* g[kAdamFlatMaxTensors];
+    int chunk_start[kAdamFlatMaxTensors + 1];
+    int numel[kAdamFlatMaxTensors];
+    float* m_flat;
+    float* v_flat;
+    int n;
+    uint8_t group4[kAdamFlatMaxTensors / 2];     // tensor i: (group4[i >> 1] >> 4 (i & 1)) & 15
+    static constexpr bool ema = false;
+    static constexpr bool groups = true;
+};
+static_assert(sizeof(AdamTableFlatGroups) + 64 <= 4096, "kernel arguments are limited to 4 KB");
+struct AdamTableFlatGroupsEma {
+    float* p[kAdamFlatMaxTensors];
+    const float* g[kAdamFlatMaxTensors];
+    int chunk_start[kAdamFlatMaxTensors + 1];
+    int numel[kAdamFlatMaxTensors];
+    float* m_flat;
+    float* v_flat;
+    float* s_flat;
+    const int* ema_base;
+    int n;
+    int ema_warmup;
+    uint8_t group4[kAdamFlatMaxTensors / 2];
+    static constexpr bool ema = true;
+    static constexpr bool groups = true;
+};
+static_assert(sizeof(AdamTableFlatGroupsEma) + 64 <= 4096, "kernel arguments are limited to 4 KB");
 DEV float* table_m(const AdamTable& t, int ti) { return t.m[ti]; }
 DEV float* table_v(const AdamTable& t, int ti) { return t.v[ti]; }
 DEV float* table_m(const AdamTableFlat& t, int ti) { return t.m_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
@@ -60,6 +98,13 @@ DEV float* table_v(const AdamTableFlat& t, int ti) { return t.v_flat + (int64_t)
 DEV float* table_m(const AdamTableFlatEma& t, int ti) { return t.m_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
 DEV float* table_v(const AdamTableFlatEma& t, int ti) { return t.v_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
 DEV float* table_s(const AdamTableFlatEma& t, int ti) { return t.s_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+DEV float* table_m(const AdamTableFlatGroups& t, int ti) { return t.m_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+DEV float* table_v(const AdamTableFlatGroups& t, int ti) { return t.v_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+DEV float* table_m(const AdamTableFlatGroupsEma& t, int ti) { return t.m_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+DEV float* table_v(const AdamTableFlatGroupsEma& t, int ti) { return t.v_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+DEV float* table_s(const AdamTableFlatGroupsEma& t, int ti) { return t.s_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+template <class Table>
+DEV int table_group(const Table& t, int ti) { return (t.group4[ti >> 1] >> ((ti & 1) * 4)) & 15; }
 template <class Table>
 DEV int adam_find(const Table& t, int blk) {
     int lo = 0, hi = t.n - 1;
@@ -110,8 +155,14 @@ __global__ __launch_bounds__(256) void dpn_adam_kernel(Table t, const double* su
     // hyper (optional, device): [lr, beta1, beta2, eps, weight_decay, max_norm, grad_scale] read at run time, so that a step captured in
     // a hipGraph follows a learning-rate schedule (a by-value lr is frozen into the graph); grad_scale multiplies every gradient
     // before the norm and the update (1 / world_size after a SUM all-reduce).  Table::ema: hyper[7] is the EMA decay, hyper is not null
+    // Table::groups: hyper is float[n_groups][8], not null.  This block's tensor gives the group whose row holds lr, the betas, eps and the weight
+    // decay -- step_size and the bias corrections below are formed from them, per block; max_norm, grad_scale and the EMA decay are row 0's (the
+    // clip is global).  From there on the arithmetic is the one of every other table
     float gscale = 1.f;
-    if (hyper) { lr = hyper[0]; b1 = hyper[1]; b2 = hyper[2]; eps = hyper[3]; wd = hyper[4]; max_norm = hyper[5]; gscale = hyper[6]; }
+    if constexpr (Table::groups) {
+        const float* row = hyper + 8 * table_group(t, adam_find(t, blockIdx.x));
+        lr = row[0]; b1 = row[1]; b2 = row[2]; eps = row[3]; wd = row[4]; max_norm = hyper[5]; gscale = hyper[6];
+    } else if (hyper) { lr = hyper[0]; b1 = hyper[1]; b2 = hyper[2]; eps = hyper[3]; wd = hyper[4]; max_norm = hyper[5]; gscale = hyper[6]; }
     const float total = (float)sqrt(*sumsq) * gscale;
     if (out_norm && blockIdx.x == 0 && threadIdx.x == 0) *out_norm = total;
     const float coef = fminf(max_norm / (total + 1e-6f), 1.0f) * gscale;    // clip_grad_norm_'s clamp(max_norm / (norm + 1e-6), max=1)
@@ -307,6 +358,72 @@ int dpn_clip_adam_flat_ema(int n_tensors, float* const* params, const float* con
     if (!hyper_dev || !ema_flat) return -1;
     return clip_adam_flat_impl<AdamTableFlatEma>(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, 0.f, 0.f,
                                                  0.f, 0.f, 0.f, 0.f, out_norm_dev, hyper_dev, stream, ema_flat, ema_base_dev, ema_warmup);
+}
+
+extern "C++" template <class Table>
+static int clip_adam_flat_groups_impl(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
+                                      float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const uint8_t* group_of, int n_groups,
+                                      const float* hyper_dev, float* out_norm_dev, float* ema_flat, const int* ema_base_dev, int ema_warmup,
+                                      void* stream) {
+    if (n_tensors <= 0 || !params || !grads || !numel || !exp_avg_flat || !exp_avg_sq_flat || !scratch_dev || !step_dev) return -1;
+    if (!group_of || !hyper_dev || n_groups < 1 || n_groups > kAdamMaxGroups) return -1;
+    // every size and every group is checked before the first launch: a refusal bumps no step counter and writes no partial
+    for (int i = 0; i < n_tensors; ++i) if (numel[i] <= 0 || numel[i] > 0x7fffffff || group_of[i] >= n_groups) return -1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    double* sumsq = scratch_dev;
+    double* partial = scratch_dev + 1;
+    for (int pass = 0; pass < 2; ++pass) {
+        int base_chunk = 0;
+        for (int t0 = 0; t0 < n_tensors; t0 += kAdamFlatMaxTensors) {
+            const int n = (n_tensors - t0 < kAdamFlatMaxTensors) ? n_tensors - t0 : kAdamFlatMaxTensors;
+            if (pass == 0) {
+                // the norm is global, over every group: the launches of dpn_clip_adam_flat_dev, the same instantiation
+                AdamTableFlat t;
+                t.n = n; t.m_flat = nullptr; t.v_flat = nullptr;
+                int chunks = 0;
+                for (int i = 0; i < n; ++i) {
+                    t.p[i] = params[t0 + i]; t.g[i] = grads[t0 + i];
+                    t.numel[i] = (int)numel[t0 + i];
+                    t.chunk_start[i] = chunks;
+                    chunks += (t.numel[i] + kAdamChunk - 1) / kAdamChunk;
+                }
+                t.chunk_start[n] = chunks;
+                hipLaunchKernelGGL(dpn_gradnorm_kernel<AdamTableFlat>, dim3(chunks), dim3(256), 0, s, t, partial + base_chunk, step_dev, t0 == 0 ? 1 : 0);
+                base_chunk += chunks;
+                continue;
+            }
+            Table t;
+            t.n = n;
+            t.m_flat = exp_avg_flat + (int64_t)base_chunk * kAdamChunk;
+            t.v_flat = exp_avg_sq_flat + (int64_t)base_chunk * kAdamChunk;
+            if constexpr (Table::ema) { t.s_flat = ema_flat + (int64_t)base_chunk * kAdamChunk; t.ema_base = ema_base_dev; t.ema_warmup = ema_warmup; }
+            for (int i = 0; i < kAdamFlatMaxTensors / 2; ++i) t.group4[i] = 0;
+            int chunks = 0;
+            for (int i = 0; i < n; ++i) {
+                t.p[i] = params[t0 + i]; t.g[i] = grads[t0 + i];
+                t.numel[i] = (int)numel[t0 + i];
+                t.chunk_start[i] = chunks;
+                chunks += (t.numel[i] + kAdamChunk - 1) / kAdamChunk;
+                t.group4[i >> 1] |= (uint8_t)(group_of[t0 + i] << ((i & 1) * 4));      // this table's tensors start at t0 in the caller's list
+            }
+            t.chunk_start[n] = chunks;
+            hipLaunchKernelGGL(dpn_adam_kernel<Table>, dim3(chunks), dim3(256), 0, s, t, (const double*)sumsq, (const int*)step_dev, 0.f, 0.f, 0.f, 0.f,
+                               0.f, 0.f, out_norm_dev, hyper_dev);
+            base_chunk += chunks;
+        }
+        if (pass == 0) hipLaunchKernelGGL(dpn_gradnorm_reduce_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, base_chunk, sumsq);
+    }
+    return ck(hipGetLastError());
+}
+
+int dpn_clip_adam_flat_groups(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
+                              float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const uint8_t* group_of, int n_groups,
+                              const float* hyper_dev, float* out_norm_dev, float* ema_flat, const int* ema_base_dev, int ema_warmup, void* stream) {
+    if (ema_flat)
+        return clip_adam_flat_groups_impl<AdamTableFlatGroupsEma>(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev,
+                                                                  group_of, n_groups, hyper_dev, out_norm_dev, ema_flat, ema_base_dev, ema_warmup, stream);
+    return clip_adam_flat_groups_impl<AdamTableFlatGroups>(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev,
+                                                           group_of, n_groups, hyper_dev, out_norm_dev, nullptr, nullptr, 0, stream);
 }
 
 int dpn_ema_swap(int n_tensors, float* const* params, const int64_t* numel, float* ema_flat, void* stream) {

@@ -168,6 +168,8 @@ class GradientAllReduce:
             return
         self._check_layout()
         a, b = self.opt.bucket_bounds[i][0], self.opt.bucket_bounds[(i + 1 if end is None else end) - 1][1]
+        if a == b:                                   # an empty range (the buckets of frozen parameters): nothing to communicate, on any rank
+            return
         self.last_queued = (i, i + 1 if end is None else end)
         w = _all_reduce_mean(self.opt.flat_gradients()[a:b], dist.get_world_size(self.group), self.group, async_op)
         if w is not None and async_op:
@@ -200,7 +202,7 @@ class GradientAllReduce:
             self.wait()
             return
         world = dist.get_world_size(self.group)
-        params = list(params)
+        params = [p for p in params if p.requires_grad]      # frozen parameters are never communicated
         # generic path: every rank flattens the same parameter list (None gradients count as zeros, so the sizes agree)
         grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in params]
         buckets, cur, size = [], [], 0

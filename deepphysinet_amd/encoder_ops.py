@@ -479,7 +479,6 @@ class _HeadsFn(torch.autograd.Function):
         Lt = m3.shape[1]
         lib = L.load()
         gh, ge = _c(g_heads), _c(g_evec)
-        d_meta = torch.empty(m3.shape, dtype=torch.float32, device=dev)
         offs, off = [], 0
         for w in hw:
             offs.append(off)
@@ -487,12 +486,17 @@ class _HeadsFn(torch.autograd.Function):
         # the 36 parameter gradients (12 head weights, 12 head biases, 6 fore_h_fc weights, 6 fore_h_fc biases) go to the parameters' own
         # gradient tensors (slots of the optimiser's flat gradient buffer when one is registered, grad_arena)
         hb, fw, fb = ctx.params
-        shapes = [(w.shape[0], 256) for w in hw] + [(w.shape[0],) for w in hw] + [(256, 192)] * 6 + [(256,)] * 6
-        dest = [new_grad(t, shp) for t, shp in zip(list(hw) + list(hb) + list(fw) + list(fb), shapes)]
+        dest, want, want_meta = _HeadsFn._destinations(ctx, hw, hb, fw, fb)
+        if not want_meta:                                        # the encoder is frozen: no g_meta problems, no dpn_sum_parts
+            problems = _HeadsFn._wgrad_problems(hw, offs, gh, ge, m3, pe2, dest, want, 1, 1)
+            if problems:
+                _launch(problems)
+            return (None, None, *[d if w_ else None for d, w_ in zip(dest, want)])
         # d_meta[tok][c] = sum_k sum_j W_k[j][tok] g[c][off_k + j]: a 12-term problem would walk 24 k-tiles in sequence, so NP = 6 two-term
         # problems run side by side and dpn_sum_parts joins them (with the 12 weight gradients and the 6 outer products exactly the 24
         # problems a launch takes).  Same box, 300-step runs, three times each: NP = 2 1.614 ms per step, 3 1.591, 4 1.614 (rounds 1-3), 6 1.580
         NP = 6
+        d_meta = torch.empty(m3.shape, dtype=torch.float32, device=dev)
         parts = torch.empty((NP, 256, 256), dtype=torch.float32, device=dev)
         n_tail = (Lt - 256) * 256                                # tokens >= 256 feed no VariableNet: their gradient rows are zero
         problems = []
@@ -503,18 +507,52 @@ class _HeadsFn(torch.autograd.Function):
             for i, k in enumerate(grp):
                 q0.B[i] = gh.data_ptr() + offs[k] * 4
             problems.append(q0)
-        for k, w in enumerate(hw):                               # dW_k[j][tok] = sum_c g[c][off + j] meta[tok][c] ; db_k[j] = sum_c g[c][off + j]
-            n_k = w.shape[0]
-            q = _problem(n_k, 256, 256, [(gh, HEADS_COLS, m3, 256)], dest[k], 256, 1, 1, asum=dest[12 + k])
-            q.A[0] = gh.data_ptr() + offs[k] * 4
-            problems.append(q)
-        for k in range(6):                                       # d fore_h_fc_k.weight = g_evec[k] (outer) pe_h ; its bias gradient = g_evec[k]
-            q = _problem(256, 192, 1, [(ge, 256, pe2, 192)], dest[24 + k], 192, 1, 0, asum=dest[30 + k])    # = the "row sums" over the K = 1 reduction
-            q.A[0] = ge.data_ptr() + k * 256 * 4
-            problems.append(q)
+        # dW_k[j][tok] = sum_c g[c][off + j] meta[tok][c] ; db_k[j] = sum_c g[c][off + j]
+        # d fore_h_fc_k.weight = g_evec[k] (outer) pe_h ; its bias gradient = g_evec[k] (= the "row sums" over the K = 1 reduction)
+        problems += _HeadsFn._wgrad_problems(hw, offs, gh, ge, m3, pe2, dest, want, 1, 1)
         _launch(problems)
         L.check(lib.dpn_sum_parts(_p(parts), NP, 256 * 256, n_tail, _p(d_meta), _s()), 'dpn_sum_parts')
-        return (d_meta, None, *dest)
+        return (d_meta, None, *[d if w_ else None for d, w_ in zip(dest, want)])
+
+    @staticmethod
+    def _destinations(ctx, hw, hb, fw, fb):
+        """(dest, want, want_meta): the 36 parameter-gradient destinations in the order (12 head weights, 12 head biases, 6 fore_h_fc weights, 6
+        biases), which of them autograd asked for, and whether it asked for d meta.  A wanted gradient goes to the parameter's own gradient tensor
+        (a slot of the optimiser's flat gradient buffer when one is registered, grad_arena); an unwanted one that shares its GEMM problem with a
+        wanted one (a weight and its bias) gets a scratch tensor, and a problem neither of whose outputs is wanted is not built at all."""
+        want = list(ctx.needs_input_grad[2:38])
+        shapes = [(w.shape[0], 256) for w in hw] + [(w.shape[0],) for w in hw] + [(256, 192)] * 6 + [(256,)] * 6
+        pair = lambda i: i + 12 if i < 12 else i - 12 if i < 24 else i + 6 if i < 30 else i - 6
+        dest = []
+        for i, (t, shp) in enumerate(zip(list(hw) + list(hb) + list(fw) + list(fb), shapes)):
+            if want[i]:
+                dest.append(new_grad(t, shp))
+            elif want[pair(i)]:
+                dest.append(torch.empty(shp, dtype=torch.float32, device=t.device))
+            else:
+                dest.append(None)
+        return dest, want, bool(ctx.needs_input_grad[0])
+
+    @staticmethod
+    def _wgrad_problems(hw, offs, gh, ge, xmat, pe2, dest, want, tb, B):
+        """The weight-gradient problems of the heads (xmat, the encoder output as the K-operand: one field -- m3 read transposed, tb = 1; B fields
+        -- acat, tb = 0, the reduction runs over all B * 256 (field, channel) rows) and of the lead-time embeddings (g_evec rows 256 apart for
+        one field, 6 * 256 for B), those only of which an output is wanted."""
+        from .linear import _problem
+        problems = []
+        for k, w in enumerate(hw):
+            if not (want[k] or want[12 + k]):
+                continue
+            q = _problem(w.shape[0], 256, B * 256, [(gh, HEADS_COLS, xmat, 256)], dest[k], 256, 1, tb, asum=dest[12 + k])
+            q.A[0] = gh.data_ptr() + offs[k] * 4
+            problems.append(q)
+        for k in range(6):
+            if not (want[24 + k] or want[30 + k]):
+                continue
+            q = _problem(256, 192, B, [(ge, 256 if tb else 6 * 256, pe2, 192)], dest[24 + k], 192, 1, 0, asum=dest[30 + k])
+            q.A[0] = ge.data_ptr() + k * 256 * 4
+            problems.append(q)
+        return problems
 
     @staticmethod
     def _backward_batched(ctx, g_heads, g_evec):
@@ -532,31 +570,25 @@ class _HeadsFn(torch.autograd.Function):
             offs.append(off)
             off += w.shape[0]
         hb, fw, fb = ctx.params
-        shapes = [(w.shape[0], 256) for w in hw] + [(w.shape[0],) for w in hw] + [(256, 192)] * 6 + [(256,)] * 6
-        dest = [new_grad(t, shp) for t, shp in zip(list(hw) + list(hb) + list(fw) + list(fb), shapes)]
-        # (1) dmt[(f, c)][tok] = sum_k sum_j g[(f, c)][off_k + j] W_k[j][tok]
-        dmt = torch.empty((B * 256, 256), dtype=torch.float32, device=dev)
-        q0 = _problem(B * 256, 256, 256, [(gh, HEADS_COLS, hw[k], 256, hw[k].shape[0]) for k in range(12)], dmt, 256, 0, 0)
-        for k in range(12):
-            q0.A[k] = gh.data_ptr() + offs[k] * 4
-        _launch([q0])
-        d_meta = torch.empty(m3.shape, dtype=torch.float32, device=dev)
-        d_meta[:, :256, :].copy_(dmt.view(B, 256, 256).transpose(1, 2))
-        if Lt > 256:
-            d_meta[:, 256:, :].zero_()                           # tokens >= 256 feed no VariableNet
+        dest, want, want_meta = _HeadsFn._destinations(ctx, hw, hb, fw, fb)
+        d_meta = None
+        if want_meta:                                            # (the encoder frozen: launch (1) and its transposing copy do not run)
+            # (1) dmt[(f, c)][tok] = sum_k sum_j g[(f, c)][off_k + j] W_k[j][tok]
+            dmt = torch.empty((B * 256, 256), dtype=torch.float32, device=dev)
+            q0 = _problem(B * 256, 256, 256, [(gh, HEADS_COLS, hw[k], 256, hw[k].shape[0]) for k in range(12)], dmt, 256, 0, 0)
+            for k in range(12):
+                q0.A[k] = gh.data_ptr() + offs[k] * 4
+            _launch([q0])
+            d_meta = torch.empty(m3.shape, dtype=torch.float32, device=dev)
+            d_meta[:, :256, :].copy_(dmt.view(B, 256, 256).transpose(1, 2))
+            if Lt > 256:
+                d_meta[:, 256:, :].zero_()                       # tokens >= 256 feed no VariableNet
         # (2) dW_k[j][tok] = sum_(f, c) g[(f, c)][off_k + j] acat[(f, c)][tok] ; db_k[j] = sum_(f, c) g[(f, c)][off_k + j]
-        problems = []
-        for k, w in enumerate(hw):
-            n_k = w.shape[0]
-            q = _problem(n_k, 256, B * 256, [(gh, HEADS_COLS, acat, 256)], dest[k], 256, 1, 0, asum=dest[12 + k])
-            q.A[0] = gh.data_ptr() + offs[k] * 4
-            problems.append(q)
-        for k in range(6):                                       # d fore_h_fc_k.weight[c][i] = sum_f g_evec[f][k][c] pe_h[f][i] ; bias: sum_f g_evec[f][k][c]
-            q = _problem(256, 192, B, [(ge, 6 * 256, pe2, 192)], dest[24 + k], 192, 1, 0, asum=dest[30 + k])
-            q.A[0] = ge.data_ptr() + k * 256 * 4
-            problems.append(q)
-        _launch(problems)
-        return (d_meta, None, *dest)
+        #     d fore_h_fc_k.weight[c][i] = sum_f g_evec[f][k][c] pe_h[f][i] ; bias: sum_f g_evec[f][k][c]
+        problems = _HeadsFn._wgrad_problems(hw, offs, gh, ge, acat, pe2, dest, want, 0, B)
+        if problems:
+            _launch(problems)
+        return (d_meta, None, *[d if w_ else None for d, w_ in zip(dest, want)])
 
 
 # ------------------------------------------------------------------------------------------------ row-local fused encoder (round 4)

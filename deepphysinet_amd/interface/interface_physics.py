@@ -18,7 +18,7 @@ from ..balance import LossBalance
 from ..causal import CausalWeights
 from ..losses.builder import builder_loss
 from ..model.physics_net import PhysicsNet
-from ..optim import FusedClipAdam
+from ..optim import GROUP_KEYS, FusedClipAdam, resolve_param_groups
 from ..point_path import (balance_sumsq, balance_update, balanced_total, data_losses_batch, eval_step, eval_step_batch, grid_maps, label_errors,
                           LOSS_ORDER, OBS_ORDER, PackedField, pde_losses, pde_losses_batch, point_fields, point_sizes, PointConfig, require_gpu,
                           smooth_l1_data_loss, step_losses, step_losses_batch)
@@ -736,14 +736,14 @@ class InterfacePhysics(nn.Module):
     def _can_stage(self, optimizer, grad_sync, hip_unbalanced):
         """The four gradient buckets if training_step may take the staged backward, else None (the plain backward + grad_sync(parameters)): the HIP
         forward without balancing, an active bucket reducer bound to THIS optimiser, whose flat buffer is laid out in the four buckets of
-        gradient_buckets(), every parameter trainable (not: an optimiser built without `layout`, a reducer of another or no optimiser, frozen ones)."""
+        gradient_buckets() filtered to the trainable parameters -- a bucket may be empty, with the encoder frozen the last two are (not: an
+        optimiser built without `layout`, a reducer of another or no optimiser, an optimiser that holds other parameters than the trainable ones)."""
         if not (hip_unbalanced and grad_sync is not None and hasattr(grad_sync, 'reduce_bucket') and grad_sync.active()
                 and isinstance(optimizer, FusedClipAdam)):
             return None
-        buckets = self.physics_net.gradient_buckets()
+        buckets = [[p for p in b_ if p.requires_grad] for b_ in self.physics_net.gradient_buckets()]      # = PhysicsNet.trainable_buckets()
         ok = (getattr(grad_sync, 'opt', None) is optimizer and len(getattr(optimizer, 'bucket_bounds', ())) == 4
-              and getattr(optimizer, 'layout_ids', None) == [[id(p) for p in b_] for b_ in buckets]
-              and all(p.requires_grad for b_ in buckets for p in b_))
+              and getattr(optimizer, 'layout_ids', None) == [[id(p) for p in b_] for b_ in buckets])
         return buckets if ok else None
 
     # ------------------------------------------------------------------ validation (:518-530, :629-745)
@@ -878,10 +878,44 @@ class InterfacePhysics(nn.Module):
         return src
 
     # ------------------------------------------------------------------ training loops (:334-846, :848-1404; step body only)
+    def _set_trainable(self, patterns, on, what):
+        import fnmatch
+        named = list(self.physics_net.named_parameters())
+        names = [k for k, _ in named]
+        hit = set()
+        for pat in ([patterns] if isinstance(patterns, str) else list(patterns)):
+            found = fnmatch.filter(names, pat)
+            if not found:
+                raise ValueError('%s: the pattern %r matches no parameter name' % (what, pat))
+            hit |= set(found)
+        changed = [k for k, p in named if k in hit and p.requires_grad != on]
+        if not on and not any(p.requires_grad for k, p in named if k not in hit):
+            raise ValueError('freeze: no trainable parameter is left')
+        for k, p in named:
+            if k in hit:
+                p.requires_grad_(on)
+        return changed
+
+    def freeze(self, patterns):
+        """requires_grad_(False) on every parameter of the PhysicsNet whose state-dict name matches one of the fnmatch patterns ('meta_net.*',
+        '*_net.coord_*_fc.*', '*.bias'); returns the names it changed.  For callers with their own loop: freeze, THEN build_optimizer (the
+        optimiser holds the trainable parameters only; one built before does not follow).  The steps skip what a frozen part does not need -- with
+        'meta_net.*' the whole encoder backward.  ValueError: a pattern that matches nothing, nothing trainable left."""
+        return self._set_trainable(patterns, False, 'freeze')
+
+    def unfreeze(self, patterns):
+        """The reverse of freeze; returns the names it changed.  Build a new optimiser afterwards and load_state_dict the old one's state if wanted."""
+        return self._set_trainable(patterns, True, 'unfreeze')
+
     def build_optimizer(self, **overrides):
         """Fused clip + Adam over the PhysicsNet with the config's optimiser settings (cfg:151-155; `initial_lr` as :394 sets it), its flat
         gradient buffer laid out in backward-completion order (PhysicsNet.gradient_buckets).  The config's `ema_weights` entry is a loop option
-        (_ema_option), not an optimiser keyword: it becomes ema_decay / ema_warmup unless the overrides name those themselves."""
+        (_ema_option), not an optimiser keyword: it becomes ema_decay / ema_warmup unless the overrides name those themselves.
+        Fine-tuning (config keys or overrides): `freeze` = [fnmatch patterns on state-dict names] sets requires_grad_(False) on what they match;
+        `param_groups` = [dict(match=[patterns], lr=..., weight_decay=..., betas=..., eps=...), ...] -- earlier groups win, the unmatched trainable
+        parameters form the last group with the config's own values (optim.resolve_param_groups).  The optimiser then holds the trainable parameters
+        only, in gradient_buckets() order with the frozen ones left out (a bucket may be empty), every group with its `initial_lr` and the `names` of
+        its parameters.  Neither key set, nothing frozen: the one-group optimiser of before, built by the same call."""
         oc = dict(self.train_cfg.get('optimizer', {}))
         name = oc.pop('name', 'Adam')
         if name != 'Adam':
@@ -891,8 +925,17 @@ class InterfacePhysics(nn.Module):
             if ema is not None:
                 oc.update(ema_decay=ema['decay'], ema_warmup=ema['warmup'])
         oc.update(overrides)
-        opt = FusedClipAdam(self.physics_net.parameters(), layout=self.physics_net.gradient_buckets(), **oc)
-        opt.param_groups[0].setdefault('initial_lr', opt.param_groups[0]['lr'])
+        freeze, groups = oc.pop('freeze', None), oc.pop('param_groups', None)
+        net = self.physics_net
+        if freeze:
+            self.freeze(freeze)
+        if not groups and all(p.requires_grad for p in net.parameters()):
+            opt = FusedClipAdam(net.parameters(), layout=net.gradient_buckets(), **oc)
+        else:
+            _, resolved = resolve_param_groups(net.named_parameters(), None, groups, {k: oc[k] for k in GROUP_KEYS if k in oc})
+            opt = FusedClipAdam(resolved, layout=net.trainable_buckets(), **oc)
+        for g in opt.param_groups:
+            g.setdefault('initial_lr', g['lr'])
         if opt.ema_decay is not None:
             opt.bind_module(self.physics_net)                            # load_ema / ema_state_dict go by this module's parameter names
         return opt
@@ -1024,7 +1067,8 @@ class InterfacePhysics(nn.Module):
                 print('resume from epoch %d global_step %d' % (current_epoch, global_step))
             self.physics_net.load_state_dict(state_dict['model'], strict=True)
         ema = self._ema_option(kwargs)                                  # None: the optimiser, the launches, the rows and the checkpoints of before
-        optimizer = self.build_optimizer() if ema is None else self.build_optimizer(ema_decay=ema['decay'], ema_warmup=ema['warmup'])
+        tune = {k: kwargs[k] for k in ('freeze', 'param_groups') if kwargs.get(k)}      # fine-tuning: keywords win over train_cfg['optimizer']
+        optimizer = self.build_optimizer(**tune) if ema is None else self.build_optimizer(ema_decay=ema['decay'], ema_warmup=ema['warmup'], **tune)
         if dist_mode:
             D.broadcast_parameters(self.physics_net)                    # DistributedDataParallel does this at wrap time (:903-907)
             sync = D.GradientAllReduce(optimizer)
@@ -1104,7 +1148,8 @@ class InterfacePhysics(nn.Module):
             if max_steps is not None and global_step >= max_steps:
                 break
         out = {'epoch': epoch if num_epoch > current_epoch else current_epoch, 'global_step': global_step, 'optimizer': optimizer,
-               'lr': optimizer.param_groups[0]['lr'], 'last': last}
+               'lr': optimizer.param_groups[0]['lr'] if len(optimizer.param_groups) == 1 else [g['lr'] for g in optimizer.param_groups],
+               'last': last}
         if vlog is not None:
             out['last_validation'], out['last_epoch_validation'] = vlog.last, vlog.last_epoch
         return out
@@ -1211,7 +1256,11 @@ class InterfacePhysics(nn.Module):
         ema_weights (None, a decay, or dict(decay, warmup): the optimiser keeps an exponential moving average of the weights inside its update
         launch; both validation events run on it and their rows carry "weights": "ema" (train_vars stay on the raw weights), checkpoints gain
         `model_ema` -- a state dict of the PhysicsNet -- and `ema` = dict(decay, warmup, updates), and a resumed run takes the average and its
-        update count from them; unset: the loop of before).
+        update count from them; unset: the loop of before),
+        freeze ([fnmatch patterns on state-dict names]) and param_groups ([dict(match=[patterns], lr=..., weight_decay=..., betas=..., eps=...)]):
+        fine-tuning, as train_cfg['optimizer'] takes them (build_optimizer) -- with checkpoint_path naming an existing checkpoint the run starts from
+        its weights, frozen parameters stay bit-identical, the checkpoints written still hold the full model (and a complete model_ema), and the
+        result's `lr` is a list, one per group, when there are several.
         With a validation source the result carries `last_validation`."""
         return self._run_train(False, **kwargs)
 
@@ -1338,6 +1387,9 @@ class StagedPdeStep:
                    other 6.4 MB of the encoder start one launch earlier) -> layout bucket 3: stage_buckets[2] = (3, 4)
     One field on the fused encoder (round 6): stages[1] and stages[2] are ONE stage and buckets 2, 3 one all-reduce -- the token convolution's gradient is
     written by the encoder stack's own weight-gradient launch, so both buckets complete together (encoder_ops.embed_wgrad_rides_with_stack).
+    Fine-tuning with the encoder frozen (no trainable parameter in buckets 2 and 3): meta_out requires no grad, the encoder's and the embedding's backward do
+    not run and there is ONE stage -- stages == (stage_points_and_heads,), stage_buckets == ((0, 2),).  `buckets` are gradient_buckets() filtered to the
+    trainable parameters (PhysicsNet.trainable_buckets), the layout of the optimiser build_optimizer makes after freeze().
     The cuts are staged_backward.StagedBackward's (training_step takes the same); the forward is this class's.
     Each stage is a plain callable (capturable in a hipGraph of its own, on one capture stream and one memory pool); after stage i the caller
     queues `grad_sync.reduce_bucket(*stage_buckets[i])`.  (Round 2 cut the heads' backward off as a stage of its own: three collectives and
@@ -1353,10 +1405,16 @@ class StagedPdeStep:
         self.m, self.opt, self.b = interface, optimizer, batch
         self.lf = loss_factor or interface.train_cfg['losses']['loss_factor']
         self.lead_batch = bool(lead_batch)
-        self.buckets, self.loss = interface.physics_net.gradient_buckets(), None
+        self.buckets, self.loss = interface.physics_net.trainable_buckets(), None       # (frozen parameters left out: a bucket may be empty)
         self.stages = (self.stage_points_and_heads, self.stage_encoder, self.stage_embedding)
         self.stage_buckets = ((0, 2), (2, 3), (3, 4))
-        if not self.lead_batch and encoder_ops.embed_wgrad_rides_with_stack(1):
+        self.encoder_frozen = not (self.buckets[2] or self.buckets[3])
+        if self.encoder_frozen:
+            # fine-tuning on a frozen encoder: meta_out requires no grad, the encoder and embedding cuts vanish with their launches (the attention
+            # backward, dpn_enc_bwd, the weight-gradient launch with the token convolution's 7.4 MB, the heads' g_meta problems) -- ONE stage
+            self.stages = (self.stage_points_and_heads,)
+            self.stage_buckets = ((0, 2),)
+        elif not self.lead_batch and encoder_ops.embed_wgrad_rides_with_stack(1):
             # Round 6: one field on the fused encoder -- the token convolution's weight gradient is a problem of the stack's ONE weight-gradient launch,
             # the embedding's own backward launches nothing: buckets 2 and 3 complete together.  Two all-reduces behind each other (and a graph
             # segment that is empty) were 73 us of exposed tail on a one-rank RCCL group (gap 21 + 10 + gap 17 + 8 + gap 17); one is gap + 16 + gap.
@@ -1389,6 +1447,8 @@ class StagedPdeStep:
     def stage_points_and_heads(self):
         loss = self.stage_points()
         self.stage_heads()
+        if self.encoder_frozen:
+            self.stage_embedding()               # the last stage: nothing left to differentiate, release what the cuts hold
         return loss
 
     def stage_heads(self):

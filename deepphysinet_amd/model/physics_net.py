@@ -127,6 +127,11 @@ class PhysicsNet(nn.Module):
         rest = [p for p in self.parameters() if id(p) not in seen]
         return [statics, heads, rest, embed]
 
+    def trainable_buckets(self):
+        """gradient_buckets() without the parameters whose requires_grad is False: the layout of an optimiser over the trainable parameters
+        (fine-tuning).  Always four buckets; a bucket may be empty -- with the encoder frozen the last two are."""
+        return [[p for p in b if p.requires_grad] for b in self.gradient_buckets()]
+
     def _cfg(self):
         from ..point_path import PointConfig
         return self.point_cfg or PointConfig()

@@ -19,9 +19,16 @@ that has just formed p' (dpn_clip_adam_flat_ema: no extra launch, and a step rep
 is min(ema_decay, (1 + n) / (10 + n)), n = the number of EMA updates so far (device step counter + `ema_base`), so a young average is not
 dominated by the initial weights.  `ema_weights()` exchanges parameters and shadow for validation, `ema_state_dict()` writes the shadow out as a
 module state dict.
+
+Parameter groups (fine-tuning): the constructor takes torch's list-of-dicts form, every group with its own lr, betas, eps and weight_decay; the
+clip stays global (one max_norm, the norm over every optimised parameter) and so do the step counter and the EMA decay.  Several groups run
+dpn_clip_adam_flat_groups (the same three launches; the update kernel looks up its tensor's group row), one group runs exactly the entry points it
+always ran.  The optimiser owns only the parameters it is given: a frozen parameter of the module has no slot, no moments and no shadow.
+`resolve_param_groups` turns name patterns (train_cfg['optimizer']['freeze'] / ['param_groups']) into those groups.
 """
 import contextlib
 import ctypes
+import fnmatch
 import math
 import weakref
 from collections import OrderedDict
@@ -32,6 +39,68 @@ from . import _lib as L
 from . import grad_arena
 
 _CHUNK = 2048            # dpn_clip_adam_flat: every tensor is padded to whole 2048-element chunks
+MAX_GROUPS = 16          # dpn_clip_adam_flat_groups: kAdamMaxGroups
+GROUP_KEYS = ('lr', 'betas', 'eps', 'weight_decay')       # what a parameter group may set: Adam's hyper-parameters
+
+
+def resolve_param_groups(named_parameters, freeze=None, groups=None, defaults=None):
+    """Name patterns -> parameter groups, without touching a parameter (no GPU needed).
+
+    named_parameters: (name, parameter) pairs in the module's order (state-dict names); a parameter whose `requires_grad` is already False counts
+    as frozen.  freeze: fnmatch patterns of the parameters to freeze.  groups: [dict(match=[patterns], lr=..., weight_decay=..., betas=..., eps=...)]
+    -- a trainable parameter belongs to the FIRST group one of whose patterns matches its name; the trainable parameters no group claims form the
+    last group, with `defaults` (a dict of the same four keys, may be empty) and nothing else.  A group's missing keys are filled from `defaults`.
+    Returns (frozen names, [dict(names=[...], params=[...], **hyper-parameters)]).
+    ValueError: a pattern (of freeze or of a group) that matches no name at all, a freeze that leaves nothing trainable, a group key that is not
+    one of match, lr, betas, eps, weight_decay, a group left without parameters (everything it matches is frozen or claimed by an earlier
+    group), more than 16 groups."""
+    named = [(str(k), p) for k, p in named_parameters]
+    names = [k for k, _ in named]
+    defaults = dict(defaults or {})
+    for k in defaults:
+        if k not in GROUP_KEYS:
+            raise ValueError('param_groups: %r is not an Adam hyper-parameter of a group (%s)' % (k, ', '.join(GROUP_KEYS)))
+    as_list = lambda x: [x] if isinstance(x, str) else list(x or ())
+
+    def matching(pattern, what):
+        hit = set(fnmatch.filter(names, pattern))
+        if not hit:
+            raise ValueError('%s: the pattern %r matches no parameter name' % (what, pattern))
+        return hit
+
+    frozen = {k for k, p in named if not getattr(p, 'requires_grad', True)}
+    for pat in as_list(freeze):
+        frozen |= matching(pat, 'freeze')
+    if len(frozen) == len(names):
+        raise ValueError('freeze: no trainable parameter is left')
+    out, claimed = [], set(frozen)
+    for gi, g in enumerate(groups or ()):
+        g = dict(g)
+        pats = as_list(g.pop('match', None))
+        if not pats:
+            raise ValueError('param_groups[%d]: `match` (a list of name patterns) is required' % gi)
+        for k in g:
+            if k not in GROUP_KEYS:
+                raise ValueError('param_groups[%d]: %r is not an Adam hyper-parameter of a group (%s)' % (gi, k, ', '.join(GROUP_KEYS)))
+        if 'betas' in g:
+            g['betas'] = tuple(float(b) for b in g['betas'])
+        hit = set()
+        for pat in pats:
+            hit |= matching(pat, 'param_groups[%d]' % gi)
+        mine = [k for k in names if k in hit and k not in claimed]
+        if not mine:
+            raise ValueError('param_groups[%d]: every parameter it matches is frozen or belongs to an earlier group' % gi)
+        claimed |= set(mine)
+        out.append(dict(defaults, **g, names=mine))
+    rest = [k for k in names if k not in claimed]
+    if rest:
+        out.append(dict(defaults, names=rest))
+    if len(out) > MAX_GROUPS:
+        raise ValueError('param_groups: %d groups, the fused optimiser takes at most %d' % (len(out), MAX_GROUPS))
+    by_name = dict(named)
+    for g in out:
+        g['params'] = [by_name[k] for k in g['names']]
+    return [k for k in names if k in frozen], out
 
 
 class FusedClipAdam(torch.optim.Optimizer):
@@ -42,10 +111,17 @@ class FusedClipAdam(torch.optim.Optimizer):
             if not (math.isfinite(ema_decay) and 0.0 <= ema_decay < 1.0):
                 raise ValueError('FusedClipAdam: ema_decay must be a finite number in [0, 1), got %r' % (ema_decay,))
         self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)       # attributes, not param_groups entries: state dicts keep their keys
+        self._built = False
         super().__init__(params, defaults)
-        if len(self.param_groups) != 1:
-            raise NotImplementedError('FusedClipAdam takes one parameter group (the reference trains with one, cfg:151-155)')
-        given = list(self.param_groups[0]['params'])
+        self._built = True                                          # from here on add_param_group refuses
+        if len(self.param_groups) > MAX_GROUPS:
+            raise ValueError('FusedClipAdam takes at most %d parameter groups, got %d' % (MAX_GROUPS, len(self.param_groups)))
+        for g in self.param_groups:                                 # the clip is global: one norm over every optimised parameter, one max_norm
+            if float(g['max_norm']) != defaults['max_norm']:
+                raise ValueError('FusedClipAdam: max_norm is one value for the optimiser (%r), a parameter group names %r'
+                                 % (defaults['max_norm'], g['max_norm']))
+            g['betas'] = tuple(g['betas'])
+        given = [p for g in self.param_groups for p in g['params']]   # the optimised set: what the groups hold, nothing else of the module
         if not given or not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in given):
             raise RuntimeError('FusedClipAdam needs contiguous fp32 HIP parameters (no CPU fallback)')
         if layout is None:
@@ -84,8 +160,12 @@ class FusedClipAdam(torch.optim.Optimizer):
             self.state[p] = {'step': self.step_count, 'exp_avg': m, 'exp_avg_sq': v}
         self._p = (ctypes.c_void_p * n)(*[p.data_ptr() for p in self.params])
         self._g = (ctypes.c_void_p * n)(*[s.data_ptr() for s in self._slots])
-        # [lr, beta1, beta2, eps, weight_decay, max_norm, grad_scale] on the device, read by the kernels at run time
-        self._hyper = torch.zeros(8, dtype=torch.float32, device=dev)
+        # [lr, beta1, beta2, eps, weight_decay, max_norm, grad_scale] on the device, read by the kernels at run time; several groups: a row each,
+        # and the group of every tensor in kernel order (dpn_clip_adam_flat_groups)
+        n_groups = len(self.param_groups)
+        self._hyper = torch.zeros(8 if n_groups == 1 else (n_groups, 8), dtype=torch.float32, device=dev)
+        group_of = {id(p): k for k, g in enumerate(self.param_groups) for p in g['params']}
+        self._group_of = (ctypes.c_uint8 * n)(*[group_of[id(p)] for p in self.params])
         self._hyper_host = None
         self.grad_scale = 1.0
         self.steps_done = 0                                         # host-side count of step() calls (point_path's forward / backward stamps)
@@ -99,6 +179,12 @@ class FusedClipAdam(torch.optim.Optimizer):
             self.reset_ema()
         self.sync_hyper()
         grad_arena.register(self, self.params, self._offsets)
+
+    def add_param_group(self, param_group):
+        if getattr(self, '_built', False):
+            raise NotImplementedError('FusedClipAdam.add_param_group: the flat buffers are laid out at construction; build a new optimiser over the '
+                                      'new groups and load_state_dict the old state into it')
+        super().add_param_group(param_group)
 
     def __del__(self):
         try:
@@ -121,15 +207,17 @@ class FusedClipAdam(torch.optim.Optimizer):
 
     @max_norm.setter
     def max_norm(self, v):
-        self.param_groups[0]['max_norm'] = float(v)
+        for g in self.param_groups:
+            g['max_norm'] = float(v)
 
     def _hyper_values(self):
-        g = self.param_groups[0]
-        return (float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay']), float(g['max_norm']),
-                float(self.grad_scale), 0.0 if self.ema_decay is None else self.ema_decay)
+        """One group: its row; several: a tuple of rows (max_norm, grad_scale and the decay are read from row 0, every row carries them)."""
+        rows = tuple((float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay']), float(self.max_norm),
+                      float(self.grad_scale), 0.0 if self.ema_decay is None else self.ema_decay) for g in self.param_groups)
+        return rows[0] if len(rows) == 1 else rows
 
     def sync_hyper(self):
-        """Upload param_groups[0] (lr after a scheduler step, ...) to the device scalars the kernels read.  step() does it by itself
+        """Upload every group's row (lr after a scheduler step, ...) to the device scalars the kernels read.  step() does it by itself
         outside a graph capture; call it after `scheduler.step()` when the optimiser step is replayed from a hipGraph."""
         vals = self._hyper_values()
         if vals != self._hyper_host:
@@ -164,7 +252,9 @@ class FusedClipAdam(torch.optim.Optimizer):
         if getattr(self, '_slot_of', None) is None:
             self._slot_of = {id(p): s for p, s in zip(self.params, self._slots)}
         for p, g in zip(params, grads):
-            s = self._slot_of[id(p)]
+            s = self._slot_of.get(id(p))
+            if s is None:                           # not this optimiser's (a frozen parameter): its gradient is dropped
+                continue
             if g is None:
                 s.zero_()
             elif g.data_ptr() != s.data_ptr() or not g.is_contiguous():
@@ -196,7 +286,17 @@ class FusedClipAdam(torch.optim.Optimizer):
         else:
             grad_arena.captured_step[0] = True      # replays of this step rewrite the parameters without passing through here
         lib = L.load()
-        if self._ema_flat is None:
+        if len(self.param_groups) > 1:
+            ema = self._ema_flat is not None
+            L.check(lib.dpn_clip_adam_flat_groups(len(self.params), self._p, self._g, self._numel, ctypes.c_void_p(self._m_flat.data_ptr()),
+                                                  ctypes.c_void_p(self._v_flat.data_ptr()), ctypes.c_void_p(self._sumsq.data_ptr()),
+                                                  ctypes.c_void_p(self.step_count.data_ptr()), self._group_of, len(self.param_groups),
+                                                  ctypes.c_void_p(self._hyper.data_ptr()), ctypes.c_void_p(self.grad_norm.data_ptr()),
+                                                  ctypes.c_void_p(self._ema_flat.data_ptr()) if ema else None,
+                                                  ctypes.c_void_p(self.ema_base.data_ptr()) if ema else None, int(self.ema_warmup),
+                                                  torch.cuda.current_stream().cuda_stream),
+                    'dpn_clip_adam_flat_groups')
+        elif self._ema_flat is None:
             L.check(lib.dpn_clip_adam_flat_dev(len(self.params), self._p, self._g, self._numel, ctypes.c_void_p(self._m_flat.data_ptr()),
                                                ctypes.c_void_p(self._v_flat.data_ptr()), ctypes.c_void_p(self._sumsq.data_ptr()),
                                                ctypes.c_void_p(self.step_count.data_ptr()), ctypes.c_void_p(self._hyper.data_ptr()),
@@ -262,7 +362,7 @@ class FusedClipAdam(torch.optim.Optimizer):
 
     def ema_state_dict(self, module):
         """`module.state_dict()` with every optimised parameter replaced by a clone of its shadow: same names, shapes and order; buffers and
-        parameters this optimiser does not hold come from the module."""
+        parameters this optimiser does not hold (frozen ones) come from the module with their own values, so the result is a complete state dict."""
         self._need_ema('ema_state_dict')
         self.bind_module(module)
         if self._ema_swapped:
@@ -273,7 +373,8 @@ class FusedClipAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def load_ema(self, state_dict, updates, module=None):
-        """Fill the shadow from an `ema_state_dict` (strict: every optimised parameter's name must be there with its shape) and set `ema_base` so
+        """Fill the shadow from an `ema_state_dict` (strict: every optimised parameter's name must be there with its shape; entries for parameters
+        this optimiser does not own are ignored) and set `ema_base` so
         that step counter + base = `updates`: the warm-up of a resumed run does not restart.  The names are those of `module`, or of the module
         last given to `bind_module` / `ema_state_dict`."""
         self._need_ema('load_ema')
@@ -303,9 +404,9 @@ class FusedClipAdam(torch.optim.Optimizer):
         sd['state'] = {k: {'step': step.clone(), 'exp_avg': st['exp_avg'].detach().clone(), 'exp_avg_sq': st['exp_avg_sq'].detach().clone()}
                        for k, st in sd['state'].items()}
         if self._ema_flat is not None:
-            # sd['state'] is keyed by the parameter's index in param_groups[0]['params'] (the order they were given in)
+            # sd['state'] is keyed by the parameter's index over the groups' 'params' lists, group after group (the order they were given in)
             shadow = {id(p): s for p, s in zip(self.params, self.ema)}
-            for k, p in enumerate(self.param_groups[0]['params']):
+            for k, p in enumerate(p for g in self.param_groups for p in g['params']):
                 sd['state'][k]['ema'] = shadow[id(p)].detach().clone()
             sd['ema_updates'] = self.ema_updates()
         return sd
@@ -318,12 +419,14 @@ class FusedClipAdam(torch.optim.Optimizer):
         if ema_updates is not None:                 # torch's load_state_dict knows 'state' and 'param_groups' only
             state_dict = {k: v for k, v in state_dict.items() if k != 'ema_updates'}
         super().load_state_dict(state_dict)
-        for k, v in self.defaults.items():          # a torch.optim.Adam state dict has no 'max_norm' (load_state_dict replaces the group wholesale)
-            self.param_groups[0].setdefault(k, v)
+        for g in self.param_groups:                 # a torch.optim.Adam state dict has no 'max_norm' (load_state_dict replaces the groups wholesale)
+            for k, v in self.defaults.items():
+                g.setdefault(k, v)
+        self.max_norm = self.param_groups[0]['max_norm']
         step = None
         shadow = {id(p): s for p, s in zip(self.params, self.ema)} if self._ema_flat is not None else {}
         have_ema = bool(shadow) and ema_updates is not None
-        for p in self.param_groups[0]['params']:
+        for p in (p for g in self.param_groups for p in g['params']):
             st = self.state.get(p, {})
             m, v = views[id(p)]
             if have_ema and 'ema' in st:

@@ -485,6 +485,17 @@ int dpn_clip_adam_flat_dev(int n_tensors, float* const* params, const float* con
 int dpn_clip_adam_flat_ema(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
                            float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const float* hyper_dev, float* out_norm_dev,
                            float* ema_flat, const int* ema_base_dev, int ema_warmup, void* stream);
+/* dpn_clip_adam_flat_dev / dpn_clip_adam_flat_ema with PARAMETER GROUPS (fine-tuning: a learning rate, betas, eps and weight decay per group).
+ * group_of: HOST array of n_tensors bytes, the group of each tensor; n_groups: 1 .. 16; hyper_dev: device float[n_groups][8], row k =
+ * {lr, beta1, beta2, eps, weight_decay, max_norm, grad_scale, ema_decay} of group k -- max_norm, grad_scale and ema_decay are read from row 0
+ * only: the norm is taken over ALL tensors and the clip coefficient is global, as clip_grad_norm_ over every trainable parameter.  ema_flat
+ * NULL: no EMA (ema_base_dev and ema_warmup are not read); otherwise as dpn_clip_adam_flat_ema.  One shared step counter.  Every tensor comes out
+ * bit-identical to dpn_clip_adam_flat_dev / _ema called with its group's row as hyper_dev; with one group the call IS that call.  Three launches
+ * per 160 tensors, no atomics.  A group without tensors is allowed.  -1 (nothing launched, nothing written): n_groups outside 1 .. 16, a group_of
+ * entry >= n_groups, group_of or hyper_dev NULL, and everything dpn_clip_adam_flat_dev refuses. */
+int dpn_clip_adam_flat_groups(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
+                              float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const uint8_t* group_of, int n_groups,
+                              const float* hyper_dev, float* out_norm_dev, float* ema_flat, const int* ema_base_dev, int ema_warmup, void* stream);
 /* Exchanges every parameter with its shadow in ema_flat in place, bit for bit (validation and inference on the averaged weights without a second
  * model): one launch per 160 tensors over the same chunk table; the padding of ema_flat and everything outside the tensors stay untouched; two
  * calls are the identity.  -1: n_tensors <= 0, a NULL pointer, a numel outside 1 .. 2^31 - 1. */

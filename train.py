@@ -3,6 +3,7 @@
 
     python train.py [--config_file cfg.py] [--checkpoint_path DIR] [--log_path DIR] [--dist] [--max_steps N] [--synthetic] [--valid_synthetic]
                     [--adaptive_interior] [--causal_weights EPS] [--balance_losses EVERY] [--lead_batch K] [--ema DECAY]
+                    [--freeze PATTERN]... [--param_group 'PATTERN[,PATTERN...]:lr=...,weight_decay=...']...
 
 The reference reads the config with mmcv.Config.fromfile (absent here, and moved to mmengine in the pinned mmcv: SURVEY section 0, defect
 3), builds the interface with `builder_models(**cfg['config'])` and calls `run_train_interface(checkpoint_path=..., log_path=...)`.  The
@@ -10,7 +11,8 @@ same happens here: a python config file that defines `config = dict(...)` is exe
 without --config_file the built-in copy of that config (deepphysinet_amd.configs.ncep_config) is used.  The reference's PhysicsDataset
 reads GeoTIFF / xarray files that do not exist offline (out of scope); a config that names no `samples`
 source therefore FAILS like the reference without its files, unless --synthetic asks for random field samples and batches from the
-on-device CollocationSampler (smoke runs: the checkpoints are trained on noise).  --dist selects run_train_interface_dist (torchrun)."""
+on-device CollocationSampler (smoke runs: the checkpoints are trained on noise).  --dist selects run_train_interface_dist (torchrun).
+Fine-tuning: --checkpoint_path naming an existing checkpoint, with --freeze / --param_group (fnmatch patterns on state-dict names)."""
 import argparse
 import os
 import runpy
@@ -47,6 +49,37 @@ parse.add_argument('--lead_batch', default=None, type=int, metavar='K', help='K 
                    'per step); not together with --causal_weights / --balance_losses')
 parse.add_argument('--ema', default=None, type=float, metavar='DECAY', help='keep an exponential moving average of the weights inside the optimiser step '
                    '(ema_weights=dict(decay=DECAY, warmup=True)): validation runs on it and the checkpoints carry it as model_ema (infer.py --ema)')
+
+
+def param_group_arg(text):
+    """'PATTERN[,PATTERN...]:key=value[,key=value...]' -> dict(match=[patterns], key=value, ...) for the `param_groups` option.  Keys: lr, eps,
+    weight_decay (a number each) and betas (two numbers joined by '/': betas=0.9/0.999)."""
+    pats, sep, rest = text.partition(':')
+    match = [p for p in (q.strip() for q in pats.split(',')) if p]
+    if not sep or not match:
+        raise argparse.ArgumentTypeError("expected 'PATTERN[,PATTERN...]:key=value[,key=value...]', got %r" % text)
+    group = dict(match=match)
+    for item in (q.strip() for q in rest.split(',')):
+        if not item:
+            continue
+        key, eq, val = item.partition('=')
+        key = key.strip()
+        try:
+            if key not in ('lr', 'eps', 'weight_decay', 'betas') or not eq:
+                raise ValueError
+            group[key] = tuple(float(v) for v in val.split('/')) if key == 'betas' else float(val)
+            if key == 'betas' and len(group[key]) != 2:
+                raise ValueError
+        except ValueError:
+            raise argparse.ArgumentTypeError('%r: expected lr=, eps=, weight_decay= (a number) or betas=B1/B2 in %r' % (item, text))
+    return group
+
+
+parse.add_argument('--freeze', action='append', default=None, metavar='PATTERN', help='fine-tuning: freeze the parameters whose state-dict name matches '
+                   "the fnmatch pattern ('meta_net.*': the whole grid encoder, whose backward then does not run); repeatable (freeze=[...])")
+parse.add_argument('--param_group', action='append', default=None, type=param_group_arg, metavar='PATTERNS:KEY=VALUE,...', help='fine-tuning: a parameter '
+                   "group with hyper-parameters of its own, e.g. '*_net.coord_*_fc.*:lr=1e-5' or '*.bias,*norm*:weight_decay=0'; repeatable, earlier "
+                   'groups win, the rest keeps the config\'s values (param_groups=[...])')
 
 
 def load_config(path):
@@ -86,8 +119,13 @@ if __name__ == '__main__':
         kwargs['lead_batch'] = args.lead_batch
     if args.ema is not None:
         kwargs['ema_weights'] = dict(decay=args.ema, warmup=True)
+    if args.freeze:
+        kwargs['freeze'] = args.freeze
+    if args.param_group:
+        kwargs['param_groups'] = args.param_group
     run = model.run_train_interface_dist if args.dist else model.run_train_interface
     out = run(**kwargs)
-    print('done: epoch %d, global_step %d, lr %.3e' % (out['epoch'], out['global_step'], out['lr']))
+    lrs = out['lr'] if isinstance(out['lr'], list) else [out['lr']]
+    print('done: epoch %d, global_step %d, lr %s' % (out['epoch'], out['global_step'], ' '.join('%.3e' % v for v in lrs)))
     if out.get('last_validation') is not None:
         print('last validation: valid loss %.6g at step %d' % (float(out['last_validation']['valid_loss']), out['last_validation']['global_step']))
