@@ -105,6 +105,11 @@ class DpnLattice(Structure):
     _fields_ = [(n, c_double) for n in ('x0', 'xstep', 'y0', 'ystep', 't0', 'tstep')] + [(n, c_int32) for n in ('nx', 'ny', 'nt')]
 
 
+class DpnStepGuard(Structure):
+    _fields_ = [(n, c_int32) for n in ('skipped_nonfinite', 'skipped_spike', 'verdict', 'seen', 'consecutive', 'reserved')] + \
+               [('running', c_double), ('last', c_double)]
+
+
 class DpnSizes(Structure):
     _fields_ = [('n_pad', c_int64), ('packed', c_int64), ('saved', c_int64), ('operands', c_int64), ('partials', c_int64),
                 ('k_splits', c_int32)]
@@ -186,6 +191,8 @@ EXPORTS = {
                                        c_void_p, c_int, c_void_p]),
     'dpn_clip_adam_flat_groups': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    'dpn_clip_adam_flat_guard': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_double, c_double, c_int, c_int, c_void_p]),
     'dpn_ema_swap': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dpn_gemm_fp8_mx': (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'dpn_selftest': (c_int, [c_void_p, c_void_p]),

@@ -4,6 +4,8 @@
 //   dpn_gradnorm_kernel / dpn_gradnorm_reduce_kernel   one fp64 partial per 2048-element chunk, added in a fixed order
 //   dpn_adam_kernel                                    the clipped update; the AdamTableFlatEma instantiation also moves the weight EMA, the
 //                                                      AdamTableFlatGroups* ones read their hyper-parameters from their tensor's group row
+//   dpn_gradnorm_reduce_guard_kernel                   the reduction plus the step guard's verdict (skip non-finite and spiking steps); the
+//                                                      AdamTableFlatGuard* instantiations of dpn_adam_kernel obey it
 //   dpn_ema_swap_kernel                                exchanges the parameters with their EMA shadow
 // No kernel in this file uses atomics: every reduction is fixed-order, the whole step is bitwise reproducible.
 #include "dpn_device.h"
@@ -23,6 +25,7 @@ struct AdamTable {
     int n;
     static constexpr bool ema = false;
     static constexpr bool groups = false;
+    static constexpr bool guard_on = false;
 };
 // Optimiser state kept by the caller as ONE flat buffer per moment, tensor i at offset chunk_start[i] * kAdamChunk (each tensor padded to
 // whole chunks): no per-tensor state pointers, so 160 tensors fit in the kernel arguments and a PhysicsNet is one launch per pass.
@@ -37,6 +40,7 @@ struct AdamTableFlat {
     int n;
     static constexpr bool ema = false;
     static constexpr bool groups = false;
+    static constexpr bool guard_on = false;
 };
 static_assert(sizeof(AdamTableFlat) + 64 <= 4096, "kernel arguments are limited to 4 KB");
 // AdamTableFlat plus an exponential moving average of the parameters (the shadow `s_flat`, laid out like the moments), updated by the thread
@@ -55,6 +59,7 @@ struct AdamTableFlatEma {
     int ema_warmup;
     static constexpr bool ema = true;
     static constexpr bool groups = false;
+    static constexpr bool guard_on = false;
 };
 static_assert(sizeof(AdamTableFlatEma) + 64 <= 4096, "kernel arguments are limited to 4 KB");
 // AdamTableFlat / AdamTableFlatEma plus a parameter group per tensor (fine-tuning: a learning rate, betas, eps and weight decay per group).  How
@@ -73,6 +78,7 @@ struct AdamTableFlatGroups {
     uint8_t group4[kAdamFlatMaxTensors / 2];     // tensor i: (group4[i >> 1] >> 4 (i & 1)) & 15
     static constexpr bool ema = false;
     static constexpr bool groups = true;
+    static constexpr bool guard_on = false;
 };
 static_assert(sizeof(AdamTableFlatGroups) + 64 <= 4096, "kernel arguments are limited to 4 KB");
 struct AdamTableFlatGroupsEma {
@@ -89,8 +95,47 @@ struct AdamTableFlatGroupsEma {
     uint8_t group4[kAdamFlatMaxTensors / 2];
     static constexpr bool ema = true;
     static constexpr bool groups = true;
+    static constexpr bool guard_on = false;
 };
 static_assert(sizeof(AdamTableFlatGroupsEma) + 64 <= 4096, "kernel arguments are limited to 4 KB");
+// The grouped tables plus the step guard (dpn_clip_adam_flat_guard): `guard` points at the DpnStepGuard whose verdict dpn_gradnorm_reduce_guard_kernel
+// formed one launch earlier.  A non-zero verdict returns the block before it touches p, m, v or the shadow; a zero one runs the arithmetic of every
+// other table with the step number *step - skipped_nonfinite - skipped_spike.  One group rides as group 0 of a one-row hyper_dev (the grouped kernel
+// with one group IS the one-group kernel, bit for bit), so two tables cover every combination.  Types of their own again: the instantiations without
+// the guard keep their code (tools/kernel_isa_digest.py on both trees: DESIGN.md section 6e).
+struct AdamTableFlatGuard {
+    float* p[kAdamFlatMaxTensors];
+    const float* g[kAdamFlatMaxTensors];
+    int chunk_start[kAdamFlatMaxTensors + 1];
+    int numel[kAdamFlatMaxTensors];
+    float* m_flat;
+    float* v_flat;
+    const DpnStepGuard* guard;
+    int n;
+    uint8_t group4[kAdamFlatMaxTensors / 2];
+    static constexpr bool ema = false;
+    static constexpr bool groups = true;
+    static constexpr bool guard_on = true;
+};
+static_assert(sizeof(AdamTableFlatGuard) + 64 <= 4096, "kernel arguments are limited to 4 KB");
+struct AdamTableFlatGuardEma {
+    float* p[kAdamFlatMaxTensors];
+    const float* g[kAdamFlatMaxTensors];
+    int chunk_start[kAdamFlatMaxTensors + 1];
+    int numel[kAdamFlatMaxTensors];
+    float* m_flat;
+    float* v_flat;
+    float* s_flat;
+    const int* ema_base;
+    const DpnStepGuard* guard;
+    int n;
+    int ema_warmup;
+    uint8_t group4[kAdamFlatMaxTensors / 2];
+    static constexpr bool ema = true;
+    static constexpr bool groups = true;
+    static constexpr bool guard_on = true;
+};
+static_assert(sizeof(AdamTableFlatGuardEma) + 64 <= 4096, "kernel arguments are limited to 4 KB");
 DEV float* table_m(const AdamTable& t, int ti) { return t.m[ti]; }
 DEV float* table_v(const AdamTable& t, int ti) { return t.v[ti]; }
 DEV float* table_m(const AdamTableFlat& t, int ti) { return t.m_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
@@ -103,6 +148,11 @@ DEV float* table_v(const AdamTableFlatGroups& t, int ti) { return t.v_flat + (in
 DEV float* table_m(const AdamTableFlatGroupsEma& t, int ti) { return t.m_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
 DEV float* table_v(const AdamTableFlatGroupsEma& t, int ti) { return t.v_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
 DEV float* table_s(const AdamTableFlatGroupsEma& t, int ti) { return t.s_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+DEV float* table_m(const AdamTableFlatGuard& t, int ti) { return t.m_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+DEV float* table_v(const AdamTableFlatGuard& t, int ti) { return t.v_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+DEV float* table_m(const AdamTableFlatGuardEma& t, int ti) { return t.m_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+DEV float* table_v(const AdamTableFlatGuardEma& t, int ti) { return t.v_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+DEV float* table_s(const AdamTableFlatGuardEma& t, int ti) { return t.s_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
 template <class Table>
 DEV int table_group(const Table& t, int ti) { return (t.group4[ti >> 1] >> ((ti & 1) * 4)) & 15; }
 template <class Table>
@@ -149,6 +199,54 @@ __global__ __launch_bounds__(256) void dpn_gradnorm_reduce_kernel(const double* 
     __syncthreads();
     if (threadIdx.x == 0) *sumsq = (red[0] + red[1]) + (red[2] + red[3]);
 }
+// dpn_gradnorm_reduce_kernel (the same sum in the same order) whose thread 0 then forms the step guard's verdict from the fp32 total norm exactly as
+// dpn_adam_kernel forms it.  fp64, every operation rounded once (no contraction); the rule is restated on the host in deepphysinet_amd/guard.py.
+// hyper: row 0 of hyper_dev (grad_scale = hyper[6]).  Plain vector stores by one thread, no atomics.
+__global__ __launch_bounds__(256) void dpn_gradnorm_reduce_guard_kernel(const double* partial, int n, double* sumsq, const float* hyper,
+                                                                        DpnStepGuard* guard, double spike_factor, double spike_decay, int spike_warmup,
+                                                                        int spike_patience) {
+#pragma clang fp contract(off)
+    double d = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) d += partial[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o);
+    __shared__ double red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = d;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const double sum = (red[0] + red[1]) + (red[2] + red[3]);
+    *sumsq = sum;
+    const float total = (float)sqrt(sum) * hyper[6];
+    const double tot = (double)total;
+    int seen = guard->seen, consecutive = guard->consecutive;
+    double running = guard->running;
+    int verdict = 0;
+    if (!(fabsf(total) <= 3.402823466e+38f)) {                                // NaN, +-inf (a finite sum of squares past FLT_MAX^2 cannot occur: the cast gives inf)
+        verdict = 1;
+        guard->skipped_nonfinite += 1;
+        consecutive = 0;
+    } else if (spike_factor > 0.0 && seen >= spike_warmup && tot > spike_factor * running && consecutive < spike_patience) {
+        verdict = 2;
+        guard->skipped_spike += 1;
+        consecutive += 1;
+    } else {
+        if (consecutive == spike_patience) seen = 0;                          // overruled: the level of the norms has moved, the mean starts again
+        if (seen == 0) running = tot;
+        else {
+            const double a = spike_decay * running;
+            const double b = 1.0 - spike_decay;
+            const double c = b * tot;
+            running = a + c;
+        }
+        if (seen < 0x7fffffff) seen += 1;
+        consecutive = 0;
+        guard->running = running;
+        guard->seen = seen;
+    }
+    guard->verdict = verdict;
+    guard->consecutive = consecutive;
+    guard->last = tot;
+}
 template <class Table>
 __global__ __launch_bounds__(256) void dpn_adam_kernel(Table t, const double* sumsq, const int* step, float lr, float b1, float b2, float eps,
                                                        float wd, float max_norm, float* out_norm, const float* hyper) {
@@ -165,8 +263,15 @@ __global__ __launch_bounds__(256) void dpn_adam_kernel(Table t, const double* su
     } else if (hyper) { lr = hyper[0]; b1 = hyper[1]; b2 = hyper[2]; eps = hyper[3]; wd = hyper[4]; max_norm = hyper[5]; gscale = hyper[6]; }
     const float total = (float)sqrt(*sumsq) * gscale;
     if (out_norm && blockIdx.x == 0 && threadIdx.x == 0) *out_norm = total;
+    // Table::guard_on: a refused step (verdict != 0) ends here, p, m, v and the shadow neither read nor written (out_norm above still shows the norm
+    // that was refused); an applied one counts its step number without the skipped calls, in the bias corrections and in the EMA's te alike
+    int tstep = *step;
+    if constexpr (Table::guard_on) {
+        if (t.guard->verdict != 0) return;
+        tstep -= t.guard->skipped_nonfinite + t.guard->skipped_spike;
+    }
     const float coef = fminf(max_norm / (total + 1e-6f), 1.0f) * gscale;    // clip_grad_norm_'s clamp(max_norm / (norm + 1e-6), max=1)
-    const float st = (float)(*step);
+    const float st = (float)tstep;
     const float bc1 = 1.f - powf(b1, st), bc2s = sqrtf(1.f - powf(b2, st));
     const float step_size = lr / bc1;
     const int ti = adam_find(t, blockIdx.x);
@@ -174,12 +279,12 @@ __global__ __launch_bounds__(256) void dpn_adam_kernel(Table t, const double* su
     float* p = t.p[ti]; const float* g = t.g[ti]; float* m = table_m(t, ti); float* v = table_v(t, ti);
     const int end = min(base + kAdamChunk, t.numel[ti]);
     // Table::ema: s' = d s + (1 - d) p' with the p' this thread stores; d = decay, or min(decay, (1 + te) / (10 + te)) during the warm-up,
-    // te = *step + *ema_base.  One rounding per operation, the one fma written here
+    // te = the step number + *ema_base.  One rounding per operation, the one fma written here
     float* sh = nullptr;
     float ema_d = 0.f, ema_1md = 0.f;
     if constexpr (Table::ema) {
         sh = table_s(t, ti);
-        const float te = (float)(*step + (t.ema_base ? *t.ema_base : 0));
+        const float te = (float)(tstep + (t.ema_base ? *t.ema_base : 0));
         ema_d = t.ema_warmup ? fminf(hyper[7], (1.f + te) / (10.f + te)) : hyper[7];
         ema_1md = 1.f - ema_d;
     }
@@ -424,6 +529,79 @@ int dpn_clip_adam_flat_groups(int n_tensors, float* const* params, const float* 
                                                                   group_of, n_groups, hyper_dev, out_norm_dev, ema_flat, ema_base_dev, ema_warmup, stream);
     return clip_adam_flat_groups_impl<AdamTableFlatGroups>(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev,
                                                            group_of, n_groups, hyper_dev, out_norm_dev, nullptr, nullptr, 0, stream);
+}
+
+extern "C++" template <class Table>
+static int clip_adam_flat_guard_impl(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
+                                     float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const uint8_t* group_of, const float* hyper_dev,
+                                     float* out_norm_dev, float* ema_flat, const int* ema_base_dev, int ema_warmup, DpnStepGuard* guard_dev,
+                                     double spike_factor, double spike_decay, int spike_warmup, int spike_patience, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    double* sumsq = scratch_dev;
+    double* partial = scratch_dev + 1;
+    for (int pass = 0; pass < 2; ++pass) {
+        int base_chunk = 0;
+        for (int t0 = 0; t0 < n_tensors; t0 += kAdamFlatMaxTensors) {
+            const int n = (n_tensors - t0 < kAdamFlatMaxTensors) ? n_tensors - t0 : kAdamFlatMaxTensors;
+            if (pass == 0) {
+                // the gradient-norm launch is the existing one, the instantiation of dpn_clip_adam_flat_dev; it bumps *step_dev whatever the verdict
+                AdamTableFlat t;
+                t.n = n; t.m_flat = nullptr; t.v_flat = nullptr;
+                int chunks = 0;
+                for (int i = 0; i < n; ++i) {
+                    t.p[i] = params[t0 + i]; t.g[i] = grads[t0 + i];
+                    t.numel[i] = (int)numel[t0 + i];
+                    t.chunk_start[i] = chunks;
+                    chunks += (t.numel[i] + kAdamChunk - 1) / kAdamChunk;
+                }
+                t.chunk_start[n] = chunks;
+                hipLaunchKernelGGL(dpn_gradnorm_kernel<AdamTableFlat>, dim3(chunks), dim3(256), 0, s, t, partial + base_chunk, step_dev, t0 == 0 ? 1 : 0);
+                base_chunk += chunks;
+                continue;
+            }
+            Table t;
+            t.n = n;
+            t.m_flat = exp_avg_flat + (int64_t)base_chunk * kAdamChunk;
+            t.v_flat = exp_avg_sq_flat + (int64_t)base_chunk * kAdamChunk;
+            t.guard = guard_dev;                                                       // every update launch obeys the one verdict
+            if constexpr (Table::ema) { t.s_flat = ema_flat + (int64_t)base_chunk * kAdamChunk; t.ema_base = ema_base_dev; t.ema_warmup = ema_warmup; }
+            for (int i = 0; i < kAdamFlatMaxTensors / 2; ++i) t.group4[i] = 0;
+            int chunks = 0;
+            for (int i = 0; i < n; ++i) {
+                t.p[i] = params[t0 + i]; t.g[i] = grads[t0 + i];
+                t.numel[i] = (int)numel[t0 + i];
+                t.chunk_start[i] = chunks;
+                chunks += (t.numel[i] + kAdamChunk - 1) / kAdamChunk;
+                if (group_of) t.group4[i >> 1] |= (uint8_t)(group_of[t0 + i] << ((i & 1) * 4));
+            }
+            t.chunk_start[n] = chunks;
+            hipLaunchKernelGGL(dpn_adam_kernel<Table>, dim3(chunks), dim3(256), 0, s, t, (const double*)sumsq, (const int*)step_dev, 0.f, 0.f, 0.f, 0.f,
+                               0.f, 0.f, out_norm_dev, hyper_dev);
+            base_chunk += chunks;
+        }
+        if (pass == 0) hipLaunchKernelGGL(dpn_gradnorm_reduce_guard_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, base_chunk, sumsq, hyper_dev,
+                                          guard_dev, spike_factor, spike_decay, spike_warmup, spike_patience);
+    }
+    return ck(hipGetLastError());
+}
+
+int dpn_clip_adam_flat_guard(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
+                             float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const uint8_t* group_of, int n_groups,
+                             const float* hyper_dev, float* out_norm_dev, float* ema_flat, const int* ema_base_dev, int ema_warmup,
+                             DpnStepGuard* guard_dev, double spike_factor, double spike_decay, int spike_warmup, int spike_patience, void* stream) {
+    if (n_tensors <= 0 || !params || !grads || !numel || !exp_avg_flat || !exp_avg_sq_flat || !scratch_dev || !step_dev || !hyper_dev) return -1;
+    if (!guard_dev || !(spike_factor >= 0.0 && spike_factor <= 1.7976931348623157e308) || !(spike_decay >= 0.0 && spike_decay < 1.0) ||
+        spike_warmup < 1 || spike_patience < 1) return -1;
+    if (group_of && (n_groups < 1 || n_groups > kAdamMaxGroups)) return -1;           // group_of NULL: one group, n_groups is not read
+    // every size and every group is checked before the first launch: a refusal bumps no step counter and writes no partial
+    for (int i = 0; i < n_tensors; ++i) if (numel[i] <= 0 || numel[i] > 0x7fffffff || (group_of && group_of[i] >= n_groups)) return -1;
+    if (ema_flat)
+        return clip_adam_flat_guard_impl<AdamTableFlatGuardEma>(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, group_of,
+                                                                hyper_dev, out_norm_dev, ema_flat, ema_base_dev, ema_warmup, guard_dev, spike_factor,
+                                                                spike_decay, spike_warmup, spike_patience, stream);
+    return clip_adam_flat_guard_impl<AdamTableFlatGuard>(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, group_of,
+                                                         hyper_dev, out_norm_dev, nullptr, nullptr, 0, guard_dev, spike_factor, spike_decay, spike_warmup,
+                                                         spike_patience, stream);
 }
 
 int dpn_ema_swap(int n_tensors, float* const* params, const int64_t* numel, float* ema_flat, void* stream) {

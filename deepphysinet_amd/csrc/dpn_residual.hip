@@ -169,7 +169,7 @@ template <class Args> __global__ __launch_bounds__(256) void dpn_residual_kernel
 #pragma clang fp contract(off)
                 const float d = a.out_n[i * 6 + k] - a.labels[(i - a.n_inter) * 6 + k];
                 const float ad = fabsf(d);
-                const float gd = a.data_scale * a.gtot[0] * ((ad < a.data_beta) ? d / a.data_beta : (d > 0.f ? 1.f : -1.f));
+                const float gd = a.data_scale * a.gtot[0] * ((ad < a.data_beta) ? d / a.data_beta : (d > 0.f ? 1.f : (d < 0.f ? -1.f : d)));   // (NaN stays NaN: dpn_smooth_l1_kernel)
                 go = go + gd;
             }
         }
@@ -262,7 +262,8 @@ __global__ __launch_bounds__(256) void dpn_smooth_l1_kernel(const float* out_n, 
         const float ad = fabsf(d);
         l = (ad < beta) ? 0.5f * d * d / beta : ad - 0.5f * beta;    // nn.SmoothL1Loss(beta), weights_loss.py:15-19
         if (g_out) {
-            const float gv = scale * (scale_dev ? scale_dev[0] : 1.f) * ((ad < beta) ? d / beta : (d > 0.f ? 1.f : -1.f));
+            const float gv = scale * (scale_dev ? scale_dev[0] : 1.f) * ((ad < beta) ? d / beta : (d > 0.f ? 1.f : (d < 0.f ? -1.f : d)));   // (a NaN residual
+            // gives a NaN slope, as torch's backward does -- not -1: the optimiser's step guard sees a poisoned label through the gradient norm)
             g_out[i] = accumulate ? g_out[i] + gv : gv;             // accumulate: joins the PDE cotangent of the same points
         }
     }

@@ -18,6 +18,7 @@ from ..balance import LossBalance
 from ..causal import CausalWeights
 from ..losses.builder import builder_loss
 from ..model.physics_net import PhysicsNet
+from ..guard import StepGuard
 from ..optim import GROUP_KEYS, FusedClipAdam, resolve_param_groups
 from ..point_path import (balance_sumsq, balance_update, balanced_total, data_losses_batch, eval_step, eval_step_batch, grid_maps, label_errors,
                           LOSS_ORDER, OBS_ORDER, PackedField, pde_losses, pde_losses_batch, point_fields, point_sizes, PointConfig, require_gpu,
@@ -452,6 +453,26 @@ class InterfacePhysics(nn.Module):
                 raise ValueError('ema_weights: decay is required')
             return dict(decay=float(o['decay']), warmup=bool(o.get('warmup', True)))
         return _loop_option({'ema_weights': opt}, {}, 'ema_weights', 'optimizer', ('decay', 'warmup'), False, None, build)
+
+    def _step_guard_option(self, kwargs):
+        """The loops' `step_guard` option (keyword, or train_cfg['optimizer']['step_guard']): None (off), True (skip a step whose gradient norm is
+        non-finite), a guard.StepGuard, or a dict of spike_factor, spike_decay, spike_warmup, spike_patience (the spike rule on top) -> a
+        guard.StepGuard with the C ABI's argument rules."""
+        return _loop_option(kwargs, self.train_cfg, 'step_guard', 'optimizer', StepGuard.KEYS, True, StepGuard, lambda opt: StepGuard(**opt))
+
+    @staticmethod
+    def _step_guard_log(optimizer, prev):
+        """At a log step (the loop synchronises there anyway): the guard's counters as the extra keys of the log line and the metrics row, and the
+        (calls, skipped) pair the next log step compares with.  RuntimeError when every call since the previous log step was skipped: training is
+        stuck, and a run that silently does nothing is worse than one that stops."""
+        st = optimizer.guard_stats()
+        calls, skipped = int(optimizer.step_count), st['skipped_nonfinite'] + st['skipped_spike']
+        if calls > prev[0] and skipped - prev[1] == calls - prev[0]:
+            raise RuntimeError('step_guard: all %d optimiser steps since the previous log step were skipped (in total skipped_nonfinite %d, '
+                               'skipped_spike %d of %d calls; last norm %r, running norm %r): training is stuck'
+                               % (calls - prev[0], st['skipped_nonfinite'], st['skipped_spike'], calls, st['last'], st['running']))
+        row = {'skipped_nonfinite': st['skipped_nonfinite'], 'skipped_spike': st['skipped_spike'], 'running_norm': st['running']}
+        return row, (calls, skipped)
 
     def _lead_batch_option(self, kwargs):
         """The loops' `lead_batch` option (keyword, or train_cfg['train_data']['lead_batch']): samples per optimiser step, 1 when unset.  Refused
@@ -910,7 +931,8 @@ class InterfacePhysics(nn.Module):
     def build_optimizer(self, **overrides):
         """Fused clip + Adam over the PhysicsNet with the config's optimiser settings (cfg:151-155; `initial_lr` as :394 sets it), its flat
         gradient buffer laid out in backward-completion order (PhysicsNet.gradient_buckets).  The config's `ema_weights` entry is a loop option
-        (_ema_option), not an optimiser keyword: it becomes ema_decay / ema_warmup unless the overrides name those themselves.
+        (_ema_option), not an optimiser keyword: it becomes ema_decay / ema_warmup unless the overrides name those themselves.  Likewise
+        `step_guard` (config key or override; _step_guard_option): it becomes skip_nonfinite and the four spike keywords of FusedClipAdam.
         Fine-tuning (config keys or overrides): `freeze` = [fnmatch patterns on state-dict names] sets requires_grad_(False) on what they match;
         `param_groups` = [dict(match=[patterns], lr=..., weight_decay=..., betas=..., eps=...), ...] -- earlier groups win, the unmatched trainable
         parameters form the last group with the config's own values (optim.resolve_param_groups).  The optimiser then holds the trainable parameters
@@ -925,6 +947,9 @@ class InterfacePhysics(nn.Module):
             if ema is not None:
                 oc.update(ema_decay=ema['decay'], ema_warmup=ema['warmup'])
         oc.update(overrides)
+        guard = self._step_guard_option({'step_guard': oc.pop('step_guard', None)})
+        if guard is not None:
+            oc.update(skip_nonfinite=True, **guard.as_dict())
         freeze, groups = oc.pop('freeze', None), oc.pop('param_groups', None)
         net = self.physics_net
         if freeze:
@@ -1068,7 +1093,15 @@ class InterfacePhysics(nn.Module):
             self.physics_net.load_state_dict(state_dict['model'], strict=True)
         ema = self._ema_option(kwargs)                                  # None: the optimiser, the launches, the rows and the checkpoints of before
         tune = {k: kwargs[k] for k in ('freeze', 'param_groups') if kwargs.get(k)}      # fine-tuning: keywords win over train_cfg['optimizer']
+        guard = self._step_guard_option(kwargs)                         # None: likewise
+        if guard is not None:
+            tune['step_guard'] = guard
         optimizer = self.build_optimizer(**tune) if ema is None else self.build_optimizer(ema_decay=ema['decay'], ema_warmup=ema['warmup'], **tune)
+        if guard is not None and not (isinstance(optimizer, FusedClipAdam) and optimizer.step_guard is not None):
+            raise ValueError('step_guard: the guard lives inside the fused clip + Adam step (FusedClipAdam); the optimiser built here is %s'
+                             % type(optimizer).__name__)
+        guard_seen = (int(optimizer.step_count), 0) if guard is not None else None      # (calls, skipped) at the previous log step
+        self.last_step_guard = None
         if dist_mode:
             D.broadcast_parameters(self.physics_net)                    # DistributedDataParallel does this at wrap time (:903-907)
             sync = D.GradientAllReduce(optimizer)
@@ -1122,10 +1155,15 @@ class InterfacePhysics(nn.Module):
                 else:
                     loss, parts, gnorm, _ = self.training_step_batch(group, optimizer, with_pde=with_pde, grad_sync=sync)
                 last = {'loss': loss, 'parts': parts, 'grad_norm': gnorm}
+                guard_text = ''
+                if guard is not None and global_step % log_step == 1:   # read at log steps only; raises when every step since the last one was skipped
+                    self.last_step_guard, guard_seen = self._step_guard_log(optimizer, guard_seen)
+                    guard_text = ' skipped_nonfinite %d skipped_spike %d running_norm %.4g' % tuple(
+                        self.last_step_guard[k] for k in ('skipped_nonfinite', 'skipped_spike', 'running_norm'))
                 if rank == 0 and global_step % log_step == 1:
-                    print('epoch %d step %d loss %.6g %s%s' % (epoch, global_step, float(loss),
-                                                                ' '.join('%s %.4g' % (k, float(v)) for k, v in parts.items()),
-                                                                self._balance_log_text(balance is not None and with_pde)))
+                    print('epoch %d step %d loss %.6g %s%s%s' % (epoch, global_step, float(loss),
+                                                                  ' '.join('%s %.4g' % (k, float(v)) for k, v in parts.items()),
+                                                                  self._balance_log_text(balance is not None and with_pde), guard_text))
                 if global_step % log_step == 1:                       # (the loop synchronises here anyway: float(loss))
                     encoder_ops.check_enc_status()                                # an encoder weight outside the f16 hi+lo split's range raises HERE, named
                 if log_now:
@@ -1214,6 +1252,7 @@ class InterfacePhysics(nn.Module):
                     bins = (lc['inter'].numel() - 2) // 3
                     extra = {'causal_min_w': float(lc['inter'][3 * bins]), 'causal_w': lc['inter'][:bins].tolist()}
                 extra.update(m._balance_log(with_pde))       # the K balancing weights and gradient norms (likewise read here only)
+                extra.update(getattr(m, 'last_step_guard', None) or {})       # the step guard's counters and running norm (likewise)
                 self.log.event('training', epoch=epoch, global_step=global_step, train_loss=loss, forecast_hours=f_train, fps=fps, variables=train_vars,
                                **parts, **extra)
                 self.log.event('validation', epoch=epoch, global_step=global_step, forecast_hours=f_valid, fps=fps,
@@ -1257,6 +1296,14 @@ class InterfacePhysics(nn.Module):
         launch; both validation events run on it and their rows carry "weights": "ema" (train_vars stay on the raw weights), checkpoints gain
         `model_ema` -- a state dict of the PhysicsNet -- and `ema` = dict(decay, warmup, updates), and a resumed run takes the average and its
         update count from them; unset: the loop of before),
+        step_guard (None, True, a guard.StepGuard, or dict(spike_factor, spike_decay, spike_warmup, spike_patience): the fused optimiser step refuses,
+        on the device, an update whose total gradient norm is NaN / +-inf -- with a spike_factor also one above spike_factor times the running mean
+        of the applied steps' norms; a refused step leaves parameters, moments and the weight EMA bit for bit as they were, for the single-sample
+        step and the lead_batch step alike (a bad sample skips the whole step); the log line and the log-step row of metrics.jsonl gain
+        skipped_nonfinite, skipped_spike and running_norm, read at log steps only; RuntimeError when every step since the previous log step was
+        skipped; ValueError at loop start with an optimiser that is not a FusedClipAdam; the guard's state rides in the optimiser's state dict --
+        the loops' checkpoints hold no optimiser state, today as before; a loss that is non-finite while all gradients are finite is not seen;
+        unset: the loop of before),
         freeze ([fnmatch patterns on state-dict names]) and param_groups ([dict(match=[patterns], lr=..., weight_decay=..., betas=..., eps=...)]):
         fine-tuning, as train_cfg['optimizer'] takes them (build_optimizer) -- with checkpoint_path naming an existing checkpoint the run starts from
         its weights, frozen parameters stay bit-identical, the checkpoints written still hold the full model (and a complete model_ema), and the
@@ -1273,7 +1320,9 @@ class InterfacePhysics(nn.Module):
         lead_batch: every rank groups its OWN stream, and every optimiser step is a collective -- all ranks must form the same number of groups per
         epoch.  They do when all samples of the epoch have the same point counts (the sharding hands every rank the same number of samples; groups
         are then cut by count alone).  A source whose point counts vary from sample to sample can cut the ranks' streams differently, and the
-        rank with more groups would wait in its all-reduce for ever: give such a source to this loop only with lead_batch unset."""
+        rank with more groups would wait in its all-reduce for ever: give such a source to this loop only with lead_batch unset.
+        step_guard: the gradients are all-reduced before the norm is taken and the guard's state evolves from the norm alone, so every rank forms
+        the same verdict and the ranks stay in step without a collective of the guard's own.  This has not been run with more than one rank."""
         return self._run_train(True, **kwargs)
 
     # ------------------------------------------------------------------ inference loop (:1407-1530)

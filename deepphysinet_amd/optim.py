@@ -25,6 +25,16 @@ clip stays global (one max_norm, the norm over every optimised parameter) and so
 dpn_clip_adam_flat_groups (the same three launches; the update kernel looks up its tensor's group row), one group runs exactly the entry points it
 always ran.  The optimiser owns only the parameters it is given: a frozen parameter of the module has no slot, no moments and no shadow.
 `resolve_param_groups` turns name patterns (train_cfg['optimizer']['freeze'] / ['param_groups']) into those groups.
+
+Step guard (`skip_nonfinite`, `spike_factor`; off by default): the update is refused on the device when the total gradient norm is NaN / +-inf, or
+-- with a spike_factor -- more than spike_factor times the running mean of the applied steps' norms (after spike_warmup applied steps, at most
+spike_patience times in a row; guard.py states the rule).  It runs inside the same three launches (dpn_clip_adam_flat_guard: one thread of the
+reduction launch forms the verdict, the update launch returns early), so a step replayed from a hipGraph is guarded too.  A refused step leaves
+every byte of the parameters, the moments and the EMA shadow as it was; the device step counter `step_count` -- and `state[p]['step']`, which keeps
+pointing at it -- still advances: with the guard it counts CALLS, not updates (a sampler bound to it draws new points after a skipped step);
+`effective_step()` is the number of updates, the t of the bias corrections.  Without these options the optimiser makes exactly the calls it made
+before.  Not seen: a non-finite loss whose gradients are all finite; a finite |g| above about 1.8e19 overflows the fp32 partial and is skipped as
+non-finite.
 """
 import contextlib
 import ctypes
@@ -33,10 +43,14 @@ import math
 import weakref
 from collections import OrderedDict
 
+import warnings
+
+import numpy as np
 import torch
 
 from . import _lib as L
 from . import grad_arena
+from .guard import FIELDS as GUARD_FIELDS, StepGuard
 
 _CHUNK = 2048            # dpn_clip_adam_flat: every tensor is padded to whole 2048-element chunks
 MAX_GROUPS = 16          # dpn_clip_adam_flat_groups: kAdamMaxGroups
@@ -104,7 +118,11 @@ def resolve_param_groups(named_parameters, freeze=None, groups=None, defaults=No
 
 
 class FusedClipAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=2.5e7, layout=None, ema_decay=None, ema_warmup=True):
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=2.5e7, layout=None, ema_decay=None, ema_warmup=True,
+                 skip_nonfinite=False, spike_factor=None, spike_decay=0.99, spike_warmup=100, spike_patience=5):
+        # the step guard: a spike_factor implies the non-finite rule; neither: None, and step() never reaches dpn_clip_adam_flat_guard
+        self.step_guard = (StepGuard(spike_factor, spike_decay, spike_warmup, spike_patience)
+                           if (skip_nonfinite or (spike_factor is not None and float(spike_factor) != 0.0)) else None)
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, max_norm=float(max_norm))
         if ema_decay is not None:
             ema_decay = float(ema_decay)
@@ -177,6 +195,8 @@ class FusedClipAdam(torch.optim.Optimizer):
             self.ema = [self._ema_flat[o:o + p.numel()].view_as(p) for o, p in zip(self._offsets, self.params)]
             self.ema_base = torch.zeros(1, dtype=torch.int32, device=dev)       # EMA updates made before this optimiser was built (load_ema)
             self.reset_ema()
+        # DpnStepGuard on the device, zero-initialised: 6 int32 + 2 fp64 = 5 eight-byte words
+        self._guard = torch.zeros(5, dtype=torch.int64, device=dev) if self.step_guard is not None else None
         self.sync_hyper()
         grad_arena.register(self, self.params, self._offsets)
 
@@ -286,7 +306,20 @@ class FusedClipAdam(torch.optim.Optimizer):
         else:
             grad_arena.captured_step[0] = True      # replays of this step rewrite the parameters without passing through here
         lib = L.load()
-        if len(self.param_groups) > 1:
+        if self.step_guard is not None:
+            # one path for one group or several, with or without EMA, eager or captured
+            ema, grouped, sg = self._ema_flat is not None, len(self.param_groups) > 1, self.step_guard
+            L.check(lib.dpn_clip_adam_flat_guard(len(self.params), self._p, self._g, self._numel, ctypes.c_void_p(self._m_flat.data_ptr()),
+                                                 ctypes.c_void_p(self._v_flat.data_ptr()), ctypes.c_void_p(self._sumsq.data_ptr()),
+                                                 ctypes.c_void_p(self.step_count.data_ptr()), self._group_of if grouped else None,
+                                                 len(self.param_groups), ctypes.c_void_p(self._hyper.data_ptr()),
+                                                 ctypes.c_void_p(self.grad_norm.data_ptr()),
+                                                 ctypes.c_void_p(self._ema_flat.data_ptr()) if ema else None,
+                                                 ctypes.c_void_p(self.ema_base.data_ptr()) if ema else None, int(self.ema_warmup),
+                                                 ctypes.c_void_p(self._guard.data_ptr()), sg.spike_factor, sg.spike_decay, sg.spike_warmup,
+                                                 sg.spike_patience, torch.cuda.current_stream().cuda_stream),
+                    'dpn_clip_adam_flat_guard')
+        elif len(self.param_groups) > 1:
             ema = self._ema_flat is not None
             L.check(lib.dpn_clip_adam_flat_groups(len(self.params), self._p, self._g, self._numel, ctypes.c_void_p(self._m_flat.data_ptr()),
                                                   ctypes.c_void_p(self._v_flat.data_ptr()), ctypes.c_void_p(self._sumsq.data_ptr()),
@@ -314,6 +347,32 @@ class FusedClipAdam(torch.optim.Optimizer):
         self.steps_done += 1
         return self.grad_norm if closure is None else loss
 
+    # ---- step guard ----------------------------------------------------------------------------------------------------
+    def guard_stats(self):
+        """The DpnStepGuard struct as a dict (skipped_nonfinite, skipped_spike, verdict, seen, consecutive, reserved, running, last).  Reads the
+        device, so it synchronises: meant for log steps."""
+        if self._guard is None:
+            raise RuntimeError('FusedClipAdam.guard_stats: the optimiser was built without skip_nonfinite / spike_factor')
+        raw = self._guard.cpu().numpy()
+        ints, dbl = raw.view(np.int32), raw.view(np.float64)
+        out = {k: int(ints[i]) for i, k in enumerate(GUARD_FIELDS[:6])}
+        out.update(running=float(dbl[3]), last=float(dbl[4]))
+        return out
+
+    def _load_guard(self, stats):
+        raw = np.zeros(5, np.int64)
+        if stats is not None:
+            raw.view(np.int32)[:6] = [int(stats.get(k, 0)) for k in GUARD_FIELDS[:6]]
+            raw.view(np.float64)[3:] = [float(stats.get('running', 0.0)), float(stats.get('last', 0.0))]
+        self._guard.copy_(torch.from_numpy(raw))
+
+    def effective_step(self):
+        """The number of updates applied, the t of the bias corrections: the device step counter minus the skipped calls (reads the device)."""
+        if self._guard is None:
+            return int(self.step_count)
+        st = self.guard_stats()
+        return int(self.step_count) - st['skipped_nonfinite'] - st['skipped_spike']
+
     # ---- weight EMA ----------------------------------------------------------------------------------------------------
     def _need_ema(self, what):
         if self._ema_flat is None:
@@ -329,9 +388,10 @@ class FusedClipAdam(torch.optim.Optimizer):
             s.copy_(p.detach())
 
     def ema_updates(self):
-        """EMA updates made so far: the device step counter plus `ema_base` (reads the device)."""
+        """EMA updates made so far: the applied steps (the device step counter, without the calls the step guard skipped) plus `ema_base` (reads
+        the device)."""
         self._need_ema('ema_updates')
-        return int(self.step_count) + int(self.ema_base)
+        return self.effective_step() + int(self.ema_base)
 
     def bind_module(self, module):
         """The module whose parameter names `load_ema` uses (kept as a weak reference)."""
@@ -393,7 +453,7 @@ class FusedClipAdam(torch.optim.Optimizer):
                 raise ValueError('FusedClipAdam.load_ema: %s has shape %s, expected %s' % (k, tuple(state_dict[k].shape), tuple(s.shape)))
         for k, s in names.items():
             s.copy_(state_dict[k])
-        self.ema_base.fill_(int(updates) - int(self.step_count))
+        self.ema_base.fill_(int(updates) - self.effective_step())
 
     # ---- checkpoints ---------------------------------------------------------------------------------------------------
     def state_dict(self):
@@ -409,6 +469,8 @@ class FusedClipAdam(torch.optim.Optimizer):
             for k, p in enumerate(p for g in self.param_groups for p in g['params']):
                 sd['state'][k]['ema'] = shadow[id(p)].detach().clone()
             sd['ema_updates'] = self.ema_updates()
+        if self._guard is not None:                 # the guard's struct and its parameters: a resumed run keeps its running mean and its counts
+            sd['step_guard'] = dict(self.step_guard.as_dict(), state=self.guard_stats())
         return sd
 
     def load_state_dict(self, state_dict):
@@ -416,8 +478,12 @@ class FusedClipAdam(torch.optim.Optimizer):
         if self._ema_swapped:
             raise RuntimeError('FusedClipAdam.load_state_dict inside ema_weights()')
         ema_updates = state_dict.get('ema_updates')
-        if ema_updates is not None:                 # torch's load_state_dict knows 'state' and 'param_groups' only
-            state_dict = {k: v for k, v in state_dict.items() if k != 'ema_updates'}
+        saved_guard = state_dict.get('step_guard')
+        if ema_updates is not None or saved_guard is not None:      # torch's load_state_dict knows 'state' and 'param_groups' only
+            state_dict = {k: v for k, v in state_dict.items() if k not in ('ema_updates', 'step_guard')}
+        if saved_guard is not None and self._guard is None:
+            warnings.warn('FusedClipAdam.load_state_dict: the state dict carries a step guard (%d + %d skipped calls), this optimiser was built '
+                          'without one: ignored' % (saved_guard['state']['skipped_nonfinite'], saved_guard['state']['skipped_spike']))
         super().load_state_dict(state_dict)
         for g in self.param_groups:                 # a torch.optim.Adam state dict has no 'max_norm' (load_state_dict replaces the groups wholesale)
             for k, v in self.defaults.items():
@@ -440,9 +506,11 @@ class FusedClipAdam(torch.optim.Optimizer):
             self.state[p] = {'step': self.step_count, 'exp_avg': m, 'exp_avg_sq': v}
         if step is not None:
             self.step_count.fill_(int(float(step)))
+        if self._guard is not None:                 # a state dict without the guard: a zeroed one (every call so far counts as applied)
+            self._load_guard(None if saved_guard is None else saved_guard['state'])
         if shadow:
             if have_ema:
-                self.ema_base.fill_(int(ema_updates) - int(self.step_count))
+                self.ema_base.fill_(int(ema_updates) - self.effective_step())
             else:
                 self.reset_ema()
                 self.ema_base.zero_()

@@ -496,6 +496,45 @@ int dpn_clip_adam_flat_ema(int n_tensors, float* const* params, const float* con
 int dpn_clip_adam_flat_groups(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
                               float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const uint8_t* group_of, int n_groups,
                               const float* hyper_dev, float* out_norm_dev, float* ema_flat, const int* ema_base_dev, int ema_warmup, void* stream);
+/* The step guard: dpn_clip_adam_flat_groups that refuses a step whose gradient norm is non-finite or a spike, on the device, inside the same three
+ * launches (a step replayed from a hipGraph cannot ask the host).  The state lives in device memory, zero-initialised by the caller: */
+typedef struct DpnStepGuard {
+    int32_t skipped_nonfinite;   /* calls whose total norm was NaN or +-inf                          */
+    int32_t skipped_spike;       /* calls skipped as a spike                                         */
+    int32_t verdict;             /* the last call: 0 applied, 1 non-finite, 2 spike                  */
+    int32_t seen;                /* applied steps that have entered `running` (saturating)           */
+    int32_t consecutive;         /* spike verdicts in a row up to and including the last call        */
+    int32_t reserved;
+    double  running;             /* running mean of the applied steps' total norms                   */
+    double  last;                /* (double) of the last call's fp32 total norm                      */
+} DpnStepGuard;
+/* Arguments of dpn_clip_adam_flat_groups plus guard_dev and the spike rule (spike_factor = 0: off).  group_of NULL: one group, hyper_dev is one row
+ * of 8 and n_groups is not read.  ema_flat NULL: no EMA.  Three launches per 160 tensors, no atomics, every sum in the order of the other entry
+ * points; the gradient-norm launch is theirs.  *step_dev is bumped on EVERY call, applied or not (a sampler bound to it draws new points after a
+ * skipped step).  One thread of the reduction launch forms the verdict from total = (float)sqrt(sumsq) * hyper_dev[6], the fp32 total exactly as the
+ * update forms it; fp64, every operation rounded once, no contraction:
+ *     !(fabsf(total) <= FLT_MAX)                                  verdict 1: skipped_nonfinite += 1, consecutive = 0
+ *     else spike_factor > 0 && seen >= spike_warmup && (double)total > spike_factor * running && consecutive < spike_patience
+ *                                                                 verdict 2: skipped_spike += 1, consecutive += 1
+ *     else                                                        verdict 0: if consecutive == spike_patience (the guard is overruled: the level
+ *                                                                 of the norms has moved for good) seen = 0; then
+ *                                                                 running = seen == 0 ? total : spike_decay * running + (1 - spike_decay) * total,
+ *                                                                 seen += 1 (saturating), consecutive = 0
+ *     last = total in every case; running and seen move on verdict 0 only.
+ * Update launches (all of them obey the one verdict): verdict != 0 -- every block returns without reading or writing p, m, v or the shadow;
+ * *out_norm_dev is still written (the norm that was refused).  verdict 0 -- the arithmetic of the unguarded kernels with the step number
+ * t = *step_dev - skipped_nonfinite - skipped_spike in both bias corrections and in the EMA's te = t + base.
+ * Contracts: (1) while no call has been skipped, p, m, v, the shadow, *out_norm_dev and *step_dev come out bit-identical to dpn_clip_adam_flat_dev,
+ * _ema or _groups on the same inputs; (2) after k skips an applied call is bit-identical to the unguarded entry called from the same state with its
+ * step counter k lower (with EMA, te lower by k as well); (3) a skipped call leaves every byte of p, m, v and the shadow as it was.
+ * What the guard does not see: a loss that is non-finite while all gradients are finite; and a finite gradient whose square overflows the fp32
+ * per-thread partial (|g| above about 1.8e19) gives an infinite total and is skipped as non-finite.
+ * -1 (nothing launched, nothing written, *step_dev included): guard_dev or hyper_dev NULL, spike_factor negative or not finite, spike_decay outside
+ * [0, 1), spike_warmup < 1, spike_patience < 1, and everything dpn_clip_adam_flat_groups refuses (with group_of NULL its group checks do not apply). */
+int dpn_clip_adam_flat_guard(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
+                             float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const uint8_t* group_of, int n_groups,
+                             const float* hyper_dev, float* out_norm_dev, float* ema_flat, const int* ema_base_dev, int ema_warmup,
+                             DpnStepGuard* guard_dev, double spike_factor, double spike_decay, int spike_warmup, int spike_patience, void* stream);
 /* Exchanges every parameter with its shadow in ema_flat in place, bit for bit (validation and inference on the averaged weights without a second
  * model): one launch per 160 tensors over the same chunk table; the padding of ema_flat and everything outside the tensors stay untouched; two
  * calls are the identity.  -1: n_tensors <= 0, a NULL pointer, a numel outside 1 .. 2^31 - 1. */

@@ -3,6 +3,7 @@
 
     python train.py [--config_file cfg.py] [--checkpoint_path DIR] [--log_path DIR] [--dist] [--max_steps N] [--synthetic] [--valid_synthetic]
                     [--adaptive_interior] [--causal_weights EPS] [--balance_losses EVERY] [--lead_batch K] [--ema DECAY]
+                    [--skip_nonfinite] [--spike_factor F [--spike_warmup N] [--spike_patience N]]
                     [--freeze PATTERN]... [--param_group 'PATTERN[,PATTERN...]:lr=...,weight_decay=...']...
 
 The reference reads the config with mmcv.Config.fromfile (absent here, and moved to mmengine in the pinned mmcv: SURVEY section 0, defect
@@ -49,6 +50,27 @@ parse.add_argument('--lead_batch', default=None, type=int, metavar='K', help='K 
                    'per step); not together with --causal_weights / --balance_losses')
 parse.add_argument('--ema', default=None, type=float, metavar='DECAY', help='keep an exponential moving average of the weights inside the optimiser step '
                    '(ema_weights=dict(decay=DECAY, warmup=True)): validation runs on it and the checkpoints carry it as model_ema (infer.py --ema)')
+parse.add_argument('--skip_nonfinite', action='store_true', help='skip, on the device, every optimiser step whose total gradient norm is NaN or +-inf: '
+                   'parameters, moments and the weight EMA stay bit for bit as they were (step_guard=True)')
+parse.add_argument('--spike_factor', default=None, type=float, metavar='F', help='also skip a step whose gradient norm exceeds F times the running mean of '
+                   'the applied steps\' norms (step_guard=dict(spike_factor=F, ...); implies --skip_nonfinite)')
+parse.add_argument('--spike_warmup', default=None, type=int, metavar='N', help='applied steps before the spike rule starts (default 100)')
+parse.add_argument('--spike_patience', default=None, type=int, metavar='N', help='spikes in a row after which the guard is overruled and the running mean '
+                   'starts again (default 5)')
+
+
+def step_guard_arg(args):
+    """The `step_guard` option of the loops from the four flags: None, True, or a dict of the spike settings."""
+    if args.spike_factor is None:
+        if args.spike_warmup is not None or args.spike_patience is not None:
+            raise SystemExit('--spike_warmup / --spike_patience need --spike_factor')
+        return True if args.skip_nonfinite else None
+    opt = dict(spike_factor=args.spike_factor)
+    if args.spike_warmup is not None:
+        opt['spike_warmup'] = args.spike_warmup
+    if args.spike_patience is not None:
+        opt['spike_patience'] = args.spike_patience
+    return opt
 
 
 def param_group_arg(text):
@@ -119,6 +141,8 @@ if __name__ == '__main__':
         kwargs['lead_batch'] = args.lead_batch
     if args.ema is not None:
         kwargs['ema_weights'] = dict(decay=args.ema, warmup=True)
+    if step_guard_arg(args) is not None:
+        kwargs['step_guard'] = step_guard_arg(args)
     if args.freeze:
         kwargs['freeze'] = args.freeze
     if args.param_group:
