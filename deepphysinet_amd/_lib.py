@@ -180,6 +180,8 @@ EXPORTS = {
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dpn_fields_out': (c_int, [c_void_p, c_int64, POINTER(DpnPhysics), c_int, c_void_p, c_void_p, POINTER(DpnLattice), c_int64, c_void_p]),
     'dpn_residual_points': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(DpnGeometry), POINTER(DpnPhysics), c_void_p, c_void_p]),
+    'dpn_diagnostics_out': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(DpnPhysics), c_int, POINTER(c_int32), c_int, c_void_p, c_void_p,
+                                    POINTER(DpnLattice), c_int64, c_void_p]),
     'dpn_label_errors_blocks': (c_int64, [c_int64]),
     'dpn_label_errors': (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(DpnPhysics), c_float, c_int, c_void_p, c_void_p]),
     'dpn_label_errors_finish': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
@@ -218,6 +220,7 @@ EXPORTS = {
 
 STEP_LOSSES = 16              # one field's row of dpn_step_finish_batch (include/dpn_hip.h)
 
+DIAG_PRODUCTS = 28            # DPN_DIAG_PRODUCTS (include/dpn_hip.h)
 CAUSAL_MAX_BINS = 64          # DPN_CAUSAL_MAX_BINS (include/dpn_hip.h)
 BALANCE_MAX_TERMS, BALANCE_STEP_TERMS = 16, 13          # DPN_BALANCE_MAX_TERMS, DPN_BALANCE_STEP_TERMS (include/dpn_hip.h)
 

@@ -13,7 +13,7 @@ LIB = os.path.join(HERE, 'libdpn_hip.so')
 
 # (source, extra flags, object name).  One unit per kernel family.  Only the point forward / backward kernels are compiled with MFMA results
 # in VGPRs (no v_accvgpr_read per epilogue element: forward kernel -10 %); the weight-gradient kernel, the GEMMs and the optimiser measure
-# better with hipcc's default AGPR accumulators.  tools/variant_build.py --unit=I and EXP_UNITS address units by index: units 0 .. 10 keep theirs.
+# better with hipcc's default AGPR accumulators.  tools/variant_build.py --unit=I and EXP_UNITS address units by index: units 0 .. 11 keep theirs.
 # dpn_causal.hip stays the LAST entry (tests/test_causal_cpu.py holds it there): a new unit goes in directly in front of it.
 def _src(name):
     return os.path.join(HERE, 'csrc', name)
@@ -31,6 +31,7 @@ UNITS = [(_src('dpn_point.hip'), ['-mllvm', '-amdgpu-mfma-vgpr-form'], 'dpn_poin
          (_src('dpn_gemm.hip'), [], 'dpn_gemm.o'),        # the exact-fp32 GEMM family
          (_src('dpn_optim.hip'), [], 'dpn_optim.o'),      # fused clip + Adam
          (_src('dpn_balance.hip'), [], 'dpn_balance.o'),  # loss balancing by gradient norms
+         (_src('dpn_diag.hip'), [], 'dpn_diag.o'),        # derived diagnostics from the Jacobian (inference)
          (_src('dpn_causal.hip'), [], 'dpn_causal.o')]    # per-point weights and causal time weighting of the PDE losses
 SRCS = [u[0] for u in UNITS]
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC']

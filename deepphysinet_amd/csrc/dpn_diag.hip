@@ -1,0 +1,100 @@
+// Derived diagnostics from the fields and their coordinate Jacobian (DESIGN.md section 6b, item f3 continued): the 18 derivatives themselves, relative
+// and absolute vorticity, divergence, Dp/Dt, temperature and moisture advection, moisture-flux divergence, wind speed, relative humidity and total
+// deformation, at stations (rows) or on a lattice (maps).  include/dpn_hip.h states every product's expression and its order of operations.
+//   dpn_diagnostics_out : the residual body per point (dpn_residual_body.inc: inverse_norm, the optional clip, the chained Jacobian J, omega, q_s), then
+//                         the selected products, one thread per point, wave64, 256 threads per block.
+// The whole kernel is compiled without contraction: every fp32 operation is rounded on its own, so a numpy float32 restatement
+// (deepphysinet_amd/diagnostics.py) reproduces every product that does not go through expf bit for bit.  No atomics, no LDS; the products leave through
+// plain per-lane stores: in map mode lane l of a wave writes place r + l of a product's plane (stores run along ix), in row mode a point's row.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/dpn_hip.h"
+
+namespace {
+
+constexpr int THREADS = 256;
+
+struct DiagArgs {
+    const float *out_n, *jac_n, *f;
+    int64_t n, first, plane;          // plane = nx * ny (map mode)
+    DpnPhysics ph;
+    int32_t n_products;
+    int32_t id[DPN_DIAG_PRODUCTS];    // the column selector, in output order
+    float *rows, *maps;
+};
+
+__global__ __launch_bounds__(THREADS) void dpn_diagnostics_kernel(DiagArgs a) {
+#pragma clang fp contract(off)
+    const int64_t ic = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    if (ic >= a.n) return;
+#include "dpn_residual_body.inc"
+    const float zeta = J[1][0] - J[0][1];
+    const float div = J[0][0] + J[1][1];
+    const float adv_T = u * J[3][0] + v * J[3][1];
+    const float adv_q = u * J[4][0] + v * J[4][1];
+    const float stretch = J[0][0] - J[1][1], shear = J[1][0] + J[0][1];
+    // A point with a NaN among its six normalised fields (a lattice point outside the coarse cube) is NaN in every product.  The arithmetic alone
+    // does not see to that: the forward kernel's ReLU masks are off where a pre-activation is NaN, so its Jacobian is finite there, and the clip
+    // sends a NaN value to its lower bound.
+    bool poisoned = false;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) { const float o_n = a.out_n[ic * 6 + k]; poisoned |= o_n != o_n; }
+    float* dst;
+    int64_t stride;
+    if (a.rows) {
+        dst = a.rows + ic * a.n_products;
+        stride = 1;
+    } else {                                                  // point g of the lattice: plane it, place r; product j of it lies at plane it * P + j
+        const int64_t g = a.first + ic, it = g / a.plane, r = g - it * a.plane;
+        dst = a.maps + it * a.n_products * a.plane + r;
+        stride = a.plane;
+    }
+    for (int j = 0; j < a.n_products; ++j) {                  // the selector is uniform: a scalar branch per product
+        float o;
+        switch (a.id[j]) {
+#define DPN_DIAG_J(k) case 3 * k: o = J[k][0]; break; case 3 * k + 1: o = J[k][1]; break; case 3 * k + 2: o = J[k][2]; break;
+            DPN_DIAG_J(0) DPN_DIAG_J(1) DPN_DIAG_J(2) DPN_DIAG_J(3) DPN_DIAG_J(4) DPN_DIAG_J(5)
+#undef DPN_DIAG_J
+            case 18: o = zeta; break;
+            case 19: o = zeta + fc; break;
+            case 20: o = div; break;
+            case 21: o = omega; break;
+            case 22: o = -adv_T; break;
+            case 23: o = -adv_q; break;
+            case 24: o = q * div + adv_q; break;
+            case 25: o = sqrtf(u * u + v * v); break;
+            case 26: o = q / q_s; break;
+            default: o = sqrtf(stretch * stretch + shear * shear); break;      // 27 (the entry point admits 0..27 only)
+        }
+        dst[j * stride] = poisoned ? __builtin_nanf("") : o;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int dpn_diagnostics_out(const float* out_n, const float* jac_n, const float* f, int64_t n, const DpnPhysics* phys, int with_clip,
+                        const int32_t* products, int n_products, float* rows, float* maps, const DpnLattice* lattice, int64_t first, void* stream) {
+    if (!out_n || !jac_n || !f || !phys || !products || n <= 0 || n_products < 1 || n_products > DPN_DIAG_PRODUCTS) return -1;
+    if ((rows != nullptr) == (maps != nullptr)) return -1;
+    DiagArgs a{out_n, jac_n, f, n, 0, 1, *phys, n_products, {}, rows, maps};
+    for (int j = 0; j < n_products; ++j) {
+        if (products[j] < 0 || products[j] >= DPN_DIAG_PRODUCTS) return -1;
+        a.id[j] = products[j];
+    }
+    if (maps) {
+        if (!lattice || lattice->nx < 1 || lattice->ny < 1 || lattice->nt < 1 || first < 0) return -1;
+        a.plane = (int64_t)lattice->nx * lattice->ny;
+        if (first + n > a.plane * lattice->nt) return -1;
+        a.first = first;
+    } else if (lattice) {
+        return -1;
+    }
+    if (!with_clip)
+        for (int k = 0; k < 6; ++k) a.ph.clip_on[k] = 0;                  // the body then neither clips nor masks
+    hipLaunchKernelGGL(dpn_diagnostics_kernel, dim3((unsigned)((n + THREADS - 1) / THREADS)), dim3(THREADS), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+}  // extern "C"

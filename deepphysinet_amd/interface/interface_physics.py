@@ -16,6 +16,7 @@ import torch.nn as nn
 
 from ..balance import LossBalance
 from ..causal import CausalWeights
+from ..diagnostics import product_ids
 from ..losses.builder import builder_loss
 from ..model.physics_net import PhysicsNet
 from ..guard import StepGuard
@@ -74,6 +75,7 @@ class InterfacePhysics(nn.Module):
         self.precision = L.PREC_NAMES[precision]
         self._cfg_cache = None
         self.loss_balance_state = None          # training_step(balance=...): {'groups', 'lam' (fp32 [K], device), 'step', 'diag' (device or None)}
+        self.last_diagnostics = None            # run_inference_interface with log.export_diagnostic: {'names', 'maps' [nt, P, ny, nx]} of the last sample
 
     # ------------------------------------------------------------------ configuration of the HIP path
     def point_config(self, loss_factor=None, criterion=None) -> PointConfig:
@@ -308,6 +310,7 @@ class InterfacePhysics(nn.Module):
     INFER_BUDGET_BYTES = 256 << 20      # per-point buffers of one chunk of a lattice evaluation (the packed weights and the output maps come on top)
     FIELD_POINT_BYTES = 4 * (4 + 6 + 6)                 # x, y, t, f | coord_data | out_n
     RESIDUAL_POINT_BYTES = 4 * (4 + 6 + 6 + 18 + 6)     # ... | Jacobian | residual rows
+    DIAG_POINT_BYTES = 4 * (4 + 6 + 6 + 18)             # ... | Jacobian (the products go straight into the output maps)
 
     @staticmethod
     def chunk_size(n_points, chunk_points=None, point_bytes=FIELD_POINT_BYTES, prec=L.PREC_BF16X2):
@@ -398,6 +401,31 @@ class InterfacePhysics(nn.Module):
         if fac is not None:
             rows *= fac
         return rows.view(lattice.nt, lattice.ny, lattice.nx, 6).permute(0, 3, 1, 2).contiguous()
+
+    @torch.no_grad()
+    def diagnostics_at(self, field_data, sampler, x_idx, y_idx, hours, forecast_h, products, with_clip=False, lonlat=False):
+        """Derived diagnostics [N, P] at N stations (positions as predict_points takes them): `products`, a sequence of names of
+        deepphysinet_amd.diagnostics.PRODUCTS -- the 18 derivatives du_dx .. drho_dt of the physical fields with respect to x (m), y (m), t (s),
+        vorticity, abs_vorticity, divergence, omega (Dp/Dt), t_advection, q_advection, q_flux_divergence, speed, rel_humidity, deformation --, formed
+        on the device from the Jacobian the forward kernel computes (dpn_diagnostics_out).  Evaluated without the clip, as predict_points is by
+        default; with_clip applies the training clip of P, T, q, rho (a clipped variable has zero derivatives where it is clipped)."""
+        ids = product_ids(products)
+        x, y, t, cd, f = self._station_inputs(sampler, x_idx, y_idx, hours, lonlat)
+        rows = torch.empty((x.shape[0], len(ids)), dtype=torch.float32, device=x.device)
+        self._inference_weights(field_data, forecast_h, x.shape[0]).diagnostics(x, y, t, f, cd, ids, with_clip, rows=rows)
+        return rows
+
+    @torch.no_grad()
+    def diagnostic_lattice(self, field_data, sampler, lattice, forecast_h, products, with_clip=False, chunk_points=None):
+        """diagnostics_at on a lattice, as maps [nt, P, ny, nx]; chunked as predict_lattice is (every chunk writes its places of the one output).  NaN
+        where the lattice leaves the coarse cube."""
+        ids = product_ids(products)
+        chunk = self.chunk_size(lattice.n_points, chunk_points, self.DIAG_POINT_BYTES, self.precision)
+        field = self._inference_weights(field_data, forecast_h, chunk)
+        maps = torch.empty((lattice.nt, len(ids), lattice.ny, lattice.nx), dtype=torch.float32, device=field_data.device)
+        for first, n, x, y, t, f, cd in self._lattice_chunks(sampler, lattice, chunk):
+            field.diagnostics(x, y, t, f, cd, ids, with_clip, maps=maps, lattice=lattice, first=first)
+        return maps
 
     @torch.no_grad()
     def adaptive_interior(self, batch: dict, sampler, pool_factor=8, k=1.0, c=1.0):
@@ -1356,6 +1384,10 @@ class InterfacePhysics(nn.Module):
         log.write_source one `<time>_<variable>.npy` [lat, lon] per time step and exported variable goes to log.result_path (start_time only labels
         the files).  Returns the maps [nt, 6, ny, nx] of the last sample (None without samples).  kwargs: checkpoint_path, samples, device, with_clip,
         weights ('ema': the checkpoint's averaged weights `model_ema` in place of `model`; KeyError when it carries none).
+        log.export_diagnostic (a list of names of deepphysinet_amd.diagnostics.PRODUCTS, default absent: no further call): per sample ONE
+        diagnostic_lattice call on the same lattice with the same with_clip, with log.write_source one `<time>_<name>.npy` [lat, lon] per time step and
+        product next to the variables' files; the last sample's {'names', 'maps' [nt, P, ny, nx]} stay in self.last_diagnostics (None without the key
+        or without samples).  An unknown name is a KeyError before the checkpoint is read.
         Plotting (log.with_vis: Basemap) is not built."""
         import datetime
         ic = self.inference_cfg or {}
@@ -1383,6 +1415,10 @@ class InterfacePhysics(nn.Module):
         for v in export_variable:
             if v.upper() not in names:
                 raise KeyError('export_variable %r: one of %s' % (v, sorted(names)))
+        export_diagnostic = list(log.get('export_diagnostic') or [])
+        if export_diagnostic:
+            product_ids(export_diagnostic)                                # an unknown name: KeyError, before the checkpoint is read
+        self.last_diagnostics = None
         self.physics_net.to(device)
         self.pe.to(device)
         state_dict, current_epoch, global_step = (None, 0, 0) if not checkpoint_path else self.load_model(checkpoint_path, prefix='physics', map_location=device)
@@ -1414,13 +1450,21 @@ class InterfacePhysics(nn.Module):
             lattice = sampler.lattice(refine=refine, hours=(0.0, dt / 3600.0, nt))
             maps = self.predict_lattice(smp['field_data'].to(device), sampler, lattice, smp['forecast_h'].to(device),
                                         with_clip=kwargs.get('with_clip', self.with_clip))
+            diag = None
+            if export_diagnostic:
+                diag = self.diagnostic_lattice(smp['field_data'].to(device), sampler, lattice, smp['forecast_h'].to(device), export_diagnostic,
+                                               with_clip=kwargs.get('with_clip', self.with_clip))
+                self.last_diagnostics = dict(names=list(export_diagnostic), maps=diag)
             if write_source:
                 import numpy as np
                 host = maps.cpu().numpy()
+                host_diag = None if diag is None else diag.cpu().numpy()
                 for it in range(nt):
                     stamp = (start + datetime.timedelta(seconds=k * window_h * 3600.0 + it * dt)).strftime('%Y-%m-%d_%H_%M_%S')
                     for v in export_variable:
                         np.save(os.path.join(result_path, '%s_%s.npy' % (stamp, v)), host[it, names[v.upper()]])
+                    for j, name in enumerate(export_diagnostic):
+                        np.save(os.path.join(result_path, '%s_%s.npy' % (stamp, name)), host_diag[it, j])
         return maps
 
 

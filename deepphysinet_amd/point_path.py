@@ -1302,6 +1302,18 @@ class PackedField:
         L.check(L.load().dpn_residual_points(_ptr(out_n), _ptr(jac_n), _ptr(f), out_n.shape[0], ctypes.byref(geo), ctypes.byref(ph), _ptr(res),
                                              _stream()), 'dpn_residual_points')
 
+    def diagnostics(self, x, y, t, f, coord_data, products, with_clip=False, rows=None, maps=None, lattice=None, first=0):
+        """Derived diagnostics (dpn_diagnostics_out; deepphysinet_amd.diagnostics.PRODUCTS) at points x, y, t, f [n], coord_data [n, 6]: `products`, a
+        sequence of P product ids, into rows [n, P], or into the places of points first .. first + n of `lattice` in maps [nt, P, ny, nx]."""
+        out_n, jac_n = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=True, want_saved=False)
+        ph = self.cfg.physics()
+        for k in range(2, L.NETS):                             # `with_clip` is this call's own, as `fields` takes it: the training clip of P, T, q, rho
+            ph.clip_on[k] = int(bool(with_clip) and bool(self.cfg.clip_vars[k]))
+        ids = (ctypes.c_int32 * len(products))(*products)
+        lat = None if lattice is None else ctypes.byref(lattice.c_struct())
+        L.check(L.load().dpn_diagnostics_out(_ptr(out_n), _ptr(jac_n), _ptr(f), out_n.shape[0], ctypes.byref(ph), int(bool(with_clip)), ids, len(ids),
+                                             _ptr(rows), _ptr(maps), lat, first, _stream()), 'dpn_diagnostics_out')
+
     def residual_scores(self, x, y, t, f, coord_data, factors, k=1.0):
         """Scores of a pool of candidate points for residual-weighted sampling (CollocationSampler.get_inter_data_adaptive): `residuals` on the m
         points, then dpn_adaptive_scores -- score_i = sum_e factors[e] * res_ie ** 2 in fp64, factors = six floats in LOSS_ORDER.  Returns

@@ -454,6 +454,36 @@ int dpn_label_errors_finish(const double* partials, int64_t n_points, int segmen
  * factor_i * mean(res_i ** 2) is dpn_residual's MSE loss term.  Inputs as dpn_residual (phys->clip_on etc. apply; the criterion is not read). */
 int dpn_residual_points(const float* out_n, const float* jac_n, const float* f, int64_t n_points, const DpnGeometry* geo, const DpnPhysics* phys,
                         float* res, void* stream);
+/* Derived diagnostics from the fields and their coordinate Jacobian (csrc/dpn_diag.hip): out_n, jac_n, f, phys as dpn_residual_points (geometry and
+ * criterion are not read).  Per point the residual body forms val = inverse_norm(out_n) (u, v, p, T, q, rho = val[0..5]) and
+ * J[k][c] = jac_n[k][c] * d val_k / d out_k, the derivative of the de-normalised variable k with respect to x (m), y (m), t (s) for c = 0, 1, 2.
+ * with_clip == 0: the clip of *phys is switched off (in the entry point's own copy), nothing is clipped or masked -- inference, as dpn_fields_out
+ * with with_clip == 0; with_clip != 0: the body as training runs it, a clipped variable has J[k][.] = 0 where it is clipped.
+ * products = n_products (1..DPN_DIAG_PRODUCTS) HOST ids, the column selector; ids may repeat and come in any order.  Every operation below is one
+ * fp32 operation rounded on its own (the kernel is compiled without contraction), evaluated left to right as written:
+ *   3 k + c (0..17)  du_dx du_dy du_dt dv_dx .. drho_dt    J[k][c]
+ *   18  vorticity           J[1][0] - J[0][1]
+ *   19  abs_vorticity       (J[1][0] - J[0][1]) + f
+ *   20  divergence          J[0][0] + J[1][1]
+ *   21  omega               (J[2][2] + u * J[2][0]) + v * J[2][1]                          (Dp/Dt, Pa/s: the body's omega)
+ *   22  t_advection         -(u * J[3][0] + v * J[3][1])
+ *   23  q_advection         -(u * J[4][0] + v * J[4][1])
+ *   24  q_flux_divergence   q * (J[0][0] + J[1][1]) + (u * J[4][0] + v * J[4][1])
+ *   25  speed               sqrtf(u * u + v * v)
+ *   26  rel_humidity        q / q_s;  tc = T - 273.15f, e_s = ((6.112f * expf((17.67f * tc) / (tc + 243.5f))) * 100.f),
+ *                           q_s = max((0.622f * e_s) / (p - 0.378f * e_s), 1e-6f), a NaN passing through (the body's q_s: get_qs)
+ *   27  deformation         sqrtf((J[0][0] - J[1][1]) * (J[0][0] - J[1][1]) + (J[1][0] + J[0][1]) * (J[1][0] + J[0][1]))
+ * Exactly one destination: rows[n][n_products] (stations; lattice = NULL), or maps[nt][n_products][ny][nx] where the n points are points
+ * first .. first + n of *lattice (stores run along ix; a chunk may begin and end anywhere in a plane).  No atomics.
+ * NaN: a point with a NaN among its six out_n is NaN in EVERY product (a lattice point outside the coarse cube: the forward kernel's Jacobian is
+ * finite there, its ReLU masks being off, and the clip sends a NaN value to its lower bound -- the rule, not the arithmetic, keeps such a point out of
+ * the maps); any other NaN input propagates through the expressions.
+ * -1 (nothing launched, nothing written): a NULL out_n, jac_n, f, phys or products; n <= 0; n_products outside 1..DPN_DIAG_PRODUCTS; an id outside
+ * 0..DPN_DIAG_PRODUCTS - 1; both destinations or neither; maps without lattice, rows with one; nx / ny / nt < 1; first < 0; first + n > nx * ny * nt. */
+#define DPN_DIAG_PRODUCTS 28
+int dpn_diagnostics_out(const float* out_n, const float* jac_n, const float* f, int64_t n, const DpnPhysics* phys, int with_clip,
+                        const int32_t* products /* HOST, n_products ids */, int n_products, float* rows, float* maps, const DpnLattice* lattice,
+                        int64_t first, void* stream);
 
 /* The same step with the optimiser state held as ONE flat fp32 buffer per moment: tensor i lives at offset (sum of ceil(numel_j / 2048)
  * over j < i) * 2048, i.e. every tensor is padded to whole 2048-element chunks; dpn_clip_adam_flat_floats gives the buffer length.

@@ -1,14 +1,15 @@
 #!/usr/bin/env python
 """Inference launcher next to train.py, with the same three flags: --config_file, --checkpoint_path, --log_path.
 
-    python infer.py [--config_file cfg.py] [--checkpoint_path DIR] [--log_path DIR] [--synthetic] [--ema]
+    python infer.py [--config_file cfg.py] [--checkpoint_path DIR] [--log_path DIR] [--synthetic] [--ema] [--diagnostics name[,name...]]
 
 Builds the interface from the config (train.py's loader), loads `physics_latest.pth` from --checkpoint_path (or inference_cfg.checkpoints) and
 calls `run_inference_interface`: every field sample is evaluated on the lattice inference_cfg.img_size (x `refine`) at every inference_cfg.dt
 seconds of its window, and with log.write_source the maps go to --log_path (or inference_cfg.log.result_path) as one .npy per time step and
 exported variable.  The reference's dataset is file I/O that does not exist offline: a config that names no `samples` source fails, unless
 --synthetic asks for a random field sample (smoke runs: the maps are noise).  --ema evaluates the checkpoint's averaged weights (`model_ema`, written by
-train.py --ema) in place of the raw ones; a checkpoint without them is a KeyError."""
+train.py --ema) in place of the raw ones; a checkpoint without them is a KeyError.  --diagnostics vorticity,dT_dt sets
+inference_cfg.log.export_diagnostic: derived products of the Jacobian (deepphysinet_amd.diagnostics.PRODUCTS), one more .npy per time step and name."""
 import argparse
 
 import torch
@@ -22,6 +23,8 @@ parse.add_argument('--checkpoint_path', default=None, type=str)
 parse.add_argument('--log_path', default=None, type=str)
 parse.add_argument('--synthetic', action='store_true', help="samples='synthetic': a random field sample over a random coarse cube")
 parse.add_argument('--ema', action='store_true', help="weights='ema': the checkpoint's averaged weights (model_ema) in place of the raw ones")
+parse.add_argument('--diagnostics', default=None, type=lambda s: [n for n in s.split(',') if n],
+                   help='name[,name...]: inference_cfg.log.export_diagnostic, derived products (deepphysinet_amd.diagnostics.PRODUCTS) written next to the variables')
 
 if __name__ == '__main__':
     args = parse.parse_args()
@@ -29,6 +32,8 @@ if __name__ == '__main__':
     cfg = load_config(args.config_file)
     if args.log_path is not None:
         cfg.setdefault('inference_cfg', {}).setdefault('log', {})['result_path'] = args.log_path
+    if args.diagnostics:
+        cfg.setdefault('inference_cfg', {}).setdefault('log', {})['export_diagnostic'] = args.diagnostics
     model = builder_models(**cfg)
     kwargs = dict(checkpoint_path=args.checkpoint_path)
     if args.synthetic:
@@ -40,3 +45,6 @@ if __name__ == '__main__':
         print('done: no samples')
     else:
         print('done: maps %s, finite %s' % (tuple(maps.shape), bool(torch.isfinite(maps).all())))
+    if model.last_diagnostics is not None:
+        d = model.last_diagnostics
+        print('diagnostics %s: maps %s, finite %s' % (','.join(d['names']), tuple(d['maps'].shape), bool(torch.isfinite(d['maps']).all())))
