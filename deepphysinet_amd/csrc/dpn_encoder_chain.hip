@@ -26,7 +26,8 @@
 // plane, lo plane, 1 KB each), once for x W^T (forward) and once for g W (backward).  A workgroup streams the images of its six GEMMs
 // (1.5 MB) from L2 straight into registers (buffer_load_dwordx4 with a scalar running offset), kPF k-steps ahead and ACROSS the row passes
 // and barriers between the GEMMs (LDS-only barriers: vmcnt stays in flight).  That stream at the CU's ~55 B/clk L2 path is the kernel's
-// bound (~12 us per launch); the MFMAs (2 304 per workgroup) take a third of it.
+// bound (~12 us per launch); the MFMAs (2 304 per workgroup) take a third of it.  Forward launches with a q / k / v tail therefore run every
+// row block on three workgroups, one projection each (dpn_enc_fwd_kernel's REP): 1.0 MB per CU, -4 us per launch.
 #include <atomic>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -59,7 +60,7 @@ constexpr float kLoScale = 2048.0f, kLoInv = 1.0f / 2048.0f;
 // Experiment build (-DDPN_ENC_TIMELINE, tools/enc_timeline.py): lane 0 of every wave writes the shader clock at the phase boundaries.
 #ifdef DPN_ENC_TIMELINE
 unsigned* g_enc_timeline = nullptr;
-#define ENC_STAMP(I) do { if (a.tl && lane == 0) a.tl[((size_t)blockIdx.x * kWaves + wave) * 32 + (I)] = (unsigned)__builtin_readcyclecounter(); } while (0)
+#define ENC_STAMP(I) do { if (a.tl && lane == 0) a.tl[((size_t)tl_block * kWaves + wave) * 32 + (I)] = (unsigned)__builtin_readcyclecounter(); } while (0)
 #define ENC_TL_ARG unsigned* tl;
 #define ENC_TL_SET(A) (A).tl = g_enc_timeline
 #else
@@ -207,26 +208,27 @@ struct WStream {
         voff = lane * 16;
         tile_off = wave * 2 * 16384;
     }
-    DEV void load(u32x4 (&dst)[2][2], int img_off, int ks) const {
+    template <int NT>
+    DEV void load(u32x4 (&dst)[NT][2], int img_off, int ks) const {
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
+        for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int p = 0; p < 2; ++p)
                 dst[t][p] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff + p * 1024, img_off + tile_off + t * 16384 + ks * 2048, 0));
     }
 };
-template <int PF> struct Ring { u32x4 a[PF][2][2]; };
+template <int PF, int NT = 2> struct Ring { u32x4 a[PF][NT][2]; };
 
 DEV f32x4 mfma(u32x4 a, u32x4 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
 
-template <int NTT>
+template <int NTT, int NT = 2>
 struct Acc {
-    f32x4 m[2][NTT], c[2][NTT];                  // main (hi.hi) and cross (hi.lo' + lo'.hi) accumulators of the wave's two channel tiles
+    f32x4 m[NT][NTT], c[NT][NTT];                // main (hi.hi) and cross (hi.lo' + lo'.hi) accumulators of the wave's NT (two) channel tiles
     DEV void zero() {
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
+        for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int tt = 0; tt < NTT; ++tt) { m[t][tt] = (f32x4)0.f; c[t][tt] = (f32x4)0.f; }
     }
@@ -234,8 +236,8 @@ struct Acc {
 
 // acc += W[wave's 32 channels][256] . X^T[256][16 NTT tokens]: eight k-steps; the ring holds this image's k-steps 0 .. kPF-1 on entry and the next
 // image's on exit (HAS_NEXT).  xr0 / xr1: the lane's read bases in the X image for even / odd k-steps.
-template <int NTT, bool HAS_NEXT>
-DEV void gemm(const WStream& ws, Ring<pf_of<NTT>()>& R, const int cur_off, const int next_off, const char* xr0, const char* xr1, Acc<NTT>& acc) {
+template <int NTT, bool HAS_NEXT, int NT = 2>
+DEV void gemm(const WStream& ws, Ring<pf_of<NTT>(), NT>& R, const int cur_off, const int next_off, const char* xr0, const char* xr1, Acc<NTT, NT>& acc) {
     u32x4 B[2][NTT][2];
     auto loadB = [&](const int ks, const int buf) __attribute__((always_inline)) {
         const char* base = ((ks & 1) ? xr1 : xr0) + ks * 1024;
@@ -254,11 +256,11 @@ DEV void gemm(const WStream& ws, Ring<pf_of<NTT>()>& R, const int cur_off, const
 #pragma unroll
         for (int tt = 0; tt < NTT; ++tt) {
 #pragma unroll
-            for (int t = 0; t < 2; ++t) acc.m[t][tt] = mfma(R.a[s][t][0], B[b][tt][0], acc.m[t][tt]);
+            for (int t = 0; t < NT; ++t) acc.m[t][tt] = mfma(R.a[s][t][0], B[b][tt][0], acc.m[t][tt]);
 #pragma unroll
-            for (int t = 0; t < 2; ++t) acc.c[t][tt] = mfma(R.a[s][t][0], B[b][tt][1], acc.c[t][tt]);
+            for (int t = 0; t < NT; ++t) acc.c[t][tt] = mfma(R.a[s][t][0], B[b][tt][1], acc.c[t][tt]);
 #pragma unroll
-            for (int t = 0; t < 2; ++t) acc.c[t][tt] = mfma(R.a[s][t][1], B[b][tt][0], acc.c[t][tt]);
+            for (int t = 0; t < NT; ++t) acc.c[t][tt] = mfma(R.a[s][t][1], B[b][tt][0], acc.c[t][tt]);
         }
         if (ks + kPF < 8) ws.load(R.a[s], cur_off, ks + kPF);
         else if (HAS_NEXT) ws.load(R.a[s], next_off, ks + kPF - 8);
@@ -266,18 +268,18 @@ DEV void gemm(const WStream& ws, Ring<pf_of<NTT>()>& R, const int cur_off, const
 }
 
 // accumulator element (tile t, token tile tt, register j) = channel 32 w + 16 t + 4 g + j of token 16 tt + (lane & 15), g = lane >> 4
-template <int NTT>
-DEV void acc_to_staging(const Acc<NTT>& acc, float* Y, const float* rscale, int wave, int lane) {
+template <int NTT, int NT = 2>
+DEV void acc_to_staging(const Acc<NTT, NT>& acc, float* Y, const float* rscale, int wave, int lane, const int first_tile = 0) {
     const int n = lane & 15, g = lane >> 4;
 #pragma unroll
     for (int tt = 0; tt < NTT; ++tt) {
         const float rs = rscale[tt * 16 + n];
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
+        for (int t = 0; t < NT; ++t) {
             f32x4 v;
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = fmaf(acc.c[t][tt][j], kLoInv, acc.m[t][tt][j]) * rs;
-            *reinterpret_cast<f32x4*>(Y + (tt * 16 + n) * kYS + wave * 32 + t * 16 + g * 4) = v;
+            *reinterpret_cast<f32x4*>(Y + (tt * 16 + n) * kYS + wave * 32 + (NT == 2 ? t : first_tile) * 16 + g * 4) = v;
         }
     }
 }
@@ -309,6 +311,8 @@ DEV void acc_to_global(const Acc<NTT>& acc, float* out, const float* bias_lds, c
 // touching one eighth of every image's 128-byte lines once -- which finish in the launch's first microseconds: the later GEMMs of the
 // 18 working workgroups then hit L2.  Nothing depends on them (a missed line is simply fetched by the stream itself).
 constexpr int kHelpers = 64;
+constexpr int kHelperMaxMain = 64;               // launches with more row blocks than this carry no helpers
+constexpr int kCUs = 256;
 DEV void l2_warm_helper(const void* wpack, const int (&img)[6], const int n_img, const int hb) {
     const int part = hb >> 3, t = threadIdx.x;                               // eight parts x (eight blocks: one per XCD)
     float sum = 0.f;
@@ -348,16 +352,37 @@ struct Lds {
 
 constexpr int kEmbAhead = 9;                   // slices of the token convolution fetched at once by the launch that assembles x0 (6 / 9 / 18 measured alike: the 18
                                                // workgroups pull 311 KB each through their CU's L2 path, +3.9 us on this launch for the 6.9-us launch it replaces)
-template <bool TAIL, int NEXT, int NTT>
+// REP == 3 (one 16-row tile per workgroup, NEXT == 1 only): every row block is run by THREE workgroups.  The q, k and v projections behind
+// LayerNorm2 read the same X image and write three separate tensors that nothing in the launch reads, so each replica runs the trunk
+// (out-projection .. LayerNorm2: the same instructions on the same inputs, the same bits) and then ONE of the three projections: a CU
+// streams 4 instead of 6 weight images (1 instead of 3 in the launch without a trunk).  Only replica 0 stores the trunk's saved tensors.
+// Block numbering: DPN_ENC_REP_ROW_MAJOR = 0: block = replica * n_main + row block; 1: block = row block * 3 + replica (dpn_enc_fwd's comment
+// has the measurement); the helpers follow the n_main * REP working blocks.
+#ifndef DPN_ENC_REP_ROW_MAJOR
+#define DPN_ENC_REP_ROW_MAJOR 0
+#endif
+template <bool TAIL, int NEXT, int NTT, int REP = 1>
 __global__ __launch_bounds__(kThreads) void dpn_enc_fwd_kernel(FwdArgs a) {
+    static_assert(REP == 1 || (REP == 3 && NEXT == 1 && NTT == 1), "replicas: one per q / k / v projection, 16-row workgroups only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* ximg = smem + Lds<NTT>::kX;
     float* Y = reinterpret_cast<float*>(smem + Lds<NTT>::kY);
     float* vecs = reinterpret_cast<float*>(smem + Lds<NTT>::kVec);
     float* rscale = reinterpret_cast<float*>(smem + Lds<NTT>::kRs);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    if ((int)blockIdx.x >= a.n_main) { l2_warm_helper(a.wpack, a.img, a.n_img, blockIdx.x - a.n_main); return; }
-    const int row0 = blockIdx.x * 16 * NTT;
+    if ((int)blockIdx.x >= a.n_main * REP) { l2_warm_helper(a.wpack, a.img, a.n_img, blockIdx.x - a.n_main * REP); return; }
+    int rb = blockIdx.x, rep = 0;                                    // workgroup-uniform (scalar registers)
+    if constexpr (REP == 3) {
+        if (DPN_ENC_REP_ROW_MAJOR) { rb = (int)blockIdx.x / 3; rep = (int)blockIdx.x - 3 * rb; }
+        else { rep = ((int)blockIdx.x >= a.n_main) + ((int)blockIdx.x >= 2 * a.n_main); rb = (int)blockIdx.x - rep * a.n_main; }
+    }
+    const bool keeper = REP == 1 || rep == 0;                        // the replica that stores everything but its own projection
+    constexpr int kFirstNext = TAIL ? 3 : 0;
+    // the replica's projection: image offset, output and bias selected as VALUES (an index into the argument block would put it in scratch)
+    const int rep_img = REP == 1 ? 0 : rep == 0 ? a.img[kFirstNext] : rep == 1 ? a.img[kFirstNext + 1] : a.img[kFirstNext + 2];
+    float* const rep_y = REP == 1 ? nullptr : rep == 0 ? a.y0 : rep == 1 ? a.y1 : a.y2;
+    const int row0 = rb * 16 * NTT;
+    [[maybe_unused]] const int tl_block = rep * a.n_main + rb;       // timeline rows: [replica][row block] in either block order
     ENC_STAMP(0);
     const RowLane rl(wave, lane);
     const int n_r = lane & 15, g_r = lane >> 4;
@@ -399,7 +424,7 @@ __global__ __launch_bounds__(kThreads) void dpn_enc_fwd_kernel(FwdArgs a) {
                 load8(e8, a.emb_te + c0, true);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) vin[tt][e] = ok[tt] ? ((tok ? v[e] : v[e] + b8[e]) + p8[e]) + e8[e] : 0.f;
-                store8(a.emb_out + (int64_t)row * kD + c0, vin[tt], ok[tt]);
+                store8(a.emb_out + (int64_t)row * kD + c0, vin[tt], ok[tt] && keeper);
                 continue;
             }
         }
@@ -419,7 +444,7 @@ __global__ __launch_bounds__(kThreads) void dpn_enc_fwd_kernel(FwdArgs a) {
     constexpr int kPF = pf_of<NTT>();
     Ring<kPF> R;
 #pragma unroll
-    for (int ks = 0; ks < kPF; ++ks) ws.load(R.a[ks], a.img[0], ks);
+    for (int ks = 0; ks < kPF; ++ks) ws.load(R.a[ks], (!TAIL && REP == 3) ? rep_img : a.img[0], ks);
 #pragma unroll
     for (int q = 0; q < kVecLoads; ++q) {
         const int i = tid + q * kThreads;
@@ -431,8 +456,10 @@ __global__ __launch_bounds__(kThreads) void dpn_enc_fwd_kernel(FwdArgs a) {
     barrier_lds();
     ENC_STAMP(2);
     Acc<NTT> acc;
-    constexpr int kFirstNext = TAIL ? 3 : 0;
     if constexpr (TAIL) {
+        bool okst[NTT];                                              // the saved-state stores: replica 0 only
+#pragma unroll
+        for (int tt = 0; tt < NTT; ++tt) okst[tt] = ok[tt] && keeper;
         // ---- out-projection, residual, LayerNorm1 (attn.py:196, transformer_net.py:33-37)
         acc.zero();
         gemm<NTT, true>(ws, R, a.img[0], a.img[1], xr0, xr1, acc);
@@ -461,9 +488,9 @@ __global__ __launch_bounds__(kThreads) void dpn_enc_fwd_kernel(FwdArgs a) {
 #pragma unroll
         for (int tt = 0; tt < NTT; ++tt) {
             const int64_t off = (int64_t)(row0 + tt * 16 + rl.n16) * kD + rl.slot * 8;
-            store8(a.x1 + off, res[tt], ok[tt]);
-            store8(a.xhat1 + off, sb[tt], ok[tt]);
-            if (ok[tt] && rl.slot == 0) a.rstd1[row0 + tt * 16 + rl.n16] = sr[tt];
+            store8(a.x1 + off, res[tt], okst[tt]);
+            store8(a.xhat1 + off, sb[tt], okst[tt]);
+            if (okst[tt] && rl.slot == 0) a.rstd1[row0 + tt * 16 + rl.n16] = sr[tt];
         }
         // ---- conv1 + GELU (transformer_net.py:38-41)
         acc.zero();
@@ -489,12 +516,12 @@ __global__ __launch_bounds__(kThreads) void dpn_enc_fwd_kernel(FwdArgs a) {
 #pragma unroll
         for (int tt = 0; tt < NTT; ++tt) {
             const int64_t off = (int64_t)(row0 + tt * 16 + rl.n16) * kD + rl.slot * 8;
-            store8(a.pre + off, sa[tt], ok[tt]);
-            store8(a.act + off, sb[tt], ok[tt]);
+            store8(a.pre + off, sa[tt], okst[tt]);
+            store8(a.act + off, sb[tt], okst[tt]);
         }
         // ---- conv2, residual, LayerNorm2 (transformer_net.py:42-44) (+ encoder.norm behind the last layer, :68)
         acc.zero();
-        gemm<NTT, NEXT != 0>(ws, R, a.img[2], a.img[3], xr0, xr1, acc);
+        gemm<NTT, NEXT != 0>(ws, R, a.img[2], REP == 3 ? rep_img : a.img[3], xr0, xr1, acc);
         ENC_STAMP(11);
         acc_to_staging<NTT>(acc, Y, rscale, wave, lane);
         barrier_lds();
@@ -526,9 +553,9 @@ __global__ __launch_bounds__(kThreads) void dpn_enc_fwd_kernel(FwdArgs a) {
 #pragma unroll
         for (int tt = 0; tt < NTT; ++tt) {
             const int64_t off = (int64_t)(row0 + tt * 16 + rl.n16) * kD + rl.slot * 8;
-            store8(a.x2 + off, sa[tt], ok[tt]);
-            store8(a.xhat2 + off, sb[tt], ok[tt]);
-            if (ok[tt] && rl.slot == 0) a.rstd2[row0 + tt * 16 + rl.n16] = sr[tt];
+            store8(a.x2 + off, sa[tt], okst[tt]);
+            store8(a.xhat2 + off, sb[tt], okst[tt]);
+            if (okst[tt] && rl.slot == 0) a.rstd2[row0 + tt * 16 + rl.n16] = sr[tt];
             if constexpr (NEXT == 2) {
                 store8(a.xf + off, sc[tt], ok[tt]);
                 store8(a.xhatf + off, sd[tt], ok[tt]);
@@ -536,7 +563,13 @@ __global__ __launch_bounds__(kThreads) void dpn_enc_fwd_kernel(FwdArgs a) {
             }
         }
     }
-    if constexpr (NEXT == 1) {
+    if constexpr (NEXT == 1 && REP == 3) {
+        // ---- ONE of the next layer's q / k / v projections: the ring holds this replica's image (the prefetch above named rep_img)
+        acc.zero();
+        gemm<NTT, false>(ws, R, rep_img, 0, xr0, xr1, acc);
+        acc_to_global<NTT>(acc, rep_y, vecs + (VF_BN0 + rep) * 256, rscale, row0, a.rows, wave, lane);
+        ENC_STAMP(17);
+    } else if constexpr (NEXT == 1) {
         // ---- the next layer's q / k / v projections (attn.py:183-185): three GEMMs on the same row block, straight to global memory
         acc.zero();
         gemm<NTT, true>(ws, R, a.img[kFirstNext], a.img[kFirstNext + 1], xr0, xr1, acc);
@@ -596,6 +629,64 @@ DEV void partials_to_global(const float* red, float* partial, int tid) {        
     partial[(int64_t)blockIdx.x * 512 + tid] = s;
 }
 
+// The first layer's q / k / v backward alone (HEAD 1 without BODY, 16-row workgroups): one K = 768 accumulation and an element-wise row pass.
+// Every accumulator chain belongs to one 16-channel tile, so two workgroups per row block can each take ONE of a wave's two tiles (replica r:
+// tile 2 w + r), stream half of the three images and store the channels they own (block = replica * n_main + row block): the same bits.
+__global__ __launch_bounds__(kThreads) void dpn_enc_bwd_qkv2_kernel(BwdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* ximg = smem + Lds<1>::kX;
+    float* Y = reinterpret_cast<float*>(smem + Lds<1>::kY);
+    float* rscale = reinterpret_cast<float*>(smem + Lds<1>::kRs);
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if ((int)blockIdx.x >= 2 * a.n_main) { l2_warm_helper(a.wpack, a.img, a.n_img, blockIdx.x - 2 * a.n_main); return; }
+    const int rep = (int)blockIdx.x >= a.n_main, rb = (int)blockIdx.x - rep * a.n_main;      // workgroup-uniform
+    const int row0 = rb * 16;
+    [[maybe_unused]] const int tl_block = blockIdx.x;
+    ENC_STAMP(0);
+    const RowLane rl(wave, lane);
+    const int n_r = lane & 15, g_r = lane >> 4;
+    const char* xr0 = ximg + (g_r * 16 + (n_r ^ g_r)) * 16;
+    const char* xr1 = ximg + (g_r * 16 + (n_r ^ g_r ^ 12)) * 16;
+    const int row = row0 + rl.n16;
+    const bool ok = row < a.rows;
+    const bool mine = ok && ((rl.slot >> 1) & 1) == rep;             // the lane's eight channels 8 slot .. + 7 lie in tile slot / 2: this replica's if it is odd / even like rep
+    const int64_t off = (int64_t)row * kD + rl.slot * 8;
+    float hq[8], hk[8], hv[8], g[8];
+    load8(hq, a.dq + off, ok); load8(hk, a.dk + off, ok); load8(hv, a.dv + off, ok);
+    WStream ws;
+    ws.init(a.wpack, a.wbytes, wave, lane);
+    ws.tile_off += rep * 16384;                                      // tile 2 w + rep
+    constexpr int kPF = pf_of<1>();
+    Ring<kPF, 1> R;
+#pragma unroll
+    for (int ks = 0; ks < kPF; ++ks) ws.load(R.a[ks], a.img[0], ks);
+    load8(g, a.res + off, mine);                                     // g <- the residual-branch cotangent; the GEMM is added to it
+    const float m = fmaxf(row_absmax(hq), fmaxf(row_absmax(hk), row_absmax(hv)));
+    row_to_ximg(hq, m, rl, ximg, rscale);
+    row_to_ximg(hk, m, rl, ximg + kXImg, rscale);
+    row_to_ximg(hv, m, rl, ximg + 2 * kXImg, rscale);
+    ENC_STAMP(1);
+    barrier_lds();
+    ENC_STAMP(2);
+    Acc<1, 1> acc;
+    acc.zero();
+    gemm<1, true, 1>(ws, R, a.img[0], a.img[1], xr0, xr1, acc);
+    gemm<1, true, 1>(ws, R, a.img[1], a.img[2], xr0 + kXImg, xr1 + kXImg, acc);
+    gemm<1, false, 1>(ws, R, a.img[2], 0, xr0 + 2 * kXImg, xr1 + 2 * kXImg, acc);
+    ENC_STAMP(3);
+    acc_to_staging<1, 1>(acc, Y, rscale, wave, lane, rep);
+    barrier_lds();
+    ENC_STAMP(4);
+    if (mine) {                                                      // (the other replica's columns of Y are not written here)
+        float v[8];
+        lds8(v, Y + rl.n16 * kYS + rl.slot * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) g[e] += v[e];
+        store8(a.gx + off, g, true);
+        if (row < a.gx_head_rows) store8(a.gx_head + off, g, true);
+    }
+}
+
 template <int HEAD, bool BODY, int NTT>
 __global__ __launch_bounds__(kThreads) void dpn_enc_bwd_kernel(BwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -607,6 +698,7 @@ __global__ __launch_bounds__(kThreads) void dpn_enc_bwd_kernel(BwdArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if ((int)blockIdx.x >= a.n_main) { l2_warm_helper(a.wpack, a.img, a.n_img, blockIdx.x - a.n_main); return; }
     const int row0 = blockIdx.x * 16 * NTT;
+    [[maybe_unused]] const int tl_block = blockIdx.x;
     ENC_STAMP(0);
     const RowLane rl(wave, lane);
     const int n_r = lane & 15, g_r = lane >> 4;
@@ -1438,6 +1530,22 @@ int dpn_enc_prep(const DpnEncPrep* p, void* stream) {
     return (int)hipGetLastError();
 }
 
+// How many workgroups run one 16-row block of a forward launch: 3 (one per q / k / v projection) or 1.  Only launches with a q / k / v tail
+// (next == 1) of 16-row workgroups (row_tiles == 1) replicate, and only while every workgroup is resident in one round of the chip:
+// replicas x row blocks + the warm-up helpers (64 up to 64 row blocks, none above) <= 256 CUs.  One field: 287 rows = 18 row blocks.
+// DPN_ENC_REP_MAX_MAIN (experiment builds): replicate up to that many row blocks instead (0: never).
+// Host only, exported for the tests and tools (bound by hand like dpn_enc_debug_set_timeline; include/dpn_hip.h and its ABI do not change).
+int dpn_enc_fwd_replicas(int rows, int row_tiles, int tail, int next) {
+    (void)tail;                                                      // both launch kinds gain (with and without the trunk)
+    if (rows <= 0 || row_tiles != 1 || next != 1) return 1;
+    const int n_main = (rows + 15) / 16;
+#ifdef DPN_ENC_REP_MAX_MAIN
+    return n_main <= DPN_ENC_REP_MAX_MAIN ? 3 : 1;
+#else
+    return n_main * 3 + (n_main <= kHelperMaxMain ? kHelpers : 0) <= kCUs ? 3 : 1;
+#endif
+}
+
 int dpn_enc_fwd(const DpnEncFwd* p, void* stream) {
     if (!p || !p->wpack || p->rows <= 0 || p->n_mats <= 0 || p->n_mats > DPN_ENC_MAX_MATS || p->next < 0 || p->next > 2) return -1;
     if (!p->tail && p->next != 1) return -1;
@@ -1473,8 +1581,16 @@ int dpn_enc_fwd(const DpnEncFwd* p, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int rpw = wide ? 32 : 16;
     a.n_main = (p->rows + rpw - 1) / rpw; a.n_img = ni;
-    // the warm-up helpers pay while the working workgroups are few (one or a few field samples); a batch of fields warms the L2s by itself
-    const dim3 grid(a.n_main + (a.n_main <= 64 ? kHelpers : 0)), block(kThreads);
+    // the warm-up helpers pay while the working workgroups are few (one or a few field samples); a batch of fields warms the L2s by itself.
+    // Replicas (dpn_enc_fwd_replicas): 16-row launches with a q / k / v tail run every row block on three workgroups while all of them are
+    // resident in one round of the 256 CUs: 3 x n_main + helpers <= 256, i.e. n_main <= 64 with the 64 helpers, 65 .. 85 without.  One field:
+    // 18 x 3 + 64 = 118 workgroups, block = replica * 18 + row block (XCD = block % 8: a row block's replicas sit two XCDs apart, every XCD
+    // has 6-7 working workgroups).  Measured (profiles/enc_replicas_ab.txt), one workgroup per row block -> three: in the captured step the
+    // layer tails 19.59 -> 15.55 us, the first launch 13.91 -> 9.95 us; row-major numbering (block = row block * 3 + replica) 15.64 / 10.02 us.
+    // L2-warm, back to back: B = 2 (36 row blocks) 19.9 -> 15.6 and 9.8 -> 5.5 us, B = 4 (72 row blocks, no helpers) 20.7 -> 16.8 and
+    // 10.2 -> 6.0 us: the bound stays at one round of the chip.
+    const int reps = dpn_enc_fwd_replicas(p->rows, p->row_tiles, p->tail, p->next);
+    const dim3 grid(a.n_main * reps + (a.n_main <= kHelperMaxMain ? kHelpers : 0)), block(kThreads);
     static std::atomic<unsigned long long> done{0};
     unsigned long long dev_bit;
 #define DPN_ENC_FWD_CASES(X) X(true, 0) X(true, 1) X(true, 2) X(false, 1)
@@ -1482,7 +1598,13 @@ int dpn_enc_fwd(const DpnEncFwd* p, void* stream) {
 #define X(T, N) if (set_lds(dpn_enc_fwd_kernel<T, N, 1>, Lds<1>::kBytes) || set_lds(dpn_enc_fwd_kernel<T, N, 2>, Lds<2>::kBytes)) return -2;
         DPN_ENC_FWD_CASES(X)
 #undef X
+        if (set_lds(dpn_enc_fwd_kernel<true, 1, 1, 3>, Lds<1>::kBytes) || set_lds(dpn_enc_fwd_kernel<false, 1, 1, 3>, Lds<1>::kBytes)) return -2;
         done.fetch_or(dev_bit, std::memory_order_release);
+    }
+    if (reps == 3) {
+        if (p->tail) hipLaunchKernelGGL((dpn_enc_fwd_kernel<true, 1, 1, 3>), grid, block, Lds<1>::kBytes, s, a);
+        else hipLaunchKernelGGL((dpn_enc_fwd_kernel<false, 1, 1, 3>), grid, block, Lds<1>::kBytes, s, a);
+        return (int)hipGetLastError();
     }
 #define X(T, N) if ((p->tail != 0) == T && p->next == N) { \
         if (wide) hipLaunchKernelGGL((dpn_enc_fwd_kernel<T, N, 2>), grid, block, Lds<2>::kBytes, s, a); \
@@ -1490,6 +1612,20 @@ int dpn_enc_fwd(const DpnEncFwd* p, void* stream) {
     DPN_ENC_FWD_CASES(X)
 #undef X
     return (int)hipGetLastError();
+}
+
+// The backward's counterpart: 2 for the q / k / v backward without a body (head == 1, body == 0) on 16-row workgroups while 2 x row blocks + the
+// helpers fit one round of the chip, else 1 (one field: 18 x 2 + 64 = 100 workgroups; each streams 384 instead of 768 KB).  Measured
+// (profiles/enc_replicas_ab.txt): 10.03 -> 7.31 us in the captured step; L2-warm 9.4 -> 6.5 us at one field, 9.4 -> 6.7 / 9.5 -> 6.6 us at
+// B = 2 / B = 4.  DPN_ENC_BWD_REP_MAX_MAIN (experiment builds): up to that many row blocks instead (0: never).
+int dpn_enc_bwd_replicas(int rows, int row_tiles, int head, int body) {
+    if (rows <= 0 || row_tiles != 1 || head != 1 || body != 0) return 1;
+    const int n_main = (rows + 15) / 16;
+#ifdef DPN_ENC_BWD_REP_MAX_MAIN
+    return n_main <= DPN_ENC_BWD_REP_MAX_MAIN ? 2 : 1;
+#else
+    return n_main * 2 + (n_main <= kHelperMaxMain ? kHelpers : 0) <= kCUs ? 2 : 1;
+#endif
 }
 
 int dpn_enc_bwd(const DpnEncBwd* p, void* stream) {
@@ -1524,7 +1660,8 @@ int dpn_enc_bwd(const DpnEncBwd* p, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int rpw = wide ? 32 : 16;
     a.n_main = (p->rows + rpw - 1) / rpw; a.n_img = ni;
-    const dim3 grid(a.n_main + (a.n_main <= 64 && ni > 0 ? kHelpers : 0)), block(kThreads);
+    const int reps = dpn_enc_bwd_replicas(p->rows, p->row_tiles, p->head, p->body);
+    const dim3 grid(a.n_main * reps + (a.n_main <= kHelperMaxMain && ni > 0 ? kHelpers : 0)), block(kThreads);
     static std::atomic<unsigned long long> done{0};
     unsigned long long dev_bit;
 #define DPN_ENC_BWD_CASES(X) X(0, true) X(1, true) X(2, true) X(1, false)
@@ -1532,7 +1669,12 @@ int dpn_enc_bwd(const DpnEncBwd* p, void* stream) {
 #define X(H, B) if (set_lds(dpn_enc_bwd_kernel<H, B, 1>, Lds<1>::kBytes) || set_lds(dpn_enc_bwd_kernel<H, B, 2>, Lds<2>::kBytes)) return -2;
         DPN_ENC_BWD_CASES(X)
 #undef X
+        if (set_lds(dpn_enc_bwd_qkv2_kernel, Lds<1>::kBytes)) return -2;
         done.fetch_or(dev_bit, std::memory_order_release);
+    }
+    if (reps == 2) {
+        hipLaunchKernelGGL(dpn_enc_bwd_qkv2_kernel, grid, block, Lds<1>::kBytes, s, a);
+        return (int)hipGetLastError();
     }
 #define X(H, B) if (p->head == H && (p->body != 0) == B) { \
         if (wide) hipLaunchKernelGGL((dpn_enc_bwd_kernel<H, B, 2>), grid, block, Lds<2>::kBytes, s, a); \

@@ -4,7 +4,8 @@ the product build.
     python tools/variant_build.py NAME [--unit=I] [-DFLAG ...]      ->  tools/_variants/libdpn_hip_NAME.so   (select it with DPN_LIB=<path>)
     (--unit=I[,J]: indices into deepphysinet_amd.build.UNITS; 0 = the point kernels, csrc/dpn_point.hip: -DDPN_TIMELINE, -DDPN_FWD_PHASES, -DTS_*, -DDPN_ABL_*;
      1 = weight packing, weight-gradient and finish kernels, csrc/dpn_wgrad.hip: -DPACK_ABL_MASK=m, -DDPN_WGRAD_PHASES, -DDPN_WGRAD_2X4_ONLY -- without
-     --unit=1 these recompile the point unit and change nothing; 5 = the row-local encoder nodes, csrc/dpn_encoder_chain.hip)
+     --unit=1 these recompile the point unit and change nothing; 5 = the row-local encoder nodes, csrc/dpn_encoder_chain.hip: -DDPN_ENC_TIMELINE, -DDPN_ENC_REP_ROW_MAJOR=1,
+     -DDPN_ENC_REP_MAX_MAIN=n / -DDPN_ENC_BWD_REP_MAX_MAIN=n -- replicate up to n row blocks, 0 = never)
 """
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
