@@ -1562,6 +1562,8 @@ int dpn_enc_fwd(const DpnEncFwd* p, void* stream) {
         a.img[ni++] = img_off(p->m_o, 0); a.img[ni++] = img_off(p->m_c1, 0); a.img[ni++] = img_off(p->m_c2, 0);
     } else if (p->emb_parts) {
         if (!p->emb_pos || !p->emb_te || !p->emb_out || p->emb_n_parts < 1 || p->emb_n_tok < 0 || (p->emb_n_tok > 0 && !p->emb_token) || p->emb_part_stride < 0) return -1;
+        // rows = emb_n_tok + the token convolution's rows, and two slices never overlap (a stride of 0 would add slice 0 emb_n_parts times)
+        if (p->emb_n_tok > p->rows || (p->emb_n_parts > 1 && p->emb_part_stride < (int64_t)(p->rows - p->emb_n_tok) * kD)) return -1;
         a.emb_parts = p->emb_parts; a.emb_bias = p->emb_bias; a.emb_pos = p->emb_pos; a.emb_te = p->emb_te; a.emb_token = p->emb_token; a.emb_out = p->emb_out;
         a.emb_part_stride = p->emb_part_stride; a.emb_n_parts = p->emb_n_parts; a.emb_n_tok = p->emb_n_tok;
     } else if (!p->xin) return -1;

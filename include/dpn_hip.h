@@ -303,7 +303,9 @@ typedef struct DpnEncFwd {
      * launch of its own (embed.py:60-64, transformer_net.py:124-126), same order of additions:
      *   row <  emb_n_tok:  x0[row] = (emb_token[row] + emb_pos[row]) + emb_te
      *   row >= emb_n_tok:  x0[row] = ((sum_p emb_parts[p][row - emb_n_tok], p = 0 .. emb_n_parts - 1, in order) + emb_bias + emb_pos[row]) + emb_te
-     * emb_parts [emb_n_parts][emb_part_stride floats] (the token convolution's split-K slices, rows of 256), emb_te [256]; x0 is also written to emb_out [rows][256]. */
+     * emb_parts [emb_n_parts][emb_part_stride floats] (the token convolution's split-K slices, rows of 256), emb_te [256]; x0 is also written to emb_out [rows][256].
+     * One field only (emb_pos and emb_te carry no batch offset).  -1: emb_n_tok > rows, or emb_n_parts > 1 with emb_part_stride < (rows - emb_n_tok) * 256
+     * (slices that overlap: a stride of 0 would add slice 0 emb_n_parts times). */
     const float *emb_parts, *emb_bias, *emb_pos, *emb_te, *emb_token;
     float* emb_out;
     int64_t emb_part_stride;
