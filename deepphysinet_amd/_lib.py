@@ -105,6 +105,12 @@ class DpnLattice(Structure):
     _fields_ = [(n, c_double) for n in ('x0', 'xstep', 'y0', 'ystep', 't0', 'tstep')] + [(n, c_int32) for n in ('nx', 'ny', 'nt')]
 
 
+class DpnTrajStage(Structure):
+    """include/dpn_hip.h DpnTrajStage: the host scalars of one Runge-Kutta stage of dpn_traj_stage."""
+    _fields_ = [(n, c_double) for n in ('t0', 'h', 'w', 'a_next', 'c_next', 'inv_wsum')] + [('step', c_int64)] + \
+               [(n, c_int32) for n in ('first', 'last', 'record_only', 'with_clip')]
+
+
 class DpnStepGuard(Structure):
     _fields_ = [(n, c_int32) for n in ('skipped_nonfinite', 'skipped_spike', 'verdict', 'seen', 'consecutive', 'reserved')] + \
                [('running', c_double), ('last', c_double)]
@@ -182,6 +188,8 @@ EXPORTS = {
     'dpn_residual_points': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(DpnGeometry), POINTER(DpnPhysics), c_void_p, c_void_p]),
     'dpn_diagnostics_out': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(DpnPhysics), c_int, POINTER(c_int32), c_int, c_void_p, c_void_p,
                                     POINTER(DpnLattice), c_int64, c_void_p]),
+    'dpn_traj_stage': (c_int, [POINTER(DpnSampler), c_void_p, POINTER(DpnPhysics), c_void_p, c_int64, POINTER(DpnTrajStage), c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dpn_label_errors_blocks': (c_int64, [c_int64]),
     'dpn_label_errors': (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(DpnPhysics), c_float, c_int, c_void_p, c_void_p]),
     'dpn_label_errors_finish': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),

@@ -14,7 +14,7 @@ LIB = os.path.join(HERE, 'libdpn_hip.so')
 # (source, extra flags, object name).  One unit per kernel family.  Only the point forward / backward kernels are compiled with MFMA results
 # in VGPRs (no v_accvgpr_read per epilogue element: forward kernel -10 %); the weight-gradient kernel, the GEMMs and the optimiser measure
 # better with hipcc's default AGPR accumulators.  tools/variant_build.py --unit=I and EXP_UNITS address units by index: units 0 .. 11 keep theirs.
-# dpn_causal.hip stays the LAST entry (tests/test_causal_cpu.py holds it there): a new unit goes in directly in front of it.
+# dpn_causal.hip stays the LAST entry (tests/test_causal_cpu.py holds it there), and the list is closed: a new unit goes into MORE_UNITS below.
 def _src(name):
     return os.path.join(HERE, 'csrc', name)
 
@@ -33,7 +33,11 @@ UNITS = [(_src('dpn_point.hip'), ['-mllvm', '-amdgpu-mfma-vgpr-form'], 'dpn_poin
          (_src('dpn_balance.hip'), [], 'dpn_balance.o'),  # loss balancing by gradient norms
          (_src('dpn_diag.hip'), [], 'dpn_diag.o'),        # derived diagnostics from the Jacobian (inference)
          (_src('dpn_causal.hip'), [], 'dpn_causal.o')]    # per-point weights and causal time weighting of the PDE losses
-SRCS = [u[0] for u in UNITS]
+# UNITS is closed at these fourteen: tests hold dpn_diag.hip at index 12, dpn_causal.hip last and the count at 14.  A unit added since goes here
+# (same tuples); it is compiled and linked with the others wherever a library is built (ALL_UNITS), and nothing addresses it by index.
+MORE_UNITS = [(_src('dpn_traj.hip'), [], 'dpn_traj.o')]   # parcel trajectories: one Runge-Kutta stage per launch (inference)
+ALL_UNITS = UNITS + MORE_UNITS
+SRCS = [u[0] for u in ALL_UNITS]
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC']
 
 
@@ -62,7 +66,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     obj_dir = os.path.join(HERE, 'csrc', '_obj')
     os.makedirs(obj_dir, exist_ok=True)
     procs = []
-    for src, flags, obj in UNITS:                                   # the units compile side by side
+    for src, flags, obj in ALL_UNITS:                               # the units compile side by side
         cmd = [hipcc, *COMMON, *flags, '-I' + os.path.join(os.path.dirname(HERE), 'include'), '-c', src, '-o', os.path.join(obj_dir, obj)]
         if verbose:
             print(' '.join(cmd))
@@ -76,7 +80,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
                 subprocess.run(retry, check=True)
                 continue
             raise subprocess.CalledProcessError(pr.returncode, cmd)
-    cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', *[os.path.join(obj_dir, u[2]) for u in UNITS], '-o', LIB + '.tmp']
+    cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', *[os.path.join(obj_dir, u[2]) for u in ALL_UNITS], '-o', LIB + '.tmp']
     if verbose:
         print(' '.join(cmd))
     subprocess.run(cmd, check=True)
@@ -97,7 +101,7 @@ def build_experiments(force: bool = False) -> str:
     hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
     obj_dir = os.path.join(HERE, 'csrc', '_obj')
     objs, procs = [], []
-    for i, (src, flags, obj) in enumerate(UNITS):
+    for i, (src, flags, obj) in enumerate(ALL_UNITS):             # (EXP_UNITS: indices into UNITS, the head of ALL_UNITS)
         if i in EXP_UNITS:
             o = os.path.join(obj_dir, 'exp_' + obj)
             procs.append(subprocess.Popen([hipcc, *COMMON, *flags, '-DDPN_EXPERIMENTS', '-I' + os.path.join(os.path.dirname(HERE), 'include'), '-c', src, '-o', o]))

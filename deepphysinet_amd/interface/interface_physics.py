@@ -17,11 +17,12 @@ import torch.nn as nn
 from ..balance import LossBalance
 from ..causal import CausalWeights
 from ..diagnostics import product_ids
+from ..trajectory import check_request, domain_of, stage_table
 from ..losses.builder import builder_loss
 from ..model.physics_net import PhysicsNet
 from ..guard import StepGuard
 from ..optim import GROUP_KEYS, FusedClipAdam, resolve_param_groups
-from ..point_path import (balance_sumsq, balance_update, balanced_total, data_losses_batch, eval_step, eval_step_batch, grid_maps, label_errors,
+from ..point_path import (balance_sumsq, balance_update, balanced_total, data_losses_batch, eval_step, eval_step_batch, grid_maps, label_errors, ParcelState,
                           LOSS_ORDER, OBS_ORDER, PackedField, pde_losses, pde_losses_batch, point_fields, point_sizes, PointConfig, require_gpu,
                           smooth_l1_data_loss, step_losses, step_losses_batch)
 from ..sampler import SyntheticSamples
@@ -75,6 +76,7 @@ class InterfacePhysics(nn.Module):
         self.precision = L.PREC_NAMES[precision]
         self._cfg_cache = None
         self.loss_balance_state = None          # training_step(balance=...): {'groups', 'lam' (fp32 [K], device), 'step', 'diag' (device or None)}
+        self.last_trajectories = None           # run_inference_interface with inference_cfg.trajectories: the last sample's trajectories() dict (lonlat)
         self.last_diagnostics = None            # run_inference_interface with log.export_diagnostic: {'names', 'maps' [nt, P, ny, nx]} of the last sample
 
     # ------------------------------------------------------------------ configuration of the HIP path
@@ -426,6 +428,55 @@ class InterfacePhysics(nn.Module):
         for first, n, x, y, t, f, cd in self._lattice_chunks(sampler, lattice, chunk):
             field.diagnostics(x, y, t, f, cd, ids, with_clip, maps=maps, lattice=lattice, first=first)
         return maps
+
+    @torch.no_grad()
+    def trajectories(self, field_data, sampler, x_idx, y_idx, hours, forecast_h, duration_hours, step_hours, method='rk4', lonlat=False,
+                     with_fields=False, with_clip=False, chunk_points=None):
+        """Where the air at N places comes from or goes to: parcels started at positions x_idx, y_idx (fine-grid index units; lonlat: degrees east /
+        north) at the one hour `hours`, carried by the network's own wind (u, v of predict_points, evaluated at the parcel, never interpolated from
+        a grid) for K = round(|duration_hours| / |step_hours|) steps of `method` ('euler', 'midpoint', 'rk4': deepphysinet_amd.trajectory.METHODS).
+        duration_hours < 0 integrates backward in time (back-trajectories).  The encoder, the heads and the weight packing run once and the start
+        positions are checked on the host once; every stage is then two launches (the fields-only forward and dpn_traj_stage), with no host
+        synchronisation until the results are read.  More parcels than chunk_size allows (chunk_points) are integrated chunk by chunk.
+        Returns {'positions' [K + 1, N, 2] fp64 (index units, or degrees when lonlat), 'hours' [K + 1], 'status' [N] int32 (0 alive, 1 left the fine
+        grid, 2 left the hour window, 3 non-finite wind), 'steps_done' [N] int32, and with_fields 'fields' [K + 1, N, 6]: the six fields along the
+        path (with_clip as predict_points takes it)}, on the device but `hours`.  A parcel that leaves keeps NaN from that step on.
+        The integration stays inside ONE field sample's hour window [0, input_time_step * input_time_step_nums]: all parcels share the clock, and
+        when it reaches either end of the window every parcel still alive stops there with status 2.  `hours` must be one scalar (ValueError);
+        fields at arbitrary (position, hour) sets are predict_points'."""
+        require_gpu(field_data, 'field_data', 'trajectories')
+        if lonlat:
+            x_idx, y_idx = sampler.lonlat_to_index(x_idx, y_idx)
+        xs, ys, t0, h, K, stages, inv_wsum = check_request(x_idx, y_idx, hours, duration_hours, step_hours, method, domain_of(sampler._s))
+        N, dev = xs.size, field_data.device
+        chunk = self.chunk_size(N, chunk_points, self.FIELD_POINT_BYTES + 48 + (K + 1) * (16 + (24 if with_fields else 0)), self.precision)
+        field = self._inference_weights(field_data, forecast_h, chunk)
+        positions = torch.empty((K + 1, N, 2), dtype=torch.float64, device=dev)
+        fields = torch.empty((K + 1, N, 6), dtype=torch.float32, device=dev) if with_fields else None
+        status, steps_done = (torch.empty(N, dtype=torch.int32, device=dev) for _ in range(2))
+        hrs = [t0]
+        for _ in range(K):
+            hrs.append(hrs[-1] + h)                    # the running sum: hour k is bit for bit the hour the k-th path point's forward was sampled at
+        xd, yd = torch.from_numpy(xs).to(dev), torch.from_numpy(ys).to(dev)
+        for first in range(0, N, chunk):
+            n = min(chunk, N - first)
+            parcels = ParcelState(sampler, xd[first:first + n].contiguous(), yd[first:first + n].contiguous(), t0, K + 1)
+            rows = torch.empty((K + 1, n, 6), dtype=torch.float32, device=dev) if with_fields else None
+            for k in range(K):
+                for stage in stages:
+                    field.trajectory_stage(sampler, parcels, stage, hrs[k], h, inv_wsum, k, rows, with_clip)
+            if with_fields:                            # the last path point's fields: one more forward, nothing moves
+                field.trajectory_stage(sampler, parcels, stages[0], hrs[K], h, inv_wsum, K, rows, with_clip, record_only=True)
+                fields[:, first:first + n] = rows
+            positions[:, first:first + n] = parcels.path
+            status[first:first + n], steps_done[first:first + n] = parcels.status, parcels.steps_done
+        if lonlat:
+            c = sampler.cfg
+            positions = torch.stack([c.begin_lon + positions[..., 0] * c.out_res_deg, c.begin_lat + positions[..., 1] * c.out_res_deg], dim=-1)
+        out = {'positions': positions, 'hours': torch.tensor(hrs, dtype=torch.float64), 'status': status, 'steps_done': steps_done}
+        if with_fields:
+            out['fields'] = fields
+        return out
 
     @torch.no_grad()
     def adaptive_interior(self, batch: dict, sampler, pool_factor=8, k=1.0, c=1.0):
@@ -1388,6 +1439,11 @@ class InterfacePhysics(nn.Module):
         diagnostic_lattice call on the same lattice with the same with_clip, with log.write_source one `<time>_<name>.npy` [lat, lon] per time step and
         product next to the variables' files; the last sample's {'names', 'maps' [nt, P, ny, nx]} stay in self.last_diagnostics (None without the key
         or without samples).  An unknown name is a KeyError before the checkpoint is read.
+        inference_cfg.trajectories (default absent: no further call): dict(lonlat=[(lon, lat), ...], start=H, hours=D, step=S, method='rk4'): per
+        sample ONE trajectories call (lonlat, with_fields, the same with_clip) for parcels started at those places at hour H of the sample's window and
+        followed for D hours (negative: backward) in steps of S hours; the last sample's result stays in self.last_trajectories, and with
+        log.write_source `<time>_traj_positions.npy` [K + 1, N, 2] (degrees), `_traj_hours.npy`, `_traj_status.npy`, `_traj_steps.npy` and
+        `_traj_fields.npy` [K + 1, N, 6] go next to the maps, <time> the sample's first time step.  A bad request fails before the checkpoint is read.
         Plotting (log.with_vis: Basemap) is not built."""
         import datetime
         ic = self.inference_cfg or {}
@@ -1419,6 +1475,15 @@ class InterfacePhysics(nn.Module):
         if export_diagnostic:
             product_ids(export_diagnostic)                                # an unknown name: KeyError, before the checkpoint is read
         self.last_diagnostics = None
+        traj = ic.get('trajectories')
+        if traj:
+            traj = dict({'method': 'rk4'}, **traj)
+            stage_table(traj['method'])                                   # an unknown method, a missing key, no place: before the checkpoint is read
+            traj_lon, traj_lat = ([float(p[j]) for p in traj['lonlat']] for j in (0, 1))
+            if not traj_lon or float(traj['step']) == 0.0 or float(traj['hours']) == 0.0:
+                raise ValueError('inference_cfg.trajectories: at least one (lon, lat), a non-zero step and a non-zero duration')
+            float(traj['start'])
+        self.last_trajectories = None
         self.physics_net.to(device)
         self.pe.to(device)
         state_dict, current_epoch, global_step = (None, 0, 0) if not checkpoint_path else self.load_model(checkpoint_path, prefix='physics', map_location=device)
@@ -1455,8 +1520,16 @@ class InterfacePhysics(nn.Module):
                 diag = self.diagnostic_lattice(smp['field_data'].to(device), sampler, lattice, smp['forecast_h'].to(device), export_diagnostic,
                                                with_clip=kwargs.get('with_clip', self.with_clip))
                 self.last_diagnostics = dict(names=list(export_diagnostic), maps=diag)
+            if traj:
+                self.last_trajectories = self.trajectories(smp['field_data'].to(device), sampler, traj_lon, traj_lat, float(traj['start']),
+                                                           smp['forecast_h'].to(device), float(traj['hours']), float(traj['step']), traj['method'],
+                                                           lonlat=True, with_fields=True, with_clip=kwargs.get('with_clip', self.with_clip))
             if write_source:
                 import numpy as np
+                if traj:
+                    stamp = (start + datetime.timedelta(seconds=k * window_h * 3600.0)).strftime('%Y-%m-%d_%H_%M_%S')
+                    for key, name in (('positions', 'positions'), ('hours', 'hours'), ('status', 'status'), ('steps_done', 'steps'), ('fields', 'fields')):
+                        np.save(os.path.join(result_path, '%s_traj_%s.npy' % (stamp, name)), self.last_trajectories[key].cpu().numpy())
                 host = maps.cpu().numpy()
                 host_diag = None if diag is None else diag.cpu().numpy()
                 for it in range(nt):

@@ -1285,6 +1285,7 @@ class PackedField:
         lib = L.load()
         L.check(lib.dpn_pack_weights_form(self.nets, cfg.prec, lib.dpn_fwd_form(cfg.prec, 0), _ptr(self.ws.packed), _stream()), 'dpn_pack_weights')
         self.ws.prepacked = True
+        self._traj_ph = None
 
     def fields(self, x, y, t, coord_data, with_clip=False, rows=None, maps=None, lattice=None, first=0):
         """The six physical fields at points x, y, t [n], coord_data [n, 6] (dpn_fields_out): into rows [n, 6], or into the places of points
@@ -1333,3 +1334,42 @@ class PackedField:
         fac = (ctypes.c_double * 6)(*[float(v) for v in factors])
         L.check(lib.dpn_adaptive_scores(_ptr(res), m, fac, float(k), _ptr(score), _ptr(stats), _ptr(scratch), _stream()), 'dpn_adaptive_scores')
         return score, stats, res, scratch
+
+    def trajectory_stage(self, sampler, parcels, stage, t0, h, inv_wsum, step, fields=None, with_clip=False, record_only=False):
+        """One Runge-Kutta stage for the parcels of `parcels` (a ParcelState): the fields-only forward at their current evaluation points, then
+        dpn_traj_stage (traj_stage), which writes the next evaluation points into the same buffers.  Two launches, nothing read back."""
+        x, y, t, _, cd = parcels.points
+        out_n, _ = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, cd, want_jac=False, want_saved=False)
+        if self._traj_ph is None:                  # the table is built once per field, not once per stage (384 stages a day)
+            self._traj_ph = self.cfg.physics()
+        traj_stage(sampler, self._traj_ph, out_n, parcels, stage, t0, h, inv_wsum, step, fields, with_clip, record_only)
+
+
+class ParcelState:
+    """Device state of n parcels between two dpn_traj_stage launches: x0, y0, accx, accy [n] fp64, status, steps_done [n] int32, path
+    [rows, n, 2] fp64 (row 0 = the start points; row k + 1 is written when step k closes), and `points` = x, y, t, f [n], coord_data [n, 6], the
+    sampler at the current evaluation points (the next forward's input)."""
+
+    def __init__(self, sampler, xr, yr, hour, rows):
+        dev, n = xr.device, xr.shape[0]
+        self.n, self.rows = n, int(rows)
+        self.x0, self.y0 = xr.clone(), yr.clone()
+        self.accx, self.accy = (torch.zeros(n, dtype=torch.float64, device=dev) for _ in range(2))
+        self.status, self.steps_done = (torch.zeros(n, dtype=torch.int32, device=dev) for _ in range(2))
+        self.path = torch.empty((self.rows, n, 2), dtype=torch.float64, device=dev)
+        self.path[0, :, 0], self.path[0, :, 1] = xr, yr
+        self.points = sampler.sample_at(n, xr, yr, torch.full((n,), float(hour), dtype=torch.float64, device=dev))
+
+
+def traj_stage(sampler, ph, out_n, parcels, stage, t0, h, inv_wsum, step, fields=None, with_clip=False, record_only=False):
+    """dpn_traj_stage on the parcels of a ParcelState with the forward's out_n [n, 6] at their evaluation points: stage (trajectory.Stage), the
+    step's start hour t0, the step h (hours), inv_wsum, the step's index; fields [rows, n, 6] fp32 or None (written by a step's first stage and by
+    record_only)."""
+    st = L.DpnTrajStage(float(t0), float(h), float(stage.w), float(stage.a_next), float(stage.c_next), float(inv_wsum), int(step),
+                        int(bool(stage.first)), int(bool(stage.last)), int(bool(record_only)), int(bool(with_clip)))
+    p = parcels
+    x, y, t, f, cd = p.points
+    want_fields = fields is not None and (stage.first or record_only)
+    L.check(L.load().dpn_traj_stage(ctypes.byref(sampler._s), _ptr(sampler.cube), ctypes.byref(ph), _ptr(out_n), p.n, ctypes.byref(st), _ptr(p.x0),
+                                    _ptr(p.y0), _ptr(p.accx), _ptr(p.accy), _ptr(p.status), _ptr(p.steps_done), _ptr(p.path), p.rows,
+                                    _ptr(fields) if want_fields else None, _ptr(x), _ptr(y), _ptr(t), _ptr(f), _ptr(cd), _stream()), 'dpn_traj_stage')

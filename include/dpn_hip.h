@@ -487,6 +487,53 @@ int dpn_diagnostics_out(const float* out_n, const float* jac_n, const float* f, 
                         const int32_t* products /* HOST, n_products ids */, int n_products, float* rows, float* maps, const DpnLattice* lattice,
                         int64_t first, void* stream);
 
+/* ---------------------------------------------------------------- parcel trajectories through the learned wind (csrc/dpn_traj.hip)
+ * One launch = one stage of an explicit Runge-Kutta step for n parcels whose stage positions depend only on the step's start point and the
+ * previous stage's slope (Euler, midpoint, classical RK4; the stage tables live in deepphysinet_amd/trajectory.py).  Between two fields-only
+ * forwards it does everything: the wind from the forward's out_n, the accumulators, the next evaluation point, the domain check, and the sampler's
+ * x, y, t, f, coord_data at that point for the next forward.
+ *   t0        the step's start hour (all parcels share the clock);  h  the step in hours, negative = backward in time
+ *   w         weight of this stage's slope in the step's sum;       inv_wsum  1 / (sum of the weights)
+ *   a_next, c_next   the next evaluation point lies a_next * h along this slope, at hour t0 + c_next * h (not read when last)
+ *   first     the step's first stage (its forward was evaluated at the path point: the optional fields row is written)
+ *   last      the stage that closes the step;   step  the step's index: path row step + 1 is written when last, fields row step when first
+ *   record_only   only write fields row `step` (the final point's); state, path and the sampler outputs are not touched
+ *   with_clip     the clip of P, T, q, rho in the fields rows (as dpn_fields_out); the wind is never clipped */
+typedef struct DpnTrajStage {
+    double t0, h, w, a_next, c_next, inv_wsum;
+    int64_t step;
+    int32_t first, last, record_only, with_clip;
+} DpnTrajStage;
+#define DPN_TRAJ_ALIVE       0
+#define DPN_TRAJ_LEFT_GRID   1   /* the next point left [0, lon - 1] x [0, lat - 1] of the fine grid */
+#define DPN_TRAJ_LEFT_WINDOW 2   /* the next hour left [0, t_hours]                                  */
+#define DPN_TRAJ_BAD_WIND    3   /* u or v not finite                                                */
+/* State per parcel: x0, y0 [n] fp64 (the start point of the current step, fine-grid index units as dpn_sample_at takes them), accx, accy [n] fp64
+ * (the weighted slope sums), status [n] int32 (DPN_TRAJ_*), steps_done [n] int32.  out_n [n][6]: the forward at the current evaluation point.
+ * Per parcel with status 0, every operation an fp64 operation rounded on its own (the kernel is compiled without contraction), left to right:
+ *   u  = (double)denorm(out_n[i][0], 0)      v  = (double)denorm(out_n[i][1], 1)       denorm: dpn_fields_out's fp32 arithmetic, no clip
+ *   kx = (u * 3600.0) / (double)s->dx        ky = (v * 3600.0) / (double)s->dy         index units per hour
+ *   ax = accx + w * kx                       ay = accy + w * ky
+ *   not last:  xe = x0 + (a_next * h) * kx   ye = y0 + (a_next * h) * ky   te = t0 + c_next * h
+ *   last:      xe = x0 + (h * inv_wsum) * ax ye = y0 + (h * inv_wsum) * ay te = t0 + h
+ *   status:    3 when u or v is not finite; else 1 unless 0 <= xe <= lon - 1 and 0 <= ye <= lat - 1; else 2 unless 0 <= te <= t_hours
+ *              (a NaN fails every comparison; the faces themselves are inside)
+ *   still 0, not last:  accx = ax, accy = ay
+ *   still 0, last:      x0 = xe, y0 = ye, accx = accy = 0, steps_done += 1, path[step + 1][i] = (xe, ye)
+ *   still 0:            x, y, t, f, coord_data [i] = the sampler at (xe, ye, te), dpn_sample_at's arithmetic
+ * A parcel whose status becomes non-zero keeps x0, y0, accx, accy, steps_done and its x, y, t, f, coord_data as they were: the state of its last
+ * completed step, and the last valid evaluation point, so that no NaN reaches the next forward (whose result for it is ignored).  When last,
+ * path[step + 1][i] of such a parcel, and of every parcel that came in with a non-zero status, is (NaN, NaN); nothing else of a dead parcel is written.
+ * fields (optional, [path_rows][n][6]): when first or record_only, fields[step][i][k] = denorm(out_n[i][k], k, with_clip) for parcels that came in
+ * with status 0, NaN for the others.  path: [path_rows][n][2] fp64; row 0 (the start points) is the caller's.
+ * 256-thread blocks, one parcel per thread, no atomics, no LDS; all stores are per-thread vector stores.
+ * -1 (nothing launched, nothing written): a NULL s, cube, phys, out_n, st, state pointer, path or sampler output; n <= 0; a sampler dimension < 2;
+ * h == 0 or not finite; t0, w, a_next, c_next or inv_wsum not finite; step < 0, step + 1 >= path_rows (record_only: step >= path_rows); fields
+ * with neither first nor record_only; record_only without fields. */
+int dpn_traj_stage(const DpnSampler* s, const float* cube, const DpnPhysics* phys, const float* out_n, int64_t n, const DpnTrajStage* st,
+                   double* x0, double* y0, double* accx, double* accy, int32_t* status, int32_t* steps_done, double* path, int64_t path_rows,
+                   float* fields, float* x, float* y, float* t, float* f, float* coord_data, void* stream);
+
 /* The same step with the optimiser state held as ONE flat fp32 buffer per moment: tensor i lives at offset (sum of ceil(numel_j / 2048)
  * over j < i) * 2048, i.e. every tensor is padded to whole 2048-element chunks; dpn_clip_adam_flat_floats gives the buffer length.
  * No per-tensor state pointers travel in the kernel arguments, so up to 160 tensors are ONE launch per pass: three launches for a

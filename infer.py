@@ -2,6 +2,7 @@
 """Inference launcher next to train.py, with the same three flags: --config_file, --checkpoint_path, --log_path.
 
     python infer.py [--config_file cfg.py] [--checkpoint_path DIR] [--log_path DIR] [--synthetic] [--ema] [--diagnostics name[,name...]]
+                    [--trajectories LON,LAT[;LON,LAT...] --traj_start H --traj_hours D --traj_step S [--traj_method rk4]]
 
 Builds the interface from the config (train.py's loader), loads `physics_latest.pth` from --checkpoint_path (or inference_cfg.checkpoints) and
 calls `run_inference_interface`: every field sample is evaluated on the lattice inference_cfg.img_size (x `refine`) at every inference_cfg.dt
@@ -9,7 +10,10 @@ seconds of its window, and with log.write_source the maps go to --log_path (or i
 exported variable.  The reference's dataset is file I/O that does not exist offline: a config that names no `samples` source fails, unless
 --synthetic asks for a random field sample (smoke runs: the maps are noise).  --ema evaluates the checkpoint's averaged weights (`model_ema`, written by
 train.py --ema) in place of the raw ones; a checkpoint without them is a KeyError.  --diagnostics vorticity,dT_dt sets
-inference_cfg.log.export_diagnostic: derived products of the Jacobian (deepphysinet_amd.diagnostics.PRODUCTS), one more .npy per time step and name."""
+inference_cfg.log.export_diagnostic: derived products of the Jacobian (deepphysinet_amd.diagnostics.PRODUCTS), one more .npy per time step and name.
+--trajectories 100.5,30.25;110,35 --traj_start 24 --traj_hours -24 --traj_step 0.25 sets inference_cfg.trajectories: parcels started at those places
+(degrees east, north) at hour 24 of each sample's window and followed backward for a day in 15-minute RK4 steps through the network's own wind
+(InterfacePhysics.trajectories); positions, hours, status, step counts and the six fields along the paths are written as <time>_traj_*.npy."""
 import argparse
 
 import torch
@@ -25,6 +29,12 @@ parse.add_argument('--synthetic', action='store_true', help="samples='synthetic'
 parse.add_argument('--ema', action='store_true', help="weights='ema': the checkpoint's averaged weights (model_ema) in place of the raw ones")
 parse.add_argument('--diagnostics', default=None, type=lambda s: [n for n in s.split(',') if n],
                    help='name[,name...]: inference_cfg.log.export_diagnostic, derived products (deepphysinet_amd.diagnostics.PRODUCTS) written next to the variables')
+parse.add_argument('--trajectories', default=None, type=lambda s: [tuple(float(v) for v in p.split(',')) for p in s.split(';') if p],
+                   help='LON,LAT[;LON,LAT...]: inference_cfg.trajectories, start places of parcel trajectories in degrees east, north')
+parse.add_argument('--traj_start', default=0.0, type=float, help='start hour inside the sample window')
+parse.add_argument('--traj_hours', default=None, type=float, help='duration in hours; negative: back-trajectories')
+parse.add_argument('--traj_step', default=0.25, type=float, help='step in hours')
+parse.add_argument('--traj_method', default='rk4', type=str, help='euler | midpoint | rk4')
 
 if __name__ == '__main__':
     args = parse.parse_args()
@@ -34,6 +44,11 @@ if __name__ == '__main__':
         cfg.setdefault('inference_cfg', {}).setdefault('log', {})['result_path'] = args.log_path
     if args.diagnostics:
         cfg.setdefault('inference_cfg', {}).setdefault('log', {})['export_diagnostic'] = args.diagnostics
+    if args.trajectories:
+        if args.traj_hours is None or any(len(p) != 2 for p in args.trajectories):
+            parse.error('--trajectories takes LON,LAT pairs and needs --traj_hours')
+        cfg.setdefault('inference_cfg', {})['trajectories'] = dict(lonlat=args.trajectories, start=args.traj_start, hours=args.traj_hours,
+                                                                   step=args.traj_step, method=args.traj_method)
     model = builder_models(**cfg)
     kwargs = dict(checkpoint_path=args.checkpoint_path)
     if args.synthetic:
@@ -48,3 +63,6 @@ if __name__ == '__main__':
     if model.last_diagnostics is not None:
         d = model.last_diagnostics
         print('diagnostics %s: maps %s, finite %s' % (','.join(d['names']), tuple(d['maps'].shape), bool(torch.isfinite(d['maps']).all())))
+    if model.last_trajectories is not None:
+        tr = model.last_trajectories
+        print('trajectories: positions %s, steps done %s, status %s' % (tuple(tr['positions'].shape), tr['steps_done'].tolist(), tr['status'].tolist()))

@@ -2,7 +2,7 @@
 
     python tools/kernel_isa_digest.py > after.txt          # no GPU needed; the same on the commit to compare with, then diff the tables
 
-Every entry of deepphysinet_amd.build.UNITS is compiled to gfx950 assembly with that unit's flags (minus -fPIC, as the hazard test does).
+Every entry of deepphysinet_amd.build.ALL_UNITS is compiled to gfx950 assembly with that unit's flags (minus -fPIC, as the hazard test does).
 Body = the text from the kernel's label to its .Lfunc_end, without `;` comments, with the function index taken out of the local labels
 (.LBB<i>_ -> .LBB_, .Ltmp<i> -> .Ltmp), the kernel's own mangled name written $self, and without the directive that returns to the kernel's
 text section (.text, or the comdat .section .text.<name> of a template instantiation): it does not change when kernels move between units,
@@ -19,7 +19,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from deepphysinet_amd.build import COMMON, UNITS
+from deepphysinet_amd.build import ALL_UNITS, COMMON
 
 
 def digest(text):
@@ -36,7 +36,7 @@ def body_text(asm, name):
 def main():
     with tempfile.TemporaryDirectory() as tmp:
         procs = []
-        for i, (src, flags, obj) in enumerate(UNITS):                   # the units compile side by side
+        for i, (src, flags, obj) in enumerate(ALL_UNITS):               # the units compile side by side
             out = os.path.join(tmp, '%d.s' % i)
             procs.append((obj, out, subprocess.Popen(['hipcc', *[f for f in COMMON if f != '-fPIC'], *flags, '--cuda-device-only', '-S',
                                                       '-I' + os.path.join(ROOT, 'include'), src, '-o', out])))

@@ -22,7 +22,7 @@ def build(extra=()):
     obj = os.path.join(B.HERE, 'csrc', '_obj')
     os.makedirs(obj, exist_ok=True)
     objs = []
-    for src, flags, name in B.UNITS:
+    for src, flags, name in B.ALL_UNITS:
         o = os.path.join(obj, 'tl_' + name)
         cmd = ['hipcc', *B.COMMON, *flags, '-DDPN_TIMELINE', *extra, '-I' + os.path.join(ROOT, 'include'), '-c', src, '-o', o]
         subprocess.run(cmd, check=True)

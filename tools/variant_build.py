@@ -19,12 +19,12 @@ def build(name, extra, unit=0):
     obj = os.path.join(B.HERE, 'csrc', '_obj')
     # the product library is NOT rebuilt here: an experiment that edits a header must not leak into libdpn_hip.so (it did once: a timing
     # ablation with wrong arithmetic sat in the product library until the next build).  Only the objects of the other units are needed.
-    others = [u for i, u in enumerate(B.UNITS) if i not in units]
+    others = [u for i, u in enumerate(B.ALL_UNITS) if i not in units]          # (indices: UNITS is the head of ALL_UNITS)
     if not all(os.path.exists(os.path.join(obj, u[2])) for u in others):
         B.build_library()
     objs = []
     for k in units:
-        src, flags, base = B.UNITS[k]
+        src, flags, base = B.ALL_UNITS[k]
         o = os.path.join(obj, 'var_%s_%s' % (name, base))
         subprocess.run(['hipcc', *B.COMMON, *flags, *extra, '-I' + os.path.join(ROOT, 'include'), '-c', src, '-o', o], check=True)
         objs.append(o)
