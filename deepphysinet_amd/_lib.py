@@ -111,6 +111,11 @@ class DpnTrajStage(Structure):
                [(n, c_int32) for n in ('first', 'last', 'record_only', 'with_clip')]
 
 
+class DpnEnsembleOut(Structure):
+    """include/dpn_hip.h DpnEnsembleOut: the six destinations of dpn_ensemble_finish, in row form or in map form."""
+    _fields_ = [(n, c_void_p) for n in ('mean', 'spread', 'min', 'max', 'count', 'prob')]
+
+
 class DpnStepGuard(Structure):
     _fields_ = [(n, c_int32) for n in ('skipped_nonfinite', 'skipped_spike', 'verdict', 'seen', 'consecutive', 'reserved')] + \
                [('running', c_double), ('last', c_double)]
@@ -188,6 +193,10 @@ EXPORTS = {
     'dpn_residual_points': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(DpnGeometry), POINTER(DpnPhysics), c_void_p, c_void_p]),
     'dpn_diagnostics_out': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(DpnPhysics), c_int, POINTER(c_int32), c_int, c_void_p, c_void_p,
                                     POINTER(DpnLattice), c_int64, c_void_p]),
+    'dpn_ensemble_accumulate': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(DpnPhysics), c_int, POINTER(c_int32), c_int, POINTER(c_int32),
+                                        POINTER(c_float), c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dpn_ensemble_finish': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, POINTER(c_int32), c_int, c_int64, c_int64,
+                                    POINTER(DpnEnsembleOut), POINTER(DpnEnsembleOut), POINTER(DpnLattice), c_void_p]),
     'dpn_traj_stage': (c_int, [POINTER(DpnSampler), c_void_p, POINTER(DpnPhysics), c_void_p, c_int64, POINTER(DpnTrajStage), c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dpn_label_errors_blocks': (c_int64, [c_int64]),
@@ -229,6 +238,7 @@ EXPORTS = {
 STEP_LOSSES = 16              # one field's row of dpn_step_finish_batch (include/dpn_hip.h)
 
 DIAG_PRODUCTS = 28            # DPN_DIAG_PRODUCTS (include/dpn_hip.h)
+ENS_PRODUCTS, ENS_MAX_THRESHOLDS = 34, 16          # DPN_ENS_PRODUCTS, DPN_ENS_MAX_THRESHOLDS (include/dpn_hip.h)
 CAUSAL_MAX_BINS = 64          # DPN_CAUSAL_MAX_BINS (include/dpn_hip.h)
 BALANCE_MAX_TERMS, BALANCE_STEP_TERMS = 16, 13          # DPN_BALANCE_MAX_TERMS, DPN_BALANCE_STEP_TERMS (include/dpn_hip.h)
 

@@ -17,13 +17,14 @@ import torch.nn as nn
 from ..balance import LossBalance
 from ..causal import CausalWeights
 from ..diagnostics import product_ids
+from ..ensemble import check_thresholds, ensemble_ids
 from ..trajectory import check_request, domain_of, stage_table
 from ..losses.builder import builder_loss
 from ..model.physics_net import PhysicsNet
 from ..guard import StepGuard
 from ..optim import GROUP_KEYS, FusedClipAdam, resolve_param_groups
 from ..point_path import (balance_sumsq, balance_update, balanced_total, data_losses_batch, eval_step, eval_step_batch, grid_maps, label_errors, ParcelState,
-                          LOSS_ORDER, OBS_ORDER, PackedField, pde_losses, pde_losses_batch, point_fields, point_sizes, PointConfig, require_gpu,
+                          EnsembleState, LOSS_ORDER, OBS_ORDER, PackedField, pde_losses, pde_losses_batch, point_fields, point_sizes, PointConfig, require_gpu,
                           smooth_l1_data_loss, step_losses, step_losses_batch)
 from ..sampler import SyntheticSamples
 from ..staged_backward import StagedBackward
@@ -78,6 +79,7 @@ class InterfacePhysics(nn.Module):
         self.loss_balance_state = None          # training_step(balance=...): {'groups', 'lam' (fp32 [K], device), 'step', 'diag' (device or None)}
         self.last_trajectories = None           # run_inference_interface with inference_cfg.trajectories: the last sample's trajectories() dict (lonlat)
         self.last_diagnostics = None            # run_inference_interface with log.export_diagnostic: {'names', 'maps' [nt, P, ny, nx]} of the last sample
+        self.last_ensemble = None               # run_inference_interface with inference_cfg.ensemble: ensemble_lattice's dict over all samples
 
     # ------------------------------------------------------------------ configuration of the HIP path
     def point_config(self, loss_factor=None, criterion=None) -> PointConfig:
@@ -428,6 +430,90 @@ class InterfacePhysics(nn.Module):
         for first, n, x, y, t, f, cd in self._lattice_chunks(sampler, lattice, chunk):
             field.diagnostics(x, y, t, f, cd, ids, with_clip, maps=maps, lattice=lattice, first=first)
         return maps
+
+    # ------------------------------------------------------------------ ensemble statistics over field samples
+    ENS_POINT_BYTES = DIAG_POINT_BYTES                  # a chunk's per-point buffers, as diagnostics (the state of ALL points stays resident, on top)
+    _ENS_SHARED = ('lat_size', 'lon_size', 'dx', 'dy', 'input_time_step', 'input_time_step_nums')
+    _ENS_SHARED_LONLAT = ('begin_lon', 'begin_lat', 'out_res_deg')
+
+    def _ensemble_request(self, members, products, thresholds, lonlat=False):
+        """The checks of ensemble_at / ensemble_lattice, all before the first launch: names (KeyError), thresholds (ValueError), at least one member,
+        and members that share the fine grid and the hour window (lonlat: origin and resolution too).  -> members (a list), names, an EnsembleState
+        factory, the (name, value) list of the thresholds."""
+        names = list(products)
+        ids = ensemble_ids(names)
+        thr_col, thr_val = check_thresholds(names, thresholds)
+        members = list(members)
+        if not members:
+            raise ValueError('ensemble: no members (a sequence of dicts with field_data, forecast_h and sampler)')
+        ref = members[0]['sampler'].cfg
+        for m, mem in enumerate(members[1:], start=1):
+            for name in self._ENS_SHARED + (self._ENS_SHARED_LONLAT if lonlat else ()):
+                if getattr(mem['sampler'].cfg, name) != getattr(ref, name):
+                    raise ValueError('ensemble member %d: %s = %r, but member 0 has %r; the members must share the fine grid and the hour window'
+                                     % (m, name, getattr(mem['sampler'].cfg, name), getattr(ref, name)))
+        dev = members[0]['sampler'].cube.device
+        return members, names, (lambda n_total: EnsembleState(n_total, ids, thr_col, thr_val, dev)), [(names[c], v) for c, v in zip(thr_col, thr_val)]
+
+    @staticmethod
+    def _ensemble_outputs(shape_of, P, E, dev):
+        out = {k: torch.empty(shape_of(P), dtype=torch.float32, device=dev) for k in ('mean', 'spread', 'min', 'max')}
+        out['count'] = torch.empty(shape_of(P), dtype=torch.int32, device=dev)
+        out['prob'] = torch.empty(shape_of(E), dtype=torch.float32, device=dev) if E else None
+        return out
+
+    @torch.no_grad()
+    def ensemble_at(self, members, x_idx, y_idx, hours, products, thresholds=None, with_clip=False, lonlat=False):
+        """Statistics over the members of an ensemble at N stations.  members: a sequence of dicts with field_data, forecast_h and sampler (what
+        _inference_samples yields) -- the forecasts of different initialisation dates that cover one window (a lagged ensemble), or perturbed members --
+        which share the fine grid and the hour window; positions and hours (as predict_points takes them) are read in each member's own window.
+        products: names of deepphysinet_amd.ensemble.ENSEMBLE_PRODUCTS (the diagnostics and u, v, p, T, q, rho); thresholds: dict name -> value(s), at
+        most 16 in all.  The members are the outer loop: encoder, heads and packing run once per member and one PackedField is alive at a time; each
+        member's values are folded into a state that stays on the device (dpn_ensemble_accumulate: Welford in fp64), and after the last member one
+        dpn_ensemble_finish per chunk writes the results, with no host synchronisation in between.  A member whose value is not finite at a point
+        is skipped there, in that column.  Returns {'names', 'mean', 'spread' (sample standard deviation, NaN below two members), 'min', 'max' [N, P]
+        fp32, 'count' [N, P] int32, 'thresholds' [(name, value)], 'prob' [N, E] (the share of the counted members above the threshold, strictly; None
+        without thresholds)}, on the device."""
+        members, names, new_state, thr = self._ensemble_request(members, products, thresholds, lonlat)
+        s0 = members[0]['sampler']
+        if lonlat:
+            x_idx, y_idx = s0.lonlat_to_index(x_idx, y_idx)
+        xr, yr, tr = s0.check_positions(x_idx, y_idx, hours)
+        N, dev = xr.shape[0], s0.cube.device
+        chunk = self.chunk_size(N, None, self.ENS_POINT_BYTES, self.precision)
+        state = new_state(N)
+        bufs = tuple(torch.empty(chunk, dtype=torch.float32, device=dev) for _ in range(4)) + (torch.empty((chunk, 6), dtype=torch.float32, device=dev),)
+        for mem in members:
+            field = self._inference_weights(mem['field_data'].to(dev), mem['forecast_h'].to(dev), chunk)
+            for first in range(0, N, chunk):
+                n = min(chunk, N - first)
+                x, y, t, f, cd = mem['sampler'].sample_at(n, xr[first:first + n], yr[first:first + n], tr[first:first + n], out=bufs)
+                field.ensemble_accumulate(x, y, t, f, cd, state, first, with_clip)
+            del field                                                     # before the next member packs its own
+        out = self._ensemble_outputs(lambda c: (N, c), len(names), len(thr), dev)
+        for first in range(0, N, chunk):
+            n = min(chunk, N - first)
+            state.finish(first, n, rows={k: None if v is None else v[first:first + n] for k, v in out.items()})
+        return dict(out, names=names, thresholds=thr)
+
+    @torch.no_grad()
+    def ensemble_lattice(self, members, lattice, products, thresholds=None, with_clip=False, chunk_points=None):
+        """ensemble_at on a lattice: the statistics as maps [nt, P, ny, nx] and the probabilities as maps [nt, E, ny, nx]; chunked as predict_lattice is,
+        inside the loop over the members (per point the members arrive in their given order whatever the chunking, so chunk_points does not change a
+        bit of the result).  count is 0 and the rest NaN where the lattice leaves every member's coarse cube."""
+        members, names, new_state, thr = self._ensemble_request(members, products, thresholds)
+        total, dev = lattice.n_points, members[0]['sampler'].cube.device
+        chunk = self.chunk_size(total, chunk_points, self.ENS_POINT_BYTES, self.precision)
+        state = new_state(total)
+        for mem in members:
+            field = self._inference_weights(mem['field_data'].to(dev), mem['forecast_h'].to(dev), chunk)
+            for first, n, x, y, t, f, cd in self._lattice_chunks(mem['sampler'], lattice, chunk):
+                field.ensemble_accumulate(x, y, t, f, cd, state, first, with_clip)
+            del field                                                     # before the next member packs its own
+        out = self._ensemble_outputs(lambda c: (lattice.nt, c, lattice.ny, lattice.nx), len(names), len(thr), dev)
+        for first in range(0, total, chunk):
+            state.finish(first, min(chunk, total - first), maps=out, lattice=lattice)
+        return dict(out, names=names, thresholds=thr)
 
     @torch.no_grad()
     def trajectories(self, field_data, sampler, x_idx, y_idx, hours, forecast_h, duration_hours, step_hours, method='rk4', lonlat=False,
@@ -1444,6 +1530,11 @@ class InterfacePhysics(nn.Module):
         followed for D hours (negative: backward) in steps of S hours; the last sample's result stays in self.last_trajectories, and with
         log.write_source `<time>_traj_positions.npy` [K + 1, N, 2] (degrees), `_traj_hours.npy`, `_traj_status.npy`, `_traj_steps.npy` and
         `_traj_fields.npy` [K + 1, N, 6] go next to the maps, <time> the sample's first time step.  A bad request fails before the checkpoint is read.
+        inference_cfg.ensemble (default absent: no further call) = dict(products=[names of deepphysinet_amd.ensemble.ENSEMBLE_PRODUCTS],
+        thresholds={name: [values]}): the per-sample loop runs as without it, then ONE ensemble_lattice call takes all samples as the members of an
+        ensemble on the first sample's lattice with the same with_clip; its dict stays in self.last_ensemble, and with log.write_source
+        `<time>_ens_<mean|spread|min|max|count>_<name>.npy` and `<time>_ens_prob_<name>_gt_<value>.npy` [lat, lon] are written per time step, <time>
+        the first sample's stamps.  An unknown name (KeyError) or a bad threshold (ValueError) fails before the checkpoint is read.
         Plotting (log.with_vis: Basemap) is not built."""
         import datetime
         ic = self.inference_cfg or {}
@@ -1484,6 +1575,12 @@ class InterfacePhysics(nn.Module):
                 raise ValueError('inference_cfg.trajectories: at least one (lon, lat), a non-zero step and a non-zero duration')
             float(traj['start'])
         self.last_trajectories = None
+        ens = ic.get('ensemble')
+        if ens:
+            ens = dict(products=list(ens['products']), thresholds=dict(ens.get('thresholds') or {}))
+            ensemble_ids(ens['products'])                                 # an unknown name (KeyError), a bad threshold (ValueError): before the
+            check_thresholds(ens['products'], ens['thresholds'])          # checkpoint is read
+        self.last_ensemble = None
         self.physics_net.to(device)
         self.pe.to(device)
         state_dict, current_epoch, global_step = (None, 0, 0) if not checkpoint_path else self.load_model(checkpoint_path, prefix='physics', map_location=device)
@@ -1504,7 +1601,11 @@ class InterfacePhysics(nn.Module):
         if write_source:
             os.makedirs(result_path, exist_ok=True)
         maps = None
-        for k, smp in enumerate(self._inference_samples(kwargs)):
+        samples = self._inference_samples(kwargs)
+        if ens:
+            samples = list(samples)                                       # the members of the ensemble call behind the loop
+        first_lattice = None
+        for k, smp in enumerate(samples):
             sampler = smp['sampler']
             c = sampler.cfg
             if (lat_size, lon_size) != (c.lat_size, c.lon_size):
@@ -1513,6 +1614,7 @@ class InterfacePhysics(nn.Module):
             window_h = c.input_time_step * c.input_time_step_nums
             nt = int(window_h * 3600.0 / dt + 1e-9) + 1                   # every dt inside [0, window], both ends
             lattice = sampler.lattice(refine=refine, hours=(0.0, dt / 3600.0, nt))
+            first_lattice = first_lattice or lattice
             maps = self.predict_lattice(smp['field_data'].to(device), sampler, lattice, smp['forecast_h'].to(device),
                                         with_clip=kwargs.get('with_clip', self.with_clip))
             diag = None
@@ -1538,6 +1640,20 @@ class InterfacePhysics(nn.Module):
                         np.save(os.path.join(result_path, '%s_%s.npy' % (stamp, v)), host[it, names[v.upper()]])
                     for j, name in enumerate(export_diagnostic):
                         np.save(os.path.join(result_path, '%s_%s.npy' % (stamp, name)), host_diag[it, j])
+        if ens and first_lattice is not None:
+            e = self.ensemble_lattice(samples, first_lattice, ens['products'], ens['thresholds'], with_clip=kwargs.get('with_clip', self.with_clip))
+            self.last_ensemble = e
+            if write_source:
+                import numpy as np
+                host = {key: e[key].cpu().numpy() for key in ('mean', 'spread', 'min', 'max', 'count')}
+                prob = None if e['prob'] is None else e['prob'].cpu().numpy()
+                for it in range(first_lattice.nt):                        # the stamps of the first sample
+                    stamp = (start + datetime.timedelta(seconds=it * dt)).strftime('%Y-%m-%d_%H_%M_%S')
+                    for j, name in enumerate(e['names']):
+                        for key, a in host.items():
+                            np.save(os.path.join(result_path, '%s_ens_%s_%s.npy' % (stamp, key, name)), a[it, j])
+                    for j, (name, value) in enumerate(e['thresholds']):
+                        np.save(os.path.join(result_path, '%s_ens_prob_%s_gt_%g.npy' % (stamp, name, value)), prob[it, j])
         return maps
 
 

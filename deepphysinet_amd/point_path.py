@@ -19,6 +19,7 @@ import torch
 
 from . import _lib as L
 from . import branch, config
+from .ensemble import reads_coriolis, reads_jacobian
 from .grad_arena import new_grad, slot_of
 
 # configs/DeepPhysiNet_NCEP_cfg.py:64-76 -- order u10, v10, pres, t2, q2, rio (network output order)
@@ -1315,6 +1316,21 @@ class PackedField:
         L.check(L.load().dpn_diagnostics_out(_ptr(out_n), _ptr(jac_n), _ptr(f), out_n.shape[0], ctypes.byref(ph), int(bool(with_clip)), ids, len(ids),
                                              _ptr(rows), _ptr(maps), lat, first, _stream()), 'dpn_diagnostics_out')
 
+    def ensemble_accumulate(self, x, y, t, f, coord_data, state, first=0, with_clip=False):
+        """This field, as one member of an ensemble, at points x, y, t, f [n], coord_data [n, 6], folded into `state` (an EnsembleState) at its points
+        first .. first + n (dpn_ensemble_accumulate).  The request chooses the forward: with the Jacobian (as `diagnostics`) iff a selected product
+        reads it, otherwise the fields-only one (as `fields`).  with_clip as `diagnostics` takes it."""
+        need_j = reads_jacobian(state.ids)
+        out_n, jac_n = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=need_j, want_saved=False)
+        ph = self.cfg.physics()
+        for k in range(2, L.NETS):                             # `with_clip` is this call's own, as in `diagnostics`
+            ph.clip_on[k] = int(bool(with_clip) and bool(self.cfg.clip_vars[k]))
+        s = state
+        L.check(L.load().dpn_ensemble_accumulate(_ptr(out_n), _ptr(jac_n) if need_j else None, _ptr(f) if reads_coriolis(s.ids) else None, out_n.shape[0],
+                                                 ctypes.byref(ph), int(bool(with_clip)), s.c_ids, len(s.ids), s.c_thr_col, s.c_thr_val, len(s.thr_col),
+                                                 int(first), s.n_total, _ptr(s.count), _ptr(s.mean), _ptr(s.m2), _ptr(s.vmin), _ptr(s.vmax),
+                                                 _ptr(s.exceed), _stream()), 'dpn_ensemble_accumulate')
+
     def residual_scores(self, x, y, t, f, coord_data, factors, k=1.0):
         """Scores of a pool of candidate points for residual-weighted sampling (CollocationSampler.get_inter_data_adaptive): `residuals` on the m
         points, then dpn_adaptive_scores -- score_i = sum_e factors[e] * res_ie ** 2 in fp64, factors = six floats in LOSS_ORDER.  Returns
@@ -1343,6 +1359,38 @@ class PackedField:
         if self._traj_ph is None:                  # the table is built once per field, not once per stage (384 stages a day)
             self._traj_ph = self.cfg.physics()
         traj_stage(sampler, self._traj_ph, out_n, parcels, stage, t0, h, inv_wsum, step, fields, with_clip, record_only)
+
+
+class EnsembleState:
+    """Device state of an ensemble request between dpn_ensemble_accumulate launches (include/dpn_hip.h): for n_total points, the P columns `ids`
+    (ensemble.ensemble_ids) and the E thresholds (thr_col, thr_val of ensemble.check_thresholds), product-major: count [P, n_total] int32, mean, m2
+    [P, n_total] fp64, vmin, vmax [P, n_total] fp32, exceed [E, n_total] int32.  count, mean, m2 and exceed start at zero; vmin and vmax are not
+    filled (count == 0 means "not yet set").  `finish` turns points first .. first + n into the six outputs, as rows or as maps."""
+
+    POINT_BYTES = 4 + 8 + 8 + 4 + 4                        # per point and column; 4 more per point and threshold
+
+    def __init__(self, n_total, ids, thr_col, thr_val, device):
+        self.n_total, self.ids, self.thr_col, self.thr_val = int(n_total), list(ids), list(thr_col), [float(v) for v in thr_val]
+        P, E = len(self.ids), len(self.thr_col)
+        if not 1 <= P <= L.ENS_PRODUCTS or E > L.ENS_MAX_THRESHOLDS or len(self.thr_val) != E or self.n_total < 1:
+            raise ValueError('EnsembleState: %d points, %d products (1..%d), %d thresholds (0..%d)' % (self.n_total, P, L.ENS_PRODUCTS, E, L.ENS_MAX_THRESHOLDS))
+        self.c_ids = (ctypes.c_int32 * P)(*self.ids)
+        self.c_thr_col = (ctypes.c_int32 * max(E, 1))(*self.thr_col)
+        self.c_thr_val = (ctypes.c_float * max(E, 1))(*self.thr_val)
+        self.count = torch.zeros((P, self.n_total), dtype=torch.int32, device=device)
+        self.mean, self.m2 = (torch.zeros((P, self.n_total), dtype=torch.float64, device=device) for _ in range(2))
+        self.vmin, self.vmax = (torch.empty((P, self.n_total), dtype=torch.float32, device=device) for _ in range(2))
+        self.exceed = torch.zeros((E, self.n_total), dtype=torch.int32, device=device) if E else None
+
+    def finish(self, first, n, rows=None, maps=None, lattice=None):
+        """dpn_ensemble_finish for points first .. first + n: rows / maps = dict(mean, spread, min, max, count, prob) of tensors in row form ([n, P],
+        [n, E]) or in map form ([nt, P, ny, nx], [nt, E, ny, nx] of `lattice`); prob may be None without thresholds."""
+        def table(d):
+            return None if d is None else ctypes.byref(L.DpnEnsembleOut(*[_ptr(d.get(k)) for k in ('mean', 'spread', 'min', 'max', 'count', 'prob')]))
+        lat = None if lattice is None else ctypes.byref(lattice.c_struct())
+        L.check(L.load().dpn_ensemble_finish(_ptr(self.count), _ptr(self.mean), _ptr(self.m2), _ptr(self.vmin), _ptr(self.vmax), _ptr(self.exceed),
+                                             self.n_total, len(self.ids), self.c_thr_col, len(self.thr_col), int(first), int(n), table(rows), table(maps),
+                                             lat, _stream()), 'dpn_ensemble_finish')
 
 
 class ParcelState:

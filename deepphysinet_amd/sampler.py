@@ -260,9 +260,9 @@ class CollocationSampler:
                                        int(first), int(n), _ptr(x), _ptr(y), _ptr(t), _ptr(f), _ptr(cd), _stream()), 'dpn_sample_at')
         return x, y, t, f, cd
 
-    def at_positions(self, x_idx, y_idx, hours):
-        """-> x, y, t, coord_data, f (as get_margin_grid) at given positions: fractional fine-grid indices and fractional hours, one per station.
-        IndexError outside the fine grid or outside [0, input_time_step * input_time_step_nums] hours."""
+    def check_positions(self, x_idx, y_idx, hours):
+        """Station positions checked on the host and put on the device: (xr, yr, tr), fp64 [n], as sample_at takes them.  IndexError outside the fine
+        grid or outside [0, input_time_step * input_time_step_nums] hours."""
         c = self.cfg
         pos = [np.ascontiguousarray(np.atleast_1d(v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)), dtype=np.float64).reshape(-1)
                for v in (x_idx, y_idx, hours)]
@@ -273,8 +273,13 @@ class CollocationSampler:
         for v, top in zip(pos, hi):
             if not (np.all(v >= 0.0) and np.all(v <= top)):          # (NaN fails both)
                 raise IndexError('position / hour outside the domain')
-        xr, yr, tr = (torch.from_numpy(v).to(self.cube.device) for v in pos)
-        x, y, t, f, cd = self.sample_at(n, xr, yr, tr)
+        return tuple(torch.from_numpy(v).to(self.cube.device) for v in pos)
+
+    def at_positions(self, x_idx, y_idx, hours):
+        """-> x, y, t, coord_data, f (as get_margin_grid) at given positions: fractional fine-grid indices and fractional hours, one per station.
+        IndexError outside the fine grid or outside [0, input_time_step * input_time_step_nums] hours."""
+        xr, yr, tr = self.check_positions(x_idx, y_idx, hours)
+        x, y, t, f, cd = self.sample_at(xr.shape[0], xr, yr, tr)
         return x, y, t, cd, f.unsqueeze(1)
 
     def lonlat_to_index(self, lon_deg, lat_deg):

@@ -486,6 +486,48 @@ int dpn_residual_points(const float* out_n, const float* jac_n, const float* f, 
 int dpn_diagnostics_out(const float* out_n, const float* jac_n, const float* f, int64_t n, const DpnPhysics* phys, int with_clip,
                         const int32_t* products /* HOST, n_products ids */, int n_products, float* rows, float* maps, const DpnLattice* lattice,
                         int64_t first, void* stream);
+/* Ensemble statistics over field samples (csrc/dpn_ensemble.inc, compiled into csrc/dpn_diag.hip): the members of a lagged or perturbed ensemble are
+ * folded one by one into a resident state, and one finish call turns the state into mean, spread, min, max, count and exceedance probabilities.
+ * Product ids: 0..27 are dpn_diagnostics_out's; 28..33 are the de-normalised variables u, v, p, T, q, rho = val[0..5] of the residual body, the value
+ * dpn_fields_out writes for the same out_n, *phys and with_clip.  The products are formed exactly as dpn_diagnostics_out forms them (same expressions,
+ * same order, no contraction, the same NaN rule: a point with a NaN among its six out_n is NaN in every product).
+ * State of a request of n_total points and P = n_products columns, E = n_thr thresholds, product-major (a wave's accesses run along the points):
+ *   int32 count[P][n_total], double mean[P][n_total], double m2[P][n_total], float vmin[P][n_total], float vmax[P][n_total], int32 exceed[E][n_total].
+ * The caller zeroes count, mean, m2 and exceed (a plain memset) before the first member; vmin and vmax need no filling: count == 0 means "not yet set".
+ * dpn_ensemble_accumulate folds ONE member's values at points first .. first + n (out_n, jac_n, f: that chunk's rows, as dpn_diagnostics_out takes them)
+ * into the state.  Per column j, with x the product products[j] at the point: if x is not finite, nothing of the column changes; otherwise, every
+ * operation an fp64 operation rounded on its own, left to right:
+ *   c = count + 1;  d = (double)x - mean;  mean = mean + d / (double)c;  m2 = m2 + d * ((double)x - mean);  count = c
+ *   vmin = (c == 1) ? x : fminf(vmin, x);   vmax = (c == 1) ? x : fmaxf(vmax, x)      (as comparisons, x < vmin and x > vmax: between +0 and -0,
+ *                                                                                      where fminf may return either, the earlier member's stays)
+ *   for every threshold e with thr_col[e] == j:  exceed[e] += (x > thr_val[e])                       (strict)
+ * products, thr_col (the column 0..n_products - 1 a threshold applies to) and thr_val are HOST arrays.  jac_n may be NULL when no selected id reads the
+ * Jacobian (ids 0..24 and 27 do), f when id 19 is not selected: the kernel instantiated for such a request reads J = 0 (f = 0) from no memory.
+ * One thread per point, 256-thread blocks, no atomics, no LDS, plain vector stores; members follow each other on one stream.
+ * dpn_ensemble_finish writes, for points first .. first + n and every column j (c = count):
+ *   mean = (float)mean, NaN when c == 0;   spread = (float)sqrt(m2 / (double)(c - 1)), NaN when c < 2;   min, max: NaN when c == 0;   count = c
+ *   prob[e] = (float)((double)exceed[e] / (double)count[thr_col[e]]), NaN when that count is 0
+ * into exactly one destination form: *rows, five arrays [n][P] (count int32) and prob [n][E] (stations; lattice = NULL), or *maps, [nt][P][ny][nx] and
+ * [nt][E][ny][nx] where the n points are points first .. first + n of *lattice (placement as dpn_diagnostics_out: stores run along ix; a chunk may begin
+ * and end anywhere in a plane).  prob may be NULL when n_thr == 0.
+ * -1 (nothing launched, nothing written), both calls: a NULL required pointer (thr_col, thr_val, exceed, prob: required when n_thr > 0); n <= 0; first < 0;
+ * first + n > n_total; n_products outside 1..DPN_ENS_PRODUCTS; n_thr outside 0..DPN_ENS_MAX_THRESHOLDS; a thr_col outside 0..n_products - 1.
+ * accumulate: an id outside 0..DPN_ENS_PRODUCTS - 1; a threshold that is not finite; a selected id that reads J (f) while jac_n (f) is NULL.
+ * finish: both destination forms or neither; maps without lattice, rows with one; nx / ny / nt < 1; first + n > nx * ny * nt. */
+#define DPN_ENS_PRODUCTS 34
+#define DPN_ENS_MAX_THRESHOLDS 16
+typedef struct DpnEnsembleOut {
+    float *mean, *spread, *min, *max;
+    int32_t* count;
+    float* prob;
+} DpnEnsembleOut;
+int dpn_ensemble_accumulate(const float* out_n, const float* jac_n, const float* f, int64_t n, const DpnPhysics* phys, int with_clip,
+                            const int32_t* products /* HOST, n_products ids */, int n_products, const int32_t* thr_col /* HOST [n_thr] */,
+                            const float* thr_val /* HOST [n_thr] */, int n_thr, int64_t first, int64_t n_total, int32_t* count, double* mean, double* m2,
+                            float* vmin, float* vmax, int32_t* exceed, void* stream);
+int dpn_ensemble_finish(const int32_t* count, const double* mean, const double* m2, const float* vmin, const float* vmax, const int32_t* exceed,
+                        int64_t n_total, int n_products, const int32_t* thr_col /* HOST [n_thr] */, int n_thr, int64_t first, int64_t n,
+                        const DpnEnsembleOut* rows, const DpnEnsembleOut* maps, const DpnLattice* lattice, void* stream);
 
 /* ---------------------------------------------------------------- parcel trajectories through the learned wind (csrc/dpn_traj.hip)
  * One launch = one stage of an explicit Runge-Kutta step for n parcels whose stage positions depend only on the step's start point and the

@@ -3,6 +3,7 @@
 
     python infer.py [--config_file cfg.py] [--checkpoint_path DIR] [--log_path DIR] [--synthetic] [--ema] [--diagnostics name[,name...]]
                     [--trajectories LON,LAT[;LON,LAT...] --traj_start H --traj_hours D --traj_step S [--traj_method rk4]]
+                    [--ensemble name[,name...] [--ensemble_threshold NAME:V[,V...]]...]
 
 Builds the interface from the config (train.py's loader), loads `physics_latest.pth` from --checkpoint_path (or inference_cfg.checkpoints) and
 calls `run_inference_interface`: every field sample is evaluated on the lattice inference_cfg.img_size (x `refine`) at every inference_cfg.dt
@@ -13,7 +14,10 @@ train.py --ema) in place of the raw ones; a checkpoint without them is a KeyErro
 inference_cfg.log.export_diagnostic: derived products of the Jacobian (deepphysinet_amd.diagnostics.PRODUCTS), one more .npy per time step and name.
 --trajectories 100.5,30.25;110,35 --traj_start 24 --traj_hours -24 --traj_step 0.25 sets inference_cfg.trajectories: parcels started at those places
 (degrees east, north) at hour 24 of each sample's window and followed backward for a day in 15-minute RK4 steps through the network's own wind
-(InterfacePhysics.trajectories); positions, hours, status, step counts and the six fields along the paths are written as <time>_traj_*.npy."""
+(InterfacePhysics.trajectories); positions, hours, status, step counts and the six fields along the paths are written as <time>_traj_*.npy.
+--ensemble speed,T --ensemble_threshold speed:10,15 sets inference_cfg.ensemble: after the per-sample maps, all samples are taken as the members of an
+ensemble (InterfacePhysics.ensemble_lattice) and the mean, spread, min, max and count of every named product (deepphysinet_amd.ensemble.ENSEMBLE_PRODUCTS)
+and the probability of exceeding each threshold are written as <time>_ens_*.npy."""
 import argparse
 
 import torch
@@ -35,6 +39,26 @@ parse.add_argument('--traj_start', default=0.0, type=float, help='start hour ins
 parse.add_argument('--traj_hours', default=None, type=float, help='duration in hours; negative: back-trajectories')
 parse.add_argument('--traj_step', default=0.25, type=float, help='step in hours')
 parse.add_argument('--traj_method', default='rk4', type=str, help='euler | midpoint | rk4')
+parse.add_argument('--ensemble', default=None, type=lambda s: [n for n in s.split(',') if n],
+                   help='name[,name...]: inference_cfg.ensemble.products, statistics over all samples as ensemble members (deepphysinet_amd.ensemble.ENSEMBLE_PRODUCTS)')
+parse.add_argument('--ensemble_threshold', default=[], action='append', type=str,
+                   help='NAME:V[,V...] (repeatable): inference_cfg.ensemble.thresholds, the probability that product NAME exceeds V')
+
+
+def ensemble_option(args):
+    """inference_cfg['ensemble'] of --ensemble / --ensemble_threshold: dict(products=[...], thresholds={name: [values]}), or None without --ensemble."""
+    if not args.ensemble:
+        if args.ensemble_threshold:
+            parse.error('--ensemble_threshold needs --ensemble')
+        return None
+    thresholds = {}
+    for item in args.ensemble_threshold:
+        name, sep, values = item.partition(':')
+        if not sep or not name or not values:
+            parse.error('--ensemble_threshold takes NAME:V[,V...], got %r' % item)
+        thresholds.setdefault(name, []).extend(float(v) for v in values.split(',') if v)
+    return dict(products=list(args.ensemble), thresholds=thresholds)
+
 
 if __name__ == '__main__':
     args = parse.parse_args()
@@ -49,6 +73,8 @@ if __name__ == '__main__':
             parse.error('--trajectories takes LON,LAT pairs and needs --traj_hours')
         cfg.setdefault('inference_cfg', {})['trajectories'] = dict(lonlat=args.trajectories, start=args.traj_start, hours=args.traj_hours,
                                                                    step=args.traj_step, method=args.traj_method)
+    if ensemble_option(args):
+        cfg.setdefault('inference_cfg', {})['ensemble'] = ensemble_option(args)
     model = builder_models(**cfg)
     kwargs = dict(checkpoint_path=args.checkpoint_path)
     if args.synthetic:
@@ -66,3 +92,7 @@ if __name__ == '__main__':
     if model.last_trajectories is not None:
         tr = model.last_trajectories
         print('trajectories: positions %s, steps done %s, status %s' % (tuple(tr['positions'].shape), tr['steps_done'].tolist(), tr['status'].tolist()))
+    if model.last_ensemble is not None:
+        e = model.last_ensemble
+        print('ensemble %s: mean %s, members counted %d..%d, thresholds %s' % (','.join(e['names']), tuple(e['mean'].shape), int(e['count'].min()),
+                                                                             int(e['count'].max()), e['thresholds']))
