@@ -116,6 +116,11 @@ class DpnEnsembleOut(Structure):
     _fields_ = [(n, c_void_p) for n in ('mean', 'spread', 'min', 'max', 'count', 'prob')]
 
 
+class DpnExtremeState(Structure):
+    """include/dpn_hip.h DpnExtremeState: the seven [C][n] arrays of a window-extremes request."""
+    _fields_ = [(n, c_void_p) for n in ('best_v', 'best_t', 'best_k', 'acc', 'status', 'lo', 'hi')]
+
+
 class DpnStepGuard(Structure):
     _fields_ = [(n, c_int32) for n in ('skipped_nonfinite', 'skipped_spike', 'verdict', 'seen', 'consecutive', 'reserved')] + \
                [('running', c_double), ('last', c_double)]
@@ -199,6 +204,14 @@ EXPORTS = {
                                     POINTER(DpnEnsembleOut), POINTER(DpnEnsembleOut), POINTER(DpnLattice), c_void_p]),
     'dpn_traj_stage': (c_int, [POINTER(DpnSampler), c_void_p, POINTER(DpnPhysics), c_void_p, c_int64, POINTER(DpnTrajStage), c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dpn_extreme_scan': (c_int, [POINTER(DpnSampler), c_void_p, POINTER(DpnPhysics), c_int, c_void_p, c_int64, POINTER(c_int32), POINTER(c_int32), c_int,
+                                 c_int, c_int, c_double, c_double, c_void_p, c_void_p, POINTER(DpnExtremeState), c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p]),
+    'dpn_extreme_begin': (c_int, [POINTER(DpnSampler), c_void_p, c_int64, POINTER(c_int32), POINTER(c_int32), c_int, c_int, c_double, c_double, c_void_p,
+                                  c_void_p, POINTER(DpnExtremeState), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dpn_extreme_refine': (c_int, [POINTER(DpnSampler), c_void_p, POINTER(DpnPhysics), c_int, c_void_p, c_void_p, c_int64, POINTER(c_int32),
+                                   POINTER(c_int32), c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p, POINTER(DpnExtremeState), c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dpn_label_errors_blocks': (c_int64, [c_int64]),
     'dpn_label_errors': (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(DpnPhysics), c_float, c_int, c_void_p, c_void_p]),
     'dpn_label_errors_finish': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
@@ -239,6 +252,9 @@ STEP_LOSSES = 16              # one field's row of dpn_step_finish_batch (includ
 
 DIAG_PRODUCTS = 28            # DPN_DIAG_PRODUCTS (include/dpn_hip.h)
 ENS_PRODUCTS, ENS_MAX_THRESHOLDS = 34, 16          # DPN_ENS_PRODUCTS, DPN_ENS_MAX_THRESHOLDS (include/dpn_hip.h)
+EXT_MAX_COLUMNS = 32          # DPN_EXT_MAX_COLUMNS (include/dpn_hip.h)
+EXT_MAX, EXT_MIN, EXT_MEAN = 0, 1, 2                                                 # DPN_EXT_MAX, _MIN, _MEAN: a column's sense
+EXT_OK, EXT_BAD_SCAN, EXT_STOPPED, EXT_AT_START, EXT_AT_END = 0, 1, 2, 3, 4         # DPN_EXT_*: a column's status
 CAUSAL_MAX_BINS = 64          # DPN_CAUSAL_MAX_BINS (include/dpn_hip.h)
 BALANCE_MAX_TERMS, BALANCE_STEP_TERMS = 16, 13          # DPN_BALANCE_MAX_TERMS, DPN_BALANCE_STEP_TERMS (include/dpn_hip.h)
 

@@ -6,10 +6,12 @@
 // The whole kernel is compiled without contraction: every fp32 operation is rounded on its own, so a numpy float32 restatement
 // (deepphysinet_amd/diagnostics.py) reproduces every product that does not go through expf bit for bit.  No atomics, no LDS; the products leave through
 // plain per-lane stores: in map mode lane l of a wave writes place r + l of a product's plane (stores run along ix), in row mode a point's row.
-// The unit also holds the member axis of the same product table, dpn_ensemble_accumulate / dpn_ensemble_finish (dpn_ensemble.inc, included at the end).
+// The unit also holds the member axis of the same product table, dpn_ensemble_accumulate / dpn_ensemble_finish (dpn_ensemble.inc, included at the end),
+// and its time axis, the window extremes and means dpn_extreme_scan / dpn_extreme_begin / dpn_extreme_refine (dpn_extreme.inc, included behind it).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/dpn_hip.h"
+#include "dpn_sample_point.h"
 
 namespace {
 
@@ -101,3 +103,4 @@ int dpn_diagnostics_out(const float* out_n, const float* jac_n, const float* f, 
 }  // extern "C"
 
 #include "dpn_ensemble.inc"          // ensemble statistics over field samples: dpn_ensemble_accumulate, dpn_ensemble_finish
+#include "dpn_extreme.inc"           // window extremes and means in time: dpn_extreme_scan, dpn_extreme_begin, dpn_extreme_refine

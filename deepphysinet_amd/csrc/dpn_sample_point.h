@@ -1,5 +1,6 @@
 // One point of the collocation sampler (sample_point) and the de-normalisation of one network output (denorm), shared by the sampler unit
-// (dpn_sampler.hip) and the trajectory unit (dpn_traj.hip).  Both are inlined into their kernels; each unit has its own copy (anonymous namespace).
+// (dpn_sampler.hip), the trajectory unit (dpn_traj.hip) and the window extremes of the diagnostics unit (dpn_extreme.inc in dpn_diag.hip).  Both are
+// inlined into their kernels; each unit has its own copy (anonymous namespace).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

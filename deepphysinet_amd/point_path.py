@@ -1287,6 +1287,7 @@ class PackedField:
         L.check(lib.dpn_pack_weights_form(self.nets, cfg.prec, lib.dpn_fwd_form(cfg.prec, 0), _ptr(self.ws.packed), _stream()), 'dpn_pack_weights')
         self.ws.prepacked = True
         self._traj_ph = None
+        self._ext_ph = {}
 
     def fields(self, x, y, t, coord_data, with_clip=False, rows=None, maps=None, lattice=None, first=0):
         """The six physical fields at points x, y, t [n], coord_data [n, 6] (dpn_fields_out): into rows [n, 6], or into the places of points
@@ -1360,6 +1361,33 @@ class PackedField:
             self._traj_ph = self.cfg.physics()
         traj_stage(sampler, self._traj_ph, out_n, parcels, stage, t0, h, inv_wsum, step, fields, with_clip, record_only)
 
+    def _extreme_physics(self, with_clip):
+        """The physics table of the extremes launches, built once per field and clip setting (a request is K + R + 2 launches per chunk)."""
+        key = bool(with_clip)
+        if key not in self._ext_ph:
+            ph = self.cfg.physics()
+            for k in range(2, L.NETS):                         # `with_clip` is this call's own, as in `diagnostics`
+                ph.clip_on[k] = int(key and bool(self.cfg.clip_vars[k]))
+            self._ext_ph[key] = ph
+        return self._ext_ph[key]
+
+    def extreme_scan(self, sampler, state, k, with_clip=False):
+        """Scan node k of a window-extremes request for the points of `state` (an ExtremeState): the fields-only forward at the node, then
+        dpn_extreme_scan, which folds it into the state and writes the next node's inputs into the same buffers; after the last node
+        dpn_extreme_begin closes the scan and writes the first probes.  Two launches (three at node K), nothing read back."""
+        x, y, t, _, cd = state.points
+        out_n, _ = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, cd, want_jac=False, want_saved=False)
+        extreme_scan(sampler, self._extreme_physics(with_clip), with_clip, out_n, state, k)
+        if k == state.K:
+            extreme_begin(sampler, state)
+
+    def extreme_refine(self, sampler, state, rnd, with_clip=False):
+        """Round `rnd` of the refinement: the forward with the Jacobian at the Cr * n probes, then dpn_extreme_refine, which keeps the best value, moves
+        the bracket and rewrites the probes.  Two launches, nothing read back."""
+        x, y, t, _, cd = state.probes
+        out_n, jac_n = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, cd, want_jac=True, want_saved=False)
+        extreme_refine(sampler, self._extreme_physics(with_clip), with_clip, out_n, jac_n, state, rnd)
+
 
 class EnsembleState:
     """Device state of an ensemble request between dpn_ensemble_accumulate launches (include/dpn_hip.h): for n_total points, the P columns `ids`
@@ -1421,3 +1449,66 @@ def traj_stage(sampler, ph, out_n, parcels, stage, t0, h, inv_wsum, step, fields
     L.check(L.load().dpn_traj_stage(ctypes.byref(sampler._s), _ptr(sampler.cube), ctypes.byref(ph), _ptr(out_n), p.n, ctypes.byref(st), _ptr(p.x0),
                                     _ptr(p.y0), _ptr(p.accx), _ptr(p.accy), _ptr(p.status), _ptr(p.steps_done), _ptr(p.path), p.rows,
                                     _ptr(fields) if want_fields else None, _ptr(x), _ptr(y), _ptr(t), _ptr(f), _ptr(cd), _stream()), 'dpn_traj_stage')
+
+
+class ExtremeState:
+    """Device state of n points of a window-extremes request between its launches (include/dpn_hip.h): for the C columns of `request` (an
+    extremes.Request) best_v [C, n] fp32, best_t, acc, lo, hi [C, n] fp64, best_k, status [C, n] int32 -- column-major, so a map [C, ny, nx] is a
+    view of it --; `points` = x, y, t, f [n], coord_data [n, 6], the sampler at the current scan node (node 0 to begin with), and `probes`, the same
+    five with Cr * n rows for the probes of the Cr max / min columns (None without one).  Nothing is filled: node 0 sets what is read."""
+
+    POINT_BYTES = 4 * (4 + 6 + 6) + 16                       # per point: the scan's buffers and xr, yr
+    COLUMN_BYTES = 4 + 8 + 4 + 8 + 4 + 8 + 8                  # per point and column: the state
+    PROBE_BYTES = 4 * (4 + 6 + 6 + 18)                        # per point and refined column: the probe's buffers, its out_n and Jacobian
+
+    def __init__(self, sampler, xr, yr, request):
+        dev, n = xr.device, xr.shape[0]
+        self.n, self.K, self.t0, self.dt = n, int(request.K), float(request.t0), float(request.dt)
+        self.ids, self.senses = list(request.ids), list(request.senses)
+        C = len(self.ids)
+        self.n_refined = sum(1 for s in self.senses if s != L.EXT_MEAN)
+        if not 1 <= C <= L.EXT_MAX_COLUMNS or len(self.senses) != C or n < 1:
+            raise ValueError('ExtremeState: %d points, %d columns (1..%d)' % (n, C, L.EXT_MAX_COLUMNS))
+        self.c_ids, self.c_senses = (ctypes.c_int32 * C)(*self.ids), (ctypes.c_int32 * C)(*self.senses)
+        self.xr, self.yr = xr.contiguous(), yr.contiguous()
+        self.best_v = torch.empty((C, n), dtype=torch.float32, device=dev)
+        self.best_t, self.acc, self.lo, self.hi = (torch.empty((C, n), dtype=torch.float64, device=dev) for _ in range(4))
+        self.best_k, self.status = (torch.empty((C, n), dtype=torch.int32, device=dev) for _ in range(2))
+        self.points = sampler.sample_at(n, self.xr, self.yr, torch.full((n,), self.t0, dtype=torch.float64, device=dev))
+        m = self.n_refined * n
+        self.probes = None if m == 0 else \
+            tuple(torch.empty(m, dtype=torch.float32, device=dev) for _ in range(4)) + (torch.empty((m, 6), dtype=torch.float32, device=dev),)
+
+    def c_struct(self):
+        return L.DpnExtremeState(*[_ptr(v) for v in (self.best_v, self.best_t, self.best_k, self.acc, self.status, self.lo, self.hi)])
+
+    def results(self):
+        """value, hour, lo, hi, status [C, n]: the state's own arrays, complete after the last round."""
+        return {'value': self.best_v, 'hour': self.best_t, 'lo': self.lo, 'hi': self.hi, 'status': self.status}
+
+
+def extreme_scan(sampler, ph, with_clip, out_n, state, k):
+    """dpn_extreme_scan on an ExtremeState with the fields-only forward's out_n [n, 6] at scan node k."""
+    s = state
+    x, y, t, f, cd = s.points
+    L.check(L.load().dpn_extreme_scan(ctypes.byref(sampler._s), _ptr(sampler.cube), ctypes.byref(ph), int(bool(with_clip)), _ptr(out_n), s.n, s.c_ids,
+                                      s.c_senses, len(s.ids), int(k), s.K, s.t0, s.dt, _ptr(s.xr), _ptr(s.yr), ctypes.byref(s.c_struct()), _ptr(x),
+                                      _ptr(y), _ptr(t), _ptr(f), _ptr(cd), _stream()), 'dpn_extreme_scan')
+
+
+def extreme_begin(sampler, state):
+    """dpn_extreme_begin: closes the scan of an ExtremeState and writes its probes (a request of mean columns alone has none: nothing is sampled)."""
+    s = state
+    x, y, t, f, cd = s.probes or s.points
+    L.check(L.load().dpn_extreme_begin(ctypes.byref(sampler._s), _ptr(sampler.cube), s.n, s.c_ids, s.c_senses, len(s.ids), s.K, s.t0, s.dt, _ptr(s.xr),
+                                       _ptr(s.yr), ctypes.byref(s.c_struct()), _ptr(x), _ptr(y), _ptr(t), _ptr(f), _ptr(cd), _stream()),
+            'dpn_extreme_begin')
+
+
+def extreme_refine(sampler, ph, with_clip, out_n, jac_n, state, rnd):
+    """dpn_extreme_refine, round rnd, with the forward's out_n [Cr * n, 6] and jac_n [Cr * n, 6, 3] at the probes of an ExtremeState."""
+    s = state
+    x, y, t, f, cd = s.probes
+    L.check(L.load().dpn_extreme_refine(ctypes.byref(sampler._s), _ptr(sampler.cube), ctypes.byref(ph), int(bool(with_clip)), _ptr(out_n), _ptr(jac_n),
+                                        s.n, s.c_ids, s.c_senses, len(s.ids), int(rnd), s.K, s.t0, s.dt, _ptr(s.xr), _ptr(s.yr),
+                                        ctypes.byref(s.c_struct()), _ptr(x), _ptr(y), _ptr(t), _ptr(f), _ptr(cd), _stream()), 'dpn_extreme_refine')

@@ -528,6 +528,72 @@ int dpn_ensemble_accumulate(const float* out_n, const float* jac_n, const float*
 int dpn_ensemble_finish(const int32_t* count, const double* mean, const double* m2, const float* vmin, const float* vmax, const int32_t* exceed,
                         int64_t n_total, int n_products, const int32_t* thr_col /* HOST [n_thr] */, int n_thr, int64_t first, int64_t n,
                         const DpnEnsembleOut* rows, const DpnEnsembleOut* maps, const DpnLattice* lattice, void* stream);
+/* Window extremes and means in time (csrc/dpn_extreme.inc, compiled into csrc/dpn_diag.hip): per point and column the maximum or minimum of a product
+ * over the hours [t0, t0 + K * dt] and the hour it occurs at, or the window mean.  A coarse scan of the K + 1 nodes (one fields-only forward each), then
+ * bisection on the sign of the network's own d/dt around the best node (one forward with the Jacobian per round, Cr probes per point).
+ * A request is C = n_columns (1..DPN_EXT_MAX_COLUMNS; repeats allowed) columns (products[c], senses[c]), HOST arrays.  Products: 28..33, the
+ * de-normalised u, v, p, T, q, rho, and 25, speed -- ids, expressions and NaN rule of dpn_ensemble_accumulate (the residual body's val, with_clip as
+ * dpn_diagnostics_out takes it, speed = sqrtf(u * u + v * v); a point with a NaN among its six out_n is NaN).  Senses: DPN_EXT_MAX, _MIN, _MEAN.
+ * The Cr refined columns are the max / min columns in request order.
+ * Clock: node k (0..K) lies at hour t0 + (double)k * dt, two fp64 roundings.  xr, yr [n] fp64: the points, as dpn_sample_at takes stations.
+ * State of a chunk of n points, column-major (a wave runs along the points; a map [C][ny][nx] is a view of it), every array [C][n]:
+ *   float best_v, double best_t (hours), int32 best_k, double acc, int32 status (DPN_EXT_*), double lo, hi.   Nothing needs filling before node 0.
+ * Every operation below is one operation rounded on its own (the kernels are compiled without contraction).
+ * dpn_extreme_scan: out_n [n][6] = the fields-only forward at node k.  Per column, x the product at the point:
+ *   k > 0 and status != 0:  nothing changes (sticky)
+ *   x not finite:           status = DPN_EXT_BAD_SCAN, nothing else changes
+ *   k == 0:                 status = 0, best_v = x, best_k = 0, acc = 0.5 * (double)x
+ *   else:                   max: x > best_v, min: x < best_v -> best_v = x, best_k = k (a tie keeps the earlier node; a mean column keeps node 0's);
+ *                           acc = acc + (k == K ? 0.5 : 1.0) * (double)x
+ * and, unless k == K, x, y, t, f, coord_data [n] = the sampler at (xr, yr, hour of node k + 1), dpn_sample_at's arithmetic, for the next forward.
+ * dpn_extreme_begin (after node K).  A mean column: best_v = (float)(acc / (double)K), NaN under a non-zero status; best_t = lo = hi = NaN.
+ *   A max / min column with status 0: lo = hour of node max(best_k - 1, 0), hi = hour of node min(best_k + 1, K), best_t = m = hour of node best_k;
+ *   under DPN_EXT_BAD_SCAN: best_v = best_t = lo = hi = NaN, m = t0.  Refined column r writes the probe inputs x, y, t, f, coord_data [r * n + i] =
+ *   the sampler at (xr, yr, m): the five arrays hold Cr * n rows.
+ * dpn_extreme_refine, round 0, 1, ..: out_n [Cr * n][6], jac_n [Cr * n][6][3] = the forward with the Jacobian at the probes.  A probe whose column
+ *   has status != 0 is skipped: its inputs stay, its forwards are ignored.  Otherwise m = the probe's hour (round 0: the hour of node best_k; later:
+ *   lo + 0.5 * (hi - lo) of the state, the expression the probe was written with), g = the product, s = its slope in time up to a positive factor:
+ *   J[k][2] for a variable, u * J[0][2] + v * J[1][2] for speed (only the sign is used, nothing is divided), J the residual body's, clip included.
+ *     g or s not finite:  status = DPN_EXT_STOPPED; the best so far stands
+ *     g strictly better than best_v:  best_v = g, best_t = m
+ *     max: s > 0 -> lo = m, else hi = m;    min: s < 0 -> lo = m, else hi = m
+ *     lo == hi:  status = best_k == 0 ? DPN_EXT_AT_START : DPN_EXT_AT_END (the extreme sits on a face of the window, the slope pointing outward; the
+ *                host keeps dt / 2^rounds above the spacing of the hours, so that a bracket closes nowhere else)
+ *     otherwise: the probe's x, y, t, f, coord_data = the sampler at (xr, yr, lo + 0.5 * (hi - lo))
+ *   Round 0 probes the best scan node itself and chooses the side; every later round halves the bracket.
+ * Results: value best_v, hour best_t, lo, hi, status.  A (value, hour) pair always comes from one evaluation, and is never worse than the best node.
+ * 256-thread blocks, one thread per (column, point) -- refine: per probe --, no atomics, no LDS, plain per-thread vector stores.
+ * -1 (nothing launched, nothing written): a NULL pointer (the state's seven included); n <= 0; K < 1; k outside 0..K; round < 0; t0 or dt not finite;
+ * dt <= 0; n_columns outside 1..DPN_EXT_MAX_COLUMNS; an id other than 25, 28..33; a sense outside 0..2; a sampler cube dimension < 2; refine without
+ * a max / min column. */
+#define DPN_EXT_MAX_COLUMNS 32
+#define DPN_EXT_MAX  0
+#define DPN_EXT_MIN  1
+#define DPN_EXT_MEAN 2
+#define DPN_EXT_OK        0
+#define DPN_EXT_BAD_SCAN  1   /* a scan node's value was not finite: everything is NaN            */
+#define DPN_EXT_STOPPED   2   /* a probe's value or slope was not finite: the best so far stands  */
+#define DPN_EXT_AT_START  3   /* the extreme sits at hour t0, the slope pointing out of the window */
+#define DPN_EXT_AT_END    4   /* ... at hour t0 + K * dt                                          */
+typedef struct DpnExtremeState {
+    float* best_v;
+    double* best_t;
+    int32_t* best_k;
+    double* acc;
+    int32_t* status;
+    double *lo, *hi;
+} DpnExtremeState;
+int dpn_extreme_scan(const DpnSampler* s, const float* cube, const DpnPhysics* phys, int with_clip, const float* out_n, int64_t n,
+                     const int32_t* products /* HOST */, const int32_t* senses /* HOST */, int n_columns, int k, int K, double t0, double dt,
+                     const double* xr, const double* yr, const DpnExtremeState* st, float* x, float* y, float* t, float* f, float* coord_data,
+                     void* stream);
+int dpn_extreme_begin(const DpnSampler* s, const float* cube, int64_t n, const int32_t* products /* HOST */, const int32_t* senses /* HOST */,
+                      int n_columns, int K, double t0, double dt, const double* xr, const double* yr, const DpnExtremeState* st, float* x, float* y,
+                      float* t, float* f, float* coord_data, void* stream);
+int dpn_extreme_refine(const DpnSampler* s, const float* cube, const DpnPhysics* phys, int with_clip, const float* out_n, const float* jac_n, int64_t n,
+                       const int32_t* products /* HOST */, const int32_t* senses /* HOST */, int n_columns, int round, int K, double t0, double dt,
+                       const double* xr, const double* yr, const DpnExtremeState* st, float* x, float* y, float* t, float* f, float* coord_data,
+                       void* stream);
 
 /* ---------------------------------------------------------------- parcel trajectories through the learned wind (csrc/dpn_traj.hip)
  * One launch = one stage of an explicit Runge-Kutta step for n parcels whose stage positions depend only on the step's start point and the

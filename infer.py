@@ -4,6 +4,7 @@
     python infer.py [--config_file cfg.py] [--checkpoint_path DIR] [--log_path DIR] [--synthetic] [--ema] [--diagnostics name[,name...]]
                     [--trajectories LON,LAT[;LON,LAT...] --traj_start H --traj_hours D --traj_step S [--traj_method rk4]]
                     [--ensemble name[,name...] [--ensemble_threshold NAME:V[,V...]]...]
+                    [--extremes T:max,T:min,speed:max --extreme_window H0,H1 [--extreme_scan S] [--extreme_refine R]]
 
 Builds the interface from the config (train.py's loader), loads `physics_latest.pth` from --checkpoint_path (or inference_cfg.checkpoints) and
 calls `run_inference_interface`: every field sample is evaluated on the lattice inference_cfg.img_size (x `refine`) at every inference_cfg.dt
@@ -17,7 +18,10 @@ inference_cfg.log.export_diagnostic: derived products of the Jacobian (deepphysi
 (InterfacePhysics.trajectories); positions, hours, status, step counts and the six fields along the paths are written as <time>_traj_*.npy.
 --ensemble speed,T --ensemble_threshold speed:10,15 sets inference_cfg.ensemble: after the per-sample maps, all samples are taken as the members of an
 ensemble (InterfacePhysics.ensemble_lattice) and the mean, spread, min, max and count of every named product (deepphysinet_amd.ensemble.ENSEMBLE_PRODUCTS)
-and the probability of exceeding each threshold are written as <time>_ens_*.npy."""
+and the probability of exceeding each threshold are written as <time>_ens_*.npy.
+--extremes T:max,T:min,speed:max --extreme_window 0,24 sets inference_cfg.extremes: per sample the maximum / minimum of the named products over those
+hours of its window and the hour they occur at (or, PRODUCT:mean, the window mean), found by a scan every --extreme_scan hours and --extreme_refine
+rounds of bisection on the network's own d/dt (InterfacePhysics.extreme_lattice), written as <time>_extreme_<value|hour|lo|hi|status>_*.npy maps."""
 import argparse
 
 import torch
@@ -43,6 +47,24 @@ parse.add_argument('--ensemble', default=None, type=lambda s: [n for n in s.spli
                    help='name[,name...]: inference_cfg.ensemble.products, statistics over all samples as ensemble members (deepphysinet_amd.ensemble.ENSEMBLE_PRODUCTS)')
 parse.add_argument('--ensemble_threshold', default=[], action='append', type=str,
                    help='NAME:V[,V...] (repeatable): inference_cfg.ensemble.thresholds, the probability that product NAME exceeds V')
+parse.add_argument('--extremes', default=None, type=lambda s: [n for n in s.split(',') if n],
+                   help='PRODUCT:SENSE[,...]: inference_cfg.extremes.columns, e.g. T:max,T:min,speed:max,q:mean (deepphysinet_amd.extremes)')
+parse.add_argument('--extreme_window', default=None, type=lambda s: tuple(float(v) for v in s.split(',')),
+                   help='H0,H1: the hours of the sample window the extremes are taken over')
+parse.add_argument('--extreme_scan', default=1.0, type=float, help='hours between the scan nodes')
+parse.add_argument('--extreme_refine', default=10, type=int, help='bisection rounds after the scan (0..32)')
+
+
+def extremes_option(args):
+    """inference_cfg['extremes'] of --extremes / --extreme_window: dict(columns=[...], window=(H0, H1), scan_hours=S, refine=R), or None without
+    --extremes."""
+    if not args.extremes:
+        if args.extreme_window is not None:
+            parse.error('--extreme_window needs --extremes')
+        return None
+    if args.extreme_window is None or len(args.extreme_window) != 2:
+        parse.error('--extremes needs --extreme_window H0,H1')
+    return dict(columns=list(args.extremes), window=tuple(args.extreme_window), scan_hours=args.extreme_scan, refine=args.extreme_refine)
 
 
 def ensemble_option(args):
@@ -75,6 +97,8 @@ if __name__ == '__main__':
                                                                    step=args.traj_step, method=args.traj_method)
     if ensemble_option(args):
         cfg.setdefault('inference_cfg', {})['ensemble'] = ensemble_option(args)
+    if extremes_option(args):
+        cfg.setdefault('inference_cfg', {})['extremes'] = extremes_option(args)
     model = builder_models(**cfg)
     kwargs = dict(checkpoint_path=args.checkpoint_path)
     if args.synthetic:
@@ -96,3 +120,6 @@ if __name__ == '__main__':
         e = model.last_ensemble
         print('ensemble %s: mean %s, members counted %d..%d, thresholds %s' % (','.join(e['names']), tuple(e['mean'].shape), int(e['count'].min()),
                                                                              int(e['count'].max()), e['thresholds']))
+    if model.last_extremes is not None:
+        x = model.last_extremes
+        print('extremes %s: value %s, status %s' % (','.join(x['names']), tuple(x['value'].shape), sorted(set(x['status'].reshape(-1).tolist()))))
