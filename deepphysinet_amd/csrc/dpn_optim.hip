@@ -2,13 +2,16 @@
 //
 // Kernel inventory
 //   dpn_gradnorm_kernel / dpn_gradnorm_reduce_kernel   one fp64 partial per 2048-element chunk, added in a fixed order
-//   dpn_adam_kernel                                    the clipped update; the AdamTableFlatEma instantiation also moves the weight EMA, the
-//                                                      AdamTableFlatGroups* ones read their hyper-parameters from their tensor's group row
-//   dpn_gradnorm_reduce_guard_kernel                   the reduction plus the step guard's verdict (skip non-finite and spiking steps); the
-//                                                      AdamTableFlatGuard* instantiations of dpn_adam_kernel obey it
+//   dpn_adam_kernel                                    the clipped update over AdamTable (pointer lists) or AdamFlat<Ema, Groups, Guard> (flat moment
+//                                                      buffers): Ema also moves the weight EMA, Groups reads the hyper-parameters from the tensor's
+//                                                      group row, Guard obeys the step guard's verdict
+//   dpn_gradnorm_reduce_guard_kernel                   the reduction plus the step guard's verdict (skip non-finite and spiking steps)
 //   dpn_ema_swap_kernel                                exchanges the parameters with their EMA shadow
 // No kernel in this file uses atomics: every reduction is fixed-order, the whole step is bitwise reproducible.
+// Host side: adam_fill writes every table, clip_adam_flat is the two-pass launcher of every flat entry point, adam_args_ok the checks they share.
 #include "dpn_device.h"
+#include <initializer_list>
+#include <type_traits>
 
 // ------------------------------------------------------------------------------------------------ fused clip + Adam
 // clip_grad_norm_(max_norm) followed by torch.optim.Adam(lr, betas, eps, weight_decay) (L2-in-gradient, not AdamW), as in
@@ -29,130 +32,52 @@ struct AdamTable {
 };
 // Optimiser state kept by the caller as ONE flat buffer per moment, tensor i at offset chunk_start[i] * kAdamChunk (each tensor padded to
 // whole chunks): no per-tensor state pointers, so 160 tensors fit in the kernel arguments and a PhysicsNet is one launch per pass.
+// AdamFlat<Ema, Groups, Guard> is that table plus the members its options need, composed as a chain of bases in this member order:
+//   head -> [Ema: s_flat, ema_base] -> [Guard: guard] -> n -> [Ema: ema_warmup] -> [Groups: group4]
+// An option that is off contributes an empty base and no code (`if constexpr` on the three flags in dpn_adam_kernel): every instantiation is the
+// kernel it would be with a hand-written struct of its own (tools/kernel_isa_digest.py, profiles/optim_tables_isa_digest_diff.txt).  The options'
+// scalars ride in the table, so dpn_adam_kernel has one argument list.
 constexpr int kAdamFlatMaxTensors = 160;
-struct AdamTableFlat {
+constexpr int kAdamMaxGroups = 16;
+struct AdamFlatHead {
     float* p[kAdamFlatMaxTensors];
     const float* g[kAdamFlatMaxTensors];
     int chunk_start[kAdamFlatMaxTensors + 1];
     int numel[kAdamFlatMaxTensors];
     float* m_flat;
     float* v_flat;
-    int n;
-    static constexpr bool ema = false;
-    static constexpr bool groups = false;
-    static constexpr bool guard_on = false;
 };
-static_assert(sizeof(AdamTableFlat) + 64 <= 4096, "kernel arguments are limited to 4 KB");
-// AdamTableFlat plus an exponential moving average of the parameters (the shadow `s_flat`, laid out like the moments), updated by the thread
-// that has just formed the new parameter value.  A type of its own (the pattern of ResArgs::weighted): AdamTableFlat keeps its layout and the
-// instantiations without EMA their code.  The EMA scalars ride in the table, so dpn_adam_kernel keeps its argument list.
-struct AdamTableFlatEma {
-    float* p[kAdamFlatMaxTensors];
-    const float* g[kAdamFlatMaxTensors];
-    int chunk_start[kAdamFlatMaxTensors + 1];
-    int numel[kAdamFlatMaxTensors];
-    float* m_flat;
-    float* v_flat;
+// Ema: an exponential moving average of the parameters (the shadow `s_flat`, laid out like the moments), updated by the thread that has just formed
+// the new parameter value
+struct AdamEmaPtrs {
     float* s_flat;
     const int* ema_base;                         // device, may be null (= 0): EMA updates made before this optimiser was built
-    int n;
-    int ema_warmup;
-    static constexpr bool ema = true;
-    static constexpr bool groups = false;
-    static constexpr bool guard_on = false;
 };
-static_assert(sizeof(AdamTableFlatEma) + 64 <= 4096, "kernel arguments are limited to 4 KB");
-// AdamTableFlat / AdamTableFlatEma plus a parameter group per tensor (fine-tuning: a learning rate, betas, eps and weight decay per group).  How
-// the group ids fit next to the by-value scalars of dpn_adam_kernel: sixteen groups are four bits, so the ids ride as NIBBLES, two tensors per
-// byte (80 bytes, not 160) -- dpn_adam_kernel keeps its argument list for every table and `numel` its 31 bits, no tensor size is refused that the
-// other forms take.  Types of their own once more: the four instantiations without groups keep their code.
-constexpr int kAdamMaxGroups = 16;
-struct AdamTableFlatGroups {
-    float* p[kAdamFlatMaxTensors];
-    const float* g[kAdamFlatMaxTensors];
-    int chunk_start[kAdamFlatMaxTensors + 1];
-    int numel[kAdamFlatMaxTensors];
-    float* m_flat;
-    float* v_flat;
-    int n;
-    uint8_t group4[kAdamFlatMaxTensors / 2];     // tensor i: (group4[i >> 1] >> 4 (i & 1)) & 15
-    static constexpr bool ema = false;
-    static constexpr bool groups = true;
-    static constexpr bool guard_on = false;
+// Guard: the DpnStepGuard whose verdict dpn_gradnorm_reduce_guard_kernel formed one launch earlier.  A non-zero verdict returns the block before it
+// touches p, m, v or the shadow; a zero one runs the arithmetic of every other table with the step number *step - skipped_nonfinite - skipped_spike
+struct AdamGuardPtr { const DpnStepGuard* guard; };
+struct AdamCount { int n; };
+struct AdamEmaWarmup { int ema_warmup; };
+// Groups: a parameter group per tensor (fine-tuning: a learning rate, betas, eps and weight decay per group).  Sixteen groups are four bits, so the
+// ids ride as NIBBLES, two tensors per byte (80 bytes, not 160), and `numel` keeps its 31 bits: no tensor size is refused that the other forms take.
+// The guard's tables are always grouped: one group rides as group 0 of a one-row hyper_dev (the grouped kernel with one group IS the one-group
+// kernel, bit for bit)
+struct AdamGroup4 { uint8_t group4[kAdamFlatMaxTensors / 2]; };     // tensor i: (group4[i >> 1] >> 4 (i & 1)) & 15
+template <int I> struct AdamNone {};             // distinct empty bases, so that each takes no room
+template <bool On, class T, int I> using AdamOpt = std::conditional_t<On, T, AdamNone<I>>;
+template <bool Ema, bool Groups, bool Guard>
+struct AdamFlat : AdamFlatHead, AdamOpt<Ema, AdamEmaPtrs, 0>, AdamOpt<Guard, AdamGuardPtr, 1>, AdamCount, AdamOpt<Ema, AdamEmaWarmup, 2>,
+                  AdamOpt<Groups, AdamGroup4, 3> {
+    static constexpr bool ema = Ema, groups = Groups, guard_on = Guard;
 };
-static_assert(sizeof(AdamTableFlatGroups) + 64 <= 4096, "kernel arguments are limited to 4 KB");
-struct AdamTableFlatGroupsEma {
-    float* p[kAdamFlatMaxTensors];
-    const float* g[kAdamFlatMaxTensors];
-    int chunk_start[kAdamFlatMaxTensors + 1];
-    int numel[kAdamFlatMaxTensors];
-    float* m_flat;
-    float* v_flat;
-    float* s_flat;
-    const int* ema_base;
-    int n;
-    int ema_warmup;
-    uint8_t group4[kAdamFlatMaxTensors / 2];
-    static constexpr bool ema = true;
-    static constexpr bool groups = true;
-    static constexpr bool guard_on = false;
-};
-static_assert(sizeof(AdamTableFlatGroupsEma) + 64 <= 4096, "kernel arguments are limited to 4 KB");
-// The grouped tables plus the step guard (dpn_clip_adam_flat_guard): `guard` points at the DpnStepGuard whose verdict dpn_gradnorm_reduce_guard_kernel
-// formed one launch earlier.  A non-zero verdict returns the block before it touches p, m, v or the shadow; a zero one runs the arithmetic of every
-// other table with the step number *step - skipped_nonfinite - skipped_spike.  One group rides as group 0 of a one-row hyper_dev (the grouped kernel
-// with one group IS the one-group kernel, bit for bit), so two tables cover every combination.  Types of their own again: the instantiations without
-// the guard keep their code (tools/kernel_isa_digest.py on both trees: DESIGN.md section 6e).
-struct AdamTableFlatGuard {
-    float* p[kAdamFlatMaxTensors];
-    const float* g[kAdamFlatMaxTensors];
-    int chunk_start[kAdamFlatMaxTensors + 1];
-    int numel[kAdamFlatMaxTensors];
-    float* m_flat;
-    float* v_flat;
-    const DpnStepGuard* guard;
-    int n;
-    uint8_t group4[kAdamFlatMaxTensors / 2];
-    static constexpr bool ema = false;
-    static constexpr bool groups = true;
-    static constexpr bool guard_on = true;
-};
-static_assert(sizeof(AdamTableFlatGuard) + 64 <= 4096, "kernel arguments are limited to 4 KB");
-struct AdamTableFlatGuardEma {
-    float* p[kAdamFlatMaxTensors];
-    const float* g[kAdamFlatMaxTensors];
-    int chunk_start[kAdamFlatMaxTensors + 1];
-    int numel[kAdamFlatMaxTensors];
-    float* m_flat;
-    float* v_flat;
-    float* s_flat;
-    const int* ema_base;
-    const DpnStepGuard* guard;
-    int n;
-    int ema_warmup;
-    uint8_t group4[kAdamFlatMaxTensors / 2];
-    static constexpr bool ema = true;
-    static constexpr bool groups = true;
-    static constexpr bool guard_on = true;
-};
-static_assert(sizeof(AdamTableFlatGuardEma) + 64 <= 4096, "kernel arguments are limited to 4 KB");
+using AdamFlatPlain = AdamFlat<false, false, false>;     // also the table of every flat entry's gradient-norm pass
+static_assert(sizeof(AdamFlat<true, true, true>) + 64 <= 4096, "kernel arguments are limited to 4 KB");
 DEV float* table_m(const AdamTable& t, int ti) { return t.m[ti]; }
 DEV float* table_v(const AdamTable& t, int ti) { return t.v[ti]; }
-DEV float* table_m(const AdamTableFlat& t, int ti) { return t.m_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
-DEV float* table_v(const AdamTableFlat& t, int ti) { return t.v_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
-DEV float* table_m(const AdamTableFlatEma& t, int ti) { return t.m_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
-DEV float* table_v(const AdamTableFlatEma& t, int ti) { return t.v_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
-DEV float* table_s(const AdamTableFlatEma& t, int ti) { return t.s_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
-DEV float* table_m(const AdamTableFlatGroups& t, int ti) { return t.m_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
-DEV float* table_v(const AdamTableFlatGroups& t, int ti) { return t.v_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
-DEV float* table_m(const AdamTableFlatGroupsEma& t, int ti) { return t.m_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
-DEV float* table_v(const AdamTableFlatGroupsEma& t, int ti) { return t.v_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
-DEV float* table_s(const AdamTableFlatGroupsEma& t, int ti) { return t.s_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
-DEV float* table_m(const AdamTableFlatGuard& t, int ti) { return t.m_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
-DEV float* table_v(const AdamTableFlatGuard& t, int ti) { return t.v_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
-DEV float* table_m(const AdamTableFlatGuardEma& t, int ti) { return t.m_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
-DEV float* table_v(const AdamTableFlatGuardEma& t, int ti) { return t.v_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
-DEV float* table_s(const AdamTableFlatGuardEma& t, int ti) { return t.s_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+DEV float* table_m(const AdamFlatHead& t, int ti) { return t.m_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+DEV float* table_v(const AdamFlatHead& t, int ti) { return t.v_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
+template <class Table>
+DEV float* table_s(const Table& t, int ti) { return t.s_flat + (int64_t)t.chunk_start[ti] * kAdamChunk; }
 template <class Table>
 DEV int table_group(const Table& t, int ti) { return (t.group4[ti >> 1] >> ((ti & 1) * 4)) & 15; }
 template <class Table>
@@ -160,6 +85,16 @@ DEV int adam_find(const Table& t, int blk) {
     int lo = 0, hi = t.n - 1;
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (t.chunk_start[mid] <= blk) lo = mid; else hi = mid - 1; }
     return lo;
+}
+// One double per thread of a 256-thread block, added in a fixed order: wave by wave through the lanes, then the four waves' sums in LDS.  For the two
+// reduce kernels; dpn_gradnorm_kernel keeps the same lines at its tail, where a call of this function compiles to other instructions
+DEV double block_sum256(double d) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o);
+    __shared__ double red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = d;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
 }
 template <class Table>
 __global__ __launch_bounds__(256) void dpn_gradnorm_kernel(Table t, double* partial, int* step, int bump_step) {
@@ -192,12 +127,8 @@ __global__ __launch_bounds__(256) void dpn_gradnorm_kernel(Table t, double* part
 __global__ __launch_bounds__(256) void dpn_gradnorm_reduce_kernel(const double* partial, int n, double* sumsq) {
     double d = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) d += partial[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o);
-    __shared__ double red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = d;
-    __syncthreads();
-    if (threadIdx.x == 0) *sumsq = (red[0] + red[1]) + (red[2] + red[3]);
+    const double sum = block_sum256(d);
+    if (threadIdx.x == 0) *sumsq = sum;
 }
 // dpn_gradnorm_reduce_kernel (the same sum in the same order) whose thread 0 then forms the step guard's verdict from the fp32 total norm exactly as
 // dpn_adam_kernel forms it.  fp64, every operation rounded once (no contraction); the rule is restated on the host in deepphysinet_amd/guard.py.
@@ -208,13 +139,8 @@ __global__ __launch_bounds__(256) void dpn_gradnorm_reduce_guard_kernel(const do
 #pragma clang fp contract(off)
     double d = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) d += partial[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o);
-    __shared__ double red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = d;
-    __syncthreads();
+    const double sum = block_sum256(d);
     if (threadIdx.x != 0) return;
-    const double sum = (red[0] + red[1]) + (red[2] + red[3]);
     *sumsq = sum;
     const float total = (float)sqrt(sum) * hyper[6];
     const double tot = (double)total;
@@ -356,22 +282,114 @@ __global__ __launch_bounds__(256) void dpn_ema_swap_kernel(EmaSwapTable t) {
     for (int i = scalar_from + threadIdx.x; i < end; i += 256) { const uint32_t a = p[i]; p[i] = sh[i]; sh[i] = a; }
 }
 
+// ------------------------------------------------------------------------------------------------ host side
+// The checks every entry shares, all made before the first launch: a refusal bumps no step counter and writes no partial, whichever table the bad
+// tensor is in.  `required`: the entry's pointers that must not be NULL.  group_of (optional): every id below n_groups, at most kAdamMaxGroups of them
+static bool adam_args_ok(int n_tensors, const int64_t* numel, std::initializer_list<const void*> required, const uint8_t* group_of = nullptr,
+                         int n_groups = 0) {
+    if (n_tensors <= 0 || !numel) return false;
+    for (const void* q : required) if (!q) return false;
+    if (group_of && (n_groups < 1 || n_groups > kAdamMaxGroups)) return false;
+    for (int i = 0; i < n_tensors; ++i) if (numel[i] <= 0 || numel[i] > 0x7fffffff || (group_of && group_of[i] >= n_groups)) return false;
+    return true;
+}
+
+static int64_t adam_chunks(int n_tensors, const int64_t* numel) {
+    int64_t chunks = 0;
+    for (int i = 0; i < n_tensors; ++i) chunks += (numel[i] + kAdamChunk - 1) / kAdamChunk;
+    return chunks;
+}
+
+// Table `t` for the caller's tensors [t0, t0 + t.n), as many as the table holds: n, p, numel and the chunk prefix sum; returns the table's chunk
+// count.  rest(i, t0 + i) fills what else the table type has per tensor (g, m, v, the group nibble)
+template <class Table, class Rest>
+static int adam_fill(Table& t, int t0, int n_tensors, float* const* params, const int64_t* numel, Rest rest) {
+    constexpr int cap = (int)(sizeof(t.p) / sizeof(t.p[0]));
+    t.n = (n_tensors - t0 < cap) ? n_tensors - t0 : cap;
+    int chunks = 0;
+    for (int i = 0; i < t.n; ++i) {
+        t.p[i] = params[t0 + i];
+        t.numel[i] = (int)numel[t0 + i];
+        t.chunk_start[i] = chunks;
+        chunks += (t.numel[i] + kAdamChunk - 1) / kAdamChunk;
+        rest(i, t0 + i);
+    }
+    t.chunk_start[t.n] = chunks;
+    return chunks;
+}
+
+// The arguments of the flat entry points by name; what an entry does not take keeps its default
+struct AdamFlatCall {
+    int n_tensors; float* const* params; const float* const* grads; const int64_t* numel;
+    float *m_flat, *v_flat;
+    double* scratch;                             // [0]: sum of squares of all gradients; [1 ..]: one partial per 2048-element chunk
+    int* step; float* out_norm; void* stream;
+    const float* hyper = nullptr;
+    float lr = 0.f, beta1 = 0.f, beta2 = 0.f, eps = 0.f, weight_decay = 0.f, max_norm = 0.f;     // by value: dpn_clip_adam_flat alone
+    const uint8_t* group_of = nullptr;           // NULL in a grouped table: every tensor in group 0
+    float* ema_flat = nullptr; const int* ema_base = nullptr; int ema_warmup = 0;
+    DpnStepGuard* guard = nullptr; double spike_factor = 0.0, spike_decay = 0.0; int spike_warmup = 0, spike_patience = 0;
+};
+
+// One table of a flat call: the tensors from t0 on, their moments (and shadow) from chunk base_chunk of the flat buffers on
+template <class Table>
+static int adam_flat_table(Table& t, const AdamFlatCall& c, int t0, int base_chunk) {
+    const int64_t off = (int64_t)base_chunk * kAdamChunk;
+    t.m_flat = c.m_flat + off; t.v_flat = c.v_flat + off;
+    if constexpr (Table::ema) { t.s_flat = c.ema_flat + off; t.ema_base = c.ema_base; t.ema_warmup = c.ema_warmup; }
+    if constexpr (Table::guard_on) t.guard = c.guard;                                  // every update launch obeys the one verdict
+    if constexpr (Table::groups) for (int i = 0; i < kAdamFlatMaxTensors / 2; ++i) t.group4[i] = 0;
+    return adam_fill(t, t0, c.n_tensors, c.params, c.numel, [&](int i, int k) {
+        t.g[i] = c.grads[k];
+        if constexpr (Table::groups) if (c.group_of) t.group4[i >> 1] |= (uint8_t)(c.group_of[k] << ((i & 1) * 4));
+    });
+}
+
+// Every flat entry point: the norm launches (the norm is global, over every group, and bumps *step whatever the guard's verdict: one instantiation,
+// the plain table's, for all of them), the reduce (with the guard's verdict for a guarded table), then the update launches of `Table`
+template <class Table>
+static int clip_adam_flat(const AdamFlatCall& c) {
+    static_assert(std::is_trivially_copyable<Table>::value && std::is_trivially_copyable<AdamFlatPlain>::value, "the tables are passed by value");
+    hipStream_t s = reinterpret_cast<hipStream_t>(c.stream);
+    double* sumsq = c.scratch;
+    double* partial = c.scratch + 1;
+    int base_chunk = 0;
+    for (int t0 = 0; t0 < c.n_tensors; t0 += kAdamFlatMaxTensors) {
+        AdamFlatPlain t;
+        const int chunks = adam_flat_table(t, c, t0, base_chunk);
+        hipLaunchKernelGGL(dpn_gradnorm_kernel<AdamFlatPlain>, dim3(chunks), dim3(256), 0, s, t, partial + base_chunk, c.step, t0 == 0 ? 1 : 0);
+        base_chunk += chunks;
+    }
+    if constexpr (Table::guard_on)
+        hipLaunchKernelGGL(dpn_gradnorm_reduce_guard_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, base_chunk, sumsq, c.hyper, c.guard,
+                           c.spike_factor, c.spike_decay, c.spike_warmup, c.spike_patience);
+    else hipLaunchKernelGGL(dpn_gradnorm_reduce_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, base_chunk, sumsq);
+    base_chunk = 0;
+    for (int t0 = 0; t0 < c.n_tensors; t0 += kAdamFlatMaxTensors) {
+        Table t;
+        const int chunks = adam_flat_table(t, c, t0, base_chunk);
+        hipLaunchKernelGGL(dpn_adam_kernel<Table>, dim3(chunks), dim3(256), 0, s, t, (const double*)sumsq, (const int*)c.step, c.lr, c.beta1, c.beta2,
+                           c.eps, c.weight_decay, c.max_norm, c.out_norm, c.hyper);
+        base_chunk += chunks;
+    }
+    return ck(hipGetLastError());
+}
+
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
 
 int64_t dpn_clip_adam_scratch_doubles(int n_tensors, const int64_t* numel) {
-    if (n_tensors <= 0 || !numel) return -1;
-    int64_t chunks = 0;
-    for (int i = 0; i < n_tensors; ++i) chunks += (numel[i] + kAdamChunk - 1) / kAdamChunk;
-    return 1 + chunks;
+    return (n_tensors <= 0 || !numel) ? -1 : 1 + adam_chunks(n_tensors, numel);
+}
+
+int64_t dpn_clip_adam_flat_floats(int n_tensors, const int64_t* numel) {
+    return (n_tensors <= 0 || !numel) ? -1 : adam_chunks(n_tensors, numel) * kAdamChunk;
 }
 
 int dpn_clip_adam(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                   const int64_t* numel, double* scratch_dev, int* step_dev, float lr, float beta1, float beta2, float eps, float weight_decay,
                   float max_norm, float* out_norm_dev, void* stream) {
-    if (n_tensors <= 0 || !params || !grads || !exp_avg || !exp_avg_sq || !numel || !scratch_dev || !step_dev) return -1;
-    // every size is checked before the first launch: a refusal bumps no step counter and writes no partial, whichever table the bad tensor is in
-    for (int i = 0; i < n_tensors; ++i) if (numel[i] <= 0 || numel[i] > 0x7fffffff) return -1;
+    if (!adam_args_ok(n_tensors, numel, {params, grads, exp_avg, exp_avg_sq, scratch_dev, step_dev})) return -1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     double* sumsq = scratch_dev;                 // [0]: sum of squares of all gradients; [1 ..]: one partial per 2048-element chunk
     double* partial = scratch_dev + 1;
@@ -379,15 +397,8 @@ int dpn_clip_adam(int n_tensors, float* const* params, const float* const* grads
         int base_chunk = 0;
         for (int t0 = 0; t0 < n_tensors; t0 += kAdamMaxTensors) {
             AdamTable t;
-            t.n = (n_tensors - t0 < kAdamMaxTensors) ? n_tensors - t0 : kAdamMaxTensors;
-            int chunks = 0;
-            for (int i = 0; i < t.n; ++i) {
-                t.p[i] = params[t0 + i]; t.g[i] = grads[t0 + i]; t.m[i] = exp_avg[t0 + i]; t.v[i] = exp_avg_sq[t0 + i];
-                t.numel[i] = (int)numel[t0 + i];
-                t.chunk_start[i] = chunks;
-                chunks += (t.numel[i] + kAdamChunk - 1) / kAdamChunk;
-            }
-            t.chunk_start[t.n] = chunks;
+            const int chunks = adam_fill(t, t0, n_tensors, params, numel,
+                                         [&](int i, int k) { t.g[i] = grads[k]; t.m[i] = exp_avg[k]; t.v[i] = exp_avg_sq[k]; });
             if (pass == 0) hipLaunchKernelGGL(dpn_gradnorm_kernel<AdamTable>, dim3(chunks), dim3(256), 0, s, t, partial + base_chunk, step_dev, t0 == 0 ? 1 : 0);
             else hipLaunchKernelGGL(dpn_adam_kernel<AdamTable>, dim3(chunks), dim3(256), 0, s, t, (const double*)sumsq, (const int*)step_dev, lr, beta1,
                                     beta2, eps, weight_decay, max_norm, out_norm_dev, (const float*)nullptr);
@@ -398,229 +409,68 @@ int dpn_clip_adam(int n_tensors, float* const* params, const float* const* grads
     return ck(hipGetLastError());
 }
 
-int64_t dpn_clip_adam_flat_floats(int n_tensors, const int64_t* numel) {
-    if (n_tensors <= 0 || !numel) return -1;
-    int64_t chunks = 0;
-    for (int i = 0; i < n_tensors; ++i) chunks += (numel[i] + kAdamChunk - 1) / kAdamChunk;
-    return chunks * kAdamChunk;
-}
-
-extern "C++" template <class Table>
-static int clip_adam_flat_impl(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
-                               float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, float lr, float beta1, float beta2, float eps,
-                               float weight_decay, float max_norm, float* out_norm_dev, const float* hyper_dev, void* stream,
-                               float* ema_flat = nullptr, const int* ema_base_dev = nullptr, int ema_warmup = 0) {
-    if (n_tensors <= 0 || !params || !grads || !numel || !exp_avg_flat || !exp_avg_sq_flat || !scratch_dev || !step_dev) return -1;
-    // every size is checked before the first launch: a refusal bumps no step counter and writes no partial, whichever table the bad tensor is in
-    for (int i = 0; i < n_tensors; ++i) if (numel[i] <= 0 || numel[i] > 0x7fffffff) return -1;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    double* sumsq = scratch_dev;
-    double* partial = scratch_dev + 1;
-    for (int pass = 0; pass < 2; ++pass) {
-        int base_chunk = 0;
-        for (int t0 = 0; t0 < n_tensors; t0 += kAdamFlatMaxTensors) {
-            Table t;
-            t.n = (n_tensors - t0 < kAdamFlatMaxTensors) ? n_tensors - t0 : kAdamFlatMaxTensors;
-            t.m_flat = exp_avg_flat + (int64_t)base_chunk * kAdamChunk;
-            t.v_flat = exp_avg_sq_flat + (int64_t)base_chunk * kAdamChunk;
-            if constexpr (Table::ema) { t.s_flat = ema_flat + (int64_t)base_chunk * kAdamChunk; t.ema_base = ema_base_dev; t.ema_warmup = ema_warmup; }
-            int chunks = 0;
-            for (int i = 0; i < t.n; ++i) {
-                t.p[i] = params[t0 + i]; t.g[i] = grads[t0 + i];
-                t.numel[i] = (int)numel[t0 + i];
-                t.chunk_start[i] = chunks;
-                chunks += (t.numel[i] + kAdamChunk - 1) / kAdamChunk;
-            }
-            t.chunk_start[t.n] = chunks;
-            if (pass == 0) hipLaunchKernelGGL(dpn_gradnorm_kernel<Table>, dim3(chunks), dim3(256), 0, s, t, partial + base_chunk, step_dev, t0 == 0 ? 1 : 0);
-            else hipLaunchKernelGGL(dpn_adam_kernel<Table>, dim3(chunks), dim3(256), 0, s, t, (const double*)sumsq, (const int*)step_dev, lr,
-                                    beta1, beta2, eps, weight_decay, max_norm, out_norm_dev, hyper_dev);
-            base_chunk += chunks;
-        }
-        if (pass == 0) hipLaunchKernelGGL(dpn_gradnorm_reduce_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, base_chunk, sumsq);
-    }
-    return ck(hipGetLastError());
-}
-
 int dpn_clip_adam_flat(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
                        float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, float lr, float beta1, float beta2, float eps,
                        float weight_decay, float max_norm, float* out_norm_dev, void* stream) {
-    return clip_adam_flat_impl<AdamTableFlat>(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, lr, beta1, beta2, eps,
-                               weight_decay, max_norm, out_norm_dev, nullptr, stream);
+    if (!adam_args_ok(n_tensors, numel, {params, grads, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev})) return -1;
+    AdamFlatCall c{n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, out_norm_dev, stream};
+    c.lr = lr; c.beta1 = beta1; c.beta2 = beta2; c.eps = eps; c.weight_decay = weight_decay; c.max_norm = max_norm;
+    return clip_adam_flat<AdamFlatPlain>(c);
 }
 
 int dpn_clip_adam_flat_dev(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
                            float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const float* hyper_dev, float* out_norm_dev,
                            void* stream) {
-    if (!hyper_dev) return -1;
-    return clip_adam_flat_impl<AdamTableFlat>(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, 0.f, 0.f, 0.f, 0.f,
-                               0.f, 0.f, out_norm_dev, hyper_dev, stream);
+    if (!adam_args_ok(n_tensors, numel, {params, grads, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, hyper_dev})) return -1;
+    AdamFlatCall c{n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, out_norm_dev, stream, hyper_dev};
+    return clip_adam_flat<AdamFlatPlain>(c);
 }
 
 int dpn_clip_adam_flat_ema(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
                            float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const float* hyper_dev, float* out_norm_dev,
                            float* ema_flat, const int* ema_base_dev, int ema_warmup, void* stream) {
-    if (!hyper_dev || !ema_flat) return -1;
-    return clip_adam_flat_impl<AdamTableFlatEma>(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, 0.f, 0.f,
-                                                 0.f, 0.f, 0.f, 0.f, out_norm_dev, hyper_dev, stream, ema_flat, ema_base_dev, ema_warmup);
-}
-
-extern "C++" template <class Table>
-static int clip_adam_flat_groups_impl(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
-                                      float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const uint8_t* group_of, int n_groups,
-                                      const float* hyper_dev, float* out_norm_dev, float* ema_flat, const int* ema_base_dev, int ema_warmup,
-                                      void* stream) {
-    if (n_tensors <= 0 || !params || !grads || !numel || !exp_avg_flat || !exp_avg_sq_flat || !scratch_dev || !step_dev) return -1;
-    if (!group_of || !hyper_dev || n_groups < 1 || n_groups > kAdamMaxGroups) return -1;
-    // every size and every group is checked before the first launch: a refusal bumps no step counter and writes no partial
-    for (int i = 0; i < n_tensors; ++i) if (numel[i] <= 0 || numel[i] > 0x7fffffff || group_of[i] >= n_groups) return -1;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    double* sumsq = scratch_dev;
-    double* partial = scratch_dev + 1;
-    for (int pass = 0; pass < 2; ++pass) {
-        int base_chunk = 0;
-        for (int t0 = 0; t0 < n_tensors; t0 += kAdamFlatMaxTensors) {
-            const int n = (n_tensors - t0 < kAdamFlatMaxTensors) ? n_tensors - t0 : kAdamFlatMaxTensors;
-            if (pass == 0) {
-                // the norm is global, over every group: the launches of dpn_clip_adam_flat_dev, the same instantiation
-                AdamTableFlat t;
-                t.n = n; t.m_flat = nullptr; t.v_flat = nullptr;
-                int chunks = 0;
-                for (int i = 0; i < n; ++i) {
-                    t.p[i] = params[t0 + i]; t.g[i] = grads[t0 + i];
-                    t.numel[i] = (int)numel[t0 + i];
-                    t.chunk_start[i] = chunks;
-                    chunks += (t.numel[i] + kAdamChunk - 1) / kAdamChunk;
-                }
-                t.chunk_start[n] = chunks;
-                hipLaunchKernelGGL(dpn_gradnorm_kernel<AdamTableFlat>, dim3(chunks), dim3(256), 0, s, t, partial + base_chunk, step_dev, t0 == 0 ? 1 : 0);
-                base_chunk += chunks;
-                continue;
-            }
-            Table t;
-            t.n = n;
-            t.m_flat = exp_avg_flat + (int64_t)base_chunk * kAdamChunk;
-            t.v_flat = exp_avg_sq_flat + (int64_t)base_chunk * kAdamChunk;
-            if constexpr (Table::ema) { t.s_flat = ema_flat + (int64_t)base_chunk * kAdamChunk; t.ema_base = ema_base_dev; t.ema_warmup = ema_warmup; }
-            for (int i = 0; i < kAdamFlatMaxTensors / 2; ++i) t.group4[i] = 0;
-            int chunks = 0;
-            for (int i = 0; i < n; ++i) {
-                t.p[i] = params[t0 + i]; t.g[i] = grads[t0 + i];
-                t.numel[i] = (int)numel[t0 + i];
-                t.chunk_start[i] = chunks;
-                chunks += (t.numel[i] + kAdamChunk - 1) / kAdamChunk;
-                t.group4[i >> 1] |= (uint8_t)(group_of[t0 + i] << ((i & 1) * 4));      // this table's tensors start at t0 in the caller's list
-            }
-            t.chunk_start[n] = chunks;
-            hipLaunchKernelGGL(dpn_adam_kernel<Table>, dim3(chunks), dim3(256), 0, s, t, (const double*)sumsq, (const int*)step_dev, 0.f, 0.f, 0.f, 0.f,
-                               0.f, 0.f, out_norm_dev, hyper_dev);
-            base_chunk += chunks;
-        }
-        if (pass == 0) hipLaunchKernelGGL(dpn_gradnorm_reduce_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, base_chunk, sumsq);
-    }
-    return ck(hipGetLastError());
+    if (!adam_args_ok(n_tensors, numel, {params, grads, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, hyper_dev, ema_flat})) return -1;
+    AdamFlatCall c{n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, out_norm_dev, stream, hyper_dev};
+    c.ema_flat = ema_flat; c.ema_base = ema_base_dev; c.ema_warmup = ema_warmup;
+    return clip_adam_flat<AdamFlat<true, false, false>>(c);
 }
 
 int dpn_clip_adam_flat_groups(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
                               float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const uint8_t* group_of, int n_groups,
                               const float* hyper_dev, float* out_norm_dev, float* ema_flat, const int* ema_base_dev, int ema_warmup, void* stream) {
-    if (ema_flat)
-        return clip_adam_flat_groups_impl<AdamTableFlatGroupsEma>(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev,
-                                                                  group_of, n_groups, hyper_dev, out_norm_dev, ema_flat, ema_base_dev, ema_warmup, stream);
-    return clip_adam_flat_groups_impl<AdamTableFlatGroups>(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev,
-                                                           group_of, n_groups, hyper_dev, out_norm_dev, nullptr, nullptr, 0, stream);
-}
-
-extern "C++" template <class Table>
-static int clip_adam_flat_guard_impl(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
-                                     float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const uint8_t* group_of, const float* hyper_dev,
-                                     float* out_norm_dev, float* ema_flat, const int* ema_base_dev, int ema_warmup, DpnStepGuard* guard_dev,
-                                     double spike_factor, double spike_decay, int spike_warmup, int spike_patience, void* stream) {
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    double* sumsq = scratch_dev;
-    double* partial = scratch_dev + 1;
-    for (int pass = 0; pass < 2; ++pass) {
-        int base_chunk = 0;
-        for (int t0 = 0; t0 < n_tensors; t0 += kAdamFlatMaxTensors) {
-            const int n = (n_tensors - t0 < kAdamFlatMaxTensors) ? n_tensors - t0 : kAdamFlatMaxTensors;
-            if (pass == 0) {
-                // the gradient-norm launch is the existing one, the instantiation of dpn_clip_adam_flat_dev; it bumps *step_dev whatever the verdict
-                AdamTableFlat t;
-                t.n = n; t.m_flat = nullptr; t.v_flat = nullptr;
-                int chunks = 0;
-                for (int i = 0; i < n; ++i) {
-                    t.p[i] = params[t0 + i]; t.g[i] = grads[t0 + i];
-                    t.numel[i] = (int)numel[t0 + i];
-                    t.chunk_start[i] = chunks;
-                    chunks += (t.numel[i] + kAdamChunk - 1) / kAdamChunk;
-                }
-                t.chunk_start[n] = chunks;
-                hipLaunchKernelGGL(dpn_gradnorm_kernel<AdamTableFlat>, dim3(chunks), dim3(256), 0, s, t, partial + base_chunk, step_dev, t0 == 0 ? 1 : 0);
-                base_chunk += chunks;
-                continue;
-            }
-            Table t;
-            t.n = n;
-            t.m_flat = exp_avg_flat + (int64_t)base_chunk * kAdamChunk;
-            t.v_flat = exp_avg_sq_flat + (int64_t)base_chunk * kAdamChunk;
-            t.guard = guard_dev;                                                       // every update launch obeys the one verdict
-            if constexpr (Table::ema) { t.s_flat = ema_flat + (int64_t)base_chunk * kAdamChunk; t.ema_base = ema_base_dev; t.ema_warmup = ema_warmup; }
-            for (int i = 0; i < kAdamFlatMaxTensors / 2; ++i) t.group4[i] = 0;
-            int chunks = 0;
-            for (int i = 0; i < n; ++i) {
-                t.p[i] = params[t0 + i]; t.g[i] = grads[t0 + i];
-                t.numel[i] = (int)numel[t0 + i];
-                t.chunk_start[i] = chunks;
-                chunks += (t.numel[i] + kAdamChunk - 1) / kAdamChunk;
-                if (group_of) t.group4[i >> 1] |= (uint8_t)(group_of[t0 + i] << ((i & 1) * 4));
-            }
-            t.chunk_start[n] = chunks;
-            hipLaunchKernelGGL(dpn_adam_kernel<Table>, dim3(chunks), dim3(256), 0, s, t, (const double*)sumsq, (const int*)step_dev, 0.f, 0.f, 0.f, 0.f,
-                               0.f, 0.f, out_norm_dev, hyper_dev);
-            base_chunk += chunks;
-        }
-        if (pass == 0) hipLaunchKernelGGL(dpn_gradnorm_reduce_guard_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, base_chunk, sumsq, hyper_dev,
-                                          guard_dev, spike_factor, spike_decay, spike_warmup, spike_patience);
-    }
-    return ck(hipGetLastError());
+    if (!group_of || !adam_args_ok(n_tensors, numel, {params, grads, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, hyper_dev}, group_of, n_groups))
+        return -1;
+    AdamFlatCall c{n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, out_norm_dev, stream, hyper_dev};
+    c.group_of = group_of;
+    if (!ema_flat) return clip_adam_flat<AdamFlat<false, true, false>>(c);
+    c.ema_flat = ema_flat; c.ema_base = ema_base_dev; c.ema_warmup = ema_warmup;
+    return clip_adam_flat<AdamFlat<true, true, false>>(c);
 }
 
 int dpn_clip_adam_flat_guard(int n_tensors, float* const* params, const float* const* grads, const int64_t* numel, float* exp_avg_flat,
                              float* exp_avg_sq_flat, double* scratch_dev, int* step_dev, const uint8_t* group_of, int n_groups,
                              const float* hyper_dev, float* out_norm_dev, float* ema_flat, const int* ema_base_dev, int ema_warmup,
                              DpnStepGuard* guard_dev, double spike_factor, double spike_decay, int spike_warmup, int spike_patience, void* stream) {
-    if (n_tensors <= 0 || !params || !grads || !numel || !exp_avg_flat || !exp_avg_sq_flat || !scratch_dev || !step_dev || !hyper_dev) return -1;
-    if (!guard_dev || !(spike_factor >= 0.0 && spike_factor <= 1.7976931348623157e308) || !(spike_decay >= 0.0 && spike_decay < 1.0) ||
-        spike_warmup < 1 || spike_patience < 1) return -1;
-    if (group_of && (n_groups < 1 || n_groups > kAdamMaxGroups)) return -1;           // group_of NULL: one group, n_groups is not read
-    // every size and every group is checked before the first launch: a refusal bumps no step counter and writes no partial
-    for (int i = 0; i < n_tensors; ++i) if (numel[i] <= 0 || numel[i] > 0x7fffffff || (group_of && group_of[i] >= n_groups)) return -1;
-    if (ema_flat)
-        return clip_adam_flat_guard_impl<AdamTableFlatGuardEma>(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, group_of,
-                                                                hyper_dev, out_norm_dev, ema_flat, ema_base_dev, ema_warmup, guard_dev, spike_factor,
-                                                                spike_decay, spike_warmup, spike_patience, stream);
-    return clip_adam_flat_guard_impl<AdamTableFlatGuard>(n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, group_of,
-                                                         hyper_dev, out_norm_dev, nullptr, nullptr, 0, guard_dev, spike_factor, spike_decay, spike_warmup,
-                                                         spike_patience, stream);
+    if (!adam_args_ok(n_tensors, numel, {params, grads, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, hyper_dev, guard_dev}, group_of, n_groups))
+        return -1;
+    if (!(spike_factor >= 0.0 && spike_factor <= 1.7976931348623157e308) || !(spike_decay >= 0.0 && spike_decay < 1.0) || spike_warmup < 1 ||
+        spike_patience < 1) return -1;
+    AdamFlatCall c{n_tensors, params, grads, numel, exp_avg_flat, exp_avg_sq_flat, scratch_dev, step_dev, out_norm_dev, stream, hyper_dev};
+    c.group_of = group_of;                                                             // NULL: one group, n_groups is not read
+    c.guard = guard_dev; c.spike_factor = spike_factor; c.spike_decay = spike_decay; c.spike_warmup = spike_warmup; c.spike_patience = spike_patience;
+    if (!ema_flat) return clip_adam_flat<AdamFlat<false, true, true>>(c);
+    c.ema_flat = ema_flat; c.ema_base = ema_base_dev; c.ema_warmup = ema_warmup;
+    return clip_adam_flat<AdamFlat<true, true, true>>(c);
 }
 
 int dpn_ema_swap(int n_tensors, float* const* params, const int64_t* numel, float* ema_flat, void* stream) {
-    if (n_tensors <= 0 || !params || !numel || !ema_flat) return -1;
-    for (int i = 0; i < n_tensors; ++i) if (numel[i] <= 0 || numel[i] > 0x7fffffff) return -1;
+    if (!adam_args_ok(n_tensors, numel, {params, ema_flat})) return -1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     int base_chunk = 0;
     for (int t0 = 0; t0 < n_tensors; t0 += kAdamFlatMaxTensors) {
         EmaSwapTable t;
-        t.n = (n_tensors - t0 < kAdamFlatMaxTensors) ? n_tensors - t0 : kAdamFlatMaxTensors;
         t.s_flat = ema_flat + (int64_t)base_chunk * kAdamChunk;
-        int chunks = 0;
-        for (int i = 0; i < t.n; ++i) {
-            t.p[i] = params[t0 + i];
-            t.numel[i] = (int)numel[t0 + i];
-            t.chunk_start[i] = chunks;
-            chunks += (t.numel[i] + kAdamChunk - 1) / kAdamChunk;
-        }
-        t.chunk_start[t.n] = chunks;
+        const int chunks = adam_fill(t, t0, n_tensors, params, numel, [](int, int) {});
         hipLaunchKernelGGL(dpn_ema_swap_kernel, dim3(chunks), dim3(256), 0, s, t);
         base_chunk += chunks;
     }

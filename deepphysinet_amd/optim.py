@@ -305,44 +305,23 @@ class FusedClipAdam(torch.optim.Optimizer):
             self.sync_hyper()
         else:
             grad_arena.captured_step[0] = True      # replays of this step rewrite the parameters without passing through here
-        lib = L.load()
-        if self.step_guard is not None:
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+        grouped, ema, sg = len(self.param_groups) > 1, self._ema_flat is not None, self.step_guard
+        # what every entry point takes first, then the tails of the options
+        head = (len(self.params), self._p, self._g, self._numel, ptr(self._m_flat), ptr(self._v_flat), ptr(self._sumsq), ptr(self.step_count))
+        hyper = (ptr(self._hyper), ptr(self.grad_norm))
+        ema_tail = (ptr(self._ema_flat), ptr(self.ema_base), int(self.ema_warmup)) if ema else (None, None, int(self.ema_warmup))
+        if sg is not None:
             # one path for one group or several, with or without EMA, eager or captured
-            ema, grouped, sg = self._ema_flat is not None, len(self.param_groups) > 1, self.step_guard
-            L.check(lib.dpn_clip_adam_flat_guard(len(self.params), self._p, self._g, self._numel, ctypes.c_void_p(self._m_flat.data_ptr()),
-                                                 ctypes.c_void_p(self._v_flat.data_ptr()), ctypes.c_void_p(self._sumsq.data_ptr()),
-                                                 ctypes.c_void_p(self.step_count.data_ptr()), self._group_of if grouped else None,
-                                                 len(self.param_groups), ctypes.c_void_p(self._hyper.data_ptr()),
-                                                 ctypes.c_void_p(self.grad_norm.data_ptr()),
-                                                 ctypes.c_void_p(self._ema_flat.data_ptr()) if ema else None,
-                                                 ctypes.c_void_p(self.ema_base.data_ptr()) if ema else None, int(self.ema_warmup),
-                                                 ctypes.c_void_p(self._guard.data_ptr()), sg.spike_factor, sg.spike_decay, sg.spike_warmup,
-                                                 sg.spike_patience, torch.cuda.current_stream().cuda_stream),
-                    'dpn_clip_adam_flat_guard')
-        elif len(self.param_groups) > 1:
-            ema = self._ema_flat is not None
-            L.check(lib.dpn_clip_adam_flat_groups(len(self.params), self._p, self._g, self._numel, ctypes.c_void_p(self._m_flat.data_ptr()),
-                                                  ctypes.c_void_p(self._v_flat.data_ptr()), ctypes.c_void_p(self._sumsq.data_ptr()),
-                                                  ctypes.c_void_p(self.step_count.data_ptr()), self._group_of, len(self.param_groups),
-                                                  ctypes.c_void_p(self._hyper.data_ptr()), ctypes.c_void_p(self.grad_norm.data_ptr()),
-                                                  ctypes.c_void_p(self._ema_flat.data_ptr()) if ema else None,
-                                                  ctypes.c_void_p(self.ema_base.data_ptr()) if ema else None, int(self.ema_warmup),
-                                                  torch.cuda.current_stream().cuda_stream),
-                    'dpn_clip_adam_flat_groups')
-        elif self._ema_flat is None:
-            L.check(lib.dpn_clip_adam_flat_dev(len(self.params), self._p, self._g, self._numel, ctypes.c_void_p(self._m_flat.data_ptr()),
-                                               ctypes.c_void_p(self._v_flat.data_ptr()), ctypes.c_void_p(self._sumsq.data_ptr()),
-                                               ctypes.c_void_p(self.step_count.data_ptr()), ctypes.c_void_p(self._hyper.data_ptr()),
-                                               ctypes.c_void_p(self.grad_norm.data_ptr()), torch.cuda.current_stream().cuda_stream),
-                    'dpn_clip_adam_flat_dev')
+            entry, args = 'dpn_clip_adam_flat_guard', (head + (self._group_of if grouped else None, len(self.param_groups)) + hyper + ema_tail +
+                                                       (ptr(self._guard), sg.spike_factor, sg.spike_decay, sg.spike_warmup, sg.spike_patience))
+        elif grouped:
+            entry, args = 'dpn_clip_adam_flat_groups', head + (self._group_of, len(self.param_groups)) + hyper + ema_tail
+        elif ema:
+            entry, args = 'dpn_clip_adam_flat_ema', head + hyper + ema_tail
         else:
-            L.check(lib.dpn_clip_adam_flat_ema(len(self.params), self._p, self._g, self._numel, ctypes.c_void_p(self._m_flat.data_ptr()),
-                                               ctypes.c_void_p(self._v_flat.data_ptr()), ctypes.c_void_p(self._sumsq.data_ptr()),
-                                               ctypes.c_void_p(self.step_count.data_ptr()), ctypes.c_void_p(self._hyper.data_ptr()),
-                                               ctypes.c_void_p(self.grad_norm.data_ptr()), ctypes.c_void_p(self._ema_flat.data_ptr()),
-                                               ctypes.c_void_p(self.ema_base.data_ptr()), int(self.ema_warmup),
-                                               torch.cuda.current_stream().cuda_stream),
-                    'dpn_clip_adam_flat_ema')
+            entry, args = 'dpn_clip_adam_flat_dev', head + hyper
+        L.check(getattr(L.load(), entry)(*args, torch.cuda.current_stream().cuda_stream), entry)
         grad_arena.param_epoch[0] += 1
         self.steps_done += 1
         return self.grad_norm if closure is None else loss

@@ -1,5 +1,5 @@
 """Case table, fp64 reference, bound and fp32 model for the weight EMA that dpn_clip_adam_flat_ema moves inside the Adam update launch
-(dpn_adam_kernel<AdamTableFlatEma>), and the inputs of dpn_ema_swap.  Imports without a GPU: tests/test_ema_cases_cpu.py runs the table through
+(dpn_adam_kernel<AdamFlat<true, false, false>>), and the inputs of dpn_ema_swap.  Imports without a GPU: tests/test_ema_cases_cpu.py runs the table through
 the numpy fp32 model below, tests/test_gpu_ema.py through the C ABI.  The Adam side (inputs, placements, hyper-parameters, arenas) is
 tests/optim_cases.py's; only what the shadow adds is here.
 

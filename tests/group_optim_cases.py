@@ -1,5 +1,5 @@
 """Case table, fp64 reference, bounds and fp32 model for clip + Adam with PARAMETER GROUPS (dpn_clip_adam_flat_groups; kernels
-dpn_gradnorm_kernel<AdamTableFlat>, dpn_gradnorm_reduce_kernel, dpn_adam_kernel<AdamTableFlatGroups / AdamTableFlatGroupsEma>).  Imports without
+dpn_gradnorm_kernel<AdamFlatPlain>, dpn_gradnorm_reduce_kernel, dpn_adam_kernel<AdamFlat<false / true, true, false>>).  Imports without
 a GPU: tests/test_group_optim_cases_cpu.py runs the table through the numpy fp32 model below, tests/test_gpu_group_optim.py through the C ABI.
 
 The definition is the one in the header of tests/optim_cases.py with the hyper-parameters of tensor i taken from the row of its group k(i),
