@@ -9,6 +9,7 @@ Drop-in surfaces (same names / arguments as the reference, /root/reference/DeepP
     deepphysinet_amd.sampler.Lattice, InterfacePhysics.predict_points / predict_lattice / residuals_at / run_inference_interface
                                                                        (inference at stations and on lattices, interface_physics.py:1407-1530)
     deepphysinet_amd.optim.FusedClipAdam, distributed.GradientAllReduce (clip_grad_norm_ + Adam, DDP gradient averaging)
+    deepphysinet_amd.lbfgs.FusedLBFGS                                  (L-BFGS refinement with a strong-Wolfe line search on the flat buffers)
 The per-point arithmetic runs in libdpn_hip.so (hand-written HIP for gfx950, C ABI in include/dpn_hip.h).
 """
 from . import _lib

@@ -126,6 +126,12 @@ class DpnStepGuard(Structure):
                [('running', c_double), ('last', c_double)]
 
 
+class DpnLbfgsState(Structure):
+    """include/dpn_hip.h DpnLbfgsState: the ring, the counters and the scalars of the L-BFGS kernels (lbfgs.py)."""
+    _fields_ = [(n, c_int32) for n in ('count', 'newest', 'iters', 'skipped', 'pending', 'reserved')] + \
+               [(n, c_double) for n in ('gamma', 'gtd', 'dnorm', 'g_l1', 'g_inf', 'gg')]
+
+
 class DpnSizes(Structure):
     _fields_ = [('n_pad', c_int64), ('packed', c_int64), ('saved', c_int64), ('operands', c_int64), ('partials', c_int64),
                 ('k_splits', c_int32)]
@@ -226,6 +232,13 @@ EXPORTS = {
     'dpn_clip_adam_flat_guard': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_double, c_double, c_int, c_int, c_void_p]),
     'dpn_ema_swap': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dpn_lbfgs_scratch_doubles': (c_int64, [c_int, c_void_p, c_int]),
+    'dpn_lbfgs_save': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dpn_lbfgs_move': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p]),
+    'dpn_lbfgs_push': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'dpn_lbfgs_gram': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dpn_lbfgs_gtd': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dpn_lbfgs_direction': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dpn_gemm_fp8_mx': (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'dpn_selftest': (c_int, [c_void_p, c_void_p]),
     'dpn_adaptive_scratch_doubles': (c_int64, [c_int64]),

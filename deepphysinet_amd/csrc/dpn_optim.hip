@@ -7,6 +7,7 @@
 //                                                      group row, Guard obeys the step guard's verdict
 //   dpn_gradnorm_reduce_guard_kernel                   the reduction plus the step guard's verdict (skip non-finite and spiking steps)
 //   dpn_ema_swap_kernel                                exchanges the parameters with their EMA shadow
+//   dpn_lbfgs.inc (included at the end)                L-BFGS on the same flat layout: save / move / push, the Gram pass, the direction
 // No kernel in this file uses atomics: every reduction is fixed-order, the whole step is bitwise reproducible.
 // Host side: adam_fill writes every table, clip_adam_flat is the two-pass launcher of every flat entry point, adam_args_ok the checks they share.
 #include "dpn_device.h"
@@ -478,3 +479,6 @@ int dpn_ema_swap(int n_tensors, float* const* params, const int64_t* numel, floa
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ L-BFGS on the flat buffers
+#include "dpn_lbfgs.inc"

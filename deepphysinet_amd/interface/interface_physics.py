@@ -24,6 +24,7 @@ from .. import extremes as X
 from ..losses.builder import builder_loss
 from ..model.physics_net import PhysicsNet
 from ..guard import StepGuard
+from ..lbfgs import FusedLBFGS
 from ..optim import GROUP_KEYS, FusedClipAdam, resolve_param_groups
 from ..point_path import (balance_sumsq, balance_update, balanced_total, data_losses_batch, eval_step, eval_step_batch, grid_maps, label_errors, ParcelState,
                           EnsembleState, ExtremeState, LOSS_ORDER, OBS_ORDER, PackedField, pde_losses, pde_losses_batch, point_fields, point_sizes, PointConfig, require_gpu,
@@ -686,6 +687,31 @@ class InterfacePhysics(nn.Module):
         guard.StepGuard with the C ABI's argument rules."""
         return _loop_option(kwargs, self.train_cfg, 'step_guard', 'optimizer', StepGuard.KEYS, True, StepGuard, lambda opt: StepGuard(**opt))
 
+    LBFGS_KEYS = ('start_epoch', 'history_size', 'max_iter', 'max_eval', 'lr', 'tolerance_grad', 'tolerance_change', 'history')
+
+    def _lbfgs_option(self, kwargs):
+        """The loops' `lbfgs` option (keyword, or train_cfg['optimizer']['lbfgs']): None (off), or a dict of start_epoch (required) and FusedLBFGS's
+        history_size, max_iter, max_eval, lr, tolerance_grad, tolerance_change, history.  From start_epoch on the loop refines with L-BFGS."""
+        def build(opt):
+            if 'start_epoch' not in opt:
+                raise ValueError('lbfgs: start_epoch is required')
+            if isinstance(opt['start_epoch'], bool) or int(opt['start_epoch']) != opt['start_epoch'] or int(opt['start_epoch']) < 0:
+                raise ValueError('lbfgs: start_epoch must be an integer >= 0, got %r' % (opt['start_epoch'],))
+            return dict(opt, start_epoch=int(opt['start_epoch']))
+        return _loop_option(kwargs, self.train_cfg, 'lbfgs', 'optimizer', self.LBFGS_KEYS, False, None, build)
+
+    def _lbfgs_refusals(self, kwargs, dist_mode):
+        """ValueError before training starts for what cannot run beside the L-BFGS phase."""
+        if dist_mode:
+            raise ValueError('lbfgs: run_train_interface_dist refuses the option: the line search decides on the loss, which would have to be reduced '
+                             'across the ranks as well as the gradients (data-parallel L-BFGS is not implemented)')
+        section = {'adaptive_interior': 'train_data', 'causal_weights': 'losses', 'balance_losses': 'losses', 'ema_weights': 'optimizer',
+                   'step_guard': 'optimizer'}
+        on = [n for n, sec in section.items() if kwargs.get(n, (self.train_cfg.get(sec) or {}).get(n)) not in (None, False)]
+        if on:
+            raise ValueError('lbfgs together with %s: with adaptive_interior, causal_weights or balance_losses the objective changes between the '
+                             'evaluations of one line search; ema_weights and step_guard live in the fused clip + Adam launch' % ' and '.join(on))
+
     @staticmethod
     def _step_guard_log(optimizer, prev):
         """At a log step (the loop synchronises there anyway): the guard's counters as the extra keys of the log line and the metrics row, and the
@@ -853,29 +879,21 @@ class InterfacePhysics(nn.Module):
             optimizer.step()
         return train_loss.detach(), {k: v.detach() for k, v in fwd.parts.items()}, gnorm
 
-    def training_step_batch(self, batches, optimizer, with_pde=True, max_norm=2.5e7, grad_sync=None):
-        """ONE optimiser step on B samples: `batches` is a list of B training_step batch dicts (device tensors) with equal point counts -- for example B
-        forecast leads.  The encoder, the hyper-network heads and the weight packing run once for all B (the lead-batch launches); the point kernels
-        run sample after sample, each sample's backward right behind its forward (point_path.step_losses_batch).  loss = the mean of the B samples'
-        totals, each total training_step's (data + interior PDE) + margin PDE: the mean keeps the gradient scale of a single-sample step, so max_norm
-        and the learning rate keep their meaning.  Then backward, grad_sync(parameters) when given (the plain backward, as a balanced
-        data-parallel step takes it: there is no staged backward for this step), clip + Adam as training_step ends.  with_pde False: the data loss
-        alone (point_path.data_losses_batch).  Returns (loss, parts, gnorm, per_sample): parts = the means over the samples of margin_loss,
-        inter_pde_loss, margin_pde_loss; per_sample = {'terms' [B, 2, 6], 'parts' [B, 3], 'totals' [B]} on the device (without the PDE losses terms
-        is None, parts [B, 1]); nothing is read back.  Point weights (an `inter_w` entry: NotImplementedError), causal weights and loss balancing are
-        implemented for one sample per step only (training_step).  A list of one sample runs the same path with B = 1."""
+    def _lead_forward(self, batches, with_pde, what):
+        """The forward of one step on B samples (training_step_batch, loss_and_gradients): its checks, the batched encoder pass, the point kernels
+        sample after sample.  (terms, sample_parts, totals) as training_step_batch returns them, totals still attached to the graph."""
         batches = list(batches)
         if not batches:
-            raise ValueError('training_step_batch: no samples')
+            raise ValueError('%s: no samples' % what)
         if any('inter_w' in b for b in batches):
-            raise NotImplementedError('training_step_batch: per-point weights (inter_w) are implemented for one sample per step (training_step), not '
-                                      'for lead batches')
+            raise NotImplementedError('%s: per-point weights (inter_w) are implemented for one sample per step (training_step), not '
+                                      'for lead batches' % what)
         shape = lambda b: (b['inter_x'].shape[0] if with_pde else 0, b['margin_x'].shape[0])
         if any(shape(b) != shape(batches[0]) for b in batches[1:]):
-            raise ValueError('training_step_batch: the samples of one step must have equal point counts, got (interior, margin) = %s'
-                             % sorted({shape(b) for b in batches}))
+            raise ValueError('%s: the samples of one step must have equal point counts, got (interior, margin) = %s'
+                             % (what, sorted({shape(b) for b in batches})))
         for b in batches:
-            require_gpu(b['field_data'], 'field_data', 'training_step_batch')
+            require_gpu(b['field_data'], 'field_data', what)
         lf = self.train_cfg['losses']['loss_factor']
         self.last_causal = None
         B = len(batches)
@@ -896,6 +914,50 @@ class InterfacePhysics(nn.Module):
         else:
             totals = data_losses_batch(cfg, pts[0], pts[1], pts[2], pts[4], labels, heads, evec, statics, beta=0.1, margin_factor=lf['margin_factor'])
             terms, sample_parts = None, totals.detach().reshape(B, 1)
+        return terms, sample_parts, totals
+
+    def loss_and_gradients(self, batch_or_batches, optimizer, with_pde=True):
+        """The forward and the backward of training_step (a batch dict) or of training_step_batch (a list of them), ending BEFORE the optimiser
+        call: (loss, parts) with the gradients left in the optimiser's arena (`optimizer.flat_gradients()` for the fused optimisers) -- the closure
+        of FusedLBFGS.step.  The same launches in the same order as those steps make without causal weights, balancing and grad_sync, so the loss and
+        the gradients are bit for bit theirs.  An `inter_w` entry (single sample) weights the interior points as in training_step."""
+        if isinstance(batch_or_batches, (list, tuple)):
+            terms, sample_parts, totals = self._lead_forward(batch_or_batches, with_pde, 'loss_and_gradients')
+            train_loss = totals.mean()
+            means = sample_parts.mean(dim=0)
+            parts = {k: means[i] for i, k in enumerate(('margin_loss', 'inter_pde_loss', 'margin_pde_loss')[:means.numel()])}
+        else:
+            batch = batch_or_batches
+            lf = self.train_cfg['losses']['loss_factor']
+            self.last_causal = None
+            self.physics_net.clear_field_cache()
+            fwd = self._step_forward(batch, with_pde, lf, batch.get('inter_w') if with_pde else None, None, keep_embedding=False)
+            train_loss = 0
+            for v in fwd.parts.values():
+                train_loss = train_loss + v
+            parts = {k: v.detach() for k, v in fwd.parts.items()}
+        optimizer.zero_grad()
+        if getattr(self, '_seed', None) is None or self._seed.device != train_loss.device:
+            self._seed = torch.ones((), dtype=train_loss.dtype, device=train_loss.device)
+        train_loss.backward(self._seed)
+        self.physics_net.clear_field_cache()
+        if hasattr(optimizer, 'gather_gradients'):        # what autograd summed outside the arena (a lead batch's samples) is copied in, as step() does
+            optimizer.gather_gradients()
+        return train_loss.detach(), parts
+
+    def training_step_batch(self, batches, optimizer, with_pde=True, max_norm=2.5e7, grad_sync=None):
+        """ONE optimiser step on B samples: `batches` is a list of B training_step batch dicts (device tensors) with equal point counts -- for example B
+        forecast leads.  The encoder, the hyper-network heads and the weight packing run once for all B (the lead-batch launches); the point kernels
+        run sample after sample, each sample's backward right behind its forward (point_path.step_losses_batch).  loss = the mean of the B samples'
+        totals, each total training_step's (data + interior PDE) + margin PDE: the mean keeps the gradient scale of a single-sample step, so max_norm
+        and the learning rate keep their meaning.  Then backward, grad_sync(parameters) when given (the plain backward, as a balanced
+        data-parallel step takes it: there is no staged backward for this step), clip + Adam as training_step ends.  with_pde False: the data loss
+        alone (point_path.data_losses_batch).  Returns (loss, parts, gnorm, per_sample): parts = the means over the samples of margin_loss,
+        inter_pde_loss, margin_pde_loss; per_sample = {'terms' [B, 2, 6], 'parts' [B, 3], 'totals' [B]} on the device (without the PDE losses terms
+        is None, parts [B, 1]); nothing is read back.  Point weights (an `inter_w` entry: NotImplementedError), causal weights and loss balancing are
+        implemented for one sample per step only (training_step).  A list of one sample runs the same path with B = 1."""
+        net = self.physics_net
+        terms, sample_parts, totals = self._lead_forward(batches, with_pde, 'training_step_batch')
         train_loss = totals.mean()
         optimizer.zero_grad()
         if getattr(self, '_seed', None) is None or self._seed.device != train_loss.device:
@@ -1287,6 +1349,10 @@ class InterfacePhysics(nn.Module):
         tc = self.train_cfg
         # samples per optimiser step (1: not one call differs below); refused here, before anything is built, together with the single-sample options
         lead_batch = self._lead_batch_option(kwargs)
+        lbfgs = self._lbfgs_option(kwargs)                              # None: not one call differs below
+        if lbfgs is not None:
+            self._lbfgs_refusals(kwargs, dist_mode)
+        self.last_lbfgs = None
         num_epoch = int(kwargs.get('num_epoch', tc['num_epoch']))
         self.dx, self.dy = float(tc['dx']), float(tc['dy'])
         time_step = tc.get('lable_time_step', 1)
@@ -1352,6 +1418,16 @@ class InterfacePhysics(nn.Module):
             self.loss_balance_state = None                              # (a checkpoint's weights are not carried into a run without the option)
         seen = global_step                                              # samples this rank has trained on (the log line's fps)
         for epoch in range(current_epoch, num_epoch):
+            if lbfgs is not None and epoch >= lbfgs['start_epoch'] and not isinstance(optimizer, FusedLBFGS):
+                # the refinement phase: Adam is dropped (its arena registration with it), L-BFGS takes over the same trainable parameters
+                grad_arena.unregister(optimizer)
+                optimizer.zero_grad()
+                optimizer = FusedLBFGS([p for p in self.physics_net.parameters() if p.requires_grad],
+                                       **{k: v for k, v in lbfgs.items() if k != 'start_epoch'})
+                lr_schedule = None                                      # (the schedule was Adam's)
+                if rank == 0:
+                    print('epoch %d: L-BFGS refinement (history %d, %d iterations per step)'
+                          % (epoch, optimizer.defaults['history_size'], optimizer.defaults['max_iter']))
             stream = self._epoch_samples(kwargs, epoch, rank, world, dist_mode)   # DistributedSampler (:936): one field sample per rank per step
             if lead_batch > 1:                                          # ... or lead_batch consecutive ones of the rank's stream
                 stream = self._lead_groups(stream, lead_batch)
@@ -1376,7 +1452,20 @@ class InterfacePhysics(nn.Module):
                         group = [redraw(b) for b in group]
                     batch = redraw(batch) if group is None else group[0]
                 # (causal time weights, balanced terms: training_step drops both until the PDE losses are on)
-                if group is None:
+                lbfgs_text = ''
+                if isinstance(optimizer, FusedLBFGS):
+                    # one L-BFGS call on this step's points: the closure is the step's forward and backward (loss_and_gradients)
+                    held = {}
+
+                    def closure():
+                        held['loss'], held['parts'] = self.loss_and_gradients(batch if group is None else group, optimizer, with_pde=with_pde)
+                        return held['loss']
+                    optimizer.step(closure)
+                    lb = optimizer.last
+                    loss, parts, gnorm = torch.tensor(lb['f']), held['parts'], None
+                    self.last_lbfgs = {'lbfgs_iters': lb['iters'], 'lbfgs_evals': lb['evals'], 'lbfgs_t': lb['t'], 'lbfgs_status': lb['status']}
+                    lbfgs_text = ' lbfgs_iters %d lbfgs_evals %d lbfgs_t %.4g lbfgs_status %s' % (lb['iters'], lb['evals'], lb['t'], lb['status'])
+                elif group is None:
                     loss, parts, gnorm = self.training_step(batch, optimizer, with_pde=with_pde, grad_sync=sync, causal=causal, balance=balance)
                 else:
                     loss, parts, gnorm, _ = self.training_step_batch(group, optimizer, with_pde=with_pde, grad_sync=sync)
@@ -1389,7 +1478,7 @@ class InterfacePhysics(nn.Module):
                 if rank == 0 and global_step % log_step == 1:
                     print('epoch %d step %d loss %.6g %s%s%s' % (epoch, global_step, float(loss),
                                                                   ' '.join('%s %.4g' % (k, float(v)) for k, v in parts.items()),
-                                                                  self._balance_log_text(balance is not None and with_pde), guard_text))
+                                                                  self._balance_log_text(balance is not None and with_pde), guard_text + lbfgs_text))
                 if global_step % log_step == 1:                       # (the loop synchronises here anyway: float(loss))
                     encoder_ops.check_enc_status()                                # an encoder weight outside the f16 hi+lo split's range raises HERE, named
                 if log_now:
@@ -1479,6 +1568,7 @@ class InterfacePhysics(nn.Module):
                     extra = {'causal_min_w': float(lc['inter'][3 * bins]), 'causal_w': lc['inter'][:bins].tolist()}
                 extra.update(m._balance_log(with_pde))       # the K balancing weights and gradient norms (likewise read here only)
                 extra.update(getattr(m, 'last_step_guard', None) or {})       # the step guard's counters and running norm (likewise)
+                extra.update(getattr(m, 'last_lbfgs', None) or {})            # the L-BFGS phase: iterations, evaluations, step length, status
                 self.log.event('training', epoch=epoch, global_step=global_step, train_loss=loss, forecast_hours=f_train, fps=fps, variables=train_vars,
                                **parts, **extra)
                 self.log.event('validation', epoch=epoch, global_step=global_step, forecast_hours=f_valid, fps=fps,
@@ -1530,6 +1620,12 @@ class InterfacePhysics(nn.Module):
         skipped; ValueError at loop start with an optimiser that is not a FusedClipAdam; the guard's state rides in the optimiser's state dict --
         the loops' checkpoints hold no optimiser state, today as before; a loss that is non-finite while all gradients are finite is not seen;
         unset: the loop of before),
+        lbfgs (None, or dict(start_epoch, history_size, max_iter, max_eval, lr, tolerance_grad, tolerance_change, history): from epoch start_epoch on
+        the loop drops the Adam optimiser and refines with lbfgs.FusedLBFGS over the same trainable parameters (frozen ones stay frozen), ONE
+        FusedLBFGS.step per loop step on that step's points -- single samples and lead_batch groups alike; the learning-rate schedule ends with Adam;
+        the log line and the log-step row of metrics.jsonl gain lbfgs_iters, lbfgs_evals, lbfgs_t and lbfgs_status; ValueError before training starts
+        together with adaptive_interior, causal_weights, balance_losses (the objective would change between the evaluations of a line search),
+        ema_weights or step_guard (they live in the Adam launch); unset: the loop of before),
         freeze ([fnmatch patterns on state-dict names]) and param_groups ([dict(match=[patterns], lr=..., weight_decay=..., betas=..., eps=...)]):
         fine-tuning, as train_cfg['optimizer'] takes them (build_optimizer) -- with checkpoint_path naming an existing checkpoint the run starts from
         its weights, frozen parameters stay bit-identical, the checkpoints written still hold the full model (and a complete model_ema), and the
@@ -1548,7 +1644,8 @@ class InterfacePhysics(nn.Module):
         are then cut by count alone).  A source whose point counts vary from sample to sample can cut the ranks' streams differently, and the
         rank with more groups would wait in its all-reduce for ever: give such a source to this loop only with lead_batch unset.
         step_guard: the gradients are all-reduced before the norm is taken and the guard's state evolves from the norm alone, so every rank forms
-        the same verdict and the ranks stay in step without a collective of the guard's own.  This has not been run with more than one rank."""
+        the same verdict and the ranks stay in step without a collective of the guard's own.  This has not been run with more than one rank.
+        lbfgs: refused (ValueError): the line search would need the loss reduced across the ranks as well."""
         return self._run_train(True, **kwargs)
 
     # ------------------------------------------------------------------ inference loop (:1407-1530)

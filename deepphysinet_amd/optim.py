@@ -217,8 +217,8 @@ class FusedClipAdam(torch.optim.Optimizer):
         build_optimizer would leave them writing into freed memory."""
         for p, ptr in zip(self.params, self._ptrs):
             if p.data_ptr() != ptr:
-                raise RuntimeError('FusedClipAdam: a parameter of shape %s was re-allocated after the optimiser was built (model.to() / '
-                                   'param.data assignment); build the optimiser again' % (tuple(p.shape),))
+                raise RuntimeError('%s: a parameter of shape %s was re-allocated after the optimiser was built (model.to() / '
+                                   'param.data assignment); build the optimiser again' % (type(self).__name__, tuple(p.shape)))
 
     # ---- hyper-parameters ----------------------------------------------------------------------------------------------
     @property
@@ -258,7 +258,7 @@ class FusedClipAdam(torch.optim.Optimizer):
             g = p.grad
             if g is None:
                 if not zero_missing:
-                    raise RuntimeError('FusedClipAdam: a parameter has no gradient')
+                    raise RuntimeError('%s: a parameter has no gradient' % type(self).__name__)
                 s.zero_()
             elif g.data_ptr() != s.data_ptr() or not g.is_contiguous():
                 s.copy_(g)

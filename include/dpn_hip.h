@@ -727,6 +727,62 @@ int dpn_clip_adam_flat_guard(int n_tensors, float* const* params, const float* c
  * calls are the identity.  -1: n_tensors <= 0, a NULL pointer, a numel outside 1 .. 2^31 - 1. */
 int dpn_ema_swap(int n_tensors, float* const* params, const int64_t* numel, float* ema_flat, void* stream);
 
+/* L-BFGS on the flat buffers ("vector-free": the inner products of an iteration are taken in ONE pass over the history, the two-loop recursion runs
+ * on the small Gram matrix, the direction is formed in one more pass).  All flat buffers use dpn_clip_adam_flat_floats' layout (`total` floats,
+ * tensor i at chunk_start[i] * 2048; the padding is never read or written); the parameters are reached through the pointer table, 160 tensors per
+ * launch.  History: ring buffers S[m][total] and Y[m][total], 1 <= m <= 32.  Gram matrix G[(2m+1)^2] fp64 and delta[2m+1] fp64 over the basis BY RING
+ * SLOT: s slot j = j, y slot j = m + j, g = 2m; entries of slots that hold no pair are never read.  No atomics; every reduction in a fixed order
+ * (thread t of a 256-thread block adds elements t, t + 256, ... of its chunk, or partials t, t + 256, ...; lanes by the xor butterfly 32 .. 1, waves
+ * as (w0 + w1) + (w2 + w3)); no contraction: deepphysinet_amd/lbfgs.py restates every kernel operation for operation.
+ * The state lives in device memory, zero-initialised by the caller (zeroing it again empties the ring): */
+typedef struct DpnLbfgsState {
+    int32_t count;               /* pairs stored, 0 .. m                                                                 */
+    int32_t newest;              /* ring slot of the newest pair (the next push writes slot (newest + 1) % m)            */
+    int32_t iters;               /* directions formed (dpn_lbfgs_direction calls)                                        */
+    int32_t skipped;             /* pairs refused by the rule s.y > 1e-10                                                */
+    int32_t pending;             /* 1: the newest pair has not been judged yet (set by push, cleared by direction)       */
+    int32_t reserved;
+    double  gamma;               /* s.y / y.y of the newest standing pair (1 with none)                                  */
+    double  gtd;                 /* g . d of the last direction                                                          */
+    double  dnorm;               /* || d ||_2 of the last direction, sqrt(delta^T G delta)                               */
+    double  g_l1;                /* sum |g|, max |g| (NaN-propagating) and g . g of the last dpn_lbfgs_gram call          */
+    double  g_inf;
+    double  gg;
+} DpnLbfgsState;
+/* Every entry: -1 with nothing launched and nothing written on n_tensors < 1, a NULL pointer, a numel outside 1 .. 2^31 - 1, m outside 1 .. 32 or a
+ * step length t that is not finite.
+ * dpn_lbfgs_scratch_doubles: the length of `scratch`, (3 (2m + 1) + 2) partials per 2048-element chunk.
+ * dpn_lbfgs_save: x0_flat = the parameters, moved as 32-bit words.
+ * dpn_lbfgs_move: p = fl(x0 + fl(t d)), fp32; every trial point is formed from the saved x0.  t == 0 copies x0's words (d is not read): the
+ *   parameters are restored bit for bit.
+ * dpn_lbfgs_push: slot (newest + 1) % m of S and Y receives s = fl(t d) and y = fl(g - g_prev), then g_prev = g; a one-thread launch then makes
+ *   that slot the newest: count = min(count + 1, m), pending = 1.
+ * dpn_lbfgs_gram: one pass over the flat buffers forms the inner products of the newest s, the newest y and g with every stored s, every stored y
+ *   and g, and sum |g|, max |g|: products of fp32 operands formed in fp64 (exact), accumulated in fp64 per thread, one partial per chunk and
+ *   quantity (partial[q * chunks + chunk], q = v (2m + 1) + b, then the two norms); a reduce launch (one block per quantity) adds the partials in
+ *   index order and writes the rows and columns of G that belong to the three vectors, and g_l1, g_inf, gg of the state.
+ * dpn_lbfgs_gtd: out_dev[0] = a . b of two flat vectors with the same arithmetic and order (the line search's g . d); scratch: one double per chunk.
+ * dpn_lbfgs_direction: a one-thread fp64 launch, then one pass.  The thread first judges a pending pair: it stands when G[s_new, y_new] > 1e-10,
+ *   otherwise the ring pointer steps back, count -= 1 and skipped += 1 (in a full ring the slot the refused pair overwrote is lost with it).  Then,
+ *   basis order s oldest -> newest, y oldest -> newest, g, every product and every sum rounded once:
+ *       delta = -e_g
+ *       i newest -> oldest:  alpha_i = (delta . G[:, s_i]) / G[s_i, y_i];  delta[y_i] -= alpha_i
+ *       delta *= gamma,      gamma = G[s_new, y_new] / G[y_new, y_new]  (no pair: 1)
+ *       i oldest -> newest:  beta = (delta . G[:, y_i]) / G[s_i, y_i];     delta[s_i] += alpha_i - beta
+ *       gtd = delta . G[:, g];  dnorm = sqrt(max(delta^T G delta, 0));  iters += 1
+ *   and the pass forms d = sum_j delta_j b_j per element in fp64 in basis order, rounded once to fp32 (no pair stored: d = -g). */
+int64_t dpn_lbfgs_scratch_doubles(int n_tensors, const int64_t* numel, int m);
+int dpn_lbfgs_save(int n_tensors, float* const* params, const int64_t* numel, float* x0_flat, void* stream);
+int dpn_lbfgs_move(int n_tensors, float* const* params, const int64_t* numel, const float* x0_flat, const float* d_flat, float t, void* stream);
+int dpn_lbfgs_push(int n_tensors, float* const* params, const int64_t* numel, const float* g_flat, float* g_prev_flat, const float* d_flat, float t,
+                   float* S, float* Y, int m, DpnLbfgsState* state, void* stream);
+int dpn_lbfgs_gram(int n_tensors, float* const* params, const int64_t* numel, const float* S, const float* Y, const float* g_flat, int m,
+                   DpnLbfgsState* state, double* scratch, double* G, void* stream);
+int dpn_lbfgs_gtd(int n_tensors, float* const* params, const int64_t* numel, const float* a_flat, const float* b_flat, double* scratch,
+                  double* out_dev, void* stream);
+int dpn_lbfgs_direction(int n_tensors, float* const* params, const int64_t* numel, const float* S, const float* Y, const float* g_flat, int m,
+                        DpnLbfgsState* state, const double* G, double* delta, float* d_flat, void* stream);
+
 /* BASELINE configs[4] (OFF by default; `bench.py --encoder-fp8` / DPN_ENCODER_FP8=mx routes the encoder layers' forward GEMMs here): C[M][N] =
  * epilogue(A[M][K] . W[N][K]^T + bias[N]) on the block-scaled (MX) fp8 instruction v_mfma_scale_f32_32x32x64_f8f6f4: OCP e4m3 operands quantised in
  * the kernel, one E8M0 power-of-two scale per 32 consecutive k of a row (OCP MX) applied by the hardware, fp32 accumulate; K % 64 == 0; epi =

@@ -5,6 +5,7 @@
                     [--adaptive_interior] [--causal_weights EPS] [--balance_losses EVERY] [--lead_batch K] [--ema DECAY]
                     [--skip_nonfinite] [--spike_factor F [--spike_warmup N] [--spike_patience N]]
                     [--freeze PATTERN]... [--param_group 'PATTERN[,PATTERN...]:lr=...,weight_decay=...']...
+                    [--lbfgs_from EPOCH [--lbfgs_history M] [--lbfgs_iters N]]
 
 The reference reads the config with mmcv.Config.fromfile (absent here, and moved to mmengine in the pinned mmcv: SURVEY section 0, defect
 3), builds the interface with `builder_models(**cfg['config'])` and calls `run_train_interface(checkpoint_path=..., log_path=...)`.  The
@@ -70,6 +71,27 @@ def step_guard_arg(args):
         opt['spike_warmup'] = args.spike_warmup
     if args.spike_patience is not None:
         opt['spike_patience'] = args.spike_patience
+    return opt
+
+
+parse.add_argument('--lbfgs_from', default=None, type=int, metavar='EPOCH', help='from this epoch on the loop drops Adam and refines with L-BFGS and a '
+                   'strong-Wolfe line search on the flat buffers, one FusedLBFGS.step per loop step (lbfgs=dict(start_epoch=EPOCH, ...)); not together '
+                   'with --adaptive_interior, --causal_weights, --balance_losses, --ema, --skip_nonfinite / --spike_factor or --dist')
+parse.add_argument('--lbfgs_history', default=None, type=int, metavar='M', help='curvature pairs kept, 1 .. 32 (default 10)')
+parse.add_argument('--lbfgs_iters', default=None, type=int, metavar='N', help='L-BFGS iterations per loop step (default 20)')
+
+
+def lbfgs_arg(args):
+    """The `lbfgs` option of the loops from the three flags: None, or dict(start_epoch, [history_size], [max_iter])."""
+    if args.lbfgs_from is None:
+        if args.lbfgs_history is not None or args.lbfgs_iters is not None:
+            raise SystemExit('--lbfgs_history / --lbfgs_iters need --lbfgs_from')
+        return None
+    opt = dict(start_epoch=args.lbfgs_from)
+    if args.lbfgs_history is not None:
+        opt['history_size'] = args.lbfgs_history
+    if args.lbfgs_iters is not None:
+        opt['max_iter'] = args.lbfgs_iters
     return opt
 
 
@@ -143,6 +165,8 @@ if __name__ == '__main__':
         kwargs['ema_weights'] = dict(decay=args.ema, warmup=True)
     if step_guard_arg(args) is not None:
         kwargs['step_guard'] = step_guard_arg(args)
+    if lbfgs_arg(args) is not None:
+        kwargs['lbfgs'] = lbfgs_arg(args)
     if args.freeze:
         kwargs['freeze'] = args.freeze
     if args.param_group:
