@@ -19,7 +19,9 @@ def _src(name):
     return os.path.join(HERE, 'csrc', name)
 
 
-UNITS = [(_src('dpn_point.hip'), ['-mllvm', '-amdgpu-mfma-vgpr-form'], 'dpn_point.o'),
+# The point unit is also compiled without SLP vectorisation: hipcc packs adjacent fp32 adds / multiplies / fmas of the feature and epilogue code into
+# v_pk_*_f32, which issue slower than the two instructions they replace beside MFMAs (profiles/valu_diet_ab.txt; the results are the same bits).
+UNITS = [(_src('dpn_point.hip'), ['-mllvm', '-amdgpu-mfma-vgpr-form', '-fno-slp-vectorize'], 'dpn_point.o'),
          (_src('dpn_wgrad.hip'), [], 'dpn_wgrad.o'),      # weight packing, weight-gradient and finish kernels, sizes, self-test
          (_src('dpn_encoder.hip'), [], 'dpn_encoder.o'),
          (_src('dpn_sampler.hip'), [], 'dpn_sampler.o'),

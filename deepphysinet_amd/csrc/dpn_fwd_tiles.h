@@ -254,14 +254,19 @@ DEV void save_tile_k(const KMat& m, const int net, const int64_t tile32, const i
     }
 }
 
-// the coordinate features of k-step ks (0..11) for the lane's point: one B fragment (hi [+ lo])
-template <int NS, class Args>
-DEV void pe3_frag(Frag<NS>& f, const Args& a, const int ks, const int h, const int64_t pc) {
-    const int c = ks >> 2;
+// the normalised coordinate xi_c of point pc: x / dx / (lon-1), two fp32 divisions in this order (interface_physics.py:324-326); t: / span / 1.
+// Evaluated ONCE per lane, point and coordinate by the kernels and handed to the helpers below (each of them used to divide for itself, behind
+// barriers where the compiler cannot merge the calls: 18 divisions of ~10 instructions in the forward kernel; 10 now, 8 of them for xi)
+template <class Args>
+DEV float xi_of(const Args& a, const int c, const int64_t pc) {
     const float* src = (c == 0) ? a.x : (c == 1) ? a.y : a.t;
     const float d1 = (c == 0) ? a.geo.dx : (c == 1) ? a.geo.dy : a.geo.pred_t_span;
-    const float d2 = (c == 0) ? a.geo.lon_m1 : (c == 1) ? a.geo.lat_m1 : 1.0f;   // x / dx / (lon-1): two fp32 divisions (interface_physics.py:324-326); t: one
-    const float xi = src[pc] / d1 / d2;
+    const float d2 = (c == 0) ? a.geo.lon_m1 : (c == 1) ? a.geo.lat_m1 : 1.0f;
+    return src[pc] / d1 / d2;
+}
+// the coordinate features of k-step ks (0..11) for the lane's point (xi: its coordinate ks >> 2): one B fragment (hi [+ lo])
+template <int NS, class Args>
+DEV void pe3_frag(Frag<NS>& f, const Args& a, const int ks, const int h, const float xi) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         float s, co;
@@ -298,12 +303,7 @@ DEV void pe6_frag_dot(Frag<NS>& f, const Args& a, const int ks, const int h, con
 }
 // backward: Z0 = g * pe + gJ_c * d pe / d xi_c for k-step ks (coordinate c = ks >> 2), build_pe3<BWD> of the ring kernels
 template <int NS, class Args>
-DEV void z0_frag(Frag<NS>& f, const Args& a, const int ks, const int h, const int64_t pc, const float g, const float gjc, float (&sc)[8]) {   // sc: (s, co) x 4, the table form's features
-    const int c = ks >> 2;
-    const float* src = (c == 0) ? a.x : (c == 1) ? a.y : a.t;
-    const float d1 = (c == 0) ? a.geo.dx : (c == 1) ? a.geo.dy : a.geo.pred_t_span;
-    const float d2 = (c == 0) ? a.geo.lon_m1 : (c == 1) ? a.geo.lat_m1 : 1.0f;
-    const float xi = src[pc] / d1 / d2;
+DEV void z0_frag(Frag<NS>& f, const Args& a, const int ks, const int h, const float xi, const float g, const float gjc, float (&sc)[8]) {   // sc: (s, co) x 4, the table form's features
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const float fr = a.freqs[8 * (ks & 3) + 4 * h + q];
@@ -316,11 +316,7 @@ DEV void z0_frag(Frag<NS>& f, const Args& a, const int ks, const int h, const in
 }
 // d pe3 / d xi_c for the 16 accumulator registers of gpe tile 2c + t (register pair rp = one angle: k-step 2T + (rp >> 2) of the coordinate PE)
 template <int NS, class Args>
-DEV void dpe_tile(float (&d)[16], const Args& a, const int c, const int t, const int h, const int64_t pc) {
-    const float* src = (c == 0) ? a.x : (c == 1) ? a.y : a.t;
-    const float d1 = (c == 0) ? a.geo.dx : (c == 1) ? a.geo.dy : a.geo.pred_t_span;
-    const float d2 = (c == 0) ? a.geo.lon_m1 : (c == 1) ? a.geo.lat_m1 : 1.0f;
-    const float xi = src[pc] / d1 / d2;
+DEV void dpe_tile(float (&d)[16], const Args& a, const int t, const int h, const float xi) {
 #pragma unroll
     for (int rp = 0; rp < 8; ++rp) {
         const int r = 2 * rp;
@@ -333,12 +329,7 @@ DEV void dpe_tile(float (&d)[16], const Args& a, const int c, const int t, const
 }
 // z0_frag + gH_c * d2 pe / d xi_c^2 = -gH_c fr^2 pe (dpn_bwd_tiles_deriv_kernel; build_z0_derivs of the ring kernels)
 template <int NS, class Args>
-DEV void z0_frag_derivs(Frag<NS>& f, const Args& a, const int ks, const int h, const int64_t pc, const float g, const float gjc, const float ghc) {
-    const int c = ks >> 2;
-    const float* src = (c == 0) ? a.x : (c == 1) ? a.y : a.t;
-    const float d1 = (c == 0) ? a.geo.dx : (c == 1) ? a.geo.dy : a.geo.pred_t_span;
-    const float d2 = (c == 0) ? a.geo.lon_m1 : (c == 1) ? a.geo.lat_m1 : 1.0f;
-    const float xi = src[pc] / d1 / d2;
+DEV void z0_frag_derivs(Frag<NS>& f, const Args& a, const int ks, const int h, const float xi, const float g, const float gjc, const float ghc) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const float fr = a.freqs[8 * (ks & 3) + 4 * h + q];
@@ -351,11 +342,7 @@ DEV void z0_frag_derivs(Frag<NS>& f, const Args& a, const int ks, const int h, c
 }
 // dpe_tile, and d2 = d2 pe3 / d xi_c^2 = -fr^2 pe3, d3 = d3 pe3 / d xi_c^3 = -fr^2 d (dpn_fwd_tiles_deriv_kernel; d is formed exactly as dpe_tile forms it)
 template <int NS, class Args>
-DEV void dpe_tile_derivs(float (&d)[16], float (&d2)[16], float (&d3)[16], const Args& a, const int c, const int t, const int h, const int64_t pc) {
-    const float* src = (c == 0) ? a.x : (c == 1) ? a.y : a.t;
-    const float d1 = (c == 0) ? a.geo.dx : (c == 1) ? a.geo.dy : a.geo.pred_t_span;
-    const float s2 = (c == 0) ? a.geo.lon_m1 : (c == 1) ? a.geo.lat_m1 : 1.0f;
-    const float xi = src[pc] / d1 / s2;
+DEV void dpe_tile_derivs(float (&d)[16], float (&d2)[16], float (&d3)[16], const Args& a, const int t, const int h, const float xi) {
 #pragma unroll
     for (int rp = 0; rp < 8; ++rp) {
         const int r = 2 * rp;

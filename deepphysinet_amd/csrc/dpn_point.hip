@@ -20,6 +20,7 @@
 // parks them in AGPRs and pays a v_accvgpr_read for every element an epilogue touches, 1775 of the forward kernel's 6457 VALU instructions.
 // (The weight-gradient kernel measures slower in that form: dpn_wgrad.hip is built without it.)
 #include "dpn_point_common.h"
+#include "dpn_sincos.h"
 
 // ------------------------------------------------------------------------------------------------ operand fragments
 template <int NS>
@@ -39,26 +40,7 @@ DEV void frag_set2(Frag<NS>& f, const int p, float a, float b) {      // element
 //  depending on unrelated code around it).  The ReLU is now a select on the compare that builds the mask bit; tools/mfma_hazard_check.py
 //  scans the generated assembly for any inline-asm reader of a fresh MFMA result.)
 
-// Cody-Waite reduction by pi/2 + minimax polynomials, |err| ~1e-7 for |theta| up to a few hundred.
-DEV void sincos_precise(float th, float& s, float& c) {
-    const float k = rintf(th * 0.63661977236758134f);
-    float r = fmaf(k, -1.5707963705062866f, th);               // float(pi/2); the fma keeps k*hi exact
-    r = fmaf(k, 4.371138828673793e-08f, r);                     // pi/2 - float(pi/2)
-    const float r2 = r * r;
-    float sp = fmaf(r2, 2.7183114939898219064e-6f, -1.9839334836096632576e-4f);
-    sp = fmaf(sp, r2, 8.3333293858894631756e-3f);
-    sp = fmaf(sp, r2, -1.6666666641626524100e-1f);
-    sp = fmaf(sp * r2, r, r);
-    float cp = fmaf(r2, 2.4433157826443582e-5f, -1.3887316255057415e-3f);
-    cp = fmaf(cp, r2, 4.1666645683529456e-2f);
-    cp = fmaf(cp, r2, -0.5f);
-    cp = fmaf(cp, r2, 1.0f);
-    const int q = ((int)k) & 3;
-    const float ss = (q & 1) ? cp : sp;
-    const float cc = (q & 1) ? sp : cp;
-    s = (q & 2) ? -ss : ss;
-    c = ((q + 1) & 2) ? -cc : cc;
-}
+// sincos_precise (Cody-Waite reduction by pi/2 + minimax polynomials, the quadrant as bit arithmetic): dpn_sincos.h, shared with host code
 // NS == 1 (plain bf16 operands): the features are rounded to 8 mantissa bits anyway -> hardware v_sin/v_cos
 template <int NS>
 DEV void sincos_t(float th, float& s, float& c) {

@@ -75,13 +75,22 @@ __global__ __launch_bounds__(256, 2) void dpn_fwd_tiles_kernel(FwdArgs a) {
 
     ts::Head<NS, 2> H;
     ts::gemm_head<NS, 12, 2>(chunk(kF0 + 2 * w * 12), lane, H);
+    // the normalised coordinates of the lane's two points, once: the wave's k-steps 3w .. 3w+2 lie in coordinates ca <= cb (wave-uniform), and the
+    // Jacobian tail of waves 0..2 contracts with d pe / d xi_w, w == cb there
+    const int ca = (3 * w) >> 2, cb = (3 * w + 2) >> 2;
+    float xia[2], xib[2];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        xia[p] = ts::xi_of(a, ca, pc[p]);
+        xib[p] = ts::xi_of(a, cb, pc[p]);
+    }
     // ---------------- coordinate features pe3 -> X (k-steps 0..11): this thread builds k-steps 3w .. 3w+2 of both column tiles
 #pragma unroll
     for (int kk = 0; kk < 3; ++kk)
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
             Frag<NS> f;
-            ts::pe3_frag<NS>(f, a, 3 * w + kk, h, pc[p]);
+            ts::pe3_frag<NS>(f, a, 3 * w + kk, h, (((3 * w + kk) >> 2) == ca) ? xia[p] : xib[p]);
             ts::x_store<NS>(xl, 3 * w + kk, p, f);
         }
     TS_STAMP(1);
@@ -290,14 +299,14 @@ __global__ __launch_bounds__(256, 2) void dpn_fwd_tiles_kernel(FwdArgs a) {
                 float d[16];
 #if DPN_DERIV
                 float d2[16], d3[16];
-                ts::dpe_tile_derivs<NS>(d, d2, d3, a, c, t, h, pc[p]);
+                ts::dpe_tile_derivs<NS>(d, d2, d3, a, t, h, xib[p]);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     hc[p] = fmaf(acc[t][p][r], d2[r], hc[p]);
                     tc[p] = fmaf(acc[t][p][r], d3[r], tc[p]);
                 }
 #else
-                ts::dpe_tile<NS>(d, a, c, t, h, pc[p]);
+                ts::dpe_tile<NS>(d, a, t, h, xib[p]);
 #endif
 #pragma unroll
                 for (int r = 0; r < 16; ++r) jc[p] = fmaf(acc[t][p][r], d[r], jc[p]);
@@ -402,16 +411,17 @@ __global__ __launch_bounds__(256, 3) void dpn_bwd_tiles_kernel(BwdArgs a) {
         const int64_t pcp = p ? pc[1] : pc[0];
         float gjc = 0.f;
         if (a.g_jxi && ((tile0 + p) * 32 + j) < a.n) gjc = gsc * a.g_jxi[(pcp * 6 + net) * 3 + (ct >> 1)];
+        const float xi = ts::xi_of(a, ct >> 1, pcp);          // both k-steps of the unit lie in coordinate ct >> 1
         Frag<NS> f0, f1;
 #if DPN_DERIV
         float ghc = 0.f;
         if (g_hxi && ((tile0 + p) * 32 + j) < a.n) ghc = gsc * g_hxi[(pcp * 6 + net) * 3 + (ct >> 1)];
-        ts::z0_frag_derivs<NS>(f0, a, 2 * ct, h, pcp, gp, gjc, ghc);
-        ts::z0_frag_derivs<NS>(f1, a, 2 * ct + 1, h, pcp, gp, gjc, ghc);
+        ts::z0_frag_derivs<NS>(f0, a, 2 * ct, h, xi, gp, gjc, ghc);
+        ts::z0_frag_derivs<NS>(f1, a, 2 * ct + 1, h, xi, gp, gjc, ghc);
 #else
         float sc0[8], sc1[8];
-        ts::z0_frag<NS>(f0, a, 2 * ct, h, pcp, gp, gjc, sc0);
-        ts::z0_frag<NS>(f1, a, 2 * ct + 1, h, pcp, gp, gjc, sc1);
+        ts::z0_frag<NS>(f0, a, 2 * ct, h, xi, gp, gjc, sc0);
+        ts::z0_frag<NS>(f1, a, 2 * ct + 1, h, xi, gp, gjc, sc1);
 #endif
         ts::x_store<NS>(xl, 2 * ct, p, f0);
         ts::x_store<NS>(xl, 2 * ct + 1, p, f1);
