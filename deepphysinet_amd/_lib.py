@@ -121,6 +121,12 @@ class DpnExtremeState(Structure):
     _fields_ = [(n, c_void_p) for n in ('best_v', 'best_t', 'best_k', 'acc', 'status', 'lo', 'hi')]
 
 
+class DpnSpellState(Structure):
+    """include/dpn_hip.h DpnSpellState: the thirteen [C][n] arrays of a threshold-spells request."""
+    _fields_ = [(n, c_void_p) for n in ('prev_x', 'hours', 'excess', 'crossings', 'k_first', 'k_last', 'status', 'part_first', 'part_last', 'f_lo', 'f_hi',
+                                        'l_lo', 'l_hi')]
+
+
 class DpnStepGuard(Structure):
     _fields_ = [(n, c_int32) for n in ('skipped_nonfinite', 'skipped_spike', 'verdict', 'seen', 'consecutive', 'reserved')] + \
                [('running', c_double), ('last', c_double)]
@@ -218,6 +224,15 @@ EXPORTS = {
     'dpn_extreme_refine': (c_int, [POINTER(DpnSampler), c_void_p, POINTER(DpnPhysics), c_int, c_void_p, c_void_p, c_int64, POINTER(c_int32),
                                    POINTER(c_int32), c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p, POINTER(DpnExtremeState), c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dpn_spell_scan': (c_int, [POINTER(DpnSampler), c_void_p, POINTER(DpnPhysics), c_int, c_void_p, c_int64, POINTER(c_int32), POINTER(c_int32),
+                               POINTER(c_float), c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p, POINTER(DpnSpellState), c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dpn_spell_begin': (c_int, [POINTER(DpnSampler), c_void_p, c_int64, POINTER(c_int32), POINTER(c_int32), POINTER(c_float), c_int, c_int, c_double,
+                                c_double, c_void_p, c_void_p, POINTER(DpnSpellState), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dpn_spell_refine': (c_int, [POINTER(DpnSampler), c_void_p, POINTER(DpnPhysics), c_int, c_void_p, c_int64, POINTER(c_int32), POINTER(c_int32),
+                                 POINTER(c_float), c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p, POINTER(DpnSpellState), c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dpn_spell_finish': (c_int, [c_int64, c_int, c_int, c_double, c_double, POINTER(DpnSpellState), c_void_p]),
     'dpn_label_errors_blocks': (c_int64, [c_int64]),
     'dpn_label_errors': (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(DpnPhysics), c_float, c_int, c_void_p, c_void_p]),
     'dpn_label_errors_finish': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
@@ -268,6 +283,9 @@ ENS_PRODUCTS, ENS_MAX_THRESHOLDS = 34, 16          # DPN_ENS_PRODUCTS, DPN_ENS_M
 EXT_MAX_COLUMNS = 32          # DPN_EXT_MAX_COLUMNS (include/dpn_hip.h)
 EXT_MAX, EXT_MIN, EXT_MEAN = 0, 1, 2                                                 # DPN_EXT_MAX, _MIN, _MEAN: a column's sense
 EXT_OK, EXT_BAD_SCAN, EXT_STOPPED, EXT_AT_START, EXT_AT_END = 0, 1, 2, 3, 4         # DPN_EXT_*: a column's status
+SPELL_MAX_COLUMNS = 16        # DPN_SPELL_MAX_COLUMNS (include/dpn_hip.h)
+SPELL_ABOVE, SPELL_BELOW = 0, 1                                                      # DPN_SPELL_ABOVE, _BELOW: a column's side
+SPELL_BAD_SCAN, SPELL_STOPPED, SPELL_NEVER, SPELL_HOLDS_AT_START, SPELL_HOLDS_AT_END = 1, 2, 4, 8, 16       # DPN_SPELL_*: the bits of a column's status
 CAUSAL_MAX_BINS = 64          # DPN_CAUSAL_MAX_BINS (include/dpn_hip.h)
 BALANCE_MAX_TERMS, BALANCE_STEP_TERMS = 16, 13          # DPN_BALANCE_MAX_TERMS, DPN_BALANCE_STEP_TERMS (include/dpn_hip.h)
 

@@ -1388,6 +1388,25 @@ class PackedField:
         out_n, jac_n = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, cd, want_jac=True, want_saved=False)
         extreme_refine(sampler, self._extreme_physics(with_clip), with_clip, out_n, jac_n, state, rnd)
 
+    def spell_scan(self, sampler, state, k, with_clip=False):
+        """Scan node k of a threshold-spells request for the points of `state` (a SpellState): the fields-only forward at the node, then
+        dpn_spell_scan, which folds it into the state and writes the next node's inputs into the same buffers; after the last node dpn_spell_begin
+        closes the scan and writes the first probes.  Two launches (three at node K), nothing read back."""
+        x, y, t, _, cd = state.points
+        out_n, _ = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, cd, want_jac=False, want_saved=False)
+        spell_scan(sampler, self._extreme_physics(with_clip), with_clip, out_n, state, k)
+        if k == state.K:
+            spell_begin(sampler, state)
+
+    def spell_refine(self, sampler, state, rnd, with_clip=False, last=False):
+        """Round `rnd` of the refinement: the fields-only forward at the 2 * C * n probes, then dpn_spell_refine, which halves the brackets and
+        rewrites the probes; `last`: dpn_spell_finish behind it.  Two launches (three when last), nothing read back."""
+        x, y, t, _, cd = state.probes
+        out_n, _ = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, cd, want_jac=False, want_saved=False)
+        spell_refine(sampler, self._extreme_physics(with_clip), with_clip, out_n, state, rnd)
+        if last:
+            spell_finish(state)
+
 
 class EnsembleState:
     """Device state of an ensemble request between dpn_ensemble_accumulate launches (include/dpn_hip.h): for n_total points, the P columns `ids`
@@ -1512,3 +1531,73 @@ def extreme_refine(sampler, ph, with_clip, out_n, jac_n, state, rnd):
     L.check(L.load().dpn_extreme_refine(ctypes.byref(sampler._s), _ptr(sampler.cube), ctypes.byref(ph), int(bool(with_clip)), _ptr(out_n), _ptr(jac_n),
                                         s.n, s.c_ids, s.c_senses, len(s.ids), int(rnd), s.K, s.t0, s.dt, _ptr(s.xr), _ptr(s.yr),
                                         ctypes.byref(s.c_struct()), _ptr(x), _ptr(y), _ptr(t), _ptr(f), _ptr(cd), _stream()), 'dpn_extreme_refine')
+
+
+class SpellState:
+    """Device state of n points of a threshold-spells request between its launches (include/dpn_hip.h): for the C columns of `request` (a
+    spells.Request) prev_x [C, n] fp32; hours, excess, part_first, part_last, f_lo, f_hi, l_lo, l_hi [C, n] fp64; crossings, k_first, k_last, status
+    [C, n] int32 -- column-major, so a map [C, ny, nx] is a view of it --; `points` = x, y, t, f [n], coord_data [n, 6], the sampler at the current
+    scan node (node 0 to begin with), and `probes`, the same five with 2 * C * n rows: the entry and the exit probe of every column.  Nothing is
+    filled: node 0 sets what is read."""
+
+    KEYS = ('prev_x', 'hours', 'excess', 'crossings', 'k_first', 'k_last', 'status', 'part_first', 'part_last', 'f_lo', 'f_hi', 'l_lo', 'l_hi')
+    POINT_BYTES = 4 * (4 + 6 + 6) + 16                       # per point: the scan's buffers and xr, yr
+    COLUMN_BYTES = 4 + 8 * 8 + 4 * 4 + 2 * 4 * (4 + 6 + 6)    # per point and column: the state; the two probes' buffers and their out_n
+
+    def __init__(self, sampler, xr, yr, request):
+        dev, n = xr.device, xr.shape[0]
+        self.n, self.K, self.t0, self.dt = n, int(request.K), float(request.t0), float(request.dt)
+        self.ids, self.sides, self.thr = list(request.ids), list(request.sides), [float(v) for v in request.thr]
+        C = len(self.ids)
+        if not 1 <= C <= L.SPELL_MAX_COLUMNS or len(self.sides) != C or len(self.thr) != C or n < 1:
+            raise ValueError('SpellState: %d points, %d columns (1..%d)' % (n, C, L.SPELL_MAX_COLUMNS))
+        self.c_ids, self.c_sides, self.c_thr = (ctypes.c_int32 * C)(*self.ids), (ctypes.c_int32 * C)(*self.sides), (ctypes.c_float * C)(*self.thr)
+        self.xr, self.yr = xr.contiguous(), yr.contiguous()
+        i32 = ('crossings', 'k_first', 'k_last', 'status')
+        for key in self.KEYS:
+            dtype = torch.float32 if key == 'prev_x' else torch.int32 if key in i32 else torch.float64
+            setattr(self, key, torch.empty((C, n), dtype=dtype, device=dev))
+        self.points = sampler.sample_at(n, self.xr, self.yr, torch.full((n,), self.t0, dtype=torch.float64, device=dev))
+        m = 2 * C * n
+        self.probes = tuple(torch.empty(m, dtype=torch.float32, device=dev) for _ in range(4)) + (torch.empty((m, 6), dtype=torch.float32, device=dev),)
+
+    def c_struct(self):
+        return L.DpnSpellState(*[_ptr(getattr(self, key)) for key in self.KEYS])
+
+    def results(self):
+        """hours, first, last, first_lo, last_hi, excess, crossings, status [C, n]: the state's own arrays, complete after dpn_spell_finish."""
+        return {'hours': self.hours, 'first': self.f_hi, 'last': self.l_lo, 'first_lo': self.f_lo, 'last_hi': self.l_hi, 'excess': self.excess,
+                'crossings': self.crossings, 'status': self.status}
+
+
+def spell_scan(sampler, ph, with_clip, out_n, state, k):
+    """dpn_spell_scan on a SpellState with the fields-only forward's out_n [n, 6] at scan node k."""
+    s = state
+    x, y, t, f, cd = s.points
+    L.check(L.load().dpn_spell_scan(ctypes.byref(sampler._s), _ptr(sampler.cube), ctypes.byref(ph), int(bool(with_clip)), _ptr(out_n), s.n, s.c_ids,
+                                    s.c_sides, s.c_thr, len(s.ids), int(k), s.K, s.t0, s.dt, _ptr(s.xr), _ptr(s.yr), ctypes.byref(s.c_struct()),
+                                    _ptr(x), _ptr(y), _ptr(t), _ptr(f), _ptr(cd), _stream()), 'dpn_spell_scan')
+
+
+def spell_begin(sampler, state):
+    """dpn_spell_begin: closes the scan of a SpellState and writes its 2 * C * n probes."""
+    s = state
+    x, y, t, f, cd = s.probes
+    L.check(L.load().dpn_spell_begin(ctypes.byref(sampler._s), _ptr(sampler.cube), s.n, s.c_ids, s.c_sides, s.c_thr, len(s.ids), s.K, s.t0, s.dt,
+                                     _ptr(s.xr), _ptr(s.yr), ctypes.byref(s.c_struct()), _ptr(x), _ptr(y), _ptr(t), _ptr(f), _ptr(cd), _stream()),
+            'dpn_spell_begin')
+
+
+def spell_refine(sampler, ph, with_clip, out_n, state, rnd):
+    """dpn_spell_refine, round rnd, with the fields-only forward's out_n [2 * C * n, 6] at the probes of a SpellState."""
+    s = state
+    x, y, t, f, cd = s.probes
+    L.check(L.load().dpn_spell_refine(ctypes.byref(sampler._s), _ptr(sampler.cube), ctypes.byref(ph), int(bool(with_clip)), _ptr(out_n), s.n, s.c_ids,
+                                      s.c_sides, s.c_thr, len(s.ids), int(rnd), s.K, s.t0, s.dt, _ptr(s.xr), _ptr(s.yr),
+                                      ctypes.byref(s.c_struct()), _ptr(x), _ptr(y), _ptr(t), _ptr(f), _ptr(cd), _stream()), 'dpn_spell_refine')
+
+
+def spell_finish(state):
+    """dpn_spell_finish: once, after the last round (or after the scan when there is none)."""
+    s = state
+    L.check(L.load().dpn_spell_finish(s.n, len(s.ids), s.K, s.t0, s.dt, ctypes.byref(s.c_struct()), _stream()), 'dpn_spell_finish')

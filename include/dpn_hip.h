@@ -594,6 +594,81 @@ int dpn_extreme_refine(const DpnSampler* s, const float* cube, const DpnPhysics*
                        const int32_t* products /* HOST */, const int32_t* senses /* HOST */, int n_columns, int round, int K, double t0, double dt,
                        const double* xr, const double* yr, const DpnExtremeState* st, float* x, float* y, float* t, float* f, float* coord_data,
                        void* stream);
+/* Threshold spells in time (csrc/dpn_spell.inc, compiled into csrc/dpn_diag.hip): per point and column how long a product stays above (below) a
+ * threshold over the hours [t0, t0 + K * dt], the hour of the first entry and of the last exit, the number of crossings and the time integral of the
+ * margin.  The window extremes' scan of K + 1 nodes, then bisection on the sign of value - threshold inside the scan step of the first entry and the
+ * scan step of the last exit: one fields-only forward per round, two probes per point and column.
+ * A request is C = n_columns (1..DPN_SPELL_MAX_COLUMNS; repeats allowed) columns (products[c], sides[c], thr[c]), HOST arrays.  Products, their
+ * expressions, NaN rule and with_clip: dpn_extreme_scan's (25 speed, 28..33 u, v, p, T, q, rho).  sides[c]: DPN_SPELL_ABOVE or _BELOW; thr[c] finite.
+ * x is "in" when x > thr (above) or x < thr (below): strict, compared in float32, as the ensemble's thresholds are.  The margin of x is
+ * d(x) = (double)x - (double)thr for above and -((double)x - (double)thr) for below: d(x) > 0 exactly where x is in.
+ * Clock: node k (0..K) lies at hour(k) = t0 + (double)k * dt, the extremes' expression.  xr, yr [n] fp64: the points, as dpn_sample_at takes stations.
+ * State of a chunk of n points, column-major (a wave runs along the points; a map [C][ny][nx] is a view of it), every array [C][n]:
+ *   float prev_x; double hours, excess; int32 crossings, k_first, k_last, status (DPN_SPELL_* bits); double part_first, part_last, f_lo, f_hi, l_lo, l_hi.
+ *   k_first / k_last: the first / last scan node that is in, -1: none.  Nothing needs filling before node 0.
+ * Every operation below is one operation rounded on its own (the kernels are compiled without contraction), left to right.
+ * dpn_spell_scan: out_n [n][6] = the fields-only forward at node k.  Per column, x the product at the point:
+ *   k > 0 and status != 0:  nothing changes (sticky)
+ *   x not finite:           status = DPN_SPELL_BAD_SCAN, nothing else changes
+ *   k == 0:                 status = 0, hours = excess = part_first = part_last = 0, crossings = 0, k_first = k_last = (x in ? 0 : -1), prev_x = x
+ *   else, a = d(prev_x), b = d(x), then prev_x = x:
+ *     a > 0, b > 0 (both in):   hours = hours + dt;  excess = excess + 0.5 * (a + b) * dt;  k_last = k;  part_last = 0
+ *     a <= 0, b <= 0:           nothing
+ *     a <= 0 < b (entry):       w = b / (b - a) * dt;  hours = hours + w;  excess = excess + 0.5 * b * w;  crossings += 1;  k_last = k;  part_last = 0;
+ *                               if k_first < 0: k_first = k, part_first = w
+ *     b <= 0 < a (exit):        w = a / (a - b) * dt;  hours = hours + w;  excess = excess + 0.5 * a * w;  crossings += 1;  part_last = w  (k_last is k - 1)
+ *   and, unless k == K, x, y, t, f, coord_data [n] = the sampler at (xr, yr, hour(k + 1)), dpn_sample_at's arithmetic, for the next forward.
+ *   hours and excess are the time in and the integral of max(d, 0) of the piecewise-linear series through the nodes (the clipped trapezoid).
+ * dpn_spell_begin (after node K), per column:
+ *   DPN_SPELL_BAD_SCAN:  hours = excess = f_lo = f_hi = l_lo = l_hi = NaN
+ *   k_first < 0:         status |= DPN_SPELL_NEVER;  f_lo = f_hi = l_lo = l_hi = NaN
+ *   otherwise  k_first >= 1 (an entry bracket): f_lo = hour(k_first - 1), f_hi = hour(k_first);  k_first == 0: f_lo = f_hi = t0, status |= _HOLDS_AT_START
+ *              k_last < K (an exit bracket):    l_lo = hour(k_last), l_hi = hour(k_last + 1);    k_last == K:  l_lo = l_hi = hour(K), status |= _HOLDS_AT_END
+ *   Probe e (0 entry, 1 exit) of column c at point i is row (2 * c + e) * n + i of x, y, t, f, coord_data (2 * C * n rows) = the sampler at (xr, yr, m),
+ *   m = lo + 0.5 * (hi - lo) of its bracket; a probe without a bracket is written at t0 (a valid input; its forwards are ignored).
+ * dpn_spell_refine, round 0, 1, ..: out_n [2 * C * n][6] = the fields-only forward at the probes.  A probe is skipped when its column's status has
+ *   _BAD_SCAN, _STOPPED or _NEVER, or when it has no bracket: its inputs stay.  g = the product at the probe, m = lo + 0.5 * (hi - lo) of the state, the
+ *   expression the probe was written with.
+ *     g of either probe of the column (that has a bracket) not finite:  status |= DPN_SPELL_STOPPED; both brackets stand
+ *     entry probe:  g in -> f_hi = m, else f_lo = m;      exit probe:  g in -> l_lo = m, else l_hi = m
+ *     then the probe's x, y, t, f, coord_data = the sampler at (xr, yr, lo + 0.5 * (hi - lo)) of the new bracket
+ *   f_hi and l_lo are hours at which the network itself was evaluated and found in, f_lo and l_hi hours at which it was found out.
+ * dpn_spell_finish (once, after the last round), per column: DPN_SPELL_BAD_SCAN: nothing;  DPN_SPELL_NEVER: hours = excess = 0;  otherwise
+ *     with an entry bracket:  hours = hours - part_first;  hours = hours + (hour(k_first) - f_hi)
+ *     with an exit bracket:   hours = hours - part_last;   hours = hours + (l_lo - hour(k_last))
+ *   the scan's interpolated ends of the spell replaced by the refined ones.  excess stays the scan's clipped trapezoid, as the extremes' mean does.
+ * Results: hours, first = f_hi, last = l_lo (first_lo = f_lo, last_hi = l_hi: the other ends of the brackets), excess, crossings, status.
+ * 256-thread blocks, one thread per (column, point) -- refine: per probe --, no atomics, no LDS, plain per-thread vector stores.
+ * -1 (nothing launched, nothing written): a NULL pointer (the state's thirteen included); n <= 0; K < 1; k outside 0..K; round < 0; t0 or dt not finite;
+ * dt <= 0; n_columns outside 1..DPN_SPELL_MAX_COLUMNS; an id other than 25, 28..33; a side outside 0..1; a threshold that is not finite; a sampler
+ * cube dimension < 2. */
+#define DPN_SPELL_MAX_COLUMNS 16
+#define DPN_SPELL_ABOVE 0
+#define DPN_SPELL_BELOW 1
+#define DPN_SPELL_BAD_SCAN        1   /* a scan node's value was not finite: everything is NaN                */
+#define DPN_SPELL_STOPPED         2   /* a probe's value was not finite: the brackets stand as they were      */
+#define DPN_SPELL_NEVER           4   /* no scan node is in: hours = excess = 0, first = last = NaN           */
+#define DPN_SPELL_HOLDS_AT_START  8   /* node 0 is in: first = t0                                             */
+#define DPN_SPELL_HOLDS_AT_END   16   /* node K is in: last = t0 + K * dt                                     */
+typedef struct DpnSpellState {
+    float* prev_x;
+    double *hours, *excess;
+    int32_t *crossings, *k_first, *k_last, *status;
+    double *part_first, *part_last;
+    double *f_lo, *f_hi, *l_lo, *l_hi;
+} DpnSpellState;
+int dpn_spell_scan(const DpnSampler* s, const float* cube, const DpnPhysics* phys, int with_clip, const float* out_n, int64_t n,
+                   const int32_t* products /* HOST */, const int32_t* sides /* HOST */, const float* thr /* HOST */, int n_columns, int k, int K, double t0,
+                   double dt, const double* xr, const double* yr, const DpnSpellState* st, float* x, float* y, float* t, float* f, float* coord_data,
+                   void* stream);
+int dpn_spell_begin(const DpnSampler* s, const float* cube, int64_t n, const int32_t* products /* HOST */, const int32_t* sides /* HOST */,
+                    const float* thr /* HOST */, int n_columns, int K, double t0, double dt, const double* xr, const double* yr, const DpnSpellState* st,
+                    float* x, float* y, float* t, float* f, float* coord_data, void* stream);
+int dpn_spell_refine(const DpnSampler* s, const float* cube, const DpnPhysics* phys, int with_clip, const float* out_n, int64_t n,
+                     const int32_t* products /* HOST */, const int32_t* sides /* HOST */, const float* thr /* HOST */, int n_columns, int round, int K,
+                     double t0, double dt, const double* xr, const double* yr, const DpnSpellState* st, float* x, float* y, float* t, float* f,
+                     float* coord_data, void* stream);
+int dpn_spell_finish(int64_t n, int n_columns, int K, double t0, double dt, const DpnSpellState* st, void* stream);
 
 /* ---------------------------------------------------------------- parcel trajectories through the learned wind (csrc/dpn_traj.hip)
  * One launch = one stage of an explicit Runge-Kutta step for n parcels whose stage positions depend only on the step's start point and the

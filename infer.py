@@ -5,6 +5,7 @@
                     [--trajectories LON,LAT[;LON,LAT...] --traj_start H --traj_hours D --traj_step S [--traj_method rk4]]
                     [--ensemble name[,name...] [--ensemble_threshold NAME:V[,V...]]...]
                     [--extremes T:max,T:min,speed:max --extreme_window H0,H1 [--extreme_scan S] [--extreme_refine R]]
+                    [--spells T:below:273.15,speed:above:15 --spell_window H0,H1 [--spell_scan S] [--spell_refine R]]
 
 Builds the interface from the config (train.py's loader), loads `physics_latest.pth` from --checkpoint_path (or inference_cfg.checkpoints) and
 calls `run_inference_interface`: every field sample is evaluated on the lattice inference_cfg.img_size (x `refine`) at every inference_cfg.dt
@@ -21,7 +22,11 @@ ensemble (InterfacePhysics.ensemble_lattice) and the mean, spread, min, max and 
 and the probability of exceeding each threshold are written as <time>_ens_*.npy.
 --extremes T:max,T:min,speed:max --extreme_window 0,24 sets inference_cfg.extremes: per sample the maximum / minimum of the named products over those
 hours of its window and the hour they occur at (or, PRODUCT:mean, the window mean), found by a scan every --extreme_scan hours and --extreme_refine
-rounds of bisection on the network's own d/dt (InterfacePhysics.extreme_lattice), written as <time>_extreme_<value|hour|lo|hi|status>_*.npy maps."""
+rounds of bisection on the network's own d/dt (InterfacePhysics.extreme_lattice), written as <time>_extreme_<value|hour|lo|hi|status>_*.npy maps.
+--spells T:below:273.15,speed:above:15 --spell_window 0,24 sets inference_cfg.spells: per sample how long the named products stay strictly below / above
+the thresholds over those hours of its window, the hour of the first entry and of the last exit, the crossings and the degree-hours, found by a scan
+every --spell_scan hours and --spell_refine rounds of bisection on the sign of value - threshold (InterfacePhysics.spell_lattice), written as
+<time>_spell_<hours|first|last|first_lo|last_hi|excess|crossings|status>_*.npy maps."""
 import argparse
 
 import torch
@@ -53,6 +58,12 @@ parse.add_argument('--extreme_window', default=None, type=lambda s: tuple(float(
                    help='H0,H1: the hours of the sample window the extremes are taken over')
 parse.add_argument('--extreme_scan', default=1.0, type=float, help='hours between the scan nodes')
 parse.add_argument('--extreme_refine', default=10, type=int, help='bisection rounds after the scan (0..32)')
+parse.add_argument('--spells', default=None, type=lambda s: [n for n in s.split(',') if n],
+                   help='PRODUCT:SIDE:THRESHOLD[,...]: inference_cfg.spells.columns, e.g. T:below:273.15,speed:above:15 (deepphysinet_amd.spells)')
+parse.add_argument('--spell_window', default=None, type=lambda s: tuple(float(v) for v in s.split(',')),
+                   help='H0,H1: the hours of the sample window the spells are looked for in')
+parse.add_argument('--spell_scan', default=1.0, type=float, help='hours between the scan nodes')
+parse.add_argument('--spell_refine', default=10, type=int, help='bisection rounds after the scan (0..32)')
 
 
 def extremes_option(args):
@@ -65,6 +76,17 @@ def extremes_option(args):
     if args.extreme_window is None or len(args.extreme_window) != 2:
         parse.error('--extremes needs --extreme_window H0,H1')
     return dict(columns=list(args.extremes), window=tuple(args.extreme_window), scan_hours=args.extreme_scan, refine=args.extreme_refine)
+
+
+def spells_option(args):
+    """inference_cfg['spells'] of --spells / --spell_window: dict(columns=[...], window=(H0, H1), scan_hours=S, refine=R), or None without --spells."""
+    if not args.spells:
+        if args.spell_window is not None:
+            parse.error('--spell_window needs --spells')
+        return None
+    if args.spell_window is None or len(args.spell_window) != 2:
+        parse.error('--spells needs --spell_window H0,H1')
+    return dict(columns=list(args.spells), window=tuple(args.spell_window), scan_hours=args.spell_scan, refine=args.spell_refine)
 
 
 def ensemble_option(args):
@@ -99,6 +121,8 @@ if __name__ == '__main__':
         cfg.setdefault('inference_cfg', {})['ensemble'] = ensemble_option(args)
     if extremes_option(args):
         cfg.setdefault('inference_cfg', {})['extremes'] = extremes_option(args)
+    if spells_option(args):
+        cfg.setdefault('inference_cfg', {})['spells'] = spells_option(args)
     model = builder_models(**cfg)
     kwargs = dict(checkpoint_path=args.checkpoint_path)
     if args.synthetic:
@@ -123,3 +147,6 @@ if __name__ == '__main__':
     if model.last_extremes is not None:
         x = model.last_extremes
         print('extremes %s: value %s, status %s' % (','.join(x['names']), tuple(x['value'].shape), sorted(set(x['status'].reshape(-1).tolist()))))
+    if model.last_spells is not None:
+        x = model.last_spells
+        print('spells %s: hours %s, status %s' % (','.join(x['names']), tuple(x['hours'].shape), sorted(set(x['status'].reshape(-1).tolist()))))
