@@ -133,27 +133,46 @@ __global__ __launch_bounds__(THREADS) void dpn_extreme_refine_kernel(ExtArgs a) 
     sample_point(a.s, a.cube, a.xr[i], a.yr[i], lo + 0.5 * (hi - lo), p, a.x, a.y, a.t, a.f, a.coord_data);
 }
 
+// the clock of a time-window request (extremes here, spells in dpn_spell.inc): n points, 1..max_columns columns, K >= 1 steps of dt > 0 from t0
+bool window_clock_ok(int64_t n, int n_columns, int max_columns, int K, double t0, double dt) {
+    if (n <= 0 || K < 1 || n_columns < 1 || n_columns > max_columns) return false;
+    return t0 - t0 == 0.0 && dt - dt == 0.0 && dt > 0.0;      // (a NaN or an infinity fails the first two)
+}
+
+// the checks the scan, begin and refine entry points of both time-window products share -- the pointers, the clock, the sampler's dimensions, the
+// product ids (25 or 28..33) --, and what they all fill of `a` (an ExtArgs or a SpellArgs).  false: refuse.
+template <class Args>
+bool window_request(Args& a, int max_columns, const DpnSampler* s, const float* cube, const DpnPhysics* phys, int with_clip, int64_t n,
+                    const int32_t* products, int n_columns, int K, double t0, double dt, const double* xr, const double* yr, float* x, float* y,
+                    float* t, float* f, float* coord_data) {
+    if (!s || !cube || !phys || !products || !xr || !yr || !x || !y || !t || !f || !coord_data) return false;
+    if (!window_clock_ok(n, n_columns, max_columns, K, t0, dt)) return false;
+    if (s->lon_in < 2 || s->lat_in < 2 || s->t_in < 2) return false;
+    a.s = *s; a.cube = cube; a.ph = *phys; a.n = n; a.n_columns = n_columns; a.K = K; a.t0 = t0; a.dt = dt; a.xr = xr; a.yr = yr;
+    a.x = x; a.y = y; a.t = t; a.f = f; a.coord_data = coord_data;
+    for (int c = 0; c < n_columns; ++c) {
+        if (!(products[c] == 25 || (products[c] >= 28 && products[c] <= 33))) return false;
+        a.id[c] = products[c];
+    }
+    if (!with_clip)
+        for (int k = 0; k < 6; ++k) a.ph.clip_on[k] = 0;      // the body then neither clips nor masks
+    return true;
+}
+
 // the checks the three entry points share; fills the column tables of `a`.  false: refuse.
 bool ext_request(ExtArgs& a, const DpnSampler* s, const float* cube, const DpnPhysics* phys, int with_clip, int64_t n, const int32_t* products,
                  const int32_t* senses, int n_columns, int K, double t0, double dt, const double* xr, const double* yr, const DpnExtremeState* st,
-                 const float* x, const float* y, const float* t, const float* f, const float* coord_data) {
-    if (!s || !cube || !phys || !products || !senses || !xr || !yr || !st || !x || !y || !t || !f || !coord_data) return false;
-    if (!st->best_v || !st->best_t || !st->best_k || !st->acc || !st->status || !st->lo || !st->hi) return false;
-    if (n <= 0 || K < 1 || n_columns < 1 || n_columns > DPN_EXT_MAX_COLUMNS) return false;
-    if (s->lon_in < 2 || s->lat_in < 2 || s->t_in < 2) return false;
-    if (!(t0 - t0 == 0.0) || !(dt - dt == 0.0) || !(dt > 0.0)) return false;                 // (a NaN or an infinity fails the first two)
-    a.s = *s; a.cube = cube; a.ph = *phys; a.n = n; a.n_columns = n_columns; a.K = K; a.t0 = t0; a.dt = dt; a.xr = xr; a.yr = yr; a.st = *st;
+                 float* x, float* y, float* t, float* f, float* coord_data) {
+    if (!senses || !st || !st->best_v || !st->best_t || !st->best_k || !st->acc || !st->status || !st->lo || !st->hi) return false;
+    if (!window_request(a, DPN_EXT_MAX_COLUMNS, s, cube, phys, with_clip, n, products, n_columns, K, t0, dt, xr, yr, x, y, t, f, coord_data)) return false;
+    a.st = *st;
     a.n_refined = 0;
     for (int c = 0; c < n_columns; ++c) {
-        if (!(products[c] == 25 || (products[c] >= 28 && products[c] <= 33))) return false;
         if (senses[c] != DPN_EXT_MAX && senses[c] != DPN_EXT_MIN && senses[c] != DPN_EXT_MEAN) return false;
-        a.id[c] = products[c];
         a.sense[c] = senses[c];
         a.refined_of[c] = -1;
         if (senses[c] != DPN_EXT_MEAN) { a.refined_of[c] = a.n_refined; a.column_of[a.n_refined++] = c; }
     }
-    if (!with_clip)
-        for (int k = 0; k < 6; ++k) a.ph.clip_on[k] = 0;                  // the body then neither clips nor masks
     return true;
 }
 
@@ -169,7 +188,7 @@ int dpn_extreme_scan(const DpnSampler* s, const float* cube, const DpnPhysics* p
     ExtArgs a{};
     if (!out_n || !ext_request(a, s, cube, phys, with_clip, n, products, senses, n_columns, K, t0, dt, xr, yr, st, x, y, t, f, coord_data)) return -1;
     if (k < 0 || k > K) return -1;
-    a.out_n = out_n; a.k = k; a.x = x; a.y = y; a.t = t; a.f = f; a.coord_data = coord_data;
+    a.out_n = out_n; a.k = k;
     hipLaunchKernelGGL(dpn_extreme_scan_kernel, ext_grid(n * n_columns), dim3(THREADS), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -180,7 +199,6 @@ int dpn_extreme_begin(const DpnSampler* s, const float* cube, int64_t n, const i
     ExtArgs a{};
     const DpnPhysics none{};
     if (!ext_request(a, s, cube, &none, 0, n, products, senses, n_columns, K, t0, dt, xr, yr, st, x, y, t, f, coord_data)) return -1;
-    a.x = x; a.y = y; a.t = t; a.f = f; a.coord_data = coord_data;
     hipLaunchKernelGGL(dpn_extreme_begin_kernel, ext_grid(n * n_columns), dim3(THREADS), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -192,7 +210,7 @@ int dpn_extreme_refine(const DpnSampler* s, const float* cube, const DpnPhysics*
     if (!out_n || !jac_n || !ext_request(a, s, cube, phys, with_clip, n, products, senses, n_columns, K, t0, dt, xr, yr, st, x, y, t, f, coord_data))
         return -1;
     if (round < 0 || a.n_refined < 1) return -1;
-    a.out_n = out_n; a.jac_n = jac_n; a.round = round; a.x = x; a.y = y; a.t = t; a.f = f; a.coord_data = coord_data;
+    a.out_n = out_n; a.jac_n = jac_n; a.round = round;
     hipLaunchKernelGGL(dpn_extreme_refine_kernel, ext_grid(n * a.n_refined), dim3(THREADS), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

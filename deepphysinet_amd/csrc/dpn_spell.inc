@@ -182,30 +182,19 @@ bool spell_state_ok(const DpnSpellState* st) {
            st->f_lo && st->f_hi && st->l_lo && st->l_hi;
 }
 
-bool spell_clock_ok(int64_t n, int n_columns, int K, double t0, double dt) {
-    if (n <= 0 || K < 1 || n_columns < 1 || n_columns > DPN_SPELL_MAX_COLUMNS) return false;
-    return t0 - t0 == 0.0 && dt - dt == 0.0 && dt > 0.0;      // (a NaN or an infinity fails the first two)
-}
-
-// the checks scan, begin and refine share; fills the column tables of `a`.  false: refuse.
+// the checks scan, begin and refine share (window_request: dpn_extreme.inc); fills the column tables of `a`.  false: refuse.
 bool spell_request(SpellArgs& a, const DpnSampler* s, const float* cube, const DpnPhysics* phys, int with_clip, int64_t n, const int32_t* products,
                    const int32_t* sides, const float* thr, int n_columns, int K, double t0, double dt, const double* xr, const double* yr,
                    const DpnSpellState* st, float* x, float* y, float* t, float* f, float* coord_data) {
-    if (!s || !cube || !phys || !products || !sides || !thr || !xr || !yr || !x || !y || !t || !f || !coord_data) return false;
-    if (!spell_state_ok(st) || !spell_clock_ok(n, n_columns, K, t0, dt)) return false;
-    if (s->lon_in < 2 || s->lat_in < 2 || s->t_in < 2) return false;
-    a.s = *s; a.cube = cube; a.ph = *phys; a.n = n; a.n_columns = n_columns; a.K = K; a.t0 = t0; a.dt = dt; a.xr = xr; a.yr = yr; a.st = *st;
-    a.x = x; a.y = y; a.t = t; a.f = f; a.coord_data = coord_data;
+    if (!sides || !thr || !spell_state_ok(st)) return false;
+    if (!window_request(a, DPN_SPELL_MAX_COLUMNS, s, cube, phys, with_clip, n, products, n_columns, K, t0, dt, xr, yr, x, y, t, f, coord_data)) return false;
+    a.st = *st;
     for (int c = 0; c < n_columns; ++c) {
-        if (!(products[c] == 25 || (products[c] >= 28 && products[c] <= 33))) return false;
         if (sides[c] != DPN_SPELL_ABOVE && sides[c] != DPN_SPELL_BELOW) return false;
         if (!(thr[c] - thr[c] == 0.f)) return false;
-        a.id[c] = products[c];
         a.side[c] = sides[c];
         a.thr[c] = thr[c];
     }
-    if (!with_clip)
-        for (int k = 0; k < 6; ++k) a.ph.clip_on[k] = 0;      // the body then neither clips nor masks
     return true;
 }
 
@@ -247,7 +236,7 @@ int dpn_spell_refine(const DpnSampler* s, const float* cube, const DpnPhysics* p
 
 int dpn_spell_finish(int64_t n, int n_columns, int K, double t0, double dt, const DpnSpellState* st, void* stream) {
     SpellArgs a{};
-    if (!spell_state_ok(st) || !spell_clock_ok(n, n_columns, K, t0, dt)) return -1;
+    if (!spell_state_ok(st) || !window_clock_ok(n, n_columns, DPN_SPELL_MAX_COLUMNS, K, t0, dt)) return -1;
     a.n = n; a.n_columns = n_columns; a.K = K; a.t0 = t0; a.dt = dt; a.st = *st;
     hipLaunchKernelGGL(dpn_spell_finish_kernel, ext_grid(n * n_columns), dim3(THREADS), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;

@@ -63,6 +63,30 @@ def node_hour(t0, dt, k):
     return np.float64(t0) + np.asarray(k, dtype=np.float64) * np.float64(dt)
 
 
+def check_clock(word, window, scan_hours=1.0, refine=10, hours_top=24):
+    """The window, scan-step and round rules of a time-window request, as check_request states them, for extremes and spells alike: -> (t0, dt, K,
+    R).  Every refusal is a ValueError whose text begins with `word` ('extremes', 'spells')."""
+    try:
+        t0, t1 = (float(v) for v in window)
+    except (TypeError, ValueError):
+        raise ValueError('%s: window = (first hour, last hour), got %r' % (word, window))
+    top = float(hours_top)
+    if not (np.isfinite(t0) and np.isfinite(t1) and 0.0 <= t0 < t1 <= top):
+        raise ValueError('%s: window %r must satisfy 0 <= t0 < t1 <= %g hours (one field sample\'s window)' % (word, window, top))
+    step = float(scan_hours)
+    if not (np.isfinite(step) and step >= MIN_SCAN_HOURS):
+        raise ValueError('%s: scan_hours must be finite and at least 2**-10 hours, got %r' % (word, scan_hours))
+    K = int(round((t1 - t0) / step))
+    if not 1 <= K <= MAX_SCAN_STEPS:
+        raise ValueError('%s: window %r in scan steps of %r hours is %d steps; 1..%d' % (word, window, scan_hours, K, MAX_SCAN_STEPS))
+    dt = step if node_hour(t0, step, K) == t1 else (t1 - t0) / K
+    while node_hour(t0, dt, K) > t1:
+        dt = float(np.nextafter(dt, 0.0))
+    if isinstance(refine, bool) or int(refine) != refine or not 0 <= int(refine) <= MAX_REFINE:
+        raise ValueError('%s: refine must be a whole number of rounds in 0..%d, got %r' % (word, MAX_REFINE, refine))
+    return t0, float(dt), K, int(refine)
+
+
 def check_request(columns, window, scan_hours=1.0, refine=10, hours_top=24):
     """The host checks of a request, once, before anything is launched: -> Request(names, ids, senses, t0, dt, K, R).  window = (t0, t1) hours inside
     [0, hours_top] (one field sample's window, input_time_step * input_time_step_nums), t1 > t0; K = round((t1 - t0) / scan_hours) >= 1 scan steps,
@@ -70,25 +94,7 @@ def check_request(columns, window, scan_hours=1.0, refine=10, hours_top=24):
     pass t1 (a node beyond the window's end would leave the coarse cube); R = refine in 0..MAX_REFINE, whole.  KeyError: an unknown column name
     (parse_columns); ValueError: everything else."""
     names, ids, senses = parse_columns(columns)
-    try:
-        t0, t1 = (float(v) for v in window)
-    except (TypeError, ValueError):
-        raise ValueError('extremes: window = (first hour, last hour), got %r' % (window,))
-    top = float(hours_top)
-    if not (np.isfinite(t0) and np.isfinite(t1) and 0.0 <= t0 < t1 <= top):
-        raise ValueError('extremes: window %r must satisfy 0 <= t0 < t1 <= %g hours (one field sample\'s window)' % (window, top))
-    step = float(scan_hours)
-    if not (np.isfinite(step) and step >= MIN_SCAN_HOURS):
-        raise ValueError('extremes: scan_hours must be finite and at least 2**-10 hours, got %r' % (scan_hours,))
-    K = int(round((t1 - t0) / step))
-    if not 1 <= K <= MAX_SCAN_STEPS:
-        raise ValueError('extremes: window %r in scan steps of %r hours is %d steps; 1..%d' % (window, scan_hours, K, MAX_SCAN_STEPS))
-    dt = step if node_hour(t0, step, K) == t1 else (t1 - t0) / K
-    while node_hour(t0, dt, K) > t1:
-        dt = float(np.nextafter(dt, 0.0))
-    if isinstance(refine, bool) or int(refine) != refine or not 0 <= int(refine) <= MAX_REFINE:
-        raise ValueError('extremes: refine must be a whole number of rounds in 0..%d, got %r' % (MAX_REFINE, refine))
-    return Request(names, ids, senses, t0, float(dt), K, int(refine))
+    return Request(names, ids, senses, *check_clock('extremes', window, scan_hours, refine, hours_top))
 
 
 def new_state(n_columns, n, dtype=np.float32, fill=0):

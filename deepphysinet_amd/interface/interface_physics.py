@@ -28,8 +28,8 @@ from ..guard import StepGuard
 from ..lbfgs import FusedLBFGS
 from ..optim import GROUP_KEYS, FusedClipAdam, resolve_param_groups
 from ..point_path import (balance_sumsq, balance_update, balanced_total, data_losses_batch, eval_step, eval_step_batch, grid_maps, label_errors, ParcelState,
-                          EnsembleState, ExtremeState, LOSS_ORDER, OBS_ORDER, PackedField, SpellState, pde_losses, pde_losses_batch, point_fields, point_sizes, PointConfig, require_gpu,
-                          smooth_l1_data_loss, spell_finish, step_losses, step_losses_batch)
+                          EnsembleState, ExtremeState, LOSS_ORDER, OBS_ORDER, PackedField, SpellState, pde_losses, pde_losses_batch, point_buffers, point_fields, point_sizes,
+                          PointConfig, require_gpu, smooth_l1_data_loss, step_losses, step_losses_batch)
 from ..sampler import SyntheticSamples
 from ..staged_backward import StagedBackward
 from ..utils.position_encoding import SineCosPE
@@ -54,6 +54,12 @@ def _loop_option(kwargs, train_cfg, name, section, known, true_is_empty, instanc
 
 def _to_device(batch, device):
     return {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in batch.items()}
+
+
+def _chunks(total, chunk):
+    """(first, n) of the chunks of `total` points, `chunk` at a time, the last one shorter."""
+    for first in range(0, total, chunk):
+        yield first, min(chunk, total - first)
 
 
 class InterfacePhysics(nn.Module):
@@ -359,11 +365,8 @@ class InterfacePhysics(nn.Module):
 
     def _lattice_chunks(self, sampler, lattice, chunk):
         """(first, n, x, y, t, f, coord_data) for the chunks of a lattice; the five buffers are allocated once and reused."""
-        dev = sampler.cube.device
-        bufs = tuple(torch.empty(chunk, dtype=torch.float32, device=dev) for _ in range(4)) + (torch.empty((chunk, 6), dtype=torch.float32, device=dev),)
-        total = lattice.n_points
-        for first in range(0, total, chunk):
-            n = min(chunk, total - first)
+        bufs = point_buffers(chunk, sampler.cube.device)
+        for first, n in _chunks(lattice.n_points, chunk):
             yield (first, n) + sampler.sample_at(n, lattice=lattice, first=first, out=bufs)
 
     @torch.no_grad()
@@ -486,17 +489,15 @@ class InterfacePhysics(nn.Module):
         N, dev = xr.shape[0], s0.cube.device
         chunk = self.chunk_size(N, None, self.ENS_POINT_BYTES, self.precision)
         state = new_state(N)
-        bufs = tuple(torch.empty(chunk, dtype=torch.float32, device=dev) for _ in range(4)) + (torch.empty((chunk, 6), dtype=torch.float32, device=dev),)
+        bufs = point_buffers(chunk, dev)
         for mem in members:
             field = self._inference_weights(mem['field_data'].to(dev), mem['forecast_h'].to(dev), chunk)
-            for first in range(0, N, chunk):
-                n = min(chunk, N - first)
+            for first, n in _chunks(N, chunk):
                 x, y, t, f, cd = mem['sampler'].sample_at(n, xr[first:first + n], yr[first:first + n], tr[first:first + n], out=bufs)
                 field.ensemble_accumulate(x, y, t, f, cd, state, first, with_clip)
             del field                                                     # before the next member packs its own
         out = self._ensemble_outputs(lambda c: (N, c), len(names), len(thr), dev)
-        for first in range(0, N, chunk):
-            n = min(chunk, N - first)
+        for first, n in _chunks(N, chunk):
             state.finish(first, n, rows={k: None if v is None else v[first:first + n] for k, v in out.items()})
         return dict(out, names=names, thresholds=thr)
 
@@ -515,8 +516,8 @@ class InterfacePhysics(nn.Module):
                 field.ensemble_accumulate(x, y, t, f, cd, state, first, with_clip)
             del field                                                     # before the next member packs its own
         out = self._ensemble_outputs(lambda c: (lattice.nt, c, lattice.ny, lattice.nx), len(names), len(thr), dev)
-        for first in range(0, total, chunk):
-            state.finish(first, min(chunk, total - first), maps=out, lattice=lattice)
+        for first, n in _chunks(total, chunk):
+            state.finish(first, n, maps=out, lattice=lattice)
         return dict(out, names=names, thresholds=thr)
 
     @torch.no_grad()
@@ -548,8 +549,7 @@ class InterfacePhysics(nn.Module):
         for _ in range(K):
             hrs.append(hrs[-1] + h)                    # the running sum: hour k is bit for bit the hour the k-th path point's forward was sampled at
         xd, yd = torch.from_numpy(xs).to(dev), torch.from_numpy(ys).to(dev)
-        for first in range(0, N, chunk):
-            n = min(chunk, N - first)
+        for first, n in _chunks(N, chunk):
             parcels = ParcelState(sampler, xd[first:first + n].contiguous(), yd[first:first + n].contiguous(), t0, K + 1)
             rows = torch.empty((K + 1, n, 6), dtype=torch.float32, device=dev) if with_fields else None
             for k in range(K):
@@ -568,24 +568,45 @@ class InterfacePhysics(nn.Module):
             out['fields'] = fields
         return out
 
-    # ------------------------------------------------------------------ window extremes and means in time
-    def _extremes_run(self, field_data, sampler, xd, yd, req, forecast_h, with_clip, chunk_points):
-        """The walk of extremes_at / extreme_lattice over N points xd, yd (fp64 on the device, checked): the state of all points as [C, N] tensors."""
-        N, dev, C = xd.shape[0], field_data.device, len(req.ids)
-        Cr = len(X.refined_columns(req.senses))
-        chunk = self.chunk_size(N, chunk_points, ExtremeState.POINT_BYTES + C * ExtremeState.COLUMN_BYTES + Cr * ExtremeState.PROBE_BYTES, self.precision)
-        field = self._inference_weights(field_data, forecast_h, chunk * max(Cr, 1))
-        out = {'value': torch.empty((C, N), dtype=torch.float32, device=dev), 'status': torch.empty((C, N), dtype=torch.int32, device=dev)}
-        out.update({k: torch.empty((C, N), dtype=torch.float64, device=dev) for k in ('hour', 'lo', 'hi')})
-        for first in range(0, N, chunk):
-            n = min(chunk, N - first)
-            state = ExtremeState(sampler, xd[first:first + n], yd[first:first + n], req)
+    # ------------------------------------------------------------------ time-window products: window extremes and means, threshold spells
+    def _window_request(self, check_request, word, field_data, sampler, columns, window, scan_hours, refine):
+        """The request of a time-window product, checked against the sample's own window of hours before anything is launched."""
+        require_gpu(field_data, 'field_data', word)
+        c = sampler.cfg
+        return check_request(columns, window, scan_hours, refine, c.input_time_step * c.input_time_step_nums)
+
+    @staticmethod
+    def _window_stations(sampler, x_idx, y_idx, lonlat, t0):
+        """Stations as predict_points takes them -> checked fp64 xr, yr on the device (t0: the hour they are first sampled at)."""
+        x_idx, y_idx = (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64) for v in (x_idx, y_idx))
+        if lonlat:
+            x_idx, y_idx = sampler.lonlat_to_index(x_idx, y_idx)
+        return sampler.check_positions(x_idx, y_idx, np.full(np.shape(np.atleast_1d(x_idx)), t0))[:2]
+
+    @staticmethod
+    def _window_lattice(lattice, device):
+        """The positions of a lattice with nt == 1 -> fp64 xd, yd on the device, in point order."""
+        xs, ys, _ = lattice.positions()
+        return tuple(torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(device) for v in (xs, ys))
+
+    def _window_run(self, State, field_data, sampler, xd, yd, req, forecast_h, with_clip, chunk_points):
+        """The walk of a time-window product over N points xd, yd (fp64 on the device, checked), State its state class (ExtremeState, SpellState):
+        per chunk the K + 1 scan nodes, the state's rounds and its finish; the results of all points as [C, N] tensors."""
+        N = xd.shape[0]
+        chunk = self.chunk_size(N, chunk_points, State.point_bytes(req), self.precision)
+        field = self._inference_weights(field_data, forecast_h, chunk * max(State.probe_rows(req), 1))
+        out = None
+        for first, n in _chunks(N, chunk):
+            state = State(sampler, xd[first:first + n], yd[first:first + n], req)
             for k in range(req.K + 1):
-                field.extreme_scan(sampler, state, k, with_clip)
-            if Cr:
-                for rnd in range(req.R + 1):
-                    field.extreme_refine(sampler, state, rnd, with_clip)
-            for key, v in state.results().items():
+                field.window_scan(sampler, state, k, with_clip)
+            for rnd in range(State.rounds(req)):
+                field.window_refine(sampler, state, rnd, with_clip)
+            state.finish()
+            results = state.results()
+            if out is None:                            # the outputs take their types from the state's own arrays
+                out = {key: torch.empty((v.shape[0], N), dtype=v.dtype, device=v.device) for key, v in results.items()}
+            for key, v in results.items():
                 out[key][:, first:first + n] = v
         return out
 
@@ -603,50 +624,21 @@ class InterfacePhysics(nn.Module):
         (the final bracket), 'status' [N, C] int32: 0 an interior extreme (or a mean), 1 a scan value was not finite (everything NaN), 2 a probe was
         not finite (the best so far stands), 3 / 4 the extreme sits at the window's start / end with the slope pointing outward}, on the device.  The
         result is never worse than the best scan node, and a (value, hour) pair always comes from one evaluation."""
-        require_gpu(field_data, 'field_data', 'extremes')
-        c = sampler.cfg
-        req = X.check_request(columns, window, scan_hours, refine, c.input_time_step * c.input_time_step_nums)
-        x_idx, y_idx = (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64) for v in (x_idx, y_idx))
-        if lonlat:
-            x_idx, y_idx = sampler.lonlat_to_index(x_idx, y_idx)
-        xr, yr, _ = sampler.check_positions(x_idx, y_idx, np.full(np.shape(np.atleast_1d(x_idx)), req.t0))
-        out = self._extremes_run(field_data, sampler, xr, yr, req, forecast_h, with_clip, chunk_points)
+        req = self._window_request(X.check_request, 'extremes', field_data, sampler, columns, window, scan_hours, refine)
+        xr, yr = self._window_stations(sampler, x_idx, y_idx, lonlat, req.t0)
+        out = self._window_run(ExtremeState, field_data, sampler, xr, yr, req, forecast_h, with_clip, chunk_points)
         return dict({k: v.t().contiguous() for k, v in out.items()}, names=req.names)
 
     @torch.no_grad()
     def extreme_lattice(self, field_data, sampler, lattice, window, forecast_h, columns, scan_hours=1.0, refine=10, with_clip=False, chunk_points=None):
         """extremes_at on the positions of a lattice with nt == 1 (ValueError otherwise: `window` gives the times), as maps [C, ny, nx]: 'value',
         'hour', 'lo', 'hi', 'status'.  Points outside the coarse cube have status 1 and NaN everywhere."""
-        require_gpu(field_data, 'field_data', 'extremes')
-        c = sampler.cfg
-        req = X.check_request(columns, window, scan_hours, refine, c.input_time_step * c.input_time_step_nums)
+        req = self._window_request(X.check_request, 'extremes', field_data, sampler, columns, window, scan_hours, refine)
         if lattice.nt != 1:
             raise ValueError('extreme_lattice: the lattice gives the positions (nt == 1, got %d); `window` gives the times' % lattice.nt)
-        xs, ys, _ = lattice.positions()
-        xd, yd = (torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(field_data.device) for v in (xs, ys))
-        out = self._extremes_run(field_data, sampler, xd, yd, req, forecast_h, with_clip, chunk_points)
+        xd, yd = self._window_lattice(lattice, field_data.device)
+        out = self._window_run(ExtremeState, field_data, sampler, xd, yd, req, forecast_h, with_clip, chunk_points)
         return dict({k: v.view(len(req.ids), lattice.ny, lattice.nx) for k, v in out.items()}, names=req.names)
-
-    # ------------------------------------------------------------------ threshold spells in time
-    def _spells_run(self, field_data, sampler, xd, yd, req, forecast_h, with_clip, chunk_points):
-        """The walk of spells_at / spell_lattice over N points xd, yd (fp64 on the device, checked): the results of all points as [C, N] tensors."""
-        N, dev, C = xd.shape[0], field_data.device, len(req.ids)
-        chunk = self.chunk_size(N, chunk_points, SpellState.POINT_BYTES + C * SpellState.COLUMN_BYTES, self.precision)
-        field = self._inference_weights(field_data, forecast_h, chunk * 2 * C)
-        out = {k: torch.empty((C, N), dtype=torch.float64, device=dev) for k in ('hours', 'first', 'last', 'first_lo', 'last_hi', 'excess')}
-        out.update({k: torch.empty((C, N), dtype=torch.int32, device=dev) for k in ('crossings', 'status')})
-        for first in range(0, N, chunk):
-            n = min(chunk, N - first)
-            state = SpellState(sampler, xd[first:first + n], yd[first:first + n], req)
-            for k in range(req.K + 1):
-                field.spell_scan(sampler, state, k, with_clip)
-            for rnd in range(req.R):
-                field.spell_refine(sampler, state, rnd, with_clip, last=rnd == req.R - 1)
-            if req.R == 0:
-                spell_finish(state)
-            for key, v in state.results().items():
-                out[key][:, first:first + n] = v
-        return out
 
     @torch.no_grad()
     def spells_at(self, field_data, sampler, x_idx, y_idx, window, forecast_h, columns, scan_hours=1.0, refine=10, with_clip=False, lonlat=False,
@@ -665,29 +657,26 @@ class InterfacePhysics(nn.Module):
         the refinement does not change), 'crossings' [N, C] int32 (entries and exits the scan saw), 'status' [N, C] int32, bits: 1 a scan value was
         not finite (everything NaN), 2 a probe was not finite (the brackets stand), 4 never in, 8 in at t0, 16 in at t1}, on the device.  A spell
         shorter than a scan step that lies between two nodes is not seen."""
-        require_gpu(field_data, 'field_data', 'spells')
-        c = sampler.cfg
-        req = SP.check_request(columns, window, scan_hours, refine, c.input_time_step * c.input_time_step_nums)
-        x_idx, y_idx = (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64) for v in (x_idx, y_idx))
-        if lonlat:
-            x_idx, y_idx = sampler.lonlat_to_index(x_idx, y_idx)
-        xr, yr, _ = sampler.check_positions(x_idx, y_idx, np.full(np.shape(np.atleast_1d(x_idx)), req.t0))
-        out = self._spells_run(field_data, sampler, xr, yr, req, forecast_h, with_clip, chunk_points)
+        req = self._window_request(SP.check_request, 'spells', field_data, sampler, columns, window, scan_hours, refine)
+        xr, yr = self._window_stations(sampler, x_idx, y_idx, lonlat, req.t0)
+        out = self._window_run(SpellState, field_data, sampler, xr, yr, req, forecast_h, with_clip, chunk_points)
         return dict({k: v.t().contiguous() for k, v in out.items()}, names=req.names)
 
     @torch.no_grad()
     def spell_lattice(self, field_data, sampler, lattice, window, forecast_h, columns, scan_hours=1.0, refine=10, with_clip=False, chunk_points=None):
         """spells_at on the positions of a lattice with nt == 1 (ValueError otherwise: `window` gives the times), as maps [C, ny, nx]: 'hours',
         'first', 'last', 'first_lo', 'last_hi', 'excess', 'crossings', 'status'.  Points outside the coarse cube have status 1 and NaN everywhere."""
-        require_gpu(field_data, 'field_data', 'spells')
-        c = sampler.cfg
-        req = SP.check_request(columns, window, scan_hours, refine, c.input_time_step * c.input_time_step_nums)
+        req = self._window_request(SP.check_request, 'spells', field_data, sampler, columns, window, scan_hours, refine)
         if lattice.nt != 1:
             raise ValueError('spell_lattice: the lattice gives the positions (nt == 1, got %d); `window` gives the times' % lattice.nt)
-        xs, ys, _ = lattice.positions()
-        xd, yd = (torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(field_data.device) for v in (xs, ys))
-        out = self._spells_run(field_data, sampler, xd, yd, req, forecast_h, with_clip, chunk_points)
+        xd, yd = self._window_lattice(lattice, field_data.device)
+        out = self._window_run(SpellState, field_data, sampler, xd, yd, req, forecast_h, with_clip, chunk_points)
         return dict({k: v.view(len(req.ids), lattice.ny, lattice.nx) for k, v in out.items()}, names=req.names)
+
+    # the inference loop's time-window keys: inference_cfg key, file word, the request check, the lattice method, the station method, where the last
+    # sample's result stays
+    _WINDOW_PRODUCTS = (('extremes', 'extreme', X.check_request, 'extreme_lattice', 'extremes_at', 'last_extremes'),
+                        ('spells', 'spell', SP.check_request, 'spell_lattice', 'spells_at', 'last_spells'))
 
     @torch.no_grad()
     def adaptive_interior(self, batch: dict, sampler, pool_factor=8, k=1.0, c=1.0):
@@ -1814,24 +1803,19 @@ class InterfacePhysics(nn.Module):
             ensemble_ids(ens['products'])                                 # an unknown name (KeyError), a bad threshold (ValueError): before the
             check_thresholds(ens['products'], ens['thresholds'])          # checkpoint is read
         self.last_ensemble = None
-        ext = ic.get('extremes')
-        if ext:
-            ext = dict({'scan_hours': 1.0, 'refine': 10, 'lonlat': None}, **ext)
-            X.check_request(ext['columns'], ext['window'], ext['scan_hours'], ext['refine'], float('inf'))      # a bad request: before the checkpoint is read
-            if ext['lonlat'] is not None:
-                ext_lon, ext_lat = ([float(p[j]) for p in ext['lonlat']] for j in (0, 1))
-                if not ext_lon:
-                    raise ValueError('inference_cfg.extremes: lonlat names no station (leave the key out for maps)')
-        self.last_extremes = None
-        spl = ic.get('spells')
-        if spl:
-            spl = dict({'scan_hours': 1.0, 'refine': 10, 'lonlat': None}, **spl)
-            SP.check_request(spl['columns'], spl['window'], spl['scan_hours'], spl['refine'], float('inf'))      # a bad request: before the checkpoint is read
-            if spl['lonlat'] is not None:
-                spl_lon, spl_lat = ([float(p[j]) for p in spl['lonlat']] for j in (0, 1))
-                if not spl_lon:
-                    raise ValueError('inference_cfg.spells: lonlat names no station (leave the key out for maps)')
-        self.last_spells = None
+        windows = []                                                      # (a row of _WINDOW_PRODUCTS, its options) of the keys that are set
+        for row in self._WINDOW_PRODUCTS:
+            key, _, check, _, _, last = row
+            opt = ic.get(key)
+            if opt:
+                opt = dict({'scan_hours': 1.0, 'refine': 10, 'lonlat': None}, **opt)
+                check(opt['columns'], opt['window'], opt['scan_hours'], opt['refine'], float('inf'))      # a bad request: before the checkpoint is read
+                if opt['lonlat'] is not None:
+                    opt['lonlat'] = [[float(p[j]) for p in opt['lonlat']] for j in (0, 1)]       # (lons, lats)
+                    if not opt['lonlat'][0]:
+                        raise ValueError('inference_cfg.%s: lonlat names no station (leave the key out for maps)' % key)
+                windows.append((row, opt))
+            setattr(self, last, None)
         self.physics_net.to(device)
         self.pe.to(device)
         state_dict, current_epoch, global_step = (None, 0, 0) if not checkpoint_path else self.load_model(checkpoint_path, prefix='physics', map_location=device)
@@ -1877,43 +1861,27 @@ class InterfacePhysics(nn.Module):
                 self.last_trajectories = self.trajectories(smp['field_data'].to(device), sampler, traj_lon, traj_lat, float(traj['start']),
                                                            smp['forecast_h'].to(device), float(traj['hours']), float(traj['step']), traj['method'],
                                                            lonlat=True, with_fields=True, with_clip=kwargs.get('with_clip', self.with_clip))
-            if ext:
+            for (_, _, _, on_lattice, at_stations, last), opt in windows:
                 args = (smp['field_data'].to(device), sampler)
-                kw = dict(window=ext['window'], forecast_h=smp['forecast_h'].to(device), columns=ext['columns'], scan_hours=ext['scan_hours'],
-                          refine=ext['refine'], with_clip=kwargs.get('with_clip', self.with_clip))
-                if ext['lonlat'] is None:
-                    self.last_extremes = self.extreme_lattice(*args, sampler.lattice(refine=refine, hours=0.0), **kw)
+                kw = dict(window=opt['window'], forecast_h=smp['forecast_h'].to(device), columns=opt['columns'], scan_hours=opt['scan_hours'],
+                          refine=opt['refine'], with_clip=kwargs.get('with_clip', self.with_clip))
+                if opt['lonlat'] is None:
+                    setattr(self, last, getattr(self, on_lattice)(*args, sampler.lattice(refine=refine, hours=0.0), **kw))
                 else:
-                    self.last_extremes = self.extremes_at(*args, ext_lon, ext_lat, lonlat=True, **kw)
-            if spl:
-                args = (smp['field_data'].to(device), sampler)
-                kw = dict(window=spl['window'], forecast_h=smp['forecast_h'].to(device), columns=spl['columns'], scan_hours=spl['scan_hours'],
-                          refine=spl['refine'], with_clip=kwargs.get('with_clip', self.with_clip))
-                if spl['lonlat'] is None:
-                    self.last_spells = self.spell_lattice(*args, sampler.lattice(refine=refine, hours=0.0), **kw)
-                else:
-                    self.last_spells = self.spells_at(*args, spl_lon, spl_lat, lonlat=True, **kw)
+                    setattr(self, last, getattr(self, at_stations)(*args, *opt['lonlat'], lonlat=True, **kw))
             if write_source:
-                if spl:
-                    stamp = (start + datetime.timedelta(seconds=k * window_h * 3600.0)).strftime('%Y-%m-%d_%H_%M_%S')
-                    for key in ('hours', 'first', 'last', 'first_lo', 'last_hi', 'excess', 'crossings', 'status'):
-                        a = self.last_spells[key].cpu().numpy()
-                        if spl['lonlat'] is not None:                     # stations: one [N, C] table per result
-                            np.save(os.path.join(result_path, '%s_spell_%s.npy' % (stamp, key)), a)
+                stamp = (start + datetime.timedelta(seconds=k * window_h * 3600.0)).strftime('%Y-%m-%d_%H_%M_%S')      # the sample's first time step
+                for (_, word, _, _, _, last), opt in reversed(windows):       # (the spells' files before the extremes')
+                    result = dict(getattr(self, last))
+                    columns = result.pop('names')
+                    for key, v in result.items():                         # the product's results in its state's order
+                        a = v.cpu().numpy()
+                        if opt['lonlat'] is not None:                     # stations: one [N, C] table per result
+                            np.save(os.path.join(result_path, '%s_%s_%s.npy' % (stamp, word, key)), a)
                             continue
-                        for j, name in enumerate(self.last_spells['names']):        # maps: one [lat, lon] file per result and column
-                            np.save(os.path.join(result_path, '%s_spell_%s_%s.npy' % (stamp, key, name.replace(':', '_'))), a[j])
-                if ext:
-                    stamp = (start + datetime.timedelta(seconds=k * window_h * 3600.0)).strftime('%Y-%m-%d_%H_%M_%S')
-                    for key in ('value', 'hour', 'lo', 'hi', 'status'):
-                        a = self.last_extremes[key].cpu().numpy()
-                        if ext['lonlat'] is not None:                     # stations: one [N, C] table per result
-                            np.save(os.path.join(result_path, '%s_extreme_%s.npy' % (stamp, key)), a)
-                            continue
-                        for j, name in enumerate(self.last_extremes['names']):      # maps: one [lat, lon] file per result and column
-                            np.save(os.path.join(result_path, '%s_extreme_%s_%s.npy' % (stamp, key, name.replace(':', '_'))), a[j])
+                        for j, name in enumerate(columns):                # maps: one [lat, lon] file per result and column
+                            np.save(os.path.join(result_path, '%s_%s_%s_%s.npy' % (stamp, word, key, name.replace(':', '_'))), a[j])
                 if traj:
-                    stamp = (start + datetime.timedelta(seconds=k * window_h * 3600.0)).strftime('%Y-%m-%d_%H_%M_%S')
                     for key, name in (('positions', 'positions'), ('hours', 'hours'), ('status', 'status'), ('steps_done', 'steps'), ('fields', 'fields')):
                         np.save(os.path.join(result_path, '%s_traj_%s.npy' % (stamp, name)), self.last_trajectories[key].cpu().numpy())
                 host = maps.cpu().numpy()

@@ -1265,6 +1265,12 @@ def point_sizes(n, prec):
     return int(sizes.n_pad), int(sizes.packed)
 
 
+def point_buffers(m, device):
+    """The five input buffers of an m-point forward, not filled: x, y, t, f [m], coord_data [m, 6] fp32 (what dpn_sample_at and the time-window
+    kernels write)."""
+    return tuple(torch.empty(m, dtype=torch.float32, device=device) for _ in range(4)) + (torch.empty((m, 6), dtype=torch.float32, device=device),)
+
+
 def grid_maps(cfg: PointConfig, out_n, lon_size, lat_size, with_clip=False):
     """Normalised fields of all lon x lat nodes (out_n [lon * lat, 6], x outer, y inner) de-normalised and scattered into maps [6, lat, lon]
     (dpn_grid_maps)."""
@@ -1287,7 +1293,7 @@ class PackedField:
         L.check(lib.dpn_pack_weights_form(self.nets, cfg.prec, lib.dpn_fwd_form(cfg.prec, 0), _ptr(self.ws.packed), _stream()), 'dpn_pack_weights')
         self.ws.prepacked = True
         self._traj_ph = None
-        self._ext_ph = {}
+        self._clip_ph = {}
 
     def fields(self, x, y, t, coord_data, with_clip=False, rows=None, maps=None, lattice=None, first=0):
         """The six physical fields at points x, y, t [n], coord_data [n, 6] (dpn_fields_out): into rows [n, 6], or into the places of points
@@ -1309,9 +1315,7 @@ class PackedField:
         """Derived diagnostics (dpn_diagnostics_out; deepphysinet_amd.diagnostics.PRODUCTS) at points x, y, t, f [n], coord_data [n, 6]: `products`, a
         sequence of P product ids, into rows [n, P], or into the places of points first .. first + n of `lattice` in maps [nt, P, ny, nx]."""
         out_n, jac_n = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=True, want_saved=False)
-        ph = self.cfg.physics()
-        for k in range(2, L.NETS):                             # `with_clip` is this call's own, as `fields` takes it: the training clip of P, T, q, rho
-            ph.clip_on[k] = int(bool(with_clip) and bool(self.cfg.clip_vars[k]))
+        ph = self._clip_physics(with_clip)
         ids = (ctypes.c_int32 * len(products))(*products)
         lat = None if lattice is None else ctypes.byref(lattice.c_struct())
         L.check(L.load().dpn_diagnostics_out(_ptr(out_n), _ptr(jac_n), _ptr(f), out_n.shape[0], ctypes.byref(ph), int(bool(with_clip)), ids, len(ids),
@@ -1323,9 +1327,7 @@ class PackedField:
         reads it, otherwise the fields-only one (as `fields`).  with_clip as `diagnostics` takes it."""
         need_j = reads_jacobian(state.ids)
         out_n, jac_n = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=need_j, want_saved=False)
-        ph = self.cfg.physics()
-        for k in range(2, L.NETS):                             # `with_clip` is this call's own, as in `diagnostics`
-            ph.clip_on[k] = int(bool(with_clip) and bool(self.cfg.clip_vars[k]))
+        ph = self._clip_physics(with_clip)
         s = state
         L.check(L.load().dpn_ensemble_accumulate(_ptr(out_n), _ptr(jac_n) if need_j else None, _ptr(f) if reads_coriolis(s.ids) else None, out_n.shape[0],
                                                  ctypes.byref(ph), int(bool(with_clip)), s.c_ids, len(s.ids), s.c_thr_col, s.c_thr_val, len(s.thr_col),
@@ -1361,51 +1363,35 @@ class PackedField:
             self._traj_ph = self.cfg.physics()
         traj_stage(sampler, self._traj_ph, out_n, parcels, stage, t0, h, inv_wsum, step, fields, with_clip, record_only)
 
-    def _extreme_physics(self, with_clip):
-        """The physics table of the extremes launches, built once per field and clip setting (a request is K + R + 2 launches per chunk)."""
+    def _clip_physics(self, with_clip):
+        """The physics table of a call with a clip setting of its own (`with_clip` is the call's, as `fields` takes it: the training clip of P, T, q,
+        rho), built once per field and setting: a lattice is many chunks, a time-window request K + R + 2 launches per chunk."""
         key = bool(with_clip)
-        if key not in self._ext_ph:
+        if key not in self._clip_ph:
             ph = self.cfg.physics()
-            for k in range(2, L.NETS):                         # `with_clip` is this call's own, as in `diagnostics`
+            for k in range(2, L.NETS):
                 ph.clip_on[k] = int(key and bool(self.cfg.clip_vars[k]))
-            self._ext_ph[key] = ph
-        return self._ext_ph[key]
+            self._clip_ph[key] = ph
+        return self._clip_ph[key]
 
-    def extreme_scan(self, sampler, state, k, with_clip=False):
-        """Scan node k of a window-extremes request for the points of `state` (an ExtremeState): the fields-only forward at the node, then
-        dpn_extreme_scan, which folds it into the state and writes the next node's inputs into the same buffers; after the last node
-        dpn_extreme_begin closes the scan and writes the first probes.  Two launches (three at node K), nothing read back."""
+    def window_scan(self, sampler, state, k, with_clip=False):
+        """Scan node k of a time-window request for the points of `state` (an ExtremeState or a SpellState): the fields-only forward at the node,
+        then the state's scan launch (dpn_extreme_scan, dpn_spell_scan), which folds it into the state and writes the next node's inputs into the
+        same buffers; after the last node the state's begin launch closes the scan and writes the first probes.  Two launches (three at node K),
+        nothing read back."""
         x, y, t, _, cd = state.points
         out_n, _ = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, cd, want_jac=False, want_saved=False)
-        extreme_scan(sampler, self._extreme_physics(with_clip), with_clip, out_n, state, k)
+        state.scan(sampler, self._clip_physics(with_clip), with_clip, out_n, k)
         if k == state.K:
-            extreme_begin(sampler, state)
+            state.begin(sampler)
 
-    def extreme_refine(self, sampler, state, rnd, with_clip=False):
-        """Round `rnd` of the refinement: the forward with the Jacobian at the Cr * n probes, then dpn_extreme_refine, which keeps the best value, moves
-        the bracket and rewrites the probes.  Two launches, nothing read back."""
+    def window_refine(self, sampler, state, rnd, with_clip=False):
+        """Round `rnd` of the refinement: the forward at the state's probes -- with the Jacobian where the state bisects on d/dt (extremes),
+        fields-only where it bisects on the value (spells) --, then the state's refine launch, which moves the brackets and rewrites the probes.  Two
+        launches, nothing read back."""
         x, y, t, _, cd = state.probes
-        out_n, jac_n = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, cd, want_jac=True, want_saved=False)
-        extreme_refine(sampler, self._extreme_physics(with_clip), with_clip, out_n, jac_n, state, rnd)
-
-    def spell_scan(self, sampler, state, k, with_clip=False):
-        """Scan node k of a threshold-spells request for the points of `state` (a SpellState): the fields-only forward at the node, then
-        dpn_spell_scan, which folds it into the state and writes the next node's inputs into the same buffers; after the last node dpn_spell_begin
-        closes the scan and writes the first probes.  Two launches (three at node K), nothing read back."""
-        x, y, t, _, cd = state.points
-        out_n, _ = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, cd, want_jac=False, want_saved=False)
-        spell_scan(sampler, self._extreme_physics(with_clip), with_clip, out_n, state, k)
-        if k == state.K:
-            spell_begin(sampler, state)
-
-    def spell_refine(self, sampler, state, rnd, with_clip=False, last=False):
-        """Round `rnd` of the refinement: the fields-only forward at the 2 * C * n probes, then dpn_spell_refine, which halves the brackets and
-        rewrites the probes; `last`: dpn_spell_finish behind it.  Two launches (three when last), nothing read back."""
-        x, y, t, _, cd = state.probes
-        out_n, _ = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, cd, want_jac=False, want_saved=False)
-        spell_refine(sampler, self._extreme_physics(with_clip), with_clip, out_n, state, rnd)
-        if last:
-            spell_finish(state)
+        out_n, jac_n = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, cd, want_jac=state.REFINE_JACOBIAN, want_saved=False)
+        state.refine(sampler, self._clip_physics(with_clip), with_clip, out_n, jac_n, rnd)
 
 
 class EnsembleState:
@@ -1470,99 +1456,140 @@ def traj_stage(sampler, ph, out_n, parcels, stage, t0, h, inv_wsum, step, fields
                                     _ptr(fields) if want_fields else None, _ptr(x), _ptr(y), _ptr(t), _ptr(f), _ptr(cd), _stream()), 'dpn_traj_stage')
 
 
-class ExtremeState:
+class _WindowState:
+    """What the device states of the two time-window products share (ExtremeState, SpellState): n points, the request's clock K, t0, dt, their
+    fp64 positions xr, yr, the state arrays KEYS [C, n] (fp64 but for those DTYPES names; nothing is filled: node 0 sets what is read), `points` =
+    x, y, t, f [n], coord_data [n, 6], the sampler at the current scan node (node 0 to begin with), `probes`, the same five with probe_rows * n
+    rows (None without a row), and the launches.  A subclass sets ids and c_columns (its column tables, as its entry points take them) before this
+    constructor, and says what a walk must know: probe_rows, point_bytes and rounds of a request, REFINE_JACOBIAN: whether the forward at the
+    probes is the one with the Jacobian."""
+
+    def __init__(self, sampler, xr, yr, request):
+        dev, n = xr.device, xr.shape[0]
+        self.n, self.K, self.t0, self.dt = n, int(request.K), float(request.t0), float(request.dt)
+        self.xr, self.yr = xr.contiguous(), yr.contiguous()
+        for key in self.KEYS:
+            setattr(self, key, torch.empty((len(self.ids), n), dtype=self.DTYPES.get(key, torch.float64), device=dev))
+        self.points = sampler.sample_at(n, self.xr, self.yr, torch.full((n,), self.t0, dtype=torch.float64, device=dev))
+        rows = self.probe_rows(request)
+        self.probes = point_buffers(rows * n, dev) if rows else None
+
+    def c_struct(self):
+        return self.C_STATE(*[_ptr(getattr(self, key)) for key in self.KEYS])
+
+    def _launch(self, name, sampler, bufs, head, index):
+        """The entry point `name` with the argument list the scan, begin and refine launches of both products share: sampler, cube, head, n, the
+        column tables, C, index, K, t0, dt, xr, yr, the state, the five buffers `bufs` it samples into, the stream.  head: () or (the physics table,
+        with_clip, the forward's tensors ...); index: () or (the node or the round,)."""
+        if head:
+            ph, with_clip, *forward = head
+            head = [ctypes.byref(ph), int(bool(with_clip))] + [_ptr(v) for v in forward]
+        L.check(getattr(L.load(), name)(ctypes.byref(sampler._s), _ptr(sampler.cube), *head, self.n, *self.c_columns, len(self.ids), *index, self.K,
+                                        self.t0, self.dt, _ptr(self.xr), _ptr(self.yr), ctypes.byref(self.c_struct()), *[_ptr(v) for v in bufs],
+                                        _stream()), name)
+
+    def scan(self, sampler, ph, with_clip, out_n, k):
+        """The scan launch with the fields-only forward's out_n [n, 6] at scan node k."""
+        self._launch(self.ENTRY + '_scan', sampler, self.points, (ph, with_clip, out_n), (int(k),))
+
+    def begin(self, sampler):
+        """The begin launch: closes the scan and writes the probes (a request without a probe row samples nothing)."""
+        self._launch(self.ENTRY + '_begin', sampler, self.probes or self.points, (), ())
+
+    def finish(self):
+        """Once per chunk, after the last round (or after the scan when there is none): nothing, unless the product has a finish launch."""
+
+
+class ExtremeState(_WindowState):
     """Device state of n points of a window-extremes request between its launches (include/dpn_hip.h): for the C columns of `request` (an
     extremes.Request) best_v [C, n] fp32, best_t, acc, lo, hi [C, n] fp64, best_k, status [C, n] int32 -- column-major, so a map [C, ny, nx] is a
     view of it --; `points` = x, y, t, f [n], coord_data [n, 6], the sampler at the current scan node (node 0 to begin with), and `probes`, the same
     five with Cr * n rows for the probes of the Cr max / min columns (None without one).  Nothing is filled: node 0 sets what is read."""
 
+    ENTRY, C_STATE = 'dpn_extreme', L.DpnExtremeState
+    KEYS = ('best_v', 'best_t', 'best_k', 'acc', 'status', 'lo', 'hi')
+    DTYPES = {'best_v': torch.float32, 'best_k': torch.int32, 'status': torch.int32}
+    REFINE_JACOBIAN = True                                    # bisection on the sign of d/dt
     POINT_BYTES = 4 * (4 + 6 + 6) + 16                       # per point: the scan's buffers and xr, yr
     COLUMN_BYTES = 4 + 8 + 4 + 8 + 4 + 8 + 8                  # per point and column: the state
     PROBE_BYTES = 4 * (4 + 6 + 6 + 18)                        # per point and refined column: the probe's buffers, its out_n and Jacobian
 
     def __init__(self, sampler, xr, yr, request):
-        dev, n = xr.device, xr.shape[0]
-        self.n, self.K, self.t0, self.dt = n, int(request.K), float(request.t0), float(request.dt)
         self.ids, self.senses = list(request.ids), list(request.senses)
-        C = len(self.ids)
-        self.n_refined = sum(1 for s in self.senses if s != L.EXT_MEAN)
+        C, n = len(self.ids), xr.shape[0]
+        self.n_refined = self.probe_rows(request)
         if not 1 <= C <= L.EXT_MAX_COLUMNS or len(self.senses) != C or n < 1:
             raise ValueError('ExtremeState: %d points, %d columns (1..%d)' % (n, C, L.EXT_MAX_COLUMNS))
-        self.c_ids, self.c_senses = (ctypes.c_int32 * C)(*self.ids), (ctypes.c_int32 * C)(*self.senses)
-        self.xr, self.yr = xr.contiguous(), yr.contiguous()
-        self.best_v = torch.empty((C, n), dtype=torch.float32, device=dev)
-        self.best_t, self.acc, self.lo, self.hi = (torch.empty((C, n), dtype=torch.float64, device=dev) for _ in range(4))
-        self.best_k, self.status = (torch.empty((C, n), dtype=torch.int32, device=dev) for _ in range(2))
-        self.points = sampler.sample_at(n, self.xr, self.yr, torch.full((n,), self.t0, dtype=torch.float64, device=dev))
-        m = self.n_refined * n
-        self.probes = None if m == 0 else \
-            tuple(torch.empty(m, dtype=torch.float32, device=dev) for _ in range(4)) + (torch.empty((m, 6), dtype=torch.float32, device=dev),)
+        self.c_ids, self.c_senses = self.c_columns = (ctypes.c_int32 * C)(*self.ids), (ctypes.c_int32 * C)(*self.senses)
+        super().__init__(sampler, xr, yr, request)
 
-    def c_struct(self):
-        return L.DpnExtremeState(*[_ptr(v) for v in (self.best_v, self.best_t, self.best_k, self.acc, self.status, self.lo, self.hi)])
+    @staticmethod
+    def probe_rows(request):
+        """Probe rows per point: one per max / min column."""
+        return sum(1 for s in request.senses if s != L.EXT_MEAN)
+
+    @classmethod
+    def point_bytes(cls, request):
+        return cls.POINT_BYTES + len(request.ids) * cls.COLUMN_BYTES + cls.probe_rows(request) * cls.PROBE_BYTES
+
+    @classmethod
+    def rounds(cls, request):
+        """Refine launches of a request: round 0 probes the best node, R halve the bracket; none without a max / min column."""
+        return request.R + 1 if cls.probe_rows(request) else 0
+
+    def refine(self, sampler, ph, with_clip, out_n, jac_n, rnd):
+        """dpn_extreme_refine, round rnd, with the forward's out_n [Cr * n, 6] and jac_n [Cr * n, 6, 3] at the probes."""
+        self._launch('dpn_extreme_refine', sampler, self.probes, (ph, with_clip, out_n, jac_n), (int(rnd),))
 
     def results(self):
         """value, hour, lo, hi, status [C, n]: the state's own arrays, complete after the last round."""
         return {'value': self.best_v, 'hour': self.best_t, 'lo': self.lo, 'hi': self.hi, 'status': self.status}
 
 
-def extreme_scan(sampler, ph, with_clip, out_n, state, k):
-    """dpn_extreme_scan on an ExtremeState with the fields-only forward's out_n [n, 6] at scan node k."""
-    s = state
-    x, y, t, f, cd = s.points
-    L.check(L.load().dpn_extreme_scan(ctypes.byref(sampler._s), _ptr(sampler.cube), ctypes.byref(ph), int(bool(with_clip)), _ptr(out_n), s.n, s.c_ids,
-                                      s.c_senses, len(s.ids), int(k), s.K, s.t0, s.dt, _ptr(s.xr), _ptr(s.yr), ctypes.byref(s.c_struct()), _ptr(x),
-                                      _ptr(y), _ptr(t), _ptr(f), _ptr(cd), _stream()), 'dpn_extreme_scan')
-
-
-def extreme_begin(sampler, state):
-    """dpn_extreme_begin: closes the scan of an ExtremeState and writes its probes (a request of mean columns alone has none: nothing is sampled)."""
-    s = state
-    x, y, t, f, cd = s.probes or s.points
-    L.check(L.load().dpn_extreme_begin(ctypes.byref(sampler._s), _ptr(sampler.cube), s.n, s.c_ids, s.c_senses, len(s.ids), s.K, s.t0, s.dt, _ptr(s.xr),
-                                       _ptr(s.yr), ctypes.byref(s.c_struct()), _ptr(x), _ptr(y), _ptr(t), _ptr(f), _ptr(cd), _stream()),
-            'dpn_extreme_begin')
-
-
-def extreme_refine(sampler, ph, with_clip, out_n, jac_n, state, rnd):
-    """dpn_extreme_refine, round rnd, with the forward's out_n [Cr * n, 6] and jac_n [Cr * n, 6, 3] at the probes of an ExtremeState."""
-    s = state
-    x, y, t, f, cd = s.probes
-    L.check(L.load().dpn_extreme_refine(ctypes.byref(sampler._s), _ptr(sampler.cube), ctypes.byref(ph), int(bool(with_clip)), _ptr(out_n), _ptr(jac_n),
-                                        s.n, s.c_ids, s.c_senses, len(s.ids), int(rnd), s.K, s.t0, s.dt, _ptr(s.xr), _ptr(s.yr),
-                                        ctypes.byref(s.c_struct()), _ptr(x), _ptr(y), _ptr(t), _ptr(f), _ptr(cd), _stream()), 'dpn_extreme_refine')
-
-
-class SpellState:
+class SpellState(_WindowState):
     """Device state of n points of a threshold-spells request between its launches (include/dpn_hip.h): for the C columns of `request` (a
     spells.Request) prev_x [C, n] fp32; hours, excess, part_first, part_last, f_lo, f_hi, l_lo, l_hi [C, n] fp64; crossings, k_first, k_last, status
     [C, n] int32 -- column-major, so a map [C, ny, nx] is a view of it --; `points` = x, y, t, f [n], coord_data [n, 6], the sampler at the current
     scan node (node 0 to begin with), and `probes`, the same five with 2 * C * n rows: the entry and the exit probe of every column.  Nothing is
     filled: node 0 sets what is read."""
 
+    ENTRY, C_STATE = 'dpn_spell', L.DpnSpellState
     KEYS = ('prev_x', 'hours', 'excess', 'crossings', 'k_first', 'k_last', 'status', 'part_first', 'part_last', 'f_lo', 'f_hi', 'l_lo', 'l_hi')
+    DTYPES = dict({key: torch.int32 for key in ('crossings', 'k_first', 'k_last', 'status')}, prev_x=torch.float32)
+    REFINE_JACOBIAN = False                                   # bisection on the sign of value - threshold
     POINT_BYTES = 4 * (4 + 6 + 6) + 16                       # per point: the scan's buffers and xr, yr
     COLUMN_BYTES = 4 + 8 * 8 + 4 * 4 + 2 * 4 * (4 + 6 + 6)    # per point and column: the state; the two probes' buffers and their out_n
 
     def __init__(self, sampler, xr, yr, request):
-        dev, n = xr.device, xr.shape[0]
-        self.n, self.K, self.t0, self.dt = n, int(request.K), float(request.t0), float(request.dt)
         self.ids, self.sides, self.thr = list(request.ids), list(request.sides), [float(v) for v in request.thr]
-        C = len(self.ids)
+        C, n = len(self.ids), xr.shape[0]
         if not 1 <= C <= L.SPELL_MAX_COLUMNS or len(self.sides) != C or len(self.thr) != C or n < 1:
             raise ValueError('SpellState: %d points, %d columns (1..%d)' % (n, C, L.SPELL_MAX_COLUMNS))
-        self.c_ids, self.c_sides, self.c_thr = (ctypes.c_int32 * C)(*self.ids), (ctypes.c_int32 * C)(*self.sides), (ctypes.c_float * C)(*self.thr)
-        self.xr, self.yr = xr.contiguous(), yr.contiguous()
-        i32 = ('crossings', 'k_first', 'k_last', 'status')
-        for key in self.KEYS:
-            dtype = torch.float32 if key == 'prev_x' else torch.int32 if key in i32 else torch.float64
-            setattr(self, key, torch.empty((C, n), dtype=dtype, device=dev))
-        self.points = sampler.sample_at(n, self.xr, self.yr, torch.full((n,), self.t0, dtype=torch.float64, device=dev))
-        m = 2 * C * n
-        self.probes = tuple(torch.empty(m, dtype=torch.float32, device=dev) for _ in range(4)) + (torch.empty((m, 6), dtype=torch.float32, device=dev),)
+        self.c_ids, self.c_sides, self.c_thr = self.c_columns = \
+            (ctypes.c_int32 * C)(*self.ids), (ctypes.c_int32 * C)(*self.sides), (ctypes.c_float * C)(*self.thr)
+        super().__init__(sampler, xr, yr, request)
 
-    def c_struct(self):
-        return L.DpnSpellState(*[_ptr(getattr(self, key)) for key in self.KEYS])
+    @staticmethod
+    def probe_rows(request):
+        """Probe rows per point: the entry and the exit probe of every column."""
+        return 2 * len(request.ids)
+
+    @classmethod
+    def point_bytes(cls, request):
+        return cls.POINT_BYTES + len(request.ids) * cls.COLUMN_BYTES
+
+    @staticmethod
+    def rounds(request):
+        """Refine launches of a request: R halvings of both brackets."""
+        return request.R
+
+    def refine(self, sampler, ph, with_clip, out_n, jac_n, rnd):
+        """dpn_spell_refine, round rnd, with the fields-only forward's out_n [2 * C * n, 6] at the probes (jac_n: None, not read)."""
+        self._launch('dpn_spell_refine', sampler, self.probes, (ph, with_clip, out_n), (int(rnd),))
+
+    def finish(self):
+        """dpn_spell_finish: once, after the last round (or after the scan when there is none)."""
+        L.check(L.load().dpn_spell_finish(self.n, len(self.ids), self.K, self.t0, self.dt, ctypes.byref(self.c_struct()), _stream()), 'dpn_spell_finish')
 
     def results(self):
         """hours, first, last, first_lo, last_hi, excess, crossings, status [C, n]: the state's own arrays, complete after dpn_spell_finish."""
@@ -1570,34 +1597,3 @@ class SpellState:
                 'crossings': self.crossings, 'status': self.status}
 
 
-def spell_scan(sampler, ph, with_clip, out_n, state, k):
-    """dpn_spell_scan on a SpellState with the fields-only forward's out_n [n, 6] at scan node k."""
-    s = state
-    x, y, t, f, cd = s.points
-    L.check(L.load().dpn_spell_scan(ctypes.byref(sampler._s), _ptr(sampler.cube), ctypes.byref(ph), int(bool(with_clip)), _ptr(out_n), s.n, s.c_ids,
-                                    s.c_sides, s.c_thr, len(s.ids), int(k), s.K, s.t0, s.dt, _ptr(s.xr), _ptr(s.yr), ctypes.byref(s.c_struct()),
-                                    _ptr(x), _ptr(y), _ptr(t), _ptr(f), _ptr(cd), _stream()), 'dpn_spell_scan')
-
-
-def spell_begin(sampler, state):
-    """dpn_spell_begin: closes the scan of a SpellState and writes its 2 * C * n probes."""
-    s = state
-    x, y, t, f, cd = s.probes
-    L.check(L.load().dpn_spell_begin(ctypes.byref(sampler._s), _ptr(sampler.cube), s.n, s.c_ids, s.c_sides, s.c_thr, len(s.ids), s.K, s.t0, s.dt,
-                                     _ptr(s.xr), _ptr(s.yr), ctypes.byref(s.c_struct()), _ptr(x), _ptr(y), _ptr(t), _ptr(f), _ptr(cd), _stream()),
-            'dpn_spell_begin')
-
-
-def spell_refine(sampler, ph, with_clip, out_n, state, rnd):
-    """dpn_spell_refine, round rnd, with the fields-only forward's out_n [2 * C * n, 6] at the probes of a SpellState."""
-    s = state
-    x, y, t, f, cd = s.probes
-    L.check(L.load().dpn_spell_refine(ctypes.byref(sampler._s), _ptr(sampler.cube), ctypes.byref(ph), int(bool(with_clip)), _ptr(out_n), s.n, s.c_ids,
-                                      s.c_sides, s.c_thr, len(s.ids), int(rnd), s.K, s.t0, s.dt, _ptr(s.xr), _ptr(s.yr),
-                                      ctypes.byref(s.c_struct()), _ptr(x), _ptr(y), _ptr(t), _ptr(f), _ptr(cd), _stream()), 'dpn_spell_refine')
-
-
-def spell_finish(state):
-    """dpn_spell_finish: once, after the last round (or after the scan when there is none)."""
-    s = state
-    L.check(L.load().dpn_spell_finish(s.n, len(s.ids), s.K, s.t0, s.dt, ctypes.byref(s.c_struct()), _stream()), 'dpn_spell_finish')

@@ -71,11 +71,7 @@ def check_request(columns, window, scan_hours=1.0, refine=10, hours_top=24):
     1..MAX_SCAN_STEPS, node K never past t1, R in 0..MAX_REFINE).  R rounds leave brackets dt / 2**R wide.  KeyError: a malformed column
     (parse_columns); ValueError: everything else."""
     names, ids, sides, thr = parse_columns(columns)
-    try:
-        r = X.check_request('T:max', window, scan_hours, refine, hours_top)
-    except ValueError as e:
-        raise ValueError(str(e).replace('extremes:', 'spells:', 1)) from None
-    return Request(names, ids, sides, thr, r.t0, r.dt, r.K, r.R)
+    return Request(names, ids, sides, thr, *X.check_clock('spells', window, scan_hours, refine, hours_top))
 
 
 def new_state(n_columns, n, dtype=np.float32, fill=0):

@@ -66,27 +66,27 @@ parse.add_argument('--spell_scan', default=1.0, type=float, help='hours between 
 parse.add_argument('--spell_refine', default=10, type=int, help='bisection rounds after the scan (0..32)')
 
 
+def _window_option(args, key, word):
+    """inference_cfg[key] of --<key> / --<word>_window / --<word>_scan / --<word>_refine, or None without --<key>."""
+    columns, window = getattr(args, key), getattr(args, word + '_window')
+    if not columns:
+        if window is not None:
+            parse.error('--%s_window needs --%s' % (word, key))
+        return None
+    if window is None or len(window) != 2:
+        parse.error('--%s needs --%s_window H0,H1' % (key, word))
+    return dict(columns=list(columns), window=tuple(window), scan_hours=getattr(args, word + '_scan'), refine=getattr(args, word + '_refine'))
+
+
 def extremes_option(args):
     """inference_cfg['extremes'] of --extremes / --extreme_window: dict(columns=[...], window=(H0, H1), scan_hours=S, refine=R), or None without
     --extremes."""
-    if not args.extremes:
-        if args.extreme_window is not None:
-            parse.error('--extreme_window needs --extremes')
-        return None
-    if args.extreme_window is None or len(args.extreme_window) != 2:
-        parse.error('--extremes needs --extreme_window H0,H1')
-    return dict(columns=list(args.extremes), window=tuple(args.extreme_window), scan_hours=args.extreme_scan, refine=args.extreme_refine)
+    return _window_option(args, 'extremes', 'extreme')
 
 
 def spells_option(args):
     """inference_cfg['spells'] of --spells / --spell_window: dict(columns=[...], window=(H0, H1), scan_hours=S, refine=R), or None without --spells."""
-    if not args.spells:
-        if args.spell_window is not None:
-            parse.error('--spell_window needs --spells')
-        return None
-    if args.spell_window is None or len(args.spell_window) != 2:
-        parse.error('--spells needs --spell_window H0,H1')
-    return dict(columns=list(args.spells), window=tuple(args.spell_window), scan_hours=args.spell_scan, refine=args.spell_refine)
+    return _window_option(args, 'spells', 'spell')
 
 
 def ensemble_option(args):

@@ -117,6 +117,25 @@ def test_host_refusals_and_the_clock():
     assert X.node_hour(0.1, 0.7, 3) == np.float64(0.1) + np.float64(3.0) * np.float64(0.7)
 
 
+def test_spells_refuse_a_bad_clock_in_the_extremes_words():
+    """One clock check serves both products: for the sixteen bad clocks of tests/test_spells_cpu.py the message of spells.check_request is the
+    message of extremes.check_request with its first 'extremes:' replaced by 'spells:', and it names the offending value."""
+    from deepphysinet_amd import spells as S
+    ok = dict(window=(0.0, 24.0), scan_hours=1.0, refine=10, hours_top=24)
+    bad = (dict(window=(0.0, 24.5)), dict(window=(-1.0, 3.0)), dict(window=(5.0, 5.0)), dict(window=(6.0, 5.0)), dict(window=(0.0, float('nan'))),
+           dict(window=(0.0,)), dict(window=3.0), dict(scan_hours=0.0), dict(scan_hours=-1.0), dict(scan_hours=float('inf')), dict(scan_hours=2.0 ** -11),
+           dict(scan_hours=100.0), dict(refine=-1), dict(refine=33), dict(refine=2.5), dict(refine=True))
+    assert len(bad) == 16
+    for kw in bad:
+        with pytest.raises(ValueError) as of_extremes:
+            X.check_request('T:max', **{**ok, **kw})
+        with pytest.raises(ValueError) as of_spells:
+            S.check_request('T:below:273.15', **{**ok, **kw})
+        text = str(of_extremes.value)
+        assert text.startswith('extremes: ') and text.count('extremes:') == 1 and repr(next(iter(kw.values()))) in text
+        assert str(of_spells.value) == text.replace('extremes:', 'spells:', 1)
+
+
 # ------------------------------------------------------------------------------------------------ 3. the loop's key and the launcher
 def test_run_inference_interface_checks_the_extremes_key_before_the_checkpoint(tmp_path):
     from deepphysinet_amd.configs import ncep_config

@@ -48,7 +48,7 @@ def _composed(W, xs, ys, req, with_clip):
     n, C = xs.size, len(req.ids)
     cols = X.refined_columns(req.senses)
     pf = m._inference_weights(W['field'], W['fh'], n * max(len(cols), 1))
-    ph = pf._extreme_physics(with_clip)
+    ph = pf._clip_physics(with_clip)
     xd, yd = torch.from_numpy(xs).to(dev), torch.from_numpy(ys).to(dev)
     st = PP.ExtremeState(s, xd, yd, req)
     ref = X.new_state(C, n, fill=FILL)                         # both sides start from the same fill: what a launch must not touch is compared too
@@ -68,11 +68,11 @@ def _composed(W, xs, ys, req, with_clip):
         same_inputs(st.points, xs, ys, np.full(n, X.node_hour(req.t0, req.dt, k)), 'node %d' % k)
         x, y, t, _, cd = st.points
         out_n, _ = PP._forward_points(pf.cfg, pf.ws, pf.nets, x, y, t, None, cd, want_jac=False, want_saved=False)
-        PP.extreme_scan(s, ph, with_clip, out_n, st, k)
+        st.scan(s, ph, with_clip, out_n, k)
         xv, _ = X.products_reference(out_n.cpu().numpy(), None, ph, with_clip, req.ids, n)
         ref = X.scan_reference(xv, ref, req.senses, k, req.K)
         same_state('scan %d' % k)
-    PP.extreme_begin(s, st)
+    st.begin(s)
     ref, hours = X.begin_reference(ref, req.senses, req.K, req.t0, req.dt)
     same_state('begin')
     if cols:
@@ -82,7 +82,7 @@ def _composed(W, xs, ys, req, with_clip):
             same_inputs(st.probes, px, py, hours.reshape(-1), 'round %d' % rnd)
             x, y, t, _, cd = st.probes
             out_n, jac_n = PP._forward_points(pf.cfg, pf.ws, pf.nets, x, y, t, None, cd, want_jac=True, want_saved=False)
-            PP.extreme_refine(s, ph, with_clip, out_n, jac_n, st, rnd)
+            st.refine(s, ph, with_clip, out_n, jac_n, rnd)
             g, sl = X.products_reference(out_n.cpu().numpy(), jac_n.cpu().numpy(), ph, with_clip, ids_r, n)
             ref, (nxt, moved) = X.refine_reference(g, sl, ref, req.senses, rnd, req.t0, req.dt)
             hours = np.where(moved, nxt, hours)

@@ -51,7 +51,7 @@ def _composed(W, xs, ys, req, with_clip):
     m, s, dev = W['m'], W['s'], _dev()
     n, C = xs.size, len(req.ids)
     pf = m._inference_weights(W['field'], W['fh'], n * 2 * C)
-    ph = pf._extreme_physics(with_clip)
+    ph = pf._clip_physics(with_clip)
     xd, yd = torch.from_numpy(xs).to(dev), torch.from_numpy(ys).to(dev)
     st = PP.SpellState(s, xd, yd, req)
     ref = S.new_state(C, n, fill=FILL)                         # both sides start from the same fill: what a launch must not touch is compared too
@@ -74,10 +74,10 @@ def _composed(W, xs, ys, req, with_clip):
     for k in range(req.K + 1):
         same_inputs(st.points, xs, ys, np.full(n, S.node_hour(req.t0, req.dt, k)), 'node %d' % k)
         out_n = forward(st.points)
-        PP.spell_scan(s, ph, with_clip, out_n, st, k)
+        st.scan(s, ph, with_clip, out_n, k)
         ref = S.scan_reference(S.products_reference(out_n.cpu().numpy(), ph, with_clip, req.ids, n), ref, req.sides, req.thr, k, req.dt)
         same_state('scan %d' % k)
-    PP.spell_begin(s, st)
+    st.begin(s)
     ref, hours = S.begin_reference(ref, req.K, req.t0, req.dt)
     same_state('begin')
     has_entry, has_exit = S.brackets_of(ref, req.K)
@@ -88,13 +88,13 @@ def _composed(W, xs, ys, req, with_clip):
     for rnd in range(req.R):
         same_inputs(st.probes, px, py, hours.reshape(-1), 'round %d' % rnd)
         out_n = forward(st.probes)
-        PP.spell_refine(s, ph, with_clip, out_n, st, rnd)
+        st.refine(s, ph, with_clip, out_n, None, rnd)
         ref, (nxt, moved) = S.refine_reference(S.products_reference(out_n.cpu().numpy(), ph, with_clip, ids2, n), ref, req.sides, req.thr, req.K)
         assert not moved[unbracketed].any()
         hours = np.where(moved, nxt, hours)
         same_state('round %d' % rnd)
     same_inputs(st.probes, px, py, hours.reshape(-1), 'after the last round')
-    PP.spell_finish(st)
+    st.finish()
     ref = S.finish_reference(ref, req.K, req.t0, req.dt)
     same_state('finish')
     return ref
