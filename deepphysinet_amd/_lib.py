@@ -127,6 +127,21 @@ class DpnSpellState(Structure):
                                         'l_lo', 'l_hi')]
 
 
+class DpnRegionPlan(Structure):
+    """include/dpn_hip.h DpnRegionPlan: the region-sorted list of a regional-statistics request (device arrays) and its sizes."""
+    _fields_ = [(n, c_void_p) for n in ('seg', 'wgt', 'offs')] + [('n_sel', c_int64), ('n_regions', c_int32), ('nt', c_int32)]
+
+
+class DpnRegionState(Structure):
+    """include/dpn_hip.h DpnRegionState: the eight slot-major partial arrays of a regional-statistics request."""
+    _fields_ = [(n, c_void_p) for n in ('w', 'wx', 'count', 'vmin', 'vmax', 'imin', 'imax', 'wexc')]
+
+
+class DpnRegionOut(Structure):
+    """include/dpn_hip.h DpnRegionOut: the nine destinations of dpn_region_finish."""
+    _fields_ = [(n, c_void_p) for n in ('mean', 'total', 'weight', 'min', 'max', 'where_min', 'where_max', 'count', 'frac')]
+
+
 class DpnStepGuard(Structure):
     _fields_ = [(n, c_int32) for n in ('skipped_nonfinite', 'skipped_spike', 'verdict', 'seen', 'consecutive', 'reserved')] + \
                [('running', c_double), ('last', c_double)]
@@ -214,6 +229,9 @@ EXPORTS = {
                                         POINTER(c_float), c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dpn_ensemble_finish': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, POINTER(c_int32), c_int, c_int64, c_int64,
                                     POINTER(DpnEnsembleOut), POINTER(DpnEnsembleOut), POINTER(DpnLattice), c_void_p]),
+    'dpn_region_accumulate': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(DpnPhysics), c_int, POINTER(c_int32), c_int, POINTER(c_int32),
+                                      POINTER(c_float), c_int, c_int64, POINTER(DpnRegionPlan), POINTER(DpnRegionState), c_void_p]),
+    'dpn_region_finish': (c_int, [POINTER(DpnRegionPlan), POINTER(DpnRegionState), c_int, POINTER(c_int32), c_int, POINTER(DpnRegionOut), c_void_p]),
     'dpn_traj_stage': (c_int, [POINTER(DpnSampler), c_void_p, POINTER(DpnPhysics), c_void_p, c_int64, POINTER(DpnTrajStage), c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dpn_extreme_scan': (c_int, [POINTER(DpnSampler), c_void_p, POINTER(DpnPhysics), c_int, c_void_p, c_int64, POINTER(c_int32), POINTER(c_int32), c_int,
@@ -280,6 +298,7 @@ STEP_LOSSES = 16              # one field's row of dpn_step_finish_batch (includ
 
 DIAG_PRODUCTS = 28            # DPN_DIAG_PRODUCTS (include/dpn_hip.h)
 ENS_PRODUCTS, ENS_MAX_THRESHOLDS = 34, 16          # DPN_ENS_PRODUCTS, DPN_ENS_MAX_THRESHOLDS (include/dpn_hip.h)
+REG_GROUP, REG_MAX_COLUMNS, REG_MAX_THRESHOLDS = 64, 16, 16          # DPN_REG_GROUP, DPN_REG_MAX_COLUMNS, DPN_REG_MAX_THRESHOLDS (include/dpn_hip.h)
 EXT_MAX_COLUMNS = 32          # DPN_EXT_MAX_COLUMNS (include/dpn_hip.h)
 EXT_MAX, EXT_MIN, EXT_MEAN = 0, 1, 2                                                 # DPN_EXT_MAX, _MIN, _MEAN: a column's sense
 EXT_OK, EXT_BAD_SCAN, EXT_STOPPED, EXT_AT_START, EXT_AT_END = 0, 1, 2, 3, 4         # DPN_EXT_*: a column's status

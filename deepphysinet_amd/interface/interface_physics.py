@@ -22,13 +22,14 @@ from ..ensemble import check_thresholds, ensemble_ids
 from ..trajectory import check_request, domain_of, stage_table
 from .. import extremes as X
 from .. import spells as SP
+from .. import regions as RG
 from ..losses.builder import builder_loss
 from ..model.physics_net import PhysicsNet
 from ..guard import StepGuard
 from ..lbfgs import FusedLBFGS
 from ..optim import GROUP_KEYS, FusedClipAdam, resolve_param_groups
 from ..point_path import (balance_sumsq, balance_update, balanced_total, data_losses_batch, eval_step, eval_step_batch, grid_maps, label_errors, ParcelState,
-                          EnsembleState, ExtremeState, LOSS_ORDER, OBS_ORDER, PackedField, SpellState, pde_losses, pde_losses_batch, point_buffers, point_fields, point_sizes,
+                          EnsembleState, ExtremeState, LOSS_ORDER, OBS_ORDER, PackedField, RegionState, SpellState, pde_losses, pde_losses_batch, point_buffers, point_fields, point_sizes,
                           PointConfig, require_gpu, smooth_l1_data_loss, step_losses, step_losses_batch)
 from ..sampler import SyntheticSamples
 from ..staged_backward import StagedBackward
@@ -90,6 +91,7 @@ class InterfacePhysics(nn.Module):
         self.last_trajectories = None           # run_inference_interface with inference_cfg.trajectories: the last sample's trajectories() dict (lonlat)
         self.last_diagnostics = None            # run_inference_interface with log.export_diagnostic: {'names', 'maps' [nt, P, ny, nx]} of the last sample
         self.last_ensemble = None               # run_inference_interface with inference_cfg.ensemble: ensemble_lattice's dict over all samples
+        self.last_regions = None                # run_inference_interface with inference_cfg.regions: the last sample's regional_lattice dict
 
     # ------------------------------------------------------------------ configuration of the HIP path
     def point_config(self, loss_factor=None, criterion=None) -> PointConfig:
@@ -519,6 +521,97 @@ class InterfacePhysics(nn.Module):
         for first, n in _chunks(total, chunk):
             state.finish(first, n, maps=out, lattice=lattice)
         return dict(out, names=names, thresholds=thr)
+
+    # ------------------------------------------------------------------ regional statistics in space
+    @staticmethod
+    def _region_request(products, thresholds):
+        """The name and threshold checks of regional_at / regional_lattice: names (KeyError), at most 16 of them and the thresholds (ValueError)."""
+        names = list(products)
+        ids = ensemble_ids(names)
+        if len(ids) > RG.MAX_COLUMNS:
+            raise ValueError('regions: %d products; at most %d in one request' % (len(ids), RG.MAX_COLUMNS))
+        thr_col, thr_val = check_thresholds(names, thresholds)
+        return names, ids, thr_col, thr_val
+
+    def _region_run(self, field_data, sampler, forecast_h, plan, xs, ys, hours, request, with_clip, chunk_points):
+        """The walk of a regional request: the flat, time-major point list (positions xs, ys [n_sel] of the plan's entries at every hour of `hours`
+        [nt], fp64 on the host) goes through the station route of dpn_sample_at chunk by chunk -- sample_at -> forward -> region_accumulate --, then
+        one finish.  Encoder, heads and packing run once; nothing is read back in between."""
+        require_gpu(field_data, 'field_data', 'regions')
+        names, ids, thr_col, thr_val = request
+        nt, n_sel, dev = hours.size, plan.n_sel, field_data.device
+        state = RegionState(plan, nt, ids, thr_col, thr_val, dev)              # (refuses nt * n_sel >= 2^31)
+        total = nt * n_sel
+        chunk = self.chunk_size(total, chunk_points, self.DIAG_POINT_BYTES, self.precision)
+        field = self._inference_weights(field_data, forecast_h, chunk)
+        xr, yr = (torch.from_numpy(np.ascontiguousarray(np.tile(v, nt), dtype=np.float64)).to(dev) for v in (xs, ys))
+        tr = torch.from_numpy(np.ascontiguousarray(np.repeat(hours, n_sel), dtype=np.float64)).to(dev)
+        bufs = point_buffers(chunk, dev)
+        for first, n in _chunks(total, chunk):
+            x, y, t, f, cd = sampler.sample_at(n, xr[first:first + n], yr[first:first + n], tr[first:first + n], out=bufs)
+            field.region_accumulate(x, y, t, f, cd, state, first, with_clip)
+        out = state.finish()
+        order = torch.from_numpy(plan.order).to(dev)
+        for key in ('where_min', 'where_max'):                                # entries of the plan -> station indices or (ix, iy); -1 stays
+            j = out[key].long()
+            at = torch.where(j >= 0, order[j.clamp(min=0)], j)
+            if plan.shape is not None:
+                nx = plan.shape[1]
+                at = torch.where((j >= 0).unsqueeze(-1), torch.stack([at % nx, at // nx], dim=-1), j.unsqueeze(-1))
+            out[key] = at
+        return dict(out, names=names, thresholds=[(names[c], v) for c, v in zip(thr_col, thr_val)])
+
+    @torch.no_grad()
+    def regional_lattice(self, field_data, sampler, lattice, forecast_h, regions, products, weights=None, thresholds=None, with_clip=False,
+                         chunk_points=None):
+        """A number per area and hour: the area-weighted mean of a product over a catchment, the peak wind inside a polygon and where it sits, the
+        share of a district below freezing -- without building the maps.  regions: an int label plane [ny, nx] over the lattice's positions (-1: in
+        no region, ids 0..R - 1) or a list of R boolean masks, which may overlap.  products: up to 16 names of
+        deepphysinet_amd.ensemble.ENSEMBLE_PRODUCTS; weights: None (ones), 'area' (float32(cos(latitude of the row))) or a non-negative finite plane
+        [ny, nx]; thresholds: dict name -> value(s), at most 16 in all.  Only the positions inside a region are evaluated, at every time node of the
+        lattice; a request without a product that reads the Jacobian runs the fields-only forward.  The reduction is deterministic (no atomics, one
+        fixed order: deepphysinet_amd.regions), so two runs and any chunk_points give the same bits.  Returns {'names', 'thresholds' [(name, value)],
+        'mean' (the weighted mean), 'total' (sum of weight * value), 'weight' (the counted weight), 'min', 'max' [nt, R, P] fp32, 'count' [nt, R, P]
+        int32, 'where_min', 'where_max' [nt, R, P, 2] int64 (ix, iy on the lattice; -1 without a counted point), 'frac' [nt, R, E] fp32 (the share
+        of the counted weight strictly above the threshold; None without thresholds)}, on the device.  A point whose value is not finite (outside
+        the coarse cube) or whose weight is 0 is skipped in that column; a cell without a counted point has count 0, weight 0 and NaN elsewhere.
+        KeyError: an unknown name; ValueError: labels that are not (ny, nx), a bad weight or threshold -- all before the first launch."""
+        request = self._region_request(products, thresholds)
+        shape = (lattice.ny, lattice.nx)
+        X_, Y_, T_ = lattice.positions()
+        plane = lattice.ny * lattice.nx
+        lat_deg = RG.row_latitudes(sampler.cfg, Y_[:plane:lattice.nx]) if isinstance(weights, str) else None
+        if torch.is_tensor(weights):
+            weights = weights.detach().cpu().numpy()
+        plan = RG.region_plan(regions, weights, lat_deg)
+        if plan.shape != shape:
+            raise ValueError('regional_lattice: the regions are planes of shape %s, the lattice is (ny, nx) = %s' % (plan.shape, shape))
+        return self._region_run(field_data, sampler, forecast_h, plan, X_[:plane][plan.order], Y_[:plane][plan.order], T_[::plane], request, with_clip,
+                                chunk_points)
+
+    @torch.no_grad()
+    def regional_at(self, field_data, sampler, x_idx, y_idx, hours, forecast_h, groups, products, weights=None, thresholds=None, with_clip=False,
+                    lonlat=False):
+        """regional_lattice for N stations in groups: positions as predict_points takes them (lonlat: degrees east / north), hours the 1-d list of
+        the nt time nodes shared by all stations, groups [N] int (-1: in none), weights None, 'area' (the cosine of the station's latitude) or [N].
+        The outputs are [nt, R, P] ([nt, R, E]), where_min / where_max [nt, R, P] the station index."""
+        request = self._region_request(products, thresholds)
+        hours = np.ascontiguousarray(np.atleast_1d(hours.detach().cpu().numpy() if torch.is_tensor(hours) else np.asarray(hours)), dtype=np.float64)
+        if hours.ndim != 1 or hours.size == 0:
+            raise ValueError('regional_at: hours is the 1-d list of the time nodes shared by all stations, got shape %s' % (hours.shape,))
+        x_idx, y_idx = (np.atleast_1d(v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)).reshape(-1) for v in (x_idx, y_idx))
+        if lonlat:
+            x_idx, y_idx = sampler.lonlat_to_index(x_idx, y_idx)
+        if x_idx.size != y_idx.size:
+            raise ValueError('regional_at: x_idx and y_idx must have the same length')
+        if torch.is_tensor(weights):
+            weights = weights.detach().cpu().numpy()
+        plan = RG.region_plan(groups=groups, weights=weights, lat_deg=RG.row_latitudes(sampler.cfg, y_idx) if isinstance(weights, str) else None)
+        if plan.n_candidates != x_idx.size:
+            raise ValueError('regional_at: %d groups for %d stations' % (plan.n_candidates, x_idx.size))
+        for h in (hours.min(), hours.max()):                                  # every station at the first and the last hour: IndexError outside
+            sampler.check_positions(x_idx, y_idx, np.full(x_idx.size, h))
+        return self._region_run(field_data, sampler, forecast_h, plan, x_idx[plan.order], y_idx[plan.order], hours, request, with_clip, None)
 
     @torch.no_grad()
     def trajectories(self, field_data, sampler, x_idx, y_idx, hours, forecast_h, duration_hours, step_hours, method='rk4', lonlat=False,
@@ -1757,6 +1850,14 @@ class InterfacePhysics(nn.Module):
         `<time>_spell_<hours|first|last|first_lo|last_hi|excess|crossings|status>_<product>_<side>_<threshold>.npy` [lat, lon] (stations: one
         `<time>_spell_<hours|...>.npy` [N, C] each) go next to the maps.  A malformed column (KeyError) or a bad threshold, window, scan step or round
         count (ValueError) fails before the checkpoint is read.
+        inference_cfg.regions (default absent: no further call) = dict(products=[names of deepphysinet_amd.ensemble.ENSEMBLE_PRODUCTS, at most 16],
+        labels=<an int plane [ny, nx] over the lattice, -1 = in no region, or the path of its .npy>, weights=None | 'area' | <a plane or its .npy>,
+        thresholds={name: [values]}): per sample, after the maps, ONE regional_lattice call on the lattice the loop evaluates, with the same
+        with_clip; the last sample's dict stays in self.last_regions, and with log.write_source
+        `<time>_region_<mean|total|weight|min|max|where_min|where_max|count>_<name>.npy` [nt, R] (where_*: [nt, R, 2], ix and iy) and
+        `<time>_region_frac_<name>_gt_<value>.npy` [nt, R] go next to the maps, <time> the sample's first time step.  An unknown name (KeyError) or
+        a bad threshold, label plane or weight (ValueError) fails before the checkpoint is read; labels of another shape than the lattice's at
+        the first sample.
         Plotting (log.with_vis: Basemap) is not built."""
         import datetime
         ic = self.inference_cfg or {}
@@ -1803,6 +1904,19 @@ class InterfacePhysics(nn.Module):
             ensemble_ids(ens['products'])                                 # an unknown name (KeyError), a bad threshold (ValueError): before the
             check_thresholds(ens['products'], ens['thresholds'])          # checkpoint is read
         self.last_ensemble = None
+        reg = ic.get('regions')
+        if reg:
+            unknown = set(reg) - {'products', 'labels', 'weights', 'thresholds'}
+            if unknown or 'products' not in reg or reg.get('labels') is None:
+                raise ValueError('inference_cfg.regions: products and labels (weights, thresholds optional); unknown keys %s' % sorted(unknown))
+            reg = dict(products=list(reg['products']), thresholds=dict(reg.get('thresholds') or {}), labels=reg['labels'], weights=reg.get('weights'))
+            self._region_request(reg['products'], reg['thresholds'])      # an unknown name (KeyError), a bad threshold (ValueError), and below a
+            for key in ('labels', 'weights'):                             # bad label plane or weight (ValueError): before the checkpoint is read
+                if isinstance(reg[key], os.PathLike) or (isinstance(reg[key], str) and reg[key].endswith('.npy')):
+                    reg[key] = np.load(reg[key])
+            rows = RG.region_plan(reg['labels']).shape[0]                 # (the shape itself is the first sample's lattice's to refuse)
+            RG.region_plan(reg['labels'], reg['weights'], np.zeros(rows) if isinstance(reg['weights'], str) else None)
+        self.last_regions = None
         windows = []                                                      # (a row of _WINDOW_PRODUCTS, its options) of the keys that are set
         for row in self._WINDOW_PRODUCTS:
             key, _, check, _, _, last = row
@@ -1869,8 +1983,20 @@ class InterfacePhysics(nn.Module):
                     setattr(self, last, getattr(self, on_lattice)(*args, sampler.lattice(refine=refine, hours=0.0), **kw))
                 else:
                     setattr(self, last, getattr(self, at_stations)(*args, *opt['lonlat'], lonlat=True, **kw))
+            if reg:
+                self.last_regions = self.regional_lattice(smp['field_data'].to(device), sampler, lattice, smp['forecast_h'].to(device), reg['labels'],
+                                                          reg['products'], weights=reg['weights'], thresholds=reg['thresholds'],
+                                                          with_clip=kwargs.get('with_clip', self.with_clip))
             if write_source:
                 stamp = (start + datetime.timedelta(seconds=k * window_h * 3600.0)).strftime('%Y-%m-%d_%H_%M_%S')      # the sample's first time step
+                if reg:
+                    r = self.last_regions
+                    for key in RG.OUTPUTS:                                # one [nt, R] table per result and product (where_*: [nt, R, 2] = ix, iy)
+                        a = r[key].cpu().numpy()
+                        for j, name in enumerate(r['names']):
+                            np.save(os.path.join(result_path, '%s_region_%s_%s.npy' % (stamp, key, name)), a[:, :, j])
+                    for j, (name, value) in enumerate(r['thresholds']):
+                        np.save(os.path.join(result_path, '%s_region_frac_%s_gt_%g.npy' % (stamp, name, value)), r['frac'][:, :, j].cpu().numpy())
                 for (_, word, _, _, _, last), opt in reversed(windows):       # (the spells' files before the extremes')
                     result = dict(getattr(self, last))
                     columns = result.pop('names')

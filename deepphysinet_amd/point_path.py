@@ -15,11 +15,13 @@ from dataclasses import dataclass, field
 from collections import namedtuple
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib as L
 from . import branch, config
 from .ensemble import reads_coriolis, reads_jacobian
+from .regions import FLOAT_OUTPUTS as REGION_FLOAT_OUTPUTS, INT_OUTPUTS as REGION_INT_OUTPUTS, n_slots as region_slots
 from .grad_arena import new_grad, slot_of
 
 # configs/DeepPhysiNet_NCEP_cfg.py:64-76 -- order u10, v10, pres, t2, q2, rio (network output order)
@@ -1334,6 +1336,13 @@ class PackedField:
                                                  int(first), s.n_total, _ptr(s.count), _ptr(s.mean), _ptr(s.m2), _ptr(s.vmin), _ptr(s.vmax),
                                                  _ptr(s.exceed), _stream()), 'dpn_ensemble_accumulate')
 
+    def region_accumulate(self, x, y, t, f, coord_data, state, first=0, with_clip=False):
+        """This field at points first .. first + n of the flat point list of `state` (a RegionState; first a multiple of 64): x, y, t, f [n],
+        coord_data [n, 6], folded into the state's slots (dpn_region_accumulate).  The forward is chosen as `ensemble_accumulate` chooses it."""
+        need_j = reads_jacobian(state.ids)
+        out_n, jac_n = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=need_j, want_saved=False)
+        state.accumulate(out_n, jac_n if need_j else None, f if reads_coriolis(state.ids) else None, self._clip_physics(with_clip), first, with_clip)
+
     def residual_scores(self, x, y, t, f, coord_data, factors, k=1.0):
         """Scores of a pool of candidate points for residual-weighted sampling (CollocationSampler.get_inter_data_adaptive): `residuals` on the m
         points, then dpn_adaptive_scores -- score_i = sum_e factors[e] * res_ie ** 2 in fp64, factors = six floats in LOSS_ORDER.  Returns
@@ -1424,6 +1433,55 @@ class EnsembleState:
         L.check(L.load().dpn_ensemble_finish(_ptr(self.count), _ptr(self.mean), _ptr(self.m2), _ptr(self.vmin), _ptr(self.vmax), _ptr(self.exceed),
                                              self.n_total, len(self.ids), self.c_thr_col, len(self.thr_col), int(first), int(n), table(rows), table(maps),
                                              lat, _stream()), 'dpn_ensemble_finish')
+
+
+class RegionState:
+    """Device state of a regional-statistics request (include/dpn_hip.h: DpnRegionPlan, DpnRegionState): the plan's seg, wgt and offs on the device
+    and, for nt time nodes, the P columns `ids` and the E thresholds (thr_col, thr_val of ensemble.check_thresholds), the slot-major partials w, wx
+    [P, S] fp64, count, imin, imax [P, S] int32, vmin, vmax [P, S] fp32, wexc [E, S] fp64, all zeroed once.  `accumulate` folds a chunk of the flat
+    point list in, `finish` turns the partials into the nine outputs.  ValueError: more than 16 columns or thresholds, nt * n_sel >= 2^31."""
+
+    def __init__(self, plan, nt, ids, thr_col, thr_val, device):
+        self.plan, self.nt, self.ids, self.thr_col, self.thr_val = plan, int(nt), list(ids), list(thr_col), [float(v) for v in thr_val]
+        P, E = len(self.ids), len(self.thr_col)
+        if not 1 <= P <= L.REG_MAX_COLUMNS or E > L.REG_MAX_THRESHOLDS or len(self.thr_val) != E:
+            raise ValueError('RegionState: %d products (1..%d), %d thresholds (0..%d)' % (P, L.REG_MAX_COLUMNS, E, L.REG_MAX_THRESHOLDS))
+        self.n_slots = S = region_slots(plan, self.nt)
+        self.n_points = self.nt * plan.n_sel
+        self.c_ids = (ctypes.c_int32 * P)(*self.ids)
+        self.c_thr_col = (ctypes.c_int32 * max(E, 1))(*self.thr_col)
+        self.c_thr_val = (ctypes.c_float * max(E, 1))(*self.thr_val)
+        self.seg, self.wgt, self.offs = (torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in (plan.seg, plan.wgt, plan.offs))
+        self.c_plan = L.DpnRegionPlan(_ptr(self.seg), _ptr(self.wgt), _ptr(self.offs), plan.n_sel, plan.n_regions, self.nt)
+        self.w, self.wx = (torch.zeros((P, S), dtype=torch.float64, device=device) for _ in range(2))
+        self.count, self.imin, self.imax = (torch.zeros((P, S), dtype=torch.int32, device=device) for _ in range(3))
+        self.vmin, self.vmax = (torch.zeros((P, S), dtype=torch.float32, device=device) for _ in range(2))
+        self.wexc = torch.zeros((E, S), dtype=torch.float64, device=device) if E else None
+
+    def partials(self):
+        """The eight partial arrays by DpnRegionState's names (wexc None without thresholds)."""
+        return {k: getattr(self, k) for k in ('w', 'wx', 'count', 'vmin', 'vmax', 'imin', 'imax', 'wexc')}
+
+    def c_state(self):
+        return L.DpnRegionState(*[_ptr(v) for v in self.partials().values()])
+
+    def accumulate(self, out_n, jac_n, f, ph, first, with_clip=False):
+        """dpn_region_accumulate: out_n [n, 6] (jac_n [n, 6, 3], f [n], or None where no column reads them) of points first .. first + n."""
+        L.check(L.load().dpn_region_accumulate(_ptr(out_n), _ptr(jac_n), _ptr(f), out_n.shape[0], ctypes.byref(ph), int(bool(with_clip)), self.c_ids,
+                                               len(self.ids), self.c_thr_col, self.c_thr_val, len(self.thr_col), int(first), ctypes.byref(self.c_plan),
+                                               ctypes.byref(self.c_state()), _stream()), 'dpn_region_accumulate')
+
+    def finish(self):
+        """dpn_region_finish -> dict(mean, total, weight, min, max [nt, R, P] fp32, where_min, where_max, count [nt, R, P] int32, frac [nt, R, E] fp32
+        or None without thresholds), on the device."""
+        dev, shape = self.w.device, (self.nt, self.plan.n_regions, len(self.ids))
+        out = {k: torch.empty(shape, dtype=torch.float32, device=dev) for k in REGION_FLOAT_OUTPUTS}
+        out.update({k: torch.empty(shape, dtype=torch.int32, device=dev) for k in REGION_INT_OUTPUTS})
+        out['frac'] = torch.empty(shape[:2] + (len(self.thr_col),), dtype=torch.float32, device=dev) if self.thr_col else None
+        table = L.DpnRegionOut(*[_ptr(out[k]) for k in REGION_FLOAT_OUTPUTS + REGION_INT_OUTPUTS + ('frac',)])
+        L.check(L.load().dpn_region_finish(ctypes.byref(self.c_plan), ctypes.byref(self.c_state()), len(self.ids), self.c_thr_col, len(self.thr_col),
+                                           ctypes.byref(table), _stream()), 'dpn_region_finish')
+        return out
 
 
 class ParcelState:

@@ -669,6 +669,66 @@ int dpn_spell_refine(const DpnSampler* s, const float* cube, const DpnPhysics* p
                      double t0, double dt, const double* xr, const double* yr, const DpnSpellState* st, float* x, float* y, float* t, float* f,
                      float* coord_data, void* stream);
 int dpn_spell_finish(int64_t n, int n_columns, int K, double t0, double dt, const DpnSpellState* st, void* stream);
+/* Regional statistics in space (csrc/dpn_region.inc, compiled into csrc/dpn_diag.hip): per time node and region the weighted mean and total of a
+ * product, its minimum and maximum and where they sit, the number of points counted, and the share of the counted weight above thresholds.  A
+ * deterministic segmented reduction: no atomics, one fixed order of operations, so two runs and any chunking give the same bits.
+ * The plan (DpnRegionPlan; deepphysinet_amd/regions.py builds it) is the region-sorted list of the n_sel selected positions of a plane (or of a
+ * station list), DEVICE arrays: seg[n_sel] the region 0..n_regions - 1 of entry j, non-decreasing; wgt[n_sel] its weight, finite and >= 0;
+ * offs[n_regions + 1] the first entry of every region (offs[0] = 0, offs[n_regions] = n_sel; an empty region is allowed).  A position in k regions is
+ * listed k times; a position in none is not listed and never evaluated.  The flat point list of a request with nt time nodes is time-major:
+ * point i = it * n_sel + j (nt * n_sel < 2^31).  Its cell is c = it * n_regions + seg[j], its group g = i / DPN_REG_GROUP, its slot s = g + c: g and c
+ * are both non-decreasing in i, so every (group, cell) pair that occurs has a slot of its own.  S = ceil(nt * n_sel / DPN_REG_GROUP) + nt * n_regions.
+ * Partial state (DpnRegionState) of P = n_products columns and E = n_thr thresholds, slot-major per column:
+ *   double w[P][S], wx[P][S]; int32 count[P][S]; float vmin[P][S], vmax[P][S]; int32 imin[P][S], imax[P][S] (an entry j of the plan); double wexc[E][S].
+ * The caller zeroes the whole state once (a plain memset).  A slot is written by exactly one launch, so chunking cannot change a bit.
+ * dpn_region_accumulate takes points first .. first + n of the flat list (first a multiple of DPN_REG_GROUP; out_n, jac_n, f: that chunk's rows, *phys,
+ * with_clip, products: ids, expressions, order and NaN rule of dpn_ensemble_accumulate; jac_n / f may be NULL as there).  Within a slot the points are
+ * taken in increasing i, one after the other.  With x the product and wt = wgt[j], the point is skipped in that column if x is not finite or wt == 0;
+ * otherwise, every operation rounded on its own:
+ *   the first point of the slot sets vmin = vmax = x, imin = imax = j; a later one: if (x < vmin) vmin = x, imin = j; if (x > vmax) vmax = x, imax = j
+ *   (strict: on a tie, +0 against -0 included, the earlier point stays);  count += 1;  w = w + (double)wt;  wx = wx + (double)wt * (double)x  (the
+ *   product of two floats is exact in fp64);  for every threshold e with thr_col[e] == the column and x > thr_val[e] (strict, in float32):
+ *   wexc[e] = wexc[e] + (double)wt.
+ * A slot without a counted point keeps its zeros.  256-thread blocks cover four groups: every thread forms its point's P products into an LDS tile
+ * [P][256]; lane L < P of each wave then walks its wave's 64 points for column L, lane P + e for threshold e, and stores at every change of cell.
+ * dpn_region_finish, one thread per (cell, column): over the cell's slots (it * n_sel + offs[r]) / 64 + c .. (it * n_sel + offs[r + 1] - 1) / 64 + c
+ * in increasing order, a slot with count == 0 skipped: count, w, wx and wexc added one after the other in fp64, min / max merged by the same
+ * strict comparisons (the earlier slot stays).  Outputs (DpnRegionOut), [nt][n_regions][P] and frac [nt][n_regions][E]:
+ *   mean = (float)(wx / w); total = (float)wx; weight = (float)w; min, max; where_min, where_max = imin, imax; count; frac[e] = (float)(wexc[e] / w)
+ *   with w of column thr_col[e].  A cell without a counted point: count = 0, weight = 0, where = -1, the rest NaN.
+ * products, thr_col and thr_val are HOST arrays.
+ * -1 (nothing launched, nothing written): a NULL required pointer (thr_col, thr_val, wexc, frac: required when n_thr > 0; offs: finish; seg, wgt:
+ * accumulate); n_sel < 1; n_regions < 1; nt < 1; nt * n_sel >= 2^31; n_products outside 1..DPN_REG_MAX_COLUMNS; n_thr outside
+ * 0..DPN_REG_MAX_THRESHOLDS; a thr_col outside 0..n_products - 1.  accumulate: n <= 0; first < 0; first not a multiple of DPN_REG_GROUP;
+ * first + n > nt * n_sel; an id outside 0..DPN_ENS_PRODUCTS - 1; a threshold that is not finite; a selected id that reads J (f) while jac_n (f) is NULL. */
+#define DPN_REG_GROUP 64
+#define DPN_REG_MAX_COLUMNS 16
+#define DPN_REG_MAX_THRESHOLDS 16
+typedef struct DpnRegionPlan {
+    const int32_t* seg;
+    const float* wgt;
+    const int32_t* offs;
+    int64_t n_sel;
+    int32_t n_regions, nt;
+} DpnRegionPlan;
+typedef struct DpnRegionState {
+    double *w, *wx;
+    int32_t* count;
+    float *vmin, *vmax;
+    int32_t *imin, *imax;
+    double* wexc;
+} DpnRegionState;
+typedef struct DpnRegionOut {
+    float *mean, *total, *weight, *min, *max;
+    int32_t *where_min, *where_max, *count;
+    float* frac;
+} DpnRegionOut;
+int dpn_region_accumulate(const float* out_n, const float* jac_n, const float* f, int64_t n, const DpnPhysics* phys, int with_clip,
+                          const int32_t* products /* HOST, n_products ids */, int n_products, const int32_t* thr_col /* HOST [n_thr] */,
+                          const float* thr_val /* HOST [n_thr] */, int n_thr, int64_t first, const DpnRegionPlan* plan, const DpnRegionState* state,
+                          void* stream);
+int dpn_region_finish(const DpnRegionPlan* plan, const DpnRegionState* state, int n_products, const int32_t* thr_col /* HOST [n_thr] */, int n_thr,
+                      const DpnRegionOut* out, void* stream);
 
 /* ---------------------------------------------------------------- parcel trajectories through the learned wind (csrc/dpn_traj.hip)
  * One launch = one stage of an explicit Runge-Kutta step for n parcels whose stage positions depend only on the step's start point and the

@@ -6,6 +6,7 @@
                     [--ensemble name[,name...] [--ensemble_threshold NAME:V[,V...]]...]
                     [--extremes T:max,T:min,speed:max --extreme_window H0,H1 [--extreme_scan S] [--extreme_refine R]]
                     [--spells T:below:273.15,speed:above:15 --spell_window H0,H1 [--spell_scan S] [--spell_refine R]]
+                    [--regions name[,name...] --region_labels FILE.npy [--region_weights area|FILE.npy] [--region_threshold NAME:V[,V...]]...]
 
 Builds the interface from the config (train.py's loader), loads `physics_latest.pth` from --checkpoint_path (or inference_cfg.checkpoints) and
 calls `run_inference_interface`: every field sample is evaluated on the lattice inference_cfg.img_size (x `refine`) at every inference_cfg.dt
@@ -26,7 +27,11 @@ rounds of bisection on the network's own d/dt (InterfacePhysics.extreme_lattice)
 --spells T:below:273.15,speed:above:15 --spell_window 0,24 sets inference_cfg.spells: per sample how long the named products stay strictly below / above
 the thresholds over those hours of its window, the hour of the first entry and of the last exit, the crossings and the degree-hours, found by a scan
 every --spell_scan hours and --spell_refine rounds of bisection on the sign of value - threshold (InterfacePhysics.spell_lattice), written as
-<time>_spell_<hours|first|last|first_lo|last_hi|excess|crossings|status>_*.npy maps."""
+<time>_spell_<hours|first|last|first_lo|last_hi|excess|crossings|status>_*.npy maps.
+--regions vorticity,speed,T --region_labels catchments.npy --region_weights area --region_threshold T:273.15 sets inference_cfg.regions: per sample and
+time step the area-weighted mean, total, minimum and maximum (and where they sit) of the named products over every region of the label plane, and the
+share of each region above the thresholds (InterfacePhysics.regional_lattice: only the points inside a region are evaluated), written as
+<time>_region_*.npy tables [time steps, regions]."""
 import argparse
 
 import torch
@@ -64,6 +69,12 @@ parse.add_argument('--spell_window', default=None, type=lambda s: tuple(float(v)
                    help='H0,H1: the hours of the sample window the spells are looked for in')
 parse.add_argument('--spell_scan', default=1.0, type=float, help='hours between the scan nodes')
 parse.add_argument('--spell_refine', default=10, type=int, help='bisection rounds after the scan (0..32)')
+parse.add_argument('--regions', default=None, type=lambda s: [n for n in s.split(',') if n],
+                   help='name[,name...]: inference_cfg.regions.products, statistics per region and time step (deepphysinet_amd.ensemble.ENSEMBLE_PRODUCTS)')
+parse.add_argument('--region_labels', default=None, type=str, help='FILE.npy: the int label plane [lat, lon] of the regions, -1 = in no region')
+parse.add_argument('--region_weights', default=None, type=str, help="area (the cosine of the row's latitude) or FILE.npy, a plane of weights; default: ones")
+parse.add_argument('--region_threshold', default=[], action='append', type=str,
+                   help='NAME:V[,V...] (repeatable): inference_cfg.regions.thresholds, the share of the region where product NAME exceeds V')
 
 
 def _window_option(args, key, word):
@@ -95,13 +106,31 @@ def ensemble_option(args):
         if args.ensemble_threshold:
             parse.error('--ensemble_threshold needs --ensemble')
         return None
+    return dict(products=list(args.ensemble), thresholds=_thresholds(args.ensemble_threshold, '--ensemble_threshold'))
+
+
+def _thresholds(items, flag):
+    """{name: [values]} of the repeated NAME:V[,V...] items of `flag`."""
     thresholds = {}
-    for item in args.ensemble_threshold:
+    for item in items:
         name, sep, values = item.partition(':')
         if not sep or not name or not values:
-            parse.error('--ensemble_threshold takes NAME:V[,V...], got %r' % item)
+            parse.error('%s takes NAME:V[,V...], got %r' % (flag, item))
         thresholds.setdefault(name, []).extend(float(v) for v in values.split(',') if v)
-    return dict(products=list(args.ensemble), thresholds=thresholds)
+    return thresholds
+
+
+def regions_option(args):
+    """inference_cfg['regions'] of --regions / --region_labels / --region_weights / --region_threshold: dict(products=[...], labels=FILE.npy,
+    weights=None | 'area' | FILE.npy, thresholds={name: [values]}), or None without --regions."""
+    if not args.regions:
+        if args.region_labels or args.region_weights or args.region_threshold:
+            parse.error('--region_labels, --region_weights and --region_threshold need --regions')
+        return None
+    if not args.region_labels:
+        parse.error('--regions needs --region_labels FILE.npy')
+    return dict(products=list(args.regions), labels=args.region_labels, weights=args.region_weights,
+                thresholds=_thresholds(args.region_threshold, '--region_threshold'))
 
 
 if __name__ == '__main__':
@@ -123,6 +152,8 @@ if __name__ == '__main__':
         cfg.setdefault('inference_cfg', {})['extremes'] = extremes_option(args)
     if spells_option(args):
         cfg.setdefault('inference_cfg', {})['spells'] = spells_option(args)
+    if regions_option(args):
+        cfg.setdefault('inference_cfg', {})['regions'] = regions_option(args)
     model = builder_models(**cfg)
     kwargs = dict(checkpoint_path=args.checkpoint_path)
     if args.synthetic:
@@ -150,3 +181,7 @@ if __name__ == '__main__':
     if model.last_spells is not None:
         x = model.last_spells
         print('spells %s: hours %s, status %s' % (','.join(x['names']), tuple(x['hours'].shape), sorted(set(x['status'].reshape(-1).tolist()))))
+    if model.last_regions is not None:
+        r = model.last_regions
+        print('regions %s: mean %s, points counted %d..%d, thresholds %s' % (','.join(r['names']), tuple(r['mean'].shape), int(r['count'].min()),
+                                                                           int(r['count'].max()), r['thresholds']))
