@@ -9,7 +9,8 @@
 // The unit also holds the member axis of the same product table, dpn_ensemble_accumulate / dpn_ensemble_finish (dpn_ensemble.inc, included at the end),
 // and its time axis, the window extremes and means dpn_extreme_scan / dpn_extreme_begin / dpn_extreme_refine (dpn_extreme.inc, included behind it)
 // and the threshold spells dpn_spell_scan / dpn_spell_begin / dpn_spell_refine / dpn_spell_finish (dpn_spell.inc, behind that), and its space axis,
-// the regional statistics dpn_region_accumulate / dpn_region_finish (dpn_region.inc, last).
+// the regional statistics dpn_region_accumulate / dpn_region_finish (dpn_region.inc), and the case axis of its value products, the verification
+// against observations dpn_verify_accumulate / dpn_verify_pool / dpn_verify_finish (dpn_verify.inc, last).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/dpn_hip.h"
@@ -108,3 +109,4 @@ int dpn_diagnostics_out(const float* out_n, const float* jac_n, const float* f, 
 #include "dpn_extreme.inc"           // window extremes and means in time: dpn_extreme_scan, dpn_extreme_begin, dpn_extreme_refine
 #include "dpn_spell.inc"             // threshold spells in time: dpn_spell_scan, dpn_spell_begin, dpn_spell_refine, dpn_spell_finish
 #include "dpn_region.inc"            // regional statistics in space: dpn_region_accumulate, dpn_region_finish
+#include "dpn_verify.inc"            // verification against observations: dpn_verify_accumulate, dpn_verify_pool, dpn_verify_finish

@@ -23,6 +23,7 @@ from . import branch, config
 from .ensemble import reads_coriolis, reads_jacobian
 from .regions import FLOAT_OUTPUTS as REGION_FLOAT_OUTPUTS, INT_OUTPUTS as REGION_INT_OUTPUTS, n_slots as region_slots
 from .grad_arena import new_grad, slot_of
+from . import verification as VF
 
 # configs/DeepPhysiNet_NCEP_cfg.py:64-76 -- order u10, v10, pres, t2, q2, rio (network output order)
 OBS_ORDER = ('u10', 'v10', 'pres', 't2', 'q2', 'rio')
@@ -1343,6 +1344,13 @@ class PackedField:
         out_n, jac_n = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=need_j, want_saved=False)
         state.accumulate(out_n, jac_n if need_j else None, f if reads_coriolis(state.ids) else None, self._clip_physics(with_clip), first, with_clip)
 
+    def verify_accumulate(self, x, y, t, coord_data, obs, state, first=0, with_clip=False):
+        """This field, as one case (forecast date) of a verification, at points x, y, t [n], coord_data [n, 6], against the reports obs [n, P] fp32
+        (NaN: none), folded into `state` (a VerifyState) at its points first .. first + n: the fields-only forward, then one dpn_verify_accumulate
+        launch, which forms the baseline from coord_data itself.  with_clip as `diagnostics` takes it, on forecast and baseline alike."""
+        out_n, _ = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=False, want_saved=False)
+        state.accumulate(out_n, coord_data, obs, self._clip_physics(with_clip), first, with_clip)
+
     def residual_scores(self, x, y, t, f, coord_data, factors, k=1.0):
         """Scores of a pool of candidate points for residual-weighted sampling (CollocationSampler.get_inter_data_adaptive): `residuals` on the m
         points, then dpn_adaptive_scores -- score_i = sum_e factors[e] * res_ie ** 2 in fp64, factors = six floats in LOSS_ORDER.  Returns
@@ -1433,6 +1441,94 @@ class EnsembleState:
         L.check(L.load().dpn_ensemble_finish(_ptr(self.count), _ptr(self.mean), _ptr(self.m2), _ptr(self.vmin), _ptr(self.vmax), _ptr(self.exceed),
                                              self.n_total, len(self.ids), self.c_thr_col, len(self.thr_col), int(first), int(n), table(rows), table(maps),
                                              lat, _stream()), 'dpn_ensemble_finish')
+
+
+class VerifyState:
+    """Device state of a verification request (include/dpn_hip.h: DpnVerifyState): for n_total points (or groups), the P columns `ids`
+    (verification.verify_ids) and the E thresholds (thr_col, thr_val, thr_side of verification.check_thresholds), product-major: n [P, n_total] int32,
+    the eleven fp64 arrays of verification.STATE_F64, max_ad [P, n_total] fp32 and cont [E, 6, n_total] int32 -- views of ONE zeroed buffer, so the
+    whole state is cleared by one memset.  `accumulate` folds one case's chunk in, `pool` makes the state of groups of points, `finish` turns
+    points first .. first + n into the scores."""
+
+    def __init__(self, n_total, ids, thr_col, thr_val, thr_side, device):
+        self.n_total, self.ids = int(n_total), list(ids)
+        self.thr_col, self.thr_val, self.thr_side = list(thr_col), [float(v) for v in thr_val], list(thr_side)
+        P, E, N = len(self.ids), len(self.thr_col), self.n_total
+        if not 1 <= P <= L.VERIFY_MAX_COLUMNS or E > L.VERIFY_MAX_THRESHOLDS or len(self.thr_val) != E or len(self.thr_side) != E or N < 1:
+            raise ValueError('VerifyState: %d points, %d products (1..%d), %d thresholds (0..%d)'
+                             % (N, P, L.VERIFY_MAX_COLUMNS, E, L.VERIFY_MAX_THRESHOLDS))
+        self.c_ids = (ctypes.c_int32 * P)(*self.ids)
+        self.c_thr_col = (ctypes.c_int32 * max(E, 1))(*self.thr_col)
+        self.c_thr_val = (ctypes.c_float * max(E, 1))(*self.thr_val)
+        self.c_thr_side = (ctypes.c_int32 * max(E, 1))(*self.thr_side)
+        n64 = len(VF.STATE_F64)
+        self.buffer = torch.zeros(P * N * (8 * n64 + 8) + 24 * E * N, dtype=torch.uint8, device=device)      # the doubles first: every view aligned
+        at = 0
+        for k in VF.STATE_F64:
+            setattr(self, k, self.buffer[at:at + 8 * P * N].view(torch.float64).view(P, N))
+            at += 8 * P * N
+        self.n = self.buffer[at:at + 4 * P * N].view(torch.int32).view(P, N)
+        at += 4 * P * N
+        self.max_ad = self.buffer[at:at + 4 * P * N].view(torch.float32).view(P, N)
+        at += 4 * P * N
+        self.cont = self.buffer[at:at + 24 * E * N].view(torch.int32).view(E, 6, N) if E else None
+
+    def clear(self):
+        """Back to the state before the first case: one memset."""
+        self.buffer.zero_()
+
+    def arrays(self):
+        """The fourteen arrays by DpnVerifyState's names (cont None without thresholds)."""
+        return {k: getattr(self, k) for k in VF.STATE_FIELDS}
+
+    def c_state(self):
+        return L.DpnVerifyState(*[_ptr(v) for v in self.arrays().values()])
+
+    def accumulate(self, out_n, coord_data, obs, ph, first=0, with_clip=False):
+        """dpn_verify_accumulate: one case's out_n [n, 6], coord_data [n, 6] and obs [n, P] (fp32, contiguous) at points first .. first + n."""
+        n, P = out_n.shape[0], len(self.ids)
+        if tuple(obs.shape) != (n, P) or obs.dtype != torch.float32 or not obs.is_contiguous() or tuple(coord_data.shape) != (n, 6):
+            raise ValueError('VerifyState.accumulate: obs must be a contiguous fp32 [%d, %d] and coord_data [%d, 6], got %s %s and %s'
+                             % (n, P, n, tuple(obs.shape), obs.dtype, tuple(coord_data.shape)))
+        L.check(L.load().dpn_verify_accumulate(_ptr(out_n), _ptr(_f32c(coord_data)), _ptr(obs), n, ctypes.byref(ph), int(bool(with_clip)), self.c_ids, P,
+                                               self.c_thr_col, self.c_thr_val, self.c_thr_side, len(self.thr_col), int(first), self.n_total,
+                                               ctypes.byref(self.c_state()), _stream()), 'dpn_verify_accumulate')
+
+    def upload_plan(self, order, seg_start):
+        """A plan of verification.pool_plan's (order [N] int32, seg_start [G + 1] int64, numpy) checked and put on the device, for `pool`: a caller
+        that must not wait for the device between its launches uploads its plans before the first of them."""
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        seg_start = np.ascontiguousarray(seg_start, dtype=np.int64)
+        if order.shape != (self.n_total,) or seg_start.ndim != 1 or seg_start.size < 2:
+            raise ValueError('VerifyState.pool: order [%d] and seg_start [G + 1], got %s and %s' % (self.n_total, order.shape, seg_start.shape))
+        dev = self.buffer.device
+        return seg_start, torch.from_numpy(order).to(dev), torch.from_numpy(seg_start).to(dev)
+
+    def pool(self, order=None, seg_start=None, plan=None):
+        """dpn_verify_pool: the state of the G = len(seg_start) - 1 groups of verification.pool_plan's (order, seg_start), or of a `plan` that
+        `upload_plan` returned; a new VerifyState of the same columns and thresholds."""
+        seg_start, d_order, d_seg = self.upload_plan(order, seg_start) if plan is None else plan
+        G = seg_start.size - 1
+        out = VerifyState(G, self.ids, self.thr_col, self.thr_val, self.thr_side, self.buffer.device)
+        L.check(L.load().dpn_verify_pool(ctypes.byref(self.c_state()), self.n_total, _ptr(d_order), _ptr(d_seg),
+                                         seg_start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), G, len(self.ids), self.c_thr_col, len(self.thr_col),
+                                         ctypes.byref(out.c_state()), _stream()), 'dpn_verify_pool')
+        out._plan = (d_order, d_seg)                                      # alive until the launch has read them
+        return out
+
+    def finish(self, first=0, n=None, rows=None):
+        """dpn_verify_finish for points first .. first + n (default: all): rows = a dict of verification.OUT_FIELDS tensors ([n, P]; the threshold
+        scores [n, E], None without thresholds), made here when not given.  Returns rows."""
+        n = self.n_total - int(first) if n is None else int(n)
+        dev, P, E = self.buffer.device, len(self.ids), len(self.thr_col)
+        if rows is None:
+            rows = {'count': torch.empty((n, P), dtype=torch.int32, device=dev)}
+            rows.update({k: torch.empty((n, P), dtype=torch.float32, device=dev) for k in VF.SCORES})
+            rows.update({k: torch.empty((n, E), dtype=torch.float32, device=dev) if E else None for k in VF.THRESHOLD_SCORES})
+        table = L.DpnVerifyOut(*[_ptr(rows.get(k)) for k in VF.OUT_FIELDS])
+        L.check(L.load().dpn_verify_finish(ctypes.byref(self.c_state()), self.n_total, P, self.c_thr_col, E, int(first), n, ctypes.byref(table),
+                                           _stream()), 'dpn_verify_finish')
+        return rows
 
 
 class RegionState:

@@ -729,6 +729,83 @@ int dpn_region_accumulate(const float* out_n, const float* jac_n, const float* f
                           void* stream);
 int dpn_region_finish(const DpnRegionPlan* plan, const DpnRegionState* state, int n_products, const int32_t* thr_col /* HOST [n_thr] */, int n_thr,
                       const DpnRegionOut* out, void* stream);
+/* Forecast verification against observations (csrc/dpn_verify.inc, compiled into csrc/dpn_diag.hip): per point and column the error of the forecast
+ * and of the baseline -- the interpolated coarse forecast, coord_data -- against reports, folded case by case (one forecast date each) into a resident
+ * fp64 state, pooled over groups of points in one fixed order, and turned into scores.  No atomics anywhere: two runs give the same bits.
+ * Columns: P = n_products (1..DPN_VERIFY_MAX_COLUMNS) HOST ids out of the value products 28..33 (u, v, p, T, q, rho), 25 (speed) and 26
+ * (rel_humidity); ids may repeat.  The forecast value x of a column is formed exactly as dpn_ensemble_accumulate forms that id from out_n (the
+ * residual body's val, with_clip as dpn_diagnostics_out takes it, J = 0: the fields-only forward; a point with a NaN among its six out_n is NaN in
+ * every column).  The baseline value b is formed by the same code from coord_data [n][6] in the place of out_n: for ids 28..33 what dpn_fields_out
+ * writes for out_n := coord_data, for 25 and 26 what dpn_diagnostics_out writes; with_clip applies to both sides.  The observation o = obs[i][j]
+ * (fp32 [n][P], physical units, NaN = no report) is never clipped.
+ * Thresholds: E = n_thr (0..DPN_VERIFY_MAX_THRESHOLDS) HOST triples (thr_col[e] the column, thr_val[e] finite, thr_side[e] = DPN_VERIFY_ABOVE or
+ * _BELOW).  A value z is an event when z > thr_val (above) or z < thr_val (below): strict, compared in float32.
+ * State (DpnVerifyState) of n_total points, product-major (a wave's accesses run along the points), zeroed by the caller with one memset:
+ *   int32 n[P][n_total]; double mean_f, mean_o, m2_f, m2_o, c_fo, sum_d, sum_ad, sum_d2, sum_e, sum_ae, sum_e2 [P][n_total]; float max_ad[P][n_total];
+ *   int32 cont[E][6][n_total]: hits, false alarms, misses of the forecast, then of the baseline.
+ * dpn_verify_accumulate folds ONE case at points first .. first + n (out_n, coord_data, obs: that chunk's rows).  A (point, column) pair is counted
+ * only when x, b and o are all finite; otherwise nothing of that column changes.  Per counted pair, every operation an fp64 operation rounded on
+ * its own (the kernels are compiled without contraction), left to right, with X = (double)x, O = (double)o, B = (double)b:
+ *   c = n + 1
+ *   df = X - mean_f;  mean_f = mean_f + df / (double)c;  dq = O - mean_o;  mean_o = mean_o + dq / (double)c
+ *   m2_f = m2_f + df * (X - mean_f);  m2_o = m2_o + dq * (O - mean_o);  c_fo = c_fo + df * (O - mean_o)          (the new means)
+ *   d = X - O;  sum_d = sum_d + d;  sum_ad = sum_ad + fabs(d);  sum_d2 = sum_d2 + d * d;  a = (float)fabs(d);  if (a > max_ad) max_ad = a
+ *   e = B - O;  sum_e = sum_e + e;  sum_ae = sum_ae + fabs(e);  sum_e2 = sum_e2 + e * e;  n = c
+ *   for every threshold t with thr_col[t] == j, ev(.) the event test:   hits += ev(x) && ev(o);  false alarms += ev(x) && !ev(o);
+ *   misses += !ev(x) && ev(o);  the same three with b in the place of x.  Correct negatives are n minus the three.
+ * One thread per point, 256-thread blocks, the columns looped inside the thread, no atomics, no LDS, plain vector stores.
+ * dpn_verify_pool pools the states of N points into the states of G groups (the same layout, n_total = G; written, not accumulated).  order
+ * [N] int32 (DEVICE) is a stable sort of the points by group, seg_start [G + 1] int64 (DEVICE, and the same numbers in seg_start_host, which is the
+ * copy that is checked) the first place of every group in it; an empty group is allowed, an order entry outside 0..N - 1 is skipped.  One 64-lane
+ * wave per (group, column): lane l left-folds the states of places l, l + 64, l + 128, .. of its segment in that order, then lane 0 left-folds the
+ * 64 lane results in lane order.  A fold step merges an earlier state A with a later state B: when B is empty (n == 0) A stays as it is, when A is
+ * empty the result is B, otherwise (Chan's pairwise merge), every operation rounded on its own, left to right:
+ *   n = nA + nB;  w = ((double)nA * (double)nB) / (double)n;  r = (double)nB / (double)n
+ *   gf = mean_fB - mean_fA;  go = mean_oB - mean_oA
+ *   m2_f = (m2_fA + m2_fB) + (gf * gf) * w;  m2_o = (m2_oA + m2_oB) + (go * go) * w;  c_fo = (c_foA + c_foB) + (gf * go) * w
+ *   mean_f = mean_fA + gf * r;  mean_o = mean_oA + go * r
+ *   every sum: A + B;  max_ad: B's when it is greater (strict), else A's.
+ * The contingency counts of a threshold are added (int32) over the segment of its column.  A fixed order and no atomics: two runs give the same
+ * bits, and so does any chunking of the accumulate calls before.
+ * dpn_verify_finish writes, for points (or groups) first .. first + n, rows [n][P] (DpnVerifyOut), every float an fp32 cast of the fp64 result, with
+ * N = (double)n of the column:
+ *   count = n;  bias = sum_d / N;  mae = sum_ad / N;  rmse = sqrt(sum_d2 / N);  max_abs_error = max_ad;  corr = c_fo / sqrt(m2_f * m2_o), NaN when
+ *   n < 2 or m2_f == 0 or m2_o == 0;  base_bias = sum_e / N;  base_mae = sum_ae / N;  base_rmse = sqrt(sum_e2 / N);  skill = 1.0 - sum_d2 / sum_e2,
+ *   NaN when sum_e2 == 0;  every score NaN when n == 0
+ * and per threshold [n][E], for the forecast and (base_*) for the baseline, with h, f, m the three counts as doubles and N of column thr_col[e]:
+ *   pod = h / (h + m);  far = f / (h + f);  csi = h / ((h + f) + m);  fbias = (h + f) / (h + m);
+ *   ets = (h - hr) / (((h + f) + m) - hr) with hr = ((h + f) * (h + m)) / N                           each NaN where its denominator is 0 (n == 0: all).
+ * The ten threshold destinations may be NULL when n_thr == 0.
+ * -1 (nothing launched, nothing written), all three: a NULL required pointer (the state's fourteen; cont, thr_col, thr_val, thr_side and the ten
+ * threshold destinations: required when n_thr > 0); n <= 0; first < 0; first + n > n_total; n_products outside 1..DPN_VERIFY_MAX_COLUMNS; n_thr outside
+ * 0..DPN_VERIFY_MAX_THRESHOLDS; a thr_col outside 0..n_products - 1.  accumulate: an id other than 25, 26, 28..33; a side other than the two; a
+ * threshold that is not finite.  pool: N <= 0; G <= 0; seg_start_host not non-decreasing from 0 to N. */
+#define DPN_VERIFY_MAX_COLUMNS 16
+#define DPN_VERIFY_MAX_THRESHOLDS 16
+#define DPN_VERIFY_ABOVE 0
+#define DPN_VERIFY_BELOW 1
+typedef struct DpnVerifyState {
+    int32_t* n;
+    double *mean_f, *mean_o, *m2_f, *m2_o, *c_fo;
+    double *sum_d, *sum_ad, *sum_d2;
+    double *sum_e, *sum_ae, *sum_e2;
+    float* max_ad;
+    int32_t* cont;
+} DpnVerifyState;
+typedef struct DpnVerifyOut {
+    int32_t* count;
+    float *bias, *mae, *rmse, *max_abs_error, *corr, *base_bias, *base_mae, *base_rmse, *skill;
+    float *pod, *far, *csi, *fbias, *ets, *base_pod, *base_far, *base_csi, *base_fbias, *base_ets;
+} DpnVerifyOut;
+int dpn_verify_accumulate(const float* out_n, const float* coord_data, const float* obs, int64_t n, const DpnPhysics* phys, int with_clip,
+                          const int32_t* products /* HOST, n_products ids */, int n_products, const int32_t* thr_col /* HOST [n_thr] */,
+                          const float* thr_val /* HOST [n_thr] */, const int32_t* thr_side /* HOST [n_thr] */, int n_thr, int64_t first,
+                          int64_t n_total, const DpnVerifyState* state, void* stream);
+int dpn_verify_pool(const DpnVerifyState* points, int64_t n_points, const int32_t* order /* DEVICE [n_points] */,
+                    const int64_t* seg_start /* DEVICE [n_groups + 1] */, const int64_t* seg_start_host /* HOST, the same */, int64_t n_groups,
+                    int n_products, const int32_t* thr_col /* HOST [n_thr] */, int n_thr, const DpnVerifyState* groups, void* stream);
+int dpn_verify_finish(const DpnVerifyState* state, int64_t n_total, int n_products, const int32_t* thr_col /* HOST [n_thr] */, int n_thr,
+                      int64_t first, int64_t n, const DpnVerifyOut* rows, void* stream);
 
 /* ---------------------------------------------------------------- parcel trajectories through the learned wind (csrc/dpn_traj.hip)
  * One launch = one stage of an explicit Runge-Kutta step for n parcels whose stage positions depend only on the step's start point and the

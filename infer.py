@@ -7,6 +7,7 @@
                     [--extremes T:max,T:min,speed:max --extreme_window H0,H1 [--extreme_scan S] [--extreme_refine R]]
                     [--spells T:below:273.15,speed:above:15 --spell_window H0,H1 [--spell_scan S] [--spell_refine R]]
                     [--regions name[,name...] --region_labels FILE.npy [--region_weights area|FILE.npy] [--region_threshold NAME:V[,V...]]...]
+                    [--verify name[,name...] --verify_obs FILE.npz [--verify_threshold NAME:[above|below:]V[,V...]]... [--verify_by station,hour,all]]
 
 Builds the interface from the config (train.py's loader), loads `physics_latest.pth` from --checkpoint_path (or inference_cfg.checkpoints) and
 calls `run_inference_interface`: every field sample is evaluated on the lattice inference_cfg.img_size (x `refine`) at every inference_cfg.dt
@@ -31,7 +32,12 @@ every --spell_scan hours and --spell_refine rounds of bisection on the sign of v
 --regions vorticity,speed,T --region_labels catchments.npy --region_weights area --region_threshold T:273.15 sets inference_cfg.regions: per sample and
 time step the area-weighted mean, total, minimum and maximum (and where they sit) of the named products over every region of the label plane, and the
 share of each region above the thresholds (InterfacePhysics.regional_lattice: only the points inside a region are evaluated), written as
-<time>_region_*.npy tables [time steps, regions]."""
+<time>_region_*.npy tables [time steps, regions].
+--verify T,speed --verify_obs reports.npz --verify_threshold T:below:273.15 --verify_by station,hour,all sets inference_cfg.verify: after the per-sample
+maps, all samples are taken as the cases of a verification (InterfacePhysics.verify_at) against the station reports of the file -- lon [S], lat [S],
+hours [H], names [P], obs [M, H, S, P], M the samples in the source's order, NaN where there is no report -- and bias, MAE, RMSE, correlation, the same
+for the interpolated coarse forecast, the skill against it and the contingency scores of every threshold are written per point, per station, per hour
+and over everything as <time>_verify_*.npy tables.  Without --verify_obs there is nothing to verify against (synthetic samples come with no reports)."""
 import argparse
 
 import torch
@@ -75,6 +81,13 @@ parse.add_argument('--region_labels', default=None, type=str, help='FILE.npy: th
 parse.add_argument('--region_weights', default=None, type=str, help="area (the cosine of the row's latitude) or FILE.npy, a plane of weights; default: ones")
 parse.add_argument('--region_threshold', default=[], action='append', type=str,
                    help='NAME:V[,V...] (repeatable): inference_cfg.regions.thresholds, the share of the region where product NAME exceeds V')
+parse.add_argument('--verify', default=None, type=lambda s: [n for n in s.split(',') if n],
+                   help='name[,name...]: inference_cfg.verify.products, scores against reports (deepphysinet_amd.verification.VERIFY_PRODUCTS)')
+parse.add_argument('--verify_obs', default=None, type=str, help='FILE.npz: lon [S], lat [S], hours [H], names [P], obs [M, H, S, P] (NaN: no report)')
+parse.add_argument('--verify_threshold', default=[], action='append', type=str,
+                   help='NAME:V[,V...] | NAME:above:V[,V...] | NAME:below:V[,V...] (repeatable): inference_cfg.verify.thresholds, the events that are scored')
+parse.add_argument('--verify_by', default=['station', 'hour', 'all'], type=lambda s: [n for n in s.split(',') if n],
+                   help='station,hour,all: inference_cfg.verify.by, the groupings the point scores are pooled over')
 
 
 def _window_option(args, key, word):
@@ -133,6 +146,27 @@ def regions_option(args):
                 thresholds=_thresholds(args.region_threshold, '--region_threshold'))
 
 
+def verify_option(args):
+    """inference_cfg['verify'] of --verify / --verify_obs / --verify_threshold / --verify_by: dict(products=[...], obs=FILE.npz, thresholds={name:
+    [values and ('below', value) pairs]}, by=[...]), or None without --verify."""
+    if not args.verify:
+        if args.verify_obs or args.verify_threshold:
+            parse.error('--verify_obs and --verify_threshold need --verify')
+        return None
+    if not args.verify_obs:
+        parse.error('--verify needs --verify_obs FILE.npz (lon, lat, hours, names, obs [M, H, S, P]): there is nothing to verify against without '
+                    'reports, and --synthetic samples come with none')
+    thresholds = {}
+    for item in args.verify_threshold:
+        parts = item.split(':')
+        if len(parts) == 2:
+            parts = [parts[0], 'above', parts[1]]
+        if len(parts) != 3 or not parts[0] or parts[1] not in ('above', 'below') or not parts[2]:
+            parse.error('--verify_threshold takes NAME:V[,V...], NAME:above:V[,V...] or NAME:below:V[,V...], got %r' % item)
+        thresholds.setdefault(parts[0], []).extend((parts[1], float(v)) for v in parts[2].split(',') if v)
+    return dict(products=list(args.verify), obs=args.verify_obs, thresholds=thresholds, by=list(args.verify_by))
+
+
 if __name__ == '__main__':
     args = parse.parse_args()
     print(args)
@@ -154,6 +188,8 @@ if __name__ == '__main__':
         cfg.setdefault('inference_cfg', {})['spells'] = spells_option(args)
     if regions_option(args):
         cfg.setdefault('inference_cfg', {})['regions'] = regions_option(args)
+    if verify_option(args):
+        cfg.setdefault('inference_cfg', {})['verify'] = verify_option(args)
     model = builder_models(**cfg)
     kwargs = dict(checkpoint_path=args.checkpoint_path)
     if args.synthetic:
@@ -185,3 +221,8 @@ if __name__ == '__main__':
         r = model.last_regions
         print('regions %s: mean %s, points counted %d..%d, thresholds %s' % (','.join(r['names']), tuple(r['mean'].shape), int(r['count'].min()),
                                                                            int(r['count'].max()), r['thresholds']))
+    if model.last_verification is not None:
+        v = model.last_verification
+        print('verification %s: point %s, pairs counted %d..%d, groupings %s, thresholds %s'
+              % (','.join(v['names']), tuple(v['point']['bias'].shape), int(v['point']['count'].min()), int(v['point']['count'].max()),
+                 [k for k in v if k not in ('names', 'thresholds', 'point')], v['thresholds']))
