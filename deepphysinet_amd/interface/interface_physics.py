@@ -24,13 +24,14 @@ from .. import extremes as X
 from .. import spells as SP
 from .. import regions as RG
 from .. import verification as VF
+from .. import prob_verification as PV
 from ..losses.builder import builder_loss
 from ..model.physics_net import PhysicsNet
 from ..guard import StepGuard
 from ..lbfgs import FusedLBFGS
 from ..optim import GROUP_KEYS, FusedClipAdam, resolve_param_groups
 from ..point_path import (balance_sumsq, balance_update, balanced_total, data_losses_batch, eval_step, eval_step_batch, grid_maps, label_errors, ParcelState,
-                          EnsembleState, ExtremeState, LOSS_ORDER, OBS_ORDER, PackedField, RegionState, SpellState, VerifyState, pde_losses, pde_losses_batch, point_buffers, point_fields, point_sizes,
+                          EnsembleState, ExtremeState, LOSS_ORDER, OBS_ORDER, PackedField, ProbVerifyState, RegionState, SpellState, VerifyState, pde_losses, pde_losses_batch, point_buffers, point_fields, point_sizes,
                           PointConfig, require_gpu, smooth_l1_data_loss, step_losses, step_losses_batch)
 from ..sampler import SyntheticSamples
 from ..staged_backward import StagedBackward
@@ -595,6 +596,89 @@ class InterfacePhysics(nn.Module):
             del field                                                     # before the next case packs its own
         side = {VF.ABOVE: 'above', VF.BELOW: 'below'}
         out = dict(names=names, thresholds=[(names[c], side[s], v) for c, v, s in zip(thr_col, thr_val, thr_side)], point=state.finish())
+        for name, plan in plans.items():
+            out[name] = state.pool(plan=plan).finish()
+        return out
+
+    # ------------------------------------------------------------------ probabilistic verification of ensembles
+    @staticmethod
+    def _pverify_request(products, thresholds, by_names=None, members=None):
+        """The name, threshold, grouping-name and member-count checks of verify_ensemble_at: names (KeyError), at most 16 of them, the thresholds,
+        the grouping names and 1 <= M <= 64 where `members` is given (ValueError)."""
+        names = list(products)
+        ids = PV.prob_verify_ids(names)
+        thr = PV.check_thresholds(names, thresholds)
+        for name in by_names or ():
+            if name in PV.RESULT_KEYS:
+                raise ValueError("verify_ensemble: a grouping may not be called %r (the result's own keys)" % name)
+        if members is not None:
+            PV.check_members(members)
+        return names, ids, thr
+
+    @torch.no_grad()
+    def verify_ensemble_at(self, cases, x_idx, y_idx, hours, products, thresholds=None, by=None, with_clip=False, lonlat=False):
+        """Were the ensemble's probabilities any good: probabilistic scores of the model's ensemble and of the baseline's against reports at N points
+        (station, hour), over a sequence of cases.  cases: dicts with members -- a sequence of M dicts with field_data, forecast_h and sampler, as
+        ensemble_at takes them; every case has the same M, 1..64 -- and obs, an [N, P] fp32 tensor on the device as verify_at takes it (NaN: no
+        report).  All samplers share the fine grid and the hour window.  products, thresholds, by, with_clip, lonlat as verify_at takes them; the
+        baseline ensemble is the members' interpolated coarse forecasts (coord_data).
+        The cases are the outer loop and the members the inner: encoder, heads and packing run once per member and one PackedField is alive at a
+        time; a member's forecast and baseline values are staged into two planes that stay on the device (dpn_pverify_stage), after a case's last
+        member one dpn_pverify_case per chunk folds the case into the resident state (fp64, no atomics), after the last case the groupings are
+        pooled in one fixed order (dpn_pverify_pool) and dpn_pverify_finish writes the scores, with no host synchronisation before the results.  A
+        (point, column) of a case counts only where all M forecast values, all M baseline values and the report are finite.
+        Returns {'names', 'thresholds' [(name, 'above' | 'below', value)], 'members': M, 'point': table} and, for every entry of `by`, name: table;
+        a table is a dict by deepphysinet_amd.prob_verification.OUT_FIELDS: count [G, P] int32; crps, fair_crps, bias and rmse of the ensemble
+        mean, spread, spread_skill, their base_ forms, crpss, fair_crpss [G, P] fp32; rank_hist, base_rank_hist [G, P, M + 1] int32; brier,
+        reliability, resolution, bss, roc_area, their base_ forms and uncertainty [G, E] fp32; rel_n, rel_o, base_rel_n, base_rel_o [G, E, M + 1]
+        int32 (the threshold entries None without thresholds), on the device; NaN where a score is not defined.  KeyError: an unknown name;
+        ValueError: a bad threshold, no case, unequal member counts, more than 64 members, an obs that is not [N, P] fp32 on the device, a negative
+        group id, a grouping named like a result key, a state past 2^31 - 1 elements -- all before the first launch."""
+        by = dict(by or {})
+        names, ids, (thr_col, thr_val, thr_side) = self._pverify_request(products, thresholds, by)
+        cases = [dict(case, members=list(case['members'])) for case in cases]
+        if not cases:
+            raise ValueError('verify_ensemble: no cases (a sequence of dicts with members and obs)')
+        M = len(cases[0]['members'])
+        for c, case in enumerate(cases):
+            if len(case['members']) != M:
+                raise ValueError('verify_ensemble: case %d has %d members, case 0 has %d; all cases must have the same number' % (c, len(case['members']), M))
+        if M < 1:
+            raise ValueError('verify_ensemble: a case has no members (a sequence of dicts with field_data, forecast_h and sampler)')
+        PV.check_members(M)
+        self._check_shared_window([mem for case in cases for mem in case['members']], lonlat, 'ensemble member', 'members')
+        s0 = cases[0]['members'][0]['sampler']
+        if lonlat:
+            x_idx, y_idx = s0.lonlat_to_index(x_idx, y_idx)
+        xr, yr, tr = s0.check_positions(x_idx, y_idx, hours)
+        N, dev = xr.shape[0], s0.cube.device
+        for c, case in enumerate(cases):
+            obs = case.get('obs')
+            if not torch.is_tensor(obs) or tuple(obs.shape) != (N, len(ids)) or obs.dtype != torch.float32 or obs.device != dev:
+                raise ValueError('verification case %d: obs must be an fp32 tensor [%d, %d] on %s, got %s'
+                                 % (c, N, len(ids), dev, (tuple(obs.shape), obs.dtype, obs.device) if torch.is_tensor(obs) else type(obs).__name__))
+        plans = {}
+        for name, groups in by.items():
+            g = groups.detach().cpu().numpy() if torch.is_tensor(groups) else np.asarray(groups)
+            if g.shape != (N,):
+                raise ValueError('verify_ensemble: by[%r] must hold one group id per point, [%d], got %s' % (name, N, g.shape))
+            plans[name] = PV.pool_plan(g)
+        chunk = self.chunk_size(N, None, self.FIELD_POINT_BYTES + 4 * len(ids), self.precision)
+        state = ProbVerifyState(N, ids, thr_col, thr_val, thr_side, M, dev)        # (refuses an array past 2^31 - 1 elements)
+        bufs = point_buffers(chunk, dev)
+        plans = {name: state.upload_plan(*plan) for name, plan in plans.items()}       # on the device before the first launch
+        for case in cases:
+            for m, mem in enumerate(case['members']):
+                field = self._inference_weights(mem['field_data'].to(dev), mem['forecast_h'].to(dev), chunk)
+                for first, n in _chunks(N, chunk):
+                    x, y, t, _, cd = mem['sampler'].sample_at(n, xr[first:first + n], yr[first:first + n], tr[first:first + n], out=bufs)
+                    field.pverify_stage(x, y, t, cd, state, m, first, with_clip)
+                del field                                                 # before the next member packs its own
+            obs = case['obs'].contiguous()
+            for first, n in _chunks(N, chunk):
+                state.case(obs[first:first + n], first)
+        side = {VF.ABOVE: 'above', VF.BELOW: 'below'}
+        out = dict(names=names, thresholds=[(names[c], side[s], v) for c, v, s in zip(thr_col, thr_val, thr_side)], members=M, point=state.finish())
         for name, plan in plans.items():
             out[name] = state.pool(plan=plan).finish()
         return out
@@ -1934,7 +2018,11 @@ class InterfacePhysics(nn.Module):
         i = h * S + s of the file (lonlat) with the same with_clip; its dict stays in self.last_verification, and with log.write_source
         `<time>_verify_<point|station|hour|all>_<score>.npy` [G, P] ([G, E] for the threshold scores) go next to the maps, <time> the first sample's
         first time step.  An unknown name (KeyError), a bad threshold, grouping or file (ValueError) fails before the checkpoint is read; a file with
-        another number of cases than the source has samples (ValueError) after the loop.
+        another number of cases than the source has samples (ValueError) after the loop.  The optional key members=K (default 1: all of the above,
+        unchanged) takes K consecutive samples of the source as the members of one case, obs then [M / K, H, S, P]: ONE verify_ensemble_at call
+        behind the loop, its dict in self.last_verification and its tables in `<time>_pverify_<point|station|hour|all>_<score>.npy`; K outside
+        1..64 (ValueError) fails before the checkpoint is read, a sample count that is no multiple of K or a file with another number of cases
+        (ValueError) before the first sample runs.
         inference_cfg.regions (default absent: no further call) = dict(products=[names of deepphysinet_amd.ensemble.ENSEMBLE_PRODUCTS, at most 16],
         labels=<an int plane [ny, nx] over the lattice, -1 = in no region, or the path of its .npy>, weights=None | 'area' | <a plane or its .npy>,
         thresholds={name: [values]}): per sample, after the maps, ONE regional_lattice call on the lattice the loop evaluates, with the same
@@ -1991,14 +2079,18 @@ class InterfacePhysics(nn.Module):
         self.last_ensemble = None
         ver = kwargs.get('verify', ic.get('verify'))
         if ver:
-            unknown = set(ver) - {'products', 'obs', 'thresholds', 'by'}
+            unknown = set(ver) - {'products', 'obs', 'thresholds', 'by', 'members'}
             if unknown or 'products' not in ver:
-                raise ValueError('inference_cfg.verify: products and obs (thresholds, by optional); unknown keys %s' % sorted(unknown))
+                raise ValueError('inference_cfg.verify: products and obs (thresholds, by, members optional); unknown keys %s' % sorted(unknown))
             if ver.get('obs') is None:
                 raise ValueError('inference_cfg.verify: no reports to verify against -- obs names an .npz with lon, lat, hours, names and obs '
                                  '[M, H, S, P] (infer.py --verify_obs); synthetic samples come with none')
-            ver = dict(products=list(ver['products']), thresholds=dict(ver.get('thresholds') or {}), by=list(ver.get('by') or ()), obs=ver['obs'])
-            self._verify_request(ver['products'], ver['thresholds'], ver['by'])        # KeyError / ValueError: before the checkpoint is read
+            ver = dict(products=list(ver['products']), thresholds=dict(ver.get('thresholds') or {}), by=list(ver.get('by') or ()), obs=ver['obs'],
+                       members=ver.get('members', 1))
+            if ver['members'] == 1:
+                self._verify_request(ver['products'], ver['thresholds'], ver['by'])    # KeyError / ValueError: before the checkpoint is read
+            else:
+                self._pverify_request(ver['products'], ver['thresholds'], ver['by'], ver['members'])         # (members: 1..64)
             ver['reports'] = VF.read_observations(ver['obs'], ver['products'])
             ver['points'] = VF.report_points(ver['reports'], ver['by'])
         self.last_verification = None
@@ -2051,6 +2143,13 @@ class InterfacePhysics(nn.Module):
         samples = self._inference_samples(kwargs)
         if ens or ver:
             samples = list(samples)                                       # the members of the ensemble call / the cases of the verification behind the loop
+        if ver and ver['members'] > 1:                                    # K consecutive samples are one case: refused before the first sample runs
+            K, cases_held = ver['members'], ver['reports']['obs'].shape[0]
+            if len(samples) % K:
+                raise ValueError('inference_cfg.verify: %d samples are not a multiple of members = %d' % (len(samples), K))
+            if cases_held != len(samples) // K:
+                raise ValueError('inference_cfg.verify: the reports hold %d cases, the sample source %d of %d members'
+                                 % (cases_held, len(samples) // K, K))
         first_lattice = None
         for k, smp in enumerate(samples):
             sampler = smp['sampler']
@@ -2129,7 +2228,20 @@ class InterfacePhysics(nn.Module):
                             np.save(os.path.join(result_path, '%s_ens_%s_%s.npy' % (stamp, key, name)), a[it, j])
                     for j, (name, value) in enumerate(e['thresholds']):
                         np.save(os.path.join(result_path, '%s_ens_prob_%s_gt_%g.npy' % (stamp, name, value)), prob[it, j])
-        if ver and first_lattice is not None:
+        if ver and ver['members'] > 1 and first_lattice is not None:
+            obs, K = ver['reports']['obs'], ver['members']
+            lon, lat, hrs, groups = ver['points']
+            cases = [dict(members=samples[c * K:(c + 1) * K], obs=torch.from_numpy(obs[c].reshape(lon.size, -1)).to(device)) for c in range(obs.shape[0])]
+            v = self.verify_ensemble_at(cases, lon, lat, hrs, ver['products'], ver['thresholds'], by=groups,
+                                        with_clip=kwargs.get('with_clip', self.with_clip), lonlat=True)
+            self.last_verification = v
+            if write_source:
+                stamp = start.strftime('%Y-%m-%d_%H_%M_%S')
+                for group in ['point'] + list(groups):
+                    for key, a in v[group].items():
+                        if a is not None:
+                            np.save(os.path.join(result_path, '%s_pverify_%s_%s.npy' % (stamp, group, key)), a.cpu().numpy())
+        elif ver and first_lattice is not None:
             obs = ver['reports']['obs']
             if obs.shape[0] != len(samples):
                 raise ValueError('inference_cfg.verify: the reports hold %d cases, the sample source %d' % (obs.shape[0], len(samples)))

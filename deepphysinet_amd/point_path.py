@@ -24,6 +24,7 @@ from .ensemble import reads_coriolis, reads_jacobian
 from .regions import FLOAT_OUTPUTS as REGION_FLOAT_OUTPUTS, INT_OUTPUTS as REGION_INT_OUTPUTS, n_slots as region_slots
 from .grad_arena import new_grad, slot_of
 from . import verification as VF
+from . import prob_verification as PV
 
 # configs/DeepPhysiNet_NCEP_cfg.py:64-76 -- order u10, v10, pres, t2, q2, rio (network output order)
 OBS_ORDER = ('u10', 'v10', 'pres', 't2', 'q2', 'rio')
@@ -1351,6 +1352,13 @@ class PackedField:
         out_n, _ = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=False, want_saved=False)
         state.accumulate(out_n, coord_data, obs, self._clip_physics(with_clip), first, with_clip)
 
+    def pverify_stage(self, x, y, t, coord_data, state, member, first=0, with_clip=False):
+        """This field, as member `member` of the case that `state` (a ProbVerifyState) is staging, at points x, y, t [n], coord_data [n, 6]: the
+        fields-only forward, then one dpn_pverify_stage launch, which writes the forecast and the baseline values (from coord_data itself) of every
+        column into the state's planes at points first .. first + n.  with_clip as `diagnostics` takes it, on forecast and baseline alike."""
+        out_n, _ = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=False, want_saved=False)
+        state.stage(out_n, coord_data, self._clip_physics(with_clip), member, first, with_clip)
+
     def residual_scores(self, x, y, t, f, coord_data, factors, k=1.0):
         """Scores of a pool of candidate points for residual-weighted sampling (CollocationSampler.get_inter_data_adaptive): `residuals` on the m
         points, then dpn_adaptive_scores -- score_i = sum_e factors[e] * res_ie ** 2 in fp64, factors = six floats in LOSS_ORDER.  Returns
@@ -1528,6 +1536,111 @@ class VerifyState:
         table = L.DpnVerifyOut(*[_ptr(rows.get(k)) for k in VF.OUT_FIELDS])
         L.check(L.load().dpn_verify_finish(ctypes.byref(self.c_state()), self.n_total, P, self.c_thr_col, E, int(first), n, ctypes.byref(table),
                                            _stream()), 'dpn_verify_finish')
+        return rows
+
+
+class ProbVerifyState:
+    """Device state of a probabilistic verification request (include/dpn_hip.h: DpnPVerifyState): for n_total points (or groups), the P columns
+    `ids`, the E thresholds (thr_col, thr_val, thr_side of verification.check_thresholds) and M members per case: n [P, N] int32, the five fp64 sums
+    of prob_verification.STATE_F64 [2, P, N], rank [2, P, M + 1, N] int32 and rel [E, 2, 2, M + 1, N] int32 -- views of ONE zeroed buffer, so the
+    whole state is cleared by one memset -- and, unless planes=False (a pooled state stages nothing), the two staging planes [M, P, N] fp32.
+    `stage` writes one member's chunk into the planes, `case` folds the staged case in, `pool` makes the state of groups of points, `finish` turns
+    points first .. first + n into the scores.  ValueError: sizes out of range, an array of more than 2^31 - 1 elements."""
+
+    def __init__(self, n_total, ids, thr_col, thr_val, thr_side, members, device, planes=True):
+        self.n_total, self.ids = int(n_total), list(ids)
+        self.thr_col, self.thr_val, self.thr_side = list(thr_col), [float(v) for v in thr_val], list(thr_side)
+        P, E, N = len(self.ids), len(self.thr_col), self.n_total
+        if len(self.thr_val) != E or len(self.thr_side) != E:
+            raise ValueError('ProbVerifyState: %d threshold columns, %d values, %d sides' % (E, len(self.thr_val), len(self.thr_side)))
+        PV.check_state_size(N, P, E, members)
+        self.members = M = int(members)
+        self.c_ids = (ctypes.c_int32 * P)(*self.ids)
+        self.c_thr_col = (ctypes.c_int32 * max(E, 1))(*self.thr_col)
+        self.c_thr_val = (ctypes.c_float * max(E, 1))(*self.thr_val)
+        self.c_thr_side = (ctypes.c_int32 * max(E, 1))(*self.thr_side)
+        n64, M1 = len(PV.STATE_F64), M + 1
+        sizes = {'n': P * N, 'rank': 2 * P * M1 * N, 'rel': 4 * E * M1 * N}
+        self.buffer = torch.zeros(8 * n64 * 2 * P * N + 4 * sum(sizes.values()), dtype=torch.uint8, device=device)      # the doubles first: every view aligned
+        at = 0
+        for k in PV.STATE_F64:
+            setattr(self, k, self.buffer[at:at + 16 * P * N].view(torch.float64).view(2, P, N))
+            at += 16 * P * N
+        self.n = self.buffer[at:at + 4 * sizes['n']].view(torch.int32).view(P, N)
+        at += 4 * sizes['n']
+        self.rank = self.buffer[at:at + 4 * sizes['rank']].view(torch.int32).view(2, P, M1, N)
+        at += 4 * sizes['rank']
+        self.rel = self.buffer[at:at + 4 * sizes['rel']].view(torch.int32).view(E, 2, 2, M1, N) if E else None
+        self.plane_f, self.plane_b = (torch.zeros((M, P, N), dtype=torch.float32, device=device) for _ in range(2)) if planes else (None, None)
+
+    def clear(self):
+        """Back to the state before the first case: one memset (the planes are rewritten by the next case's stages)."""
+        self.buffer.zero_()
+
+    def arrays(self):
+        """The eight arrays by DpnPVerifyState's names (rel None without thresholds)."""
+        return {k: getattr(self, k) for k in PV.STATE_FIELDS}
+
+    def c_state(self):
+        return L.DpnPVerifyState(*[_ptr(v) for v in self.arrays().values()])
+
+    def stage(self, out_n, coord_data, ph, member, first=0, with_clip=False):
+        """dpn_pverify_stage: member `member`'s out_n [n, 6] and coord_data [n, 6] (fp32, contiguous) at points first .. first + n."""
+        n = out_n.shape[0]
+        if self.plane_f is None or tuple(coord_data.shape) != (n, 6):
+            raise ValueError('ProbVerifyState.stage: a state with planes and coord_data [%d, 6], got %s' % (n, tuple(coord_data.shape)))
+        L.check(L.load().dpn_pverify_stage(_ptr(out_n), _ptr(_f32c(coord_data)), n, ctypes.byref(ph), int(bool(with_clip)), self.c_ids, len(self.ids),
+                                           int(member), self.members, int(first), self.n_total, _ptr(self.plane_f), _ptr(self.plane_b), _stream()),
+                'dpn_pverify_stage')
+
+    def case(self, obs, first=0):
+        """dpn_pverify_case: the staged case at points first .. first + n against obs [n, P] (fp32, contiguous)."""
+        n, P = obs.shape[0], len(self.ids)
+        if self.plane_f is None or tuple(obs.shape) != (n, P) or obs.dtype != torch.float32 or not obs.is_contiguous():
+            raise ValueError('ProbVerifyState.case: a state with planes and obs a contiguous fp32 [n, %d], got %s %s' % (P, tuple(obs.shape), obs.dtype))
+        L.check(L.load().dpn_pverify_case(_ptr(self.plane_f), _ptr(self.plane_b), _ptr(obs), n, P, self.c_thr_col, self.c_thr_val, self.c_thr_side,
+                                          len(self.thr_col), self.members, int(first), self.n_total, ctypes.byref(self.c_state()), _stream()),
+                'dpn_pverify_case')
+
+    def upload_plan(self, order, seg_start):
+        """A plan of verification.pool_plan's (order [N] int32, seg_start [G + 1] int64, numpy) checked and put on the device, for `pool`: a caller
+        that must not wait for the device between its launches uploads its plans before the first of them."""
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        seg_start = np.ascontiguousarray(seg_start, dtype=np.int64)
+        if order.shape != (self.n_total,) or seg_start.ndim != 1 or seg_start.size < 2:
+            raise ValueError('ProbVerifyState.pool: order [%d] and seg_start [G + 1], got %s and %s' % (self.n_total, order.shape, seg_start.shape))
+        dev = self.buffer.device
+        return seg_start, torch.from_numpy(order).to(dev), torch.from_numpy(seg_start).to(dev)
+
+    def pool(self, order=None, seg_start=None, plan=None):
+        """dpn_pverify_pool: the state of the G = len(seg_start) - 1 groups of verification.pool_plan's (order, seg_start), or of a `plan` that
+        `upload_plan` returned; a new ProbVerifyState of the same columns, thresholds and members, without planes."""
+        seg_start, d_order, d_seg = self.upload_plan(order, seg_start) if plan is None else plan
+        G = seg_start.size - 1
+        out = ProbVerifyState(G, self.ids, self.thr_col, self.thr_val, self.thr_side, self.members, self.buffer.device, planes=False)
+        L.check(L.load().dpn_pverify_pool(ctypes.byref(self.c_state()), self.n_total, _ptr(d_order), _ptr(d_seg),
+                                          seg_start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), G, len(self.ids), self.c_thr_col, len(self.thr_col),
+                                          self.members, ctypes.byref(out.c_state()), _stream()), 'dpn_pverify_pool')
+        out._plan = (d_order, d_seg)                                      # alive until the launch has read them
+        return out
+
+    def new_rows(self, n):
+        """The destinations of `finish` for n points: a dict of prob_verification.OUT_FIELDS tensors (the threshold ones None without thresholds)."""
+        dev, P, E, M1 = self.buffer.device, len(self.ids), len(self.thr_col), self.members + 1
+        rows = {'count': torch.empty((n, P), dtype=torch.int32, device=dev)}
+        rows.update({k: torch.empty((n, P), dtype=torch.float32, device=dev) for k in PV.SCORES})
+        rows.update({k: torch.empty((n, P, M1), dtype=torch.int32, device=dev) for k in PV.HISTS})
+        rows.update({k: torch.empty((n, E), dtype=torch.float32, device=dev) if E else None for k in PV.THRESHOLD_SCORES})
+        rows.update({k: torch.empty((n, E, M1), dtype=torch.int32, device=dev) if E else None for k in PV.DIAGRAMS})
+        return rows
+
+    def finish(self, first=0, n=None, rows=None):
+        """dpn_pverify_finish for points first .. first + n (default: all) into rows (`new_rows`, made here when not given).  Returns rows."""
+        n = self.n_total - int(first) if n is None else int(n)
+        rows = self.new_rows(n) if rows is None else rows
+        table = L.DpnPVerifyOut(*[_ptr(rows.get(k)) for k in PV.OUT_FIELDS])
+        L.check(L.load().dpn_pverify_finish(ctypes.byref(self.c_state()), self.n_total, len(self.ids), self.c_thr_col, len(self.thr_col), self.members,
+                                            int(first), n, ctypes.byref(table), _stream()), 'dpn_pverify_finish')
         return rows
 
 

@@ -806,6 +806,89 @@ int dpn_verify_pool(const DpnVerifyState* points, int64_t n_points, const int32_
                     int n_products, const int32_t* thr_col /* HOST [n_thr] */, int n_thr, const DpnVerifyState* groups, void* stream);
 int dpn_verify_finish(const DpnVerifyState* state, int64_t n_total, int n_products, const int32_t* thr_col /* HOST [n_thr] */, int n_thr,
                       int64_t first, int64_t n, const DpnVerifyOut* rows, void* stream);
+/* Probabilistic verification of ensembles against observations (csrc/dpn_pverify.inc, compiled into csrc/dpn_diag.hip): M members per case (one
+ * forecast date), scored as a distribution against the reports -- CRPS, rank histogram, spread against skill, and per threshold the Brier score
+ * with its decomposition, the reliability diagram and the ROC area -- for the forecast and for the baseline, folded case by case into a resident
+ * state, pooled over groups of points in one fixed order, and turned into scores.  No atomics anywhere: two runs give the same bits.
+ * Columns (P, ids 25, 26, 28..33), values x (from out_n) and b (from coord_data), with_clip and thresholds (E triples, strict float32 compares,
+ * ev(.) the event test) are those of the dpn_verify_* block above, formed by the same code.  M = n_members, 1..DPN_PV_MAX_MEMBERS, is fixed for
+ * a request.
+ * dpn_pverify_stage takes ONE member's chunk (out_n, coord_data [n][6]; member 0..M - 1; points first .. first + n of n_total) and writes x and b
+ * of every column into plane_f and plane_b, fp32 [M][P][n_total] (member-major, then product-major: a wave's accesses run along the points):
+ *   plane[(member * P + j) * n_total + first + i].  One thread per point, plain vector stores.
+ * State (DpnPVerifyState) of n_total points, zeroed by the caller with one memset; side 0 is the forecast, side 1 the baseline:
+ *   int32 n[P][n_total]; double sum_crps, sum_fair, sum_d, sum_d2, sum_var [2][P][n_total]; int32 rank[2][P][M + 1][n_total];
+ *   int32 rel[E][2][2][M + 1][n_total]: per threshold and side, for every probability level k / M, [0] the number of pairs whose ensemble has k
+ *   event members and [1] the number of those whose report is an event.
+ * dpn_pverify_case runs after the M members of ONE case are staged and folds the case in at points first .. first + n against obs [n][P] (fp32,
+ * NaN = no report, never clipped).  A (point, column) pair is counted only when all M values x_m, all M values b_m and o are finite; otherwise
+ * nothing of that column changes.  Per counted pair n = n + 1, and per side (x_m the side's values), every operation an fp64 operation rounded
+ * on its own, left to right, with X_m = (double)x_m, O = (double)o, Md = (double)M, every sum from 0.0 with m ascending:
+ *   a = sum_m fabs(X_m - O);   s = sum_m X_m;   lt = #{x_m < o};  eq = #{x_m == o}                                    (float32 compares)
+ *   g = sum_{i < k} fabs(X_i - X_k), i ascending outside, k ascending inside
+ *   mean = s / Md;  d = mean - O;  v = sum_m (X_m - mean) * (X_m - mean)
+ *   crps = a / Md - g / (Md * Md);   fair = a / Md - g / (Md * (Md - 1.0)), a when M == 1;   var = v / (Md - 1.0), 0.0 when M == 1
+ *   sum_crps += crps;  sum_fair += fair;  sum_d += d;  sum_d2 += d * d;  sum_var += var
+ *   rank[lt + eq / 2] += 1                            (integer division: the middle of the tie range, a deterministic stand-in for a random draw)
+ *   for every threshold t with thr_col[t] == j:  k = #{m: ev(x_m)};  rel[t][side][0][k] += 1;  if ev(o): rel[t][side][1][k] += 1.
+ * One 64-thread block per 64 points; a thread copies the 2 * M values of its point and column into LDS as [side][M][64] (lane = point; at most
+ * 32 KiB) and walks its own column there, so the pair loop indexes no private array.  No atomics, no barrier.
+ * dpn_pverify_pool pools the states of N points into the states of G groups (the same layout, n_total = G; written, not accumulated), with order,
+ * seg_start and seg_start_host as dpn_verify_pool takes them.  One 64-lane wave per (group, column): per fp64 field and side, lane l adds, from
+ * 0.0, the entries of places l, l + 64, l + 128, .. of its segment in that order (an order entry outside 0..N - 1 is skipped), then lane 0 adds
+ * to its own result the results of lanes 1..63 in lane order (a lane without a place holds 0.0).  Every field is a sum, so a merge is A + B; the
+ * int32 fields (n, rank, and rel of the thresholds on the column) are added over the segment.
+ * dpn_pverify_finish writes, for points (or groups) first .. first + n, every float an fp32 cast of the fp64 result, with N = (double)n of the
+ * column, per column [n][P] and side (the baseline's in the base_ destinations):
+ *   count = n;  crps = sum_crps / N;  fair_crps = sum_fair / N;  bias = sum_d / N;  rmse = sqrt(sum_d2 / N);  spread = sqrt(sum_var / N);
+ *   spread_skill = sqrt(((Md + 1.0) / Md) * (sum_var / N)) / sqrt(sum_d2 / N), NaN when M < 2 or the divisor is 0;
+ *   rank_hist [n][P][M + 1] = rank
+ * once per column: crpss = 1.0 - sum_crps(forecast) / sum_crps(baseline);  fair_crpss likewise from sum_fair;  NaN when the divisor is 0
+ * and per threshold [n][E] and side, from the integer table alone, n_k = rel[..][0][k] and o_k = rel[..][1][k], N of column thr_col[e], Md as above,
+ * p = (double)k / Md, every sum from 0.0:
+ *   brier = (sum_{k = 0..M} ((double)o_k * ((1.0 - p) * (1.0 - p)) + (double)(n_k - o_k) * (p * p))) / N
+ *   obar = (double)(sum_k o_k) / N            (the int32 sum);   f = (double)o_k / (double)n_k
+ *   reliability = (sum_{k = 0..M, n_k > 0} (double)n_k * ((p - f) * (p - f))) / N;   resolution = (sum likewise of (double)n_k * ((f - obar) * (f - obar))) / N
+ *   uncertainty = obar * (1.0 - obar), written once per threshold (from side 0; both sides hold the same reports);
+ *   bss = 1.0 - brier / uncertainty, NaN when uncertainty == 0
+ *   roc_area: the trapezoids under the M + 2 points (false-alarm rate, hit rate) of the decisions "at least j members", j = M + 1 (0, 0) down to
+ *   0 (1, 1):  area = sum_{k = M..0, descending} (double)(n_k - o_k) * ((double)A_k + (double)(A_k + o_k)) with A_k = sum_{k' > k} o_k' (int32);
+ *   roc_area = area / ((2.0 * (double)ev) * (double)(n - ev)) with ev = sum_k o_k, NaN when ev == 0 or ev == n
+ *   rel_n, rel_o [n][E][M + 1] = n_k, o_k (the reliability diagram itself).
+ * Every score is NaN when n == 0.  The threshold destinations may be NULL when n_thr == 0.
+ * -1 (nothing launched, nothing written): a NULL required pointer (the planes, obs, the state's eight -- rel, thr_col, thr_val, thr_side and the
+ * threshold destinations: required when n_thr > 0); n <= 0; first < 0; first + n > n_total; n_products outside 1..DPN_VERIFY_MAX_COLUMNS; n_thr
+ * outside 0..DPN_VERIFY_MAX_THRESHOLDS; n_members outside 1..DPN_PV_MAX_MEMBERS; a thr_col outside 0..n_products - 1.  stage: a member outside
+ * 0..n_members - 1; an id other than 25, 26, 28..33.  case: a side other than the two; a threshold that is not finite.  pool: N <= 0; G <= 0;
+ * seg_start_host not non-decreasing from 0 to N. */
+#define DPN_PV_MAX_MEMBERS 64
+typedef struct DpnPVerifyState {
+    int32_t* n;
+    double *sum_crps, *sum_fair, *sum_d, *sum_d2, *sum_var;
+    int32_t *rank, *rel;
+} DpnPVerifyState;
+typedef struct DpnPVerifyOut {
+    int32_t* count;
+    float *crps, *fair_crps, *bias, *rmse, *spread, *spread_skill;
+    float *base_crps, *base_fair_crps, *base_bias, *base_rmse, *base_spread, *base_spread_skill;
+    float *crpss, *fair_crpss;
+    int32_t *rank_hist, *base_rank_hist;
+    float *brier, *reliability, *resolution, *bss, *roc_area;
+    float *base_brier, *base_reliability, *base_resolution, *base_bss, *base_roc_area;
+    float* uncertainty;
+    int32_t *rel_n, *rel_o, *base_rel_n, *base_rel_o;
+} DpnPVerifyOut;
+int dpn_pverify_stage(const float* out_n, const float* coord_data, int64_t n, const DpnPhysics* phys, int with_clip,
+                      const int32_t* products /* HOST, n_products ids */, int n_products, int member, int n_members, int64_t first, int64_t n_total,
+                      float* plane_f, float* plane_b, void* stream);
+int dpn_pverify_case(const float* plane_f, const float* plane_b, const float* obs, int64_t n, int n_products,
+                     const int32_t* thr_col /* HOST [n_thr] */, const float* thr_val /* HOST [n_thr] */, const int32_t* thr_side /* HOST [n_thr] */,
+                     int n_thr, int n_members, int64_t first, int64_t n_total, const DpnPVerifyState* state, void* stream);
+int dpn_pverify_pool(const DpnPVerifyState* points, int64_t n_points, const int32_t* order /* DEVICE [n_points] */,
+                     const int64_t* seg_start /* DEVICE [n_groups + 1] */, const int64_t* seg_start_host /* HOST, the same */, int64_t n_groups,
+                     int n_products, const int32_t* thr_col /* HOST [n_thr] */, int n_thr, int n_members, const DpnPVerifyState* groups, void* stream);
+int dpn_pverify_finish(const DpnPVerifyState* state, int64_t n_total, int n_products, const int32_t* thr_col /* HOST [n_thr] */, int n_thr,
+                       int n_members, int64_t first, int64_t n, const DpnPVerifyOut* rows, void* stream);
 
 /* ---------------------------------------------------------------- parcel trajectories through the learned wind (csrc/dpn_traj.hip)
  * One launch = one stage of an explicit Runge-Kutta step for n parcels whose stage positions depend only on the step's start point and the

@@ -1,13 +1,14 @@
 #!/usr/bin/env python
 """Inference launcher next to train.py, with the same three flags: --config_file, --checkpoint_path, --log_path.
 
-    python infer.py [--config_file cfg.py] [--checkpoint_path DIR] [--log_path DIR] [--synthetic] [--ema] [--diagnostics name[,name...]]
+    python infer.py [--config_file cfg.py] [--checkpoint_path DIR] [--log_path DIR] [--synthetic [--synthetic_samples N]] [--ema] [--diagnostics name[,name...]]
                     [--trajectories LON,LAT[;LON,LAT...] --traj_start H --traj_hours D --traj_step S [--traj_method rk4]]
                     [--ensemble name[,name...] [--ensemble_threshold NAME:V[,V...]]...]
                     [--extremes T:max,T:min,speed:max --extreme_window H0,H1 [--extreme_scan S] [--extreme_refine R]]
                     [--spells T:below:273.15,speed:above:15 --spell_window H0,H1 [--spell_scan S] [--spell_refine R]]
                     [--regions name[,name...] --region_labels FILE.npy [--region_weights area|FILE.npy] [--region_threshold NAME:V[,V...]]...]
-                    [--verify name[,name...] --verify_obs FILE.npz [--verify_threshold NAME:[above|below:]V[,V...]]... [--verify_by station,hour,all]]
+                    [--verify name[,name...] --verify_obs FILE.npz [--verify_threshold NAME:[above|below:]V[,V...]]... [--verify_by station,hour,all]
+                     [--verify_members K]]
 
 Builds the interface from the config (train.py's loader), loads `physics_latest.pth` from --checkpoint_path (or inference_cfg.checkpoints) and
 calls `run_inference_interface`: every field sample is evaluated on the lattice inference_cfg.img_size (x `refine`) at every inference_cfg.dt
@@ -37,7 +38,10 @@ share of each region above the thresholds (InterfacePhysics.regional_lattice: on
 maps, all samples are taken as the cases of a verification (InterfacePhysics.verify_at) against the station reports of the file -- lon [S], lat [S],
 hours [H], names [P], obs [M, H, S, P], M the samples in the source's order, NaN where there is no report -- and bias, MAE, RMSE, correlation, the same
 for the interpolated coarse forecast, the skill against it and the contingency scores of every threshold are written per point, per station, per hour
-and over everything as <time>_verify_*.npy tables.  Without --verify_obs there is nothing to verify against (synthetic samples come with no reports)."""
+and over everything as <time>_verify_*.npy tables.  Without --verify_obs there is nothing to verify against (synthetic samples come with no reports).
+--verify_members K (default 1) takes K consecutive samples as the members of one case (obs then [M / K, H, S, P]) and scores the ensemble as a
+distribution (InterfacePhysics.verify_ensemble_at): CRPS, rank histogram, spread against skill, and per threshold the Brier score with its
+decomposition, the reliability diagram and the ROC area, for the model and the interpolated coarse forecast, as <time>_pverify_*.npy tables."""
 import argparse
 
 import torch
@@ -50,6 +54,7 @@ parse.add_argument('--config_file', default=None, type=str)
 parse.add_argument('--checkpoint_path', default=None, type=str)
 parse.add_argument('--log_path', default=None, type=str)
 parse.add_argument('--synthetic', action='store_true', help="samples='synthetic': a random field sample over a random coarse cube")
+parse.add_argument('--synthetic_samples', default=1, type=int, help='N: that many random field samples (the members and cases of --verify_members)')
 parse.add_argument('--ema', action='store_true', help="weights='ema': the checkpoint's averaged weights (model_ema) in place of the raw ones")
 parse.add_argument('--diagnostics', default=None, type=lambda s: [n for n in s.split(',') if n],
                    help='name[,name...]: inference_cfg.log.export_diagnostic, derived products (deepphysinet_amd.diagnostics.PRODUCTS) written next to the variables')
@@ -86,6 +91,8 @@ parse.add_argument('--verify', default=None, type=lambda s: [n for n in s.split(
 parse.add_argument('--verify_obs', default=None, type=str, help='FILE.npz: lon [S], lat [S], hours [H], names [P], obs [M, H, S, P] (NaN: no report)')
 parse.add_argument('--verify_threshold', default=[], action='append', type=str,
                    help='NAME:V[,V...] | NAME:above:V[,V...] | NAME:below:V[,V...] (repeatable): inference_cfg.verify.thresholds, the events that are scored')
+parse.add_argument('--verify_members', default=1, type=int,
+                   help='K: inference_cfg.verify.members, K consecutive samples are the members of one case (probabilistic scores; reports [M / K, H, S, P])')
 parse.add_argument('--verify_by', default=['station', 'hour', 'all'], type=lambda s: [n for n in s.split(',') if n],
                    help='station,hour,all: inference_cfg.verify.by, the groupings the point scores are pooled over')
 
@@ -150,8 +157,8 @@ def verify_option(args):
     """inference_cfg['verify'] of --verify / --verify_obs / --verify_threshold / --verify_by: dict(products=[...], obs=FILE.npz, thresholds={name:
     [values and ('below', value) pairs]}, by=[...]), or None without --verify."""
     if not args.verify:
-        if args.verify_obs or args.verify_threshold:
-            parse.error('--verify_obs and --verify_threshold need --verify')
+        if args.verify_obs or args.verify_threshold or args.verify_members != 1:
+            parse.error('--verify_obs, --verify_threshold and --verify_members need --verify')
         return None
     if not args.verify_obs:
         parse.error('--verify needs --verify_obs FILE.npz (lon, lat, hours, names, obs [M, H, S, P]): there is nothing to verify against without '
@@ -164,7 +171,10 @@ def verify_option(args):
         if len(parts) != 3 or not parts[0] or parts[1] not in ('above', 'below') or not parts[2]:
             parse.error('--verify_threshold takes NAME:V[,V...], NAME:above:V[,V...] or NAME:below:V[,V...], got %r' % item)
         thresholds.setdefault(parts[0], []).extend((parts[1], float(v)) for v in parts[2].split(',') if v)
-    return dict(products=list(args.verify), obs=args.verify_obs, thresholds=thresholds, by=list(args.verify_by))
+    option = dict(products=list(args.verify), obs=args.verify_obs, thresholds=thresholds, by=list(args.verify_by))
+    if args.verify_members != 1:
+        option['members'] = args.verify_members
+    return option
 
 
 if __name__ == '__main__':
@@ -194,6 +204,8 @@ if __name__ == '__main__':
     kwargs = dict(checkpoint_path=args.checkpoint_path)
     if args.synthetic:
         kwargs['samples'] = 'synthetic'
+        if args.synthetic_samples != 1:
+            kwargs['samples_per_epoch'] = args.synthetic_samples
     if args.ema:
         kwargs['weights'] = 'ema'
     maps = model.run_inference_interface(**kwargs)
@@ -223,6 +235,7 @@ if __name__ == '__main__':
                                                                            int(r['count'].max()), r['thresholds']))
     if model.last_verification is not None:
         v = model.last_verification
-        print('verification %s: point %s, pairs counted %d..%d, groupings %s, thresholds %s'
-              % (','.join(v['names']), tuple(v['point']['bias'].shape), int(v['point']['count'].min()), int(v['point']['count'].max()),
-                 [k for k in v if k not in ('names', 'thresholds', 'point')], v['thresholds']))
+        print('verification %s%s: point %s, pairs counted %d..%d, groupings %s, thresholds %s'
+              % (','.join(v['names']), ' of %d members' % v['members'] if 'members' in v else '', tuple(v['point']['bias'].shape),
+                 int(v['point']['count'].min()), int(v['point']['count'].max()), [k for k in v if k not in ('names', 'thresholds', 'members', 'point')],
+                 v['thresholds']))
