@@ -1,5 +1,5 @@
 // Probabilistic verification of ensembles against observations (DESIGN.md section 6b.7), included by dpn_diag.hip behind dpn_verify.inc, whose
-// verify_values / verify_pick / verify_event / verify_sizes_ok it reuses: the member axis and the case axis of the value products together.
+// verify_values / verify_pick / verify_event and host checks (verify_*_ok, verify_clip) it reuses: the member axis and the case axis of the value products together.
 // include/dpn_hip.h states the layouts and every operation's order.
 //   dpn_pverify_stage  : ONE member's forecast (out_n) and baseline (coord_data) values of every column at points first .. first + n into two resident
 //                        fp32 planes [M][P][n_total], one thread per point.
@@ -290,8 +290,6 @@ bool pv_state_ok(const DpnPVerifyState* s, const int n_thr) {
 
 bool pv_members_ok(const int n_members) { return n_members >= 1 && n_members <= DPN_PV_MAX_MEMBERS; }
 
-bool pv_range_ok(const int64_t n, const int64_t first, const int64_t n_total) { return n > 0 && first >= 0 && n_total > 0 && first <= n_total - n; }
-
 }  // namespace
 
 extern "C" {
@@ -299,16 +297,11 @@ extern "C" {
 int dpn_pverify_stage(const float* out_n, const float* coord_data, int64_t n, const DpnPhysics* phys, int with_clip, const int32_t* products,
                       int n_products, int member, int n_members, int64_t first, int64_t n_total, float* plane_f, float* plane_b, void* stream) {
     if (!out_n || !coord_data || !phys || !products || !plane_f || !plane_b) return -1;
-    if (!pv_range_ok(n, first, n_total) || !verify_sizes_ok(n_products, 0, nullptr) || !pv_members_ok(n_members)) return -1;
+    if (!verify_range_ok(n, first, n_total) || !verify_sizes_ok(n_products, 0, nullptr) || !pv_members_ok(n_members)) return -1;
     if (member < 0 || member >= n_members) return -1;
     PvStageArgs a{out_n, coord_data, n, first, n_total, *phys, n_products, member, {}, plane_f, plane_b};
-    for (int j = 0; j < n_products; ++j) {
-        const int id = products[j];
-        if (!(id == 25 || id == 26 || (id >= 28 && id <= 33))) return -1;
-        a.id[j] = id;
-    }
-    if (!with_clip)
-        for (int k = 0; k < 6; ++k) a.ph.clip_on[k] = 0;                  // the body then neither clips nor masks
+    if (!verify_ids_ok(products, n_products, a.id)) return -1;
+    verify_clip(a.ph, with_clip);
     hipLaunchKernelGGL(dpn_pverify_stage_kernel, dim3((unsigned)((n + THREADS - 1) / THREADS)), dim3(THREADS), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -317,17 +310,10 @@ int dpn_pverify_case(const float* plane_f, const float* plane_b, const float* ob
                      const float* thr_val, const int32_t* thr_side, int n_thr, int n_members, int64_t first, int64_t n_total,
                      const DpnPVerifyState* state, void* stream) {
     if (!plane_f || !plane_b || !obs) return -1;
-    if (!pv_range_ok(n, first, n_total) || !verify_sizes_ok(n_products, n_thr, thr_col) || !pv_members_ok(n_members)) return -1;
+    if (!verify_range_ok(n, first, n_total) || !verify_sizes_ok(n_products, n_thr, thr_col) || !pv_members_ok(n_members)) return -1;
     if (!pv_state_ok(state, n_thr)) return -1;
-    if (n_thr > 0 && (!thr_val || !thr_side)) return -1;
     PvCaseArgs a{plane_f, plane_b, obs, n, first, n_total, n_products, n_thr, n_members, {}, {}, {}, pv_state(*state)};
-    for (int e = 0; e < n_thr; ++e) {
-        if (!(thr_val[e] - thr_val[e] == 0.f)) return -1;                 // (a NaN or an infinity fails this)
-        if (thr_side[e] != DPN_VERIFY_ABOVE && thr_side[e] != DPN_VERIFY_BELOW) return -1;
-        a.thr_col[e] = thr_col[e];
-        a.thr_val[e] = thr_val[e];
-        a.thr_side[e] = thr_side[e];
-    }
+    if (!verify_thresholds_ok(thr_col, thr_val, thr_side, n_thr, a.thr_col, a.thr_val, a.thr_side)) return -1;
     const size_t lds = (size_t)2 * n_members * PV_TILE * sizeof(float);  // at most 32 KiB
     hipLaunchKernelGGL(dpn_pverify_case_kernel, dim3((unsigned)((n + PV_TILE - 1) / PV_TILE)), dim3(PV_TILE), lds, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
@@ -335,13 +321,9 @@ int dpn_pverify_case(const float* plane_f, const float* plane_b, const float* ob
 
 int dpn_pverify_pool(const DpnPVerifyState* points, int64_t n_points, const int32_t* order, const int64_t* seg_start, const int64_t* seg_start_host,
                      int64_t n_groups, int n_products, const int32_t* thr_col, int n_thr, int n_members, const DpnPVerifyState* groups, void* stream) {
-    if (!order || !seg_start || !seg_start_host || n_points <= 0 || n_groups <= 0) return -1;
     if (!verify_sizes_ok(n_products, n_thr, thr_col) || !pv_members_ok(n_members)) return -1;
     if (!pv_state_ok(points, n_thr) || !pv_state_ok(groups, n_thr)) return -1;
-    if (n_groups * (int64_t)n_products > 0x7fffffff) return -1;          // one block per (group, column)
-    if (seg_start_host[0] != 0 || seg_start_host[n_groups] != n_points) return -1;
-    for (int64_t g = 0; g < n_groups; ++g)
-        if (seg_start_host[g + 1] < seg_start_host[g]) return -1;
+    if (!verify_plan_ok(order, seg_start, seg_start_host, n_points, n_groups, n_products)) return -1;
     PvPoolArgs a{pv_state(*points), pv_state(*groups), order, seg_start, n_points, n_groups, n_products, n_thr, n_members, {}};
     for (int e = 0; e < n_thr; ++e) a.thr_col[e] = thr_col[e];
     hipLaunchKernelGGL(dpn_pverify_pool_kernel, dim3((unsigned)(n_groups * n_products)), dim3(64), 0, (hipStream_t)stream, a);
@@ -350,7 +332,7 @@ int dpn_pverify_pool(const DpnPVerifyState* points, int64_t n_points, const int3
 
 int dpn_pverify_finish(const DpnPVerifyState* state, int64_t n_total, int n_products, const int32_t* thr_col, int n_thr, int n_members, int64_t first,
                        int64_t n, const DpnPVerifyOut* rows, void* stream) {
-    if (!rows || !pv_range_ok(n, first, n_total)) return -1;
+    if (!rows || !verify_range_ok(n, first, n_total)) return -1;
     if (!verify_sizes_ok(n_products, n_thr, thr_col) || !pv_members_ok(n_members) || !pv_state_ok(state, n_thr)) return -1;
     const DpnPVerifyOut& r = *rows;
     if (!r.count || !r.crps || !r.fair_crps || !r.bias || !r.rmse || !r.spread || !r.spread_skill || !r.base_crps || !r.base_fair_crps || !r.base_bias ||

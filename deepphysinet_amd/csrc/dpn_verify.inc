@@ -264,6 +264,50 @@ bool verify_sizes_ok(const int n_products, const int n_thr, const int32_t* thr_c
     return true;
 }
 
+// The host checks that the seven entry points of this file and of dpn_pverify.inc share.
+// Points first .. first + n of a state of n_total.
+bool verify_range_ok(const int64_t n, const int64_t first, const int64_t n_total) { return n > 0 && first >= 0 && n_total > 0 && first <= n_total - n; }
+
+// The column selectors into id[]: the value products 25, 26, 28..33 and no other.
+bool verify_ids_ok(const int32_t* products, const int n_products, int32_t* id) {
+    for (int j = 0; j < n_products; ++j) {
+        id[j] = products[j];
+        if (!(id[j] == 25 || id[j] == 26 || (id[j] >= 28 && id[j] <= 33))) return false;
+    }
+    return true;
+}
+
+// The thresholds into the launch arguments: every value finite, every side above or below.
+bool verify_thresholds_ok(const int32_t* thr_col, const float* thr_val, const int32_t* thr_side, const int n_thr, int32_t* col, float* val,
+                          int32_t* side) {
+    if (n_thr > 0 && (!thr_val || !thr_side)) return false;
+    for (int e = 0; e < n_thr; ++e) {
+        if (!(thr_val[e] - thr_val[e] == 0.f)) return false;             // (a NaN or an infinity fails this)
+        if (thr_side[e] != DPN_VERIFY_ABOVE && thr_side[e] != DPN_VERIFY_BELOW) return false;
+        col[e] = thr_col[e];
+        val[e] = thr_val[e];
+        side[e] = thr_side[e];
+    }
+    return true;
+}
+
+// A pooling plan: segments that run from 0 to n_points without going back, and one block per (group, column).
+bool verify_plan_ok(const int32_t* order, const int64_t* seg_start, const int64_t* seg_start_host, const int64_t n_points, const int64_t n_groups,
+                    const int n_products) {
+    if (!order || !seg_start || !seg_start_host || n_points <= 0 || n_groups <= 0) return false;
+    if (n_groups * (int64_t)n_products > 0x7fffffff) return false;
+    if (seg_start_host[0] != 0 || seg_start_host[n_groups] != n_points) return false;
+    for (int64_t g = 0; g < n_groups; ++g)
+        if (seg_start_host[g + 1] < seg_start_host[g]) return false;
+    return true;
+}
+
+// with_clip == 0: the body then neither clips nor masks.
+void verify_clip(DpnPhysics& ph, const int with_clip) {
+    if (!with_clip)
+        for (int k = 0; k < 6; ++k) ph.clip_on[k] = 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -271,37 +315,19 @@ extern "C" {
 int dpn_verify_accumulate(const float* out_n, const float* coord_data, const float* obs, int64_t n, const DpnPhysics* phys, int with_clip,
                           const int32_t* products, int n_products, const int32_t* thr_col, const float* thr_val, const int32_t* thr_side, int n_thr,
                           int64_t first, int64_t n_total, const DpnVerifyState* state, void* stream) {
-    if (!out_n || !coord_data || !obs || !phys || !products) return -1;
-    if (n <= 0 || first < 0 || n_total <= 0 || first > n_total - n) return -1;
+    if (!out_n || !coord_data || !obs || !phys || !products || !verify_range_ok(n, first, n_total)) return -1;
     if (!verify_sizes_ok(n_products, n_thr, thr_col) || !verify_state_ok(state, n_thr)) return -1;
-    if (n_thr > 0 && (!thr_val || !thr_side)) return -1;
     VerArgs a{out_n, coord_data, obs, n, first, n_total, *phys, n_products, n_thr, {}, {}, {}, {}, *state};
-    for (int j = 0; j < n_products; ++j) {
-        const int id = products[j];
-        if (!(id == 25 || id == 26 || (id >= 28 && id <= 33))) return -1;
-        a.id[j] = id;
-    }
-    for (int e = 0; e < n_thr; ++e) {
-        if (!(thr_val[e] - thr_val[e] == 0.f)) return -1;                 // (a NaN or an infinity fails this)
-        if (thr_side[e] != DPN_VERIFY_ABOVE && thr_side[e] != DPN_VERIFY_BELOW) return -1;
-        a.thr_col[e] = thr_col[e];
-        a.thr_val[e] = thr_val[e];
-        a.thr_side[e] = thr_side[e];
-    }
-    if (!with_clip)
-        for (int k = 0; k < 6; ++k) a.ph.clip_on[k] = 0;                  // the body then neither clips nor masks
+    if (!verify_ids_ok(products, n_products, a.id) || !verify_thresholds_ok(thr_col, thr_val, thr_side, n_thr, a.thr_col, a.thr_val, a.thr_side)) return -1;
+    verify_clip(a.ph, with_clip);
     hipLaunchKernelGGL(dpn_verify_accumulate_kernel, dim3((unsigned)((n + THREADS - 1) / THREADS)), dim3(THREADS), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 int dpn_verify_pool(const DpnVerifyState* points, int64_t n_points, const int32_t* order, const int64_t* seg_start, const int64_t* seg_start_host,
                     int64_t n_groups, int n_products, const int32_t* thr_col, int n_thr, const DpnVerifyState* groups, void* stream) {
-    if (!order || !seg_start || !seg_start_host || n_points <= 0 || n_groups <= 0) return -1;
     if (!verify_sizes_ok(n_products, n_thr, thr_col) || !verify_state_ok(points, n_thr) || !verify_state_ok(groups, n_thr)) return -1;
-    if (n_groups * (int64_t)n_products > 0x7fffffff) return -1;          // one block per (group, column)
-    if (seg_start_host[0] != 0 || seg_start_host[n_groups] != n_points) return -1;
-    for (int64_t g = 0; g < n_groups; ++g)
-        if (seg_start_host[g + 1] < seg_start_host[g]) return -1;
+    if (!verify_plan_ok(order, seg_start, seg_start_host, n_points, n_groups, n_products)) return -1;
     VerPoolArgs a{*points, *groups, order, seg_start, n_points, n_groups, n_products, n_thr, {}};
     for (int e = 0; e < n_thr; ++e) a.thr_col[e] = thr_col[e];
     hipLaunchKernelGGL(dpn_verify_pool_kernel, dim3((unsigned)(n_groups * n_products)), dim3(64), 0, (hipStream_t)stream, a);
@@ -310,7 +336,7 @@ int dpn_verify_pool(const DpnVerifyState* points, int64_t n_points, const int32_
 
 int dpn_verify_finish(const DpnVerifyState* state, int64_t n_total, int n_products, const int32_t* thr_col, int n_thr, int64_t first, int64_t n,
                       const DpnVerifyOut* rows, void* stream) {
-    if (!rows || n <= 0 || first < 0 || n_total <= 0 || first > n_total - n) return -1;
+    if (!rows || !verify_range_ok(n, first, n_total)) return -1;
     if (!verify_sizes_ok(n_products, n_thr, thr_col) || !verify_state_ok(state, n_thr)) return -1;
     const DpnVerifyOut& r = *rows;
     if (!r.count || !r.bias || !r.mae || !r.rmse || !r.max_abs_error || !r.corr || !r.base_bias || !r.base_mae || !r.base_rmse || !r.skill) return -1;

@@ -531,17 +531,62 @@ class InterfacePhysics(nn.Module):
 
     # ------------------------------------------------------------------ verification against observations
     @staticmethod
-    def _verify_request(products, thresholds, by_names=None):
-        """The name and threshold checks of verify_at: names (KeyError), at most 16 of them, the thresholds and the grouping names (ValueError)."""
+    def _verify_request(products, thresholds, by_names=None, members=None, word='verify'):
+        """What a request of verify_at (word 'verify') or verify_ensemble_at ('verify_ensemble') names: the products (KeyError), at most 16 of
+        them, the thresholds, the grouping names -- none may be a key of the result's own -- and 1 <= M <= 64 where `members` is given
+        (ValueError).  -> names, ids, (thr_col, thr_val, thr_side)."""
         names = list(products)
         ids = VF.verify_ids(names)
         if len(ids) > VF.MAX_COLUMNS:
-            raise ValueError('verify: %d products; at most %d in one request' % (len(ids), VF.MAX_COLUMNS))
+            raise ValueError('%s: %d products; at most %d in one request' % (word, len(ids), VF.MAX_COLUMNS))
         thr = VF.check_thresholds(names, thresholds)
         for name in by_names or ():
-            if name in ('names', 'thresholds', 'point'):
-                raise ValueError("verify: a grouping may not be called %r (the result's own keys)" % name)
+            if name in (VF.RESULT_KEYS if word == 'verify' else PV.RESULT_KEYS):
+                raise ValueError("%s: a grouping may not be called %r (the result's own keys)" % (word, name))
+        if members is not None:
+            PV.check_members(members)
         return names, ids, thr
+
+    def _verify_setup(self, word, sources, cases, x_idx, y_idx, hours, lonlat, by, n_columns, new_state):
+        """What verify_at and verify_ensemble_at (`word`) do between the request and the first launch.  sources: every dict with a sampler, in
+        order (the cases, or the members of all cases) -- they must share the window; positions and hours are converted (lonlat) and checked in the
+        first one's; every case's obs must be an fp32 [N, n_columns] tensor on the device; every grouping of `by` becomes a pool plan; then the
+        chunk size, the state (new_state(N, device)), the chunk's buffers and the plans on the device, so that nothing waits for the device between
+        the launches.  -> xr, yr, tr, device, state, plans, bufs, chunk."""
+        self._check_shared_window(sources, lonlat, *(('verification case', 'cases') if word == 'verify' else ('ensemble member', 'members')))
+        s0 = sources[0]['sampler']
+        if lonlat:
+            x_idx, y_idx = s0.lonlat_to_index(x_idx, y_idx)
+        xr, yr, tr = s0.check_positions(x_idx, y_idx, hours)
+        N, dev = xr.shape[0], s0.cube.device
+        for c, case in enumerate(cases):
+            obs = case.get('obs')
+            if not torch.is_tensor(obs) or tuple(obs.shape) != (N, n_columns) or obs.dtype != torch.float32 or obs.device != dev:
+                raise ValueError('verification case %d: obs must be an fp32 tensor [%d, %d] on %s, got %s'
+                                 % (c, N, n_columns, dev, (tuple(obs.shape), obs.dtype, obs.device) if torch.is_tensor(obs) else type(obs).__name__))
+        plans = {}
+        for name, groups in dict(by or {}).items():
+            g = groups.detach().cpu().numpy() if torch.is_tensor(groups) else np.asarray(groups)
+            if g.shape != (N,):
+                raise ValueError('%s: by[%r] must hold one group id per point, [%d], got %s' % (word, name, N, g.shape))
+            plans[name] = VF.pool_plan(g)
+        chunk = self.chunk_size(N, None, self.FIELD_POINT_BYTES + 4 * n_columns, self.precision)
+        state = new_state(N, dev)
+        bufs = point_buffers(chunk, dev)
+        return xr, yr, tr, dev, state, {name: state.upload_plan(*plan) for name, plan in plans.items()}, bufs, chunk
+
+    @staticmethod
+    def _verify_result(state, plans, names, thr, members=None):
+        """The dict both calls return: names, the thresholds as (name, 'above' | 'below', value), members where given, the table of the points
+        (`finish`) and, in `plans`' order, that of every grouping (`pool`, then `finish`)."""
+        side = {VF.ABOVE: 'above', VF.BELOW: 'below'}
+        out = dict(names=names, thresholds=[(names[c], side[s], v) for c, v, s in zip(*thr)])
+        if members is not None:
+            out['members'] = members
+        out['point'] = state.finish()
+        for name, plan in plans.items():
+            out[name] = state.pool(plan=plan).finish()
+        return out
 
     @torch.no_grad()
     def verify_at(self, cases, x_idx, y_idx, hours, products, thresholds=None, by=None, with_clip=False, lonlat=False):
@@ -561,60 +606,22 @@ class InterfacePhysics(nn.Module):
         baseline) [G, P] fp32 and pod, far, csi, fbias, ets, base_pod .. base_ets [G, E] fp32 (None without thresholds), on the device; NaN where a
         score is not defined.  KeyError: an unknown name; ValueError: a bad threshold, no case, an obs that is not [N, P] fp32 on the device, a
         negative group id, more than 16 columns -- all before the first launch."""
-        by = dict(by or {})
-        names, ids, (thr_col, thr_val, thr_side) = self._verify_request(products, thresholds, by)
+        names, ids, thr = self._verify_request(products, thresholds, by)
         cases = list(cases)
         if not cases:
             raise ValueError('verify: no cases (a sequence of dicts with field_data, forecast_h, sampler and obs)')
-        self._check_shared_window(cases, lonlat, 'verification case', 'cases')
-        s0 = cases[0]['sampler']
-        if lonlat:
-            x_idx, y_idx = s0.lonlat_to_index(x_idx, y_idx)
-        xr, yr, tr = s0.check_positions(x_idx, y_idx, hours)
-        N, dev = xr.shape[0], s0.cube.device
-        for m, case in enumerate(cases):
-            obs = case.get('obs')
-            if not torch.is_tensor(obs) or tuple(obs.shape) != (N, len(ids)) or obs.dtype != torch.float32 or obs.device != dev:
-                raise ValueError('verification case %d: obs must be an fp32 tensor [%d, %d] on %s, got %s'
-                                 % (m, N, len(ids), dev, (tuple(obs.shape), obs.dtype, obs.device) if torch.is_tensor(obs) else type(obs).__name__))
-        plans = {}
-        for name, groups in by.items():
-            g = groups.detach().cpu().numpy() if torch.is_tensor(groups) else np.asarray(groups)
-            if g.shape != (N,):
-                raise ValueError('verify: by[%r] must hold one group id per point, [%d], got %s' % (name, N, g.shape))
-            plans[name] = VF.pool_plan(g)
-        chunk = self.chunk_size(N, None, self.FIELD_POINT_BYTES + 4 * len(ids), self.precision)
-        state = VerifyState(N, ids, thr_col, thr_val, thr_side, dev)
-        bufs = point_buffers(chunk, dev)
-        plans = {name: state.upload_plan(*plan) for name, plan in plans.items()}       # on the device before the first launch
+        xr, yr, tr, dev, state, plans, bufs, chunk = self._verify_setup('verify', cases, cases, x_idx, y_idx, hours, lonlat, by, len(ids),
+                                                                        lambda N, dev: VerifyState(N, ids, *thr, dev))
         for case in cases:
             field = self._inference_weights(case['field_data'].to(dev), case['forecast_h'].to(dev), chunk)
             obs = case['obs'].contiguous()
-            for first, n in _chunks(N, chunk):
+            for first, n in _chunks(state.n_total, chunk):
                 x, y, t, _, cd = case['sampler'].sample_at(n, xr[first:first + n], yr[first:first + n], tr[first:first + n], out=bufs)
                 field.verify_accumulate(x, y, t, cd, obs[first:first + n], state, first, with_clip)
             del field                                                     # before the next case packs its own
-        side = {VF.ABOVE: 'above', VF.BELOW: 'below'}
-        out = dict(names=names, thresholds=[(names[c], side[s], v) for c, v, s in zip(thr_col, thr_val, thr_side)], point=state.finish())
-        for name, plan in plans.items():
-            out[name] = state.pool(plan=plan).finish()
-        return out
+        return self._verify_result(state, plans, names, thr)
 
     # ------------------------------------------------------------------ probabilistic verification of ensembles
-    @staticmethod
-    def _pverify_request(products, thresholds, by_names=None, members=None):
-        """The name, threshold, grouping-name and member-count checks of verify_ensemble_at: names (KeyError), at most 16 of them, the thresholds,
-        the grouping names and 1 <= M <= 64 where `members` is given (ValueError)."""
-        names = list(products)
-        ids = PV.prob_verify_ids(names)
-        thr = PV.check_thresholds(names, thresholds)
-        for name in by_names or ():
-            if name in PV.RESULT_KEYS:
-                raise ValueError("verify_ensemble: a grouping may not be called %r (the result's own keys)" % name)
-        if members is not None:
-            PV.check_members(members)
-        return names, ids, thr
-
     @torch.no_grad()
     def verify_ensemble_at(self, cases, x_idx, y_idx, hours, products, thresholds=None, by=None, with_clip=False, lonlat=False):
         """Were the ensemble's probabilities any good: probabilistic scores of the model's ensemble and of the baseline's against reports at N points
@@ -634,8 +641,7 @@ class InterfacePhysics(nn.Module):
         int32 (the threshold entries None without thresholds), on the device; NaN where a score is not defined.  KeyError: an unknown name;
         ValueError: a bad threshold, no case, unequal member counts, more than 64 members, an obs that is not [N, P] fp32 on the device, a negative
         group id, a grouping named like a result key, a state past 2^31 - 1 elements -- all before the first launch."""
-        by = dict(by or {})
-        names, ids, (thr_col, thr_val, thr_side) = self._pverify_request(products, thresholds, by)
+        names, ids, thr = self._verify_request(products, thresholds, by, word='verify_ensemble')
         cases = [dict(case, members=list(case['members'])) for case in cases]
         if not cases:
             raise ValueError('verify_ensemble: no cases (a sequence of dicts with members and obs)')
@@ -646,42 +652,20 @@ class InterfacePhysics(nn.Module):
         if M < 1:
             raise ValueError('verify_ensemble: a case has no members (a sequence of dicts with field_data, forecast_h and sampler)')
         PV.check_members(M)
-        self._check_shared_window([mem for case in cases for mem in case['members']], lonlat, 'ensemble member', 'members')
-        s0 = cases[0]['members'][0]['sampler']
-        if lonlat:
-            x_idx, y_idx = s0.lonlat_to_index(x_idx, y_idx)
-        xr, yr, tr = s0.check_positions(x_idx, y_idx, hours)
-        N, dev = xr.shape[0], s0.cube.device
-        for c, case in enumerate(cases):
-            obs = case.get('obs')
-            if not torch.is_tensor(obs) or tuple(obs.shape) != (N, len(ids)) or obs.dtype != torch.float32 or obs.device != dev:
-                raise ValueError('verification case %d: obs must be an fp32 tensor [%d, %d] on %s, got %s'
-                                 % (c, N, len(ids), dev, (tuple(obs.shape), obs.dtype, obs.device) if torch.is_tensor(obs) else type(obs).__name__))
-        plans = {}
-        for name, groups in by.items():
-            g = groups.detach().cpu().numpy() if torch.is_tensor(groups) else np.asarray(groups)
-            if g.shape != (N,):
-                raise ValueError('verify_ensemble: by[%r] must hold one group id per point, [%d], got %s' % (name, N, g.shape))
-            plans[name] = PV.pool_plan(g)
-        chunk = self.chunk_size(N, None, self.FIELD_POINT_BYTES + 4 * len(ids), self.precision)
-        state = ProbVerifyState(N, ids, thr_col, thr_val, thr_side, M, dev)        # (refuses an array past 2^31 - 1 elements)
-        bufs = point_buffers(chunk, dev)
-        plans = {name: state.upload_plan(*plan) for name, plan in plans.items()}       # on the device before the first launch
+        members = [mem for case in cases for mem in case['members']]
+        xr, yr, tr, dev, state, plans, bufs, chunk = self._verify_setup(    # (the state refuses an array past 2^31 - 1 elements)
+            'verify_ensemble', members, cases, x_idx, y_idx, hours, lonlat, by, len(ids), lambda N, dev: ProbVerifyState(N, ids, *thr, M, dev))
         for case in cases:
             for m, mem in enumerate(case['members']):
                 field = self._inference_weights(mem['field_data'].to(dev), mem['forecast_h'].to(dev), chunk)
-                for first, n in _chunks(N, chunk):
+                for first, n in _chunks(state.n_total, chunk):
                     x, y, t, _, cd = mem['sampler'].sample_at(n, xr[first:first + n], yr[first:first + n], tr[first:first + n], out=bufs)
                     field.pverify_stage(x, y, t, cd, state, m, first, with_clip)
                 del field                                                 # before the next member packs its own
             obs = case['obs'].contiguous()
-            for first, n in _chunks(N, chunk):
+            for first, n in _chunks(state.n_total, chunk):
                 state.case(obs[first:first + n], first)
-        side = {VF.ABOVE: 'above', VF.BELOW: 'below'}
-        out = dict(names=names, thresholds=[(names[c], side[s], v) for c, v, s in zip(thr_col, thr_val, thr_side)], members=M, point=state.finish())
-        for name, plan in plans.items():
-            out[name] = state.pool(plan=plan).finish()
-        return out
+        return self._verify_result(state, plans, names, thr, members=M)
 
     # ------------------------------------------------------------------ regional statistics in space
     @staticmethod
@@ -2018,7 +2002,7 @@ class InterfacePhysics(nn.Module):
         i = h * S + s of the file (lonlat) with the same with_clip; its dict stays in self.last_verification, and with log.write_source
         `<time>_verify_<point|station|hour|all>_<score>.npy` [G, P] ([G, E] for the threshold scores) go next to the maps, <time> the first sample's
         first time step.  An unknown name (KeyError), a bad threshold, grouping or file (ValueError) fails before the checkpoint is read; a file with
-        another number of cases than the source has samples (ValueError) after the loop.  The optional key members=K (default 1: all of the above,
+        another number of cases than the source has samples (ValueError) before the first sample runs.  The optional key members=K (default 1: all of the above,
         unchanged) takes K consecutive samples of the source as the members of one case, obs then [M / K, H, S, P]: ONE verify_ensemble_at call
         behind the loop, its dict in self.last_verification and its tables in `<time>_pverify_<point|station|hour|all>_<score>.npy`; K outside
         1..64 (ValueError) fails before the checkpoint is read, a sample count that is no multiple of K or a file with another number of cases
@@ -2087,10 +2071,8 @@ class InterfacePhysics(nn.Module):
                                  '[M, H, S, P] (infer.py --verify_obs); synthetic samples come with none')
             ver = dict(products=list(ver['products']), thresholds=dict(ver.get('thresholds') or {}), by=list(ver.get('by') or ()), obs=ver['obs'],
                        members=ver.get('members', 1))
-            if ver['members'] == 1:
-                self._verify_request(ver['products'], ver['thresholds'], ver['by'])    # KeyError / ValueError: before the checkpoint is read
-            else:
-                self._pverify_request(ver['products'], ver['thresholds'], ver['by'], ver['members'])         # (members: 1..64)
+            self._verify_request(ver['products'], ver['thresholds'], ver['by'], None if ver['members'] == 1 else ver['members'],
+                                 'verify' if ver['members'] == 1 else 'verify_ensemble')       # KeyError / ValueError: before the checkpoint is read
             ver['reports'] = VF.read_observations(ver['obs'], ver['products'])
             ver['points'] = VF.report_points(ver['reports'], ver['by'])
         self.last_verification = None
@@ -2143,13 +2125,15 @@ class InterfacePhysics(nn.Module):
         samples = self._inference_samples(kwargs)
         if ens or ver:
             samples = list(samples)                                       # the members of the ensemble call / the cases of the verification behind the loop
-        if ver and ver['members'] > 1:                                    # K consecutive samples are one case: refused before the first sample runs
+        # K consecutive samples are one case: a count that does not fit the reports is refused before the first sample runs (K = 1: an empty
+        # source runs through untouched)
+        if ver and (ver['members'] > 1 or samples):
             K, cases_held = ver['members'], ver['reports']['obs'].shape[0]
             if len(samples) % K:
                 raise ValueError('inference_cfg.verify: %d samples are not a multiple of members = %d' % (len(samples), K))
             if cases_held != len(samples) // K:
-                raise ValueError('inference_cfg.verify: the reports hold %d cases, the sample source %d of %d members'
-                                 % (cases_held, len(samples) // K, K))
+                raise ValueError('inference_cfg.verify: the reports hold %d cases, the sample source %d' % (cases_held, len(samples) // K)
+                                 + (' of %d members' % K if K > 1 else ''))
         first_lattice = None
         for k, smp in enumerate(samples):
             sampler = smp['sampler']
@@ -2228,34 +2212,23 @@ class InterfacePhysics(nn.Module):
                             np.save(os.path.join(result_path, '%s_ens_%s_%s.npy' % (stamp, key, name)), a[it, j])
                     for j, (name, value) in enumerate(e['thresholds']):
                         np.save(os.path.join(result_path, '%s_ens_prob_%s_gt_%g.npy' % (stamp, name, value)), prob[it, j])
-        if ver and ver['members'] > 1 and first_lattice is not None:
-            obs, K = ver['reports']['obs'], ver['members']
+        if ver and first_lattice is not None:
+            K = ver['members']
             lon, lat, hrs, groups = ver['points']
-            cases = [dict(members=samples[c * K:(c + 1) * K], obs=torch.from_numpy(obs[c].reshape(lon.size, -1)).to(device)) for c in range(obs.shape[0])]
-            v = self.verify_ensemble_at(cases, lon, lat, hrs, ver['products'], ver['thresholds'], by=groups,
-                                        with_clip=kwargs.get('with_clip', self.with_clip), lonlat=True)
+            reports = [torch.from_numpy(o.reshape(lon.size, -1)).to(device) for o in ver['reports']['obs']]
+            if K == 1:
+                call, word, cases = self.verify_at, 'verify', [dict(smp, obs=o) for smp, o in zip(samples, reports)]
+            else:
+                call, word = self.verify_ensemble_at, 'pverify'
+                cases = [dict(members=samples[c * K:(c + 1) * K], obs=o) for c, o in enumerate(reports)]
+            v = call(cases, lon, lat, hrs, ver['products'], ver['thresholds'], by=groups, with_clip=kwargs.get('with_clip', self.with_clip), lonlat=True)
             self.last_verification = v
             if write_source:
                 stamp = start.strftime('%Y-%m-%d_%H_%M_%S')
                 for group in ['point'] + list(groups):
                     for key, a in v[group].items():
                         if a is not None:
-                            np.save(os.path.join(result_path, '%s_pverify_%s_%s.npy' % (stamp, group, key)), a.cpu().numpy())
-        elif ver and first_lattice is not None:
-            obs = ver['reports']['obs']
-            if obs.shape[0] != len(samples):
-                raise ValueError('inference_cfg.verify: the reports hold %d cases, the sample source %d' % (obs.shape[0], len(samples)))
-            lon, lat, hrs, groups = ver['points']
-            cases = [dict(smp, obs=torch.from_numpy(obs[m].reshape(lon.size, -1)).to(device)) for m, smp in enumerate(samples)]
-            v = self.verify_at(cases, lon, lat, hrs, ver['products'], ver['thresholds'], by=groups, with_clip=kwargs.get('with_clip', self.with_clip),
-                               lonlat=True)
-            self.last_verification = v
-            if write_source:
-                stamp = start.strftime('%Y-%m-%d_%H_%M_%S')
-                for group in ['point'] + list(groups):
-                    for key, a in v[group].items():
-                        if a is not None:
-                            np.save(os.path.join(result_path, '%s_verify_%s_%s.npy' % (stamp, group, key)), a.cpu().numpy())
+                            np.save(os.path.join(result_path, '%s_%s_%s_%s.npy' % (stamp, word, group, key)), a.cpu().numpy())
         return maps
 
 

@@ -10,6 +10,7 @@ PyTorch is used for device memory, the current HIP stream and autograd bookkeepi
 points happens in libdpn_hip.so (deepphysinet_amd/csrc/dpn_point.hip, dpn_wgrad.hip, dpn_residual.hip).  There is no CPU path.
 """
 import ctypes
+import math
 import os
 from dataclasses import dataclass, field
 from collections import namedtuple
@@ -1299,10 +1300,14 @@ class PackedField:
         self._traj_ph = None
         self._clip_ph = {}
 
+    def _forward(self, x, y, t, coord_data, want_jac=False):
+        """The forward every product here starts with, no saved state: (out_n [n, 6], jac_n [n, 6, 3] or None)."""
+        return _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=want_jac, want_saved=False)
+
     def fields(self, x, y, t, coord_data, with_clip=False, rows=None, maps=None, lattice=None, first=0):
         """The six physical fields at points x, y, t [n], coord_data [n, 6] (dpn_fields_out): into rows [n, 6], or into the places of points
         first .. first + n of `lattice` in maps [nt, 6, ny, nx]."""
-        out_n, _ = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=False, want_saved=False)
+        out_n, _ = self._forward(x, y, t, coord_data)
         ph = self.cfg.physics()
         lat = None if lattice is None else ctypes.byref(lattice.c_struct())
         L.check(L.load().dpn_fields_out(_ptr(out_n), out_n.shape[0], ctypes.byref(ph), int(bool(with_clip)), _ptr(rows), _ptr(maps), lat, first,
@@ -1310,7 +1315,7 @@ class PackedField:
 
     def residuals(self, x, y, t, f, coord_data, res):
         """The six signed residuals lhs - rhs at points x, y, t, f [n], coord_data [n, 6] into res [n, 6] (dpn_residual_points)."""
-        out_n, jac_n = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=True, want_saved=False)
+        out_n, jac_n = self._forward(x, y, t, coord_data, True)
         geo, ph = self.cfg.geometry(), self.cfg.physics()
         L.check(L.load().dpn_residual_points(_ptr(out_n), _ptr(jac_n), _ptr(f), out_n.shape[0], ctypes.byref(geo), ctypes.byref(ph), _ptr(res),
                                              _stream()), 'dpn_residual_points')
@@ -1318,7 +1323,7 @@ class PackedField:
     def diagnostics(self, x, y, t, f, coord_data, products, with_clip=False, rows=None, maps=None, lattice=None, first=0):
         """Derived diagnostics (dpn_diagnostics_out; deepphysinet_amd.diagnostics.PRODUCTS) at points x, y, t, f [n], coord_data [n, 6]: `products`, a
         sequence of P product ids, into rows [n, P], or into the places of points first .. first + n of `lattice` in maps [nt, P, ny, nx]."""
-        out_n, jac_n = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=True, want_saved=False)
+        out_n, jac_n = self._forward(x, y, t, coord_data, True)
         ph = self._clip_physics(with_clip)
         ids = (ctypes.c_int32 * len(products))(*products)
         lat = None if lattice is None else ctypes.byref(lattice.c_struct())
@@ -1330,7 +1335,7 @@ class PackedField:
         first .. first + n (dpn_ensemble_accumulate).  The request chooses the forward: with the Jacobian (as `diagnostics`) iff a selected product
         reads it, otherwise the fields-only one (as `fields`).  with_clip as `diagnostics` takes it."""
         need_j = reads_jacobian(state.ids)
-        out_n, jac_n = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=need_j, want_saved=False)
+        out_n, jac_n = self._forward(x, y, t, coord_data, need_j)
         ph = self._clip_physics(with_clip)
         s = state
         L.check(L.load().dpn_ensemble_accumulate(_ptr(out_n), _ptr(jac_n) if need_j else None, _ptr(f) if reads_coriolis(s.ids) else None, out_n.shape[0],
@@ -1342,21 +1347,21 @@ class PackedField:
         """This field at points first .. first + n of the flat point list of `state` (a RegionState; first a multiple of 64): x, y, t, f [n],
         coord_data [n, 6], folded into the state's slots (dpn_region_accumulate).  The forward is chosen as `ensemble_accumulate` chooses it."""
         need_j = reads_jacobian(state.ids)
-        out_n, jac_n = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=need_j, want_saved=False)
+        out_n, jac_n = self._forward(x, y, t, coord_data, need_j)
         state.accumulate(out_n, jac_n if need_j else None, f if reads_coriolis(state.ids) else None, self._clip_physics(with_clip), first, with_clip)
 
     def verify_accumulate(self, x, y, t, coord_data, obs, state, first=0, with_clip=False):
         """This field, as one case (forecast date) of a verification, at points x, y, t [n], coord_data [n, 6], against the reports obs [n, P] fp32
         (NaN: none), folded into `state` (a VerifyState) at its points first .. first + n: the fields-only forward, then one dpn_verify_accumulate
         launch, which forms the baseline from coord_data itself.  with_clip as `diagnostics` takes it, on forecast and baseline alike."""
-        out_n, _ = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=False, want_saved=False)
+        out_n, _ = self._forward(x, y, t, coord_data)
         state.accumulate(out_n, coord_data, obs, self._clip_physics(with_clip), first, with_clip)
 
     def pverify_stage(self, x, y, t, coord_data, state, member, first=0, with_clip=False):
         """This field, as member `member` of the case that `state` (a ProbVerifyState) is staging, at points x, y, t [n], coord_data [n, 6]: the
         fields-only forward, then one dpn_pverify_stage launch, which writes the forecast and the baseline values (from coord_data itself) of every
         column into the state's planes at points first .. first + n.  with_clip as `diagnostics` takes it, on forecast and baseline alike."""
-        out_n, _ = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, coord_data, want_jac=False, want_saved=False)
+        out_n, _ = self._forward(x, y, t, coord_data)
         state.stage(out_n, coord_data, self._clip_physics(with_clip), member, first, with_clip)
 
     def residual_scores(self, x, y, t, f, coord_data, factors, k=1.0):
@@ -1383,7 +1388,7 @@ class PackedField:
         """One Runge-Kutta stage for the parcels of `parcels` (a ParcelState): the fields-only forward at their current evaluation points, then
         dpn_traj_stage (traj_stage), which writes the next evaluation points into the same buffers.  Two launches, nothing read back."""
         x, y, t, _, cd = parcels.points
-        out_n, _ = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, cd, want_jac=False, want_saved=False)
+        out_n, _ = self._forward(x, y, t, cd)
         if self._traj_ph is None:                  # the table is built once per field, not once per stage (384 stages a day)
             self._traj_ph = self.cfg.physics()
         traj_stage(sampler, self._traj_ph, out_n, parcels, stage, t0, h, inv_wsum, step, fields, with_clip, record_only)
@@ -1405,7 +1410,7 @@ class PackedField:
         same buffers; after the last node the state's begin launch closes the scan and writes the first probes.  Two launches (three at node K),
         nothing read back."""
         x, y, t, _, cd = state.points
-        out_n, _ = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, cd, want_jac=False, want_saved=False)
+        out_n, _ = self._forward(x, y, t, cd)
         state.scan(sampler, self._clip_physics(with_clip), with_clip, out_n, k)
         if k == state.K:
             state.begin(sampler)
@@ -1415,8 +1420,16 @@ class PackedField:
         fields-only where it bisects on the value (spells) --, then the state's refine launch, which moves the brackets and rewrites the probes.  Two
         launches, nothing read back."""
         x, y, t, _, cd = state.probes
-        out_n, jac_n = _forward_points(self.cfg, self.ws, self.nets, x, y, t, None, cd, want_jac=state.REFINE_JACOBIAN, want_saved=False)
+        out_n, jac_n = self._forward(x, y, t, cd, state.REFINE_JACOBIAN)
         state.refine(sampler, self._clip_physics(with_clip), with_clip, out_n, jac_n, rnd)
+
+
+def _request_arrays(ids, thr_col, thr_val, thr_side=None):
+    """The ctypes arrays of a request, as the launchers take them: ids [P] int32, thr_col int32 and thr_val float [max(E, 1)] and, where the
+    thresholds have sides, thr_side int32 [max(E, 1)]."""
+    E = max(len(thr_col), 1)
+    arrays = (ctypes.c_int32 * len(ids))(*ids), (ctypes.c_int32 * E)(*thr_col), (ctypes.c_float * E)(*thr_val)
+    return arrays if thr_side is None else arrays + ((ctypes.c_int32 * E)(*thr_side),)
 
 
 class EnsembleState:
@@ -1432,9 +1445,7 @@ class EnsembleState:
         P, E = len(self.ids), len(self.thr_col)
         if not 1 <= P <= L.ENS_PRODUCTS or E > L.ENS_MAX_THRESHOLDS or len(self.thr_val) != E or self.n_total < 1:
             raise ValueError('EnsembleState: %d points, %d products (1..%d), %d thresholds (0..%d)' % (self.n_total, P, L.ENS_PRODUCTS, E, L.ENS_MAX_THRESHOLDS))
-        self.c_ids = (ctypes.c_int32 * P)(*self.ids)
-        self.c_thr_col = (ctypes.c_int32 * max(E, 1))(*self.thr_col)
-        self.c_thr_val = (ctypes.c_float * max(E, 1))(*self.thr_val)
+        self.c_ids, self.c_thr_col, self.c_thr_val = _request_arrays(self.ids, self.thr_col, self.thr_val)
         self.count = torch.zeros((P, self.n_total), dtype=torch.int32, device=device)
         self.mean, self.m2 = (torch.zeros((P, self.n_total), dtype=torch.float64, device=device) for _ in range(2))
         self.vmin, self.vmax = (torch.empty((P, self.n_total), dtype=torch.float32, device=device) for _ in range(2))
@@ -1451,46 +1462,110 @@ class EnsembleState:
                                              lat, _stream()), 'dpn_ensemble_finish')
 
 
-class VerifyState:
-    """Device state of a verification request (include/dpn_hip.h: DpnVerifyState): for n_total points (or groups), the P columns `ids`
-    (verification.verify_ids) and the E thresholds (thr_col, thr_val, thr_side of verification.check_thresholds), product-major: n [P, n_total] int32,
-    the eleven fp64 arrays of verification.STATE_F64, max_ad [P, n_total] fp32 and cont [E, 6, n_total] int32 -- views of ONE zeroed buffer, so the
-    whole state is cleared by one memset.  `accumulate` folds one case's chunk in, `pool` makes the state of groups of points, `finish` turns
-    points first .. first + n into the scores."""
+class _ScoreState:
+    """What the device states of the two verification requests share (VerifyState, ProbVerifyState): n_total points (or groups), the P columns `ids`
+    (verification.verify_ids), the E thresholds (thr_col, thr_val, thr_side of verification.check_thresholds) and the arrays of `layout()` -- rows
+    (name, dtype, shape) in the order of the C struct STATE -- as views of ONE zeroed byte buffer: the fp64 arrays first, so that every view is
+    aligned, then the others in their order, no gaps; an array of no elements (the threshold array without thresholds) is None.  `pool` makes the
+    state of groups of points (the launch POOL), `finish` turns points first .. first + n into the scores (the launch FINISH into the C struct
+    OUT, whose destinations `out_rows()` lists as (name, dtype, shape behind the point axis)).  A subclass checks its own sizes (`_check`), and
+    names what its launches take between the thresholds and the rest (`_extra`) and what its pooled states are made with (POOLED)."""
+
+    STATE = OUT = POOL = FINISH = None
+    POOLED = {}
 
     def __init__(self, n_total, ids, thr_col, thr_val, thr_side, device):
         self.n_total, self.ids = int(n_total), list(ids)
         self.thr_col, self.thr_val, self.thr_side = list(thr_col), [float(v) for v in thr_val], list(thr_side)
-        P, E, N = len(self.ids), len(self.thr_col), self.n_total
-        if not 1 <= P <= L.VERIFY_MAX_COLUMNS or E > L.VERIFY_MAX_THRESHOLDS or len(self.thr_val) != E or len(self.thr_side) != E or N < 1:
-            raise ValueError('VerifyState: %d points, %d products (1..%d), %d thresholds (0..%d)'
-                             % (N, P, L.VERIFY_MAX_COLUMNS, E, L.VERIFY_MAX_THRESHOLDS))
-        self.c_ids = (ctypes.c_int32 * P)(*self.ids)
-        self.c_thr_col = (ctypes.c_int32 * max(E, 1))(*self.thr_col)
-        self.c_thr_val = (ctypes.c_float * max(E, 1))(*self.thr_val)
-        self.c_thr_side = (ctypes.c_int32 * max(E, 1))(*self.thr_side)
-        n64 = len(VF.STATE_F64)
-        self.buffer = torch.zeros(P * N * (8 * n64 + 8) + 24 * E * N, dtype=torch.uint8, device=device)      # the doubles first: every view aligned
+        self._check()
+        self.c_ids, self.c_thr_col, self.c_thr_val, self.c_thr_side = _request_arrays(self.ids, self.thr_col, self.thr_val, self.thr_side)
+        rows = sorted(self.layout(), key=lambda row: row[1] != torch.float64)         # (stable) the doubles first: every view aligned
+        sizes = [math.prod(shape) * dtype.itemsize for _, dtype, shape in rows]
+        self.buffer = torch.zeros(sum(sizes), dtype=torch.uint8, device=device)
         at = 0
-        for k in VF.STATE_F64:
-            setattr(self, k, self.buffer[at:at + 8 * P * N].view(torch.float64).view(P, N))
-            at += 8 * P * N
-        self.n = self.buffer[at:at + 4 * P * N].view(torch.int32).view(P, N)
-        at += 4 * P * N
-        self.max_ad = self.buffer[at:at + 4 * P * N].view(torch.float32).view(P, N)
-        at += 4 * P * N
-        self.cont = self.buffer[at:at + 24 * E * N].view(torch.int32).view(E, 6, N) if E else None
+        for (name, dtype, shape), size in zip(rows, sizes):
+            setattr(self, name, self.buffer[at:at + size].view(dtype).view(shape) if size else None)
+            at += size
+
+    def _extra(self):
+        return ()
 
     def clear(self):
         """Back to the state before the first case: one memset."""
         self.buffer.zero_()
 
     def arrays(self):
-        """The fourteen arrays by DpnVerifyState's names (cont None without thresholds)."""
-        return {k: getattr(self, k) for k in VF.STATE_FIELDS}
+        """The arrays by STATE's names, in its order (the threshold array None without thresholds)."""
+        return {k: getattr(self, k) for k, _ in self.STATE._fields_}
 
     def c_state(self):
-        return L.DpnVerifyState(*[_ptr(v) for v in self.arrays().values()])
+        return self.STATE(*[_ptr(v) for v in self.arrays().values()])
+
+    def upload_plan(self, order, seg_start):
+        """A plan of verification.pool_plan's (order [N] int32, seg_start [G + 1] int64, numpy) checked and put on the device, for `pool`: a caller
+        that must not wait for the device between its launches uploads its plans before the first of them."""
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        seg_start = np.ascontiguousarray(seg_start, dtype=np.int64)
+        if order.shape != (self.n_total,) or seg_start.ndim != 1 or seg_start.size < 2:
+            raise ValueError('%s.pool: order [%d] and seg_start [G + 1], got %s and %s' % (type(self).__name__, self.n_total, order.shape, seg_start.shape))
+        dev = self.buffer.device
+        return seg_start, torch.from_numpy(order).to(dev), torch.from_numpy(seg_start).to(dev)
+
+    def _like(self, n_total):
+        """An empty state of this one's class and request for n_total groups."""
+        return type(self)(n_total, self.ids, self.thr_col, self.thr_val, self.thr_side, *self._extra(), self.buffer.device, **self.POOLED)
+
+    def pool(self, order=None, seg_start=None, plan=None):
+        """POOL: the state of the G = len(seg_start) - 1 groups of verification.pool_plan's (order, seg_start), or of a `plan` that `upload_plan`
+        returned; a new state of the same class, columns and thresholds (`_like`)."""
+        seg_start, d_order, d_seg = self.upload_plan(order, seg_start) if plan is None else plan
+        G = seg_start.size - 1
+        out = self._like(G)
+        L.check(getattr(L.load(), self.POOL)(ctypes.byref(self.c_state()), self.n_total, _ptr(d_order), _ptr(d_seg),
+                                             seg_start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), G, len(self.ids), self.c_thr_col,
+                                             len(self.thr_col), *self._extra(), ctypes.byref(out.c_state()), _stream()), self.POOL)
+        out._plan = (d_order, d_seg)                                      # alive until the launch has read them
+        return out
+
+    def new_rows(self, n):
+        """The destinations of `finish` for n points: a dict of tensors [n, ...] by OUT's names, in its order (the threshold ones None without
+        thresholds)."""
+        dev = self.buffer.device
+        return {k: torch.empty((n,) + shape, dtype=dtype, device=dev) if all(shape) else None for k, dtype, shape in self.out_rows()}
+
+    def finish(self, first=0, n=None, rows=None):
+        """FINISH for points first .. first + n (default: all) into rows (`new_rows`, made here when not given).  Returns rows."""
+        n = self.n_total - int(first) if n is None else int(n)
+        rows = self.new_rows(n) if rows is None else rows
+        table = self.OUT(*[_ptr(rows.get(k)) for k, _ in self.OUT._fields_])
+        L.check(getattr(L.load(), self.FINISH)(ctypes.byref(self.c_state()), self.n_total, len(self.ids), self.c_thr_col, len(self.thr_col),
+                                               *self._extra(), int(first), n, ctypes.byref(table), _stream()), self.FINISH)
+        return rows
+
+
+class VerifyState(_ScoreState):
+    """Device state of a verification request (include/dpn_hip.h: DpnVerifyState): for n_total points (or groups), the P columns `ids` and the E
+    thresholds, product-major: n [P, n_total] int32, the eleven fp64 arrays of verification.STATE_F64, max_ad [P, n_total] fp32 and cont
+    [E, 6, n_total] int32 (_ScoreState).  `accumulate` folds one case's chunk in; the scores of `finish` are verification.OUT_FIELDS, [n, P] and,
+    per threshold, [n, E]."""
+
+    STATE, OUT, POOL, FINISH = L.DpnVerifyState, L.DpnVerifyOut, 'dpn_verify_pool', 'dpn_verify_finish'
+
+    def _check(self):
+        P, E, N = len(self.ids), len(self.thr_col), self.n_total
+        if not 1 <= P <= L.VERIFY_MAX_COLUMNS or E > L.VERIFY_MAX_THRESHOLDS or len(self.thr_val) != E or len(self.thr_side) != E or N < 1:
+            raise ValueError('VerifyState: %d points, %d products (1..%d), %d thresholds (0..%d)'
+                             % (N, P, L.VERIFY_MAX_COLUMNS, E, L.VERIFY_MAX_THRESHOLDS))
+
+    def layout(self):
+        P, E, N = len(self.ids), len(self.thr_col), self.n_total
+        return ([('n', torch.int32, (P, N))] + [(k, torch.float64, (P, N)) for k in VF.STATE_F64]
+                + [('max_ad', torch.float32, (P, N)), ('cont', torch.int32, (E, 6, N))])
+
+    def out_rows(self):
+        P, E = len(self.ids), len(self.thr_col)
+        return ([('count', torch.int32, (P,))] + [(k, torch.float32, (P,)) for k in VF.SCORES]
+                + [(k, torch.float32, (E,)) for k in VF.THRESHOLD_SCORES])
 
     def accumulate(self, out_n, coord_data, obs, ph, first=0, with_clip=False):
         """dpn_verify_accumulate: one case's out_n [n, 6], coord_data [n, 6] and obs [n, P] (fp32, contiguous) at points first .. first + n."""
@@ -1502,87 +1577,43 @@ class VerifyState:
                                                self.c_thr_col, self.c_thr_val, self.c_thr_side, len(self.thr_col), int(first), self.n_total,
                                                ctypes.byref(self.c_state()), _stream()), 'dpn_verify_accumulate')
 
-    def upload_plan(self, order, seg_start):
-        """A plan of verification.pool_plan's (order [N] int32, seg_start [G + 1] int64, numpy) checked and put on the device, for `pool`: a caller
-        that must not wait for the device between its launches uploads its plans before the first of them."""
-        order = np.ascontiguousarray(order, dtype=np.int32)
-        seg_start = np.ascontiguousarray(seg_start, dtype=np.int64)
-        if order.shape != (self.n_total,) or seg_start.ndim != 1 or seg_start.size < 2:
-            raise ValueError('VerifyState.pool: order [%d] and seg_start [G + 1], got %s and %s' % (self.n_total, order.shape, seg_start.shape))
-        dev = self.buffer.device
-        return seg_start, torch.from_numpy(order).to(dev), torch.from_numpy(seg_start).to(dev)
 
-    def pool(self, order=None, seg_start=None, plan=None):
-        """dpn_verify_pool: the state of the G = len(seg_start) - 1 groups of verification.pool_plan's (order, seg_start), or of a `plan` that
-        `upload_plan` returned; a new VerifyState of the same columns and thresholds."""
-        seg_start, d_order, d_seg = self.upload_plan(order, seg_start) if plan is None else plan
-        G = seg_start.size - 1
-        out = VerifyState(G, self.ids, self.thr_col, self.thr_val, self.thr_side, self.buffer.device)
-        L.check(L.load().dpn_verify_pool(ctypes.byref(self.c_state()), self.n_total, _ptr(d_order), _ptr(d_seg),
-                                         seg_start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), G, len(self.ids), self.c_thr_col, len(self.thr_col),
-                                         ctypes.byref(out.c_state()), _stream()), 'dpn_verify_pool')
-        out._plan = (d_order, d_seg)                                      # alive until the launch has read them
-        return out
-
-    def finish(self, first=0, n=None, rows=None):
-        """dpn_verify_finish for points first .. first + n (default: all): rows = a dict of verification.OUT_FIELDS tensors ([n, P]; the threshold
-        scores [n, E], None without thresholds), made here when not given.  Returns rows."""
-        n = self.n_total - int(first) if n is None else int(n)
-        dev, P, E = self.buffer.device, len(self.ids), len(self.thr_col)
-        if rows is None:
-            rows = {'count': torch.empty((n, P), dtype=torch.int32, device=dev)}
-            rows.update({k: torch.empty((n, P), dtype=torch.float32, device=dev) for k in VF.SCORES})
-            rows.update({k: torch.empty((n, E), dtype=torch.float32, device=dev) if E else None for k in VF.THRESHOLD_SCORES})
-        table = L.DpnVerifyOut(*[_ptr(rows.get(k)) for k in VF.OUT_FIELDS])
-        L.check(L.load().dpn_verify_finish(ctypes.byref(self.c_state()), self.n_total, P, self.c_thr_col, E, int(first), n, ctypes.byref(table),
-                                           _stream()), 'dpn_verify_finish')
-        return rows
-
-
-class ProbVerifyState:
+class ProbVerifyState(_ScoreState):
     """Device state of a probabilistic verification request (include/dpn_hip.h: DpnPVerifyState): for n_total points (or groups), the P columns
-    `ids`, the E thresholds (thr_col, thr_val, thr_side of verification.check_thresholds) and M members per case: n [P, N] int32, the five fp64 sums
-    of prob_verification.STATE_F64 [2, P, N], rank [2, P, M + 1, N] int32 and rel [E, 2, 2, M + 1, N] int32 -- views of ONE zeroed buffer, so the
-    whole state is cleared by one memset -- and, unless planes=False (a pooled state stages nothing), the two staging planes [M, P, N] fp32.
-    `stage` writes one member's chunk into the planes, `case` folds the staged case in, `pool` makes the state of groups of points, `finish` turns
-    points first .. first + n into the scores.  ValueError: sizes out of range, an array of more than 2^31 - 1 elements."""
+    `ids`, the E thresholds and M members per case: n [P, N] int32, the five fp64 sums of prob_verification.STATE_F64 [2, P, N], rank
+    [2, P, M + 1, N] int32 and rel [E, 2, 2, M + 1, N] int32 (_ScoreState) and, unless planes=False (a pooled state stages nothing), the two
+    staging planes [M, P, N] fp32, which `clear` leaves: the next case's stages rewrite them.  `stage` writes one member's chunk into the planes,
+    `case` folds the staged case in; the scores of `finish` are prob_verification.OUT_FIELDS.  ValueError: sizes out of range, an array of more
+    than 2^31 - 1 elements."""
+
+    STATE, OUT, POOL, FINISH = L.DpnPVerifyState, L.DpnPVerifyOut, 'dpn_pverify_pool', 'dpn_pverify_finish'
+    POOLED = {'planes': False}
 
     def __init__(self, n_total, ids, thr_col, thr_val, thr_side, members, device, planes=True):
-        self.n_total, self.ids = int(n_total), list(ids)
-        self.thr_col, self.thr_val, self.thr_side = list(thr_col), [float(v) for v in thr_val], list(thr_side)
-        P, E, N = len(self.ids), len(self.thr_col), self.n_total
+        self.members = members
+        super().__init__(n_total, ids, thr_col, thr_val, thr_side, device)
+        shape = (self.members, len(self.ids), self.n_total)
+        self.plane_f, self.plane_b = (torch.zeros(shape, dtype=torch.float32, device=device) for _ in range(2)) if planes else (None, None)
+
+    def _check(self):
+        E = len(self.thr_col)
         if len(self.thr_val) != E or len(self.thr_side) != E:
             raise ValueError('ProbVerifyState: %d threshold columns, %d values, %d sides' % (E, len(self.thr_val), len(self.thr_side)))
-        PV.check_state_size(N, P, E, members)
-        self.members = M = int(members)
-        self.c_ids = (ctypes.c_int32 * P)(*self.ids)
-        self.c_thr_col = (ctypes.c_int32 * max(E, 1))(*self.thr_col)
-        self.c_thr_val = (ctypes.c_float * max(E, 1))(*self.thr_val)
-        self.c_thr_side = (ctypes.c_int32 * max(E, 1))(*self.thr_side)
-        n64, M1 = len(PV.STATE_F64), M + 1
-        sizes = {'n': P * N, 'rank': 2 * P * M1 * N, 'rel': 4 * E * M1 * N}
-        self.buffer = torch.zeros(8 * n64 * 2 * P * N + 4 * sum(sizes.values()), dtype=torch.uint8, device=device)      # the doubles first: every view aligned
-        at = 0
-        for k in PV.STATE_F64:
-            setattr(self, k, self.buffer[at:at + 16 * P * N].view(torch.float64).view(2, P, N))
-            at += 16 * P * N
-        self.n = self.buffer[at:at + 4 * sizes['n']].view(torch.int32).view(P, N)
-        at += 4 * sizes['n']
-        self.rank = self.buffer[at:at + 4 * sizes['rank']].view(torch.int32).view(2, P, M1, N)
-        at += 4 * sizes['rank']
-        self.rel = self.buffer[at:at + 4 * sizes['rel']].view(torch.int32).view(E, 2, 2, M1, N) if E else None
-        self.plane_f, self.plane_b = (torch.zeros((M, P, N), dtype=torch.float32, device=device) for _ in range(2)) if planes else (None, None)
+        PV.check_state_size(self.n_total, len(self.ids), E, self.members)
+        self.members = int(self.members)
 
-    def clear(self):
-        """Back to the state before the first case: one memset (the planes are rewritten by the next case's stages)."""
-        self.buffer.zero_()
+    def _extra(self):
+        return (self.members,)
 
-    def arrays(self):
-        """The eight arrays by DpnPVerifyState's names (rel None without thresholds)."""
-        return {k: getattr(self, k) for k in PV.STATE_FIELDS}
+    def layout(self):
+        P, E, N, M1 = len(self.ids), len(self.thr_col), self.n_total, self.members + 1
+        return ([('n', torch.int32, (P, N))] + [(k, torch.float64, (2, P, N)) for k in PV.STATE_F64]
+                + [('rank', torch.int32, (2, P, M1, N)), ('rel', torch.int32, (E, 2, 2, M1, N))])
 
-    def c_state(self):
-        return L.DpnPVerifyState(*[_ptr(v) for v in self.arrays().values()])
+    def out_rows(self):
+        P, E, M1 = len(self.ids), len(self.thr_col), self.members + 1
+        return ([('count', torch.int32, (P,))] + [(k, torch.float32, (P,)) for k in PV.SCORES] + [(k, torch.int32, (P, M1)) for k in PV.HISTS]
+                + [(k, torch.float32, (E,)) for k in PV.THRESHOLD_SCORES] + [(k, torch.int32, (E, M1)) for k in PV.DIAGRAMS])
 
     def stage(self, out_n, coord_data, ph, member, first=0, with_clip=False):
         """dpn_pverify_stage: member `member`'s out_n [n, 6] and coord_data [n, 6] (fp32, contiguous) at points first .. first + n."""
@@ -1602,47 +1633,6 @@ class ProbVerifyState:
                                           len(self.thr_col), self.members, int(first), self.n_total, ctypes.byref(self.c_state()), _stream()),
                 'dpn_pverify_case')
 
-    def upload_plan(self, order, seg_start):
-        """A plan of verification.pool_plan's (order [N] int32, seg_start [G + 1] int64, numpy) checked and put on the device, for `pool`: a caller
-        that must not wait for the device between its launches uploads its plans before the first of them."""
-        order = np.ascontiguousarray(order, dtype=np.int32)
-        seg_start = np.ascontiguousarray(seg_start, dtype=np.int64)
-        if order.shape != (self.n_total,) or seg_start.ndim != 1 or seg_start.size < 2:
-            raise ValueError('ProbVerifyState.pool: order [%d] and seg_start [G + 1], got %s and %s' % (self.n_total, order.shape, seg_start.shape))
-        dev = self.buffer.device
-        return seg_start, torch.from_numpy(order).to(dev), torch.from_numpy(seg_start).to(dev)
-
-    def pool(self, order=None, seg_start=None, plan=None):
-        """dpn_pverify_pool: the state of the G = len(seg_start) - 1 groups of verification.pool_plan's (order, seg_start), or of a `plan` that
-        `upload_plan` returned; a new ProbVerifyState of the same columns, thresholds and members, without planes."""
-        seg_start, d_order, d_seg = self.upload_plan(order, seg_start) if plan is None else plan
-        G = seg_start.size - 1
-        out = ProbVerifyState(G, self.ids, self.thr_col, self.thr_val, self.thr_side, self.members, self.buffer.device, planes=False)
-        L.check(L.load().dpn_pverify_pool(ctypes.byref(self.c_state()), self.n_total, _ptr(d_order), _ptr(d_seg),
-                                          seg_start.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), G, len(self.ids), self.c_thr_col, len(self.thr_col),
-                                          self.members, ctypes.byref(out.c_state()), _stream()), 'dpn_pverify_pool')
-        out._plan = (d_order, d_seg)                                      # alive until the launch has read them
-        return out
-
-    def new_rows(self, n):
-        """The destinations of `finish` for n points: a dict of prob_verification.OUT_FIELDS tensors (the threshold ones None without thresholds)."""
-        dev, P, E, M1 = self.buffer.device, len(self.ids), len(self.thr_col), self.members + 1
-        rows = {'count': torch.empty((n, P), dtype=torch.int32, device=dev)}
-        rows.update({k: torch.empty((n, P), dtype=torch.float32, device=dev) for k in PV.SCORES})
-        rows.update({k: torch.empty((n, P, M1), dtype=torch.int32, device=dev) for k in PV.HISTS})
-        rows.update({k: torch.empty((n, E), dtype=torch.float32, device=dev) if E else None for k in PV.THRESHOLD_SCORES})
-        rows.update({k: torch.empty((n, E, M1), dtype=torch.int32, device=dev) if E else None for k in PV.DIAGRAMS})
-        return rows
-
-    def finish(self, first=0, n=None, rows=None):
-        """dpn_pverify_finish for points first .. first + n (default: all) into rows (`new_rows`, made here when not given).  Returns rows."""
-        n = self.n_total - int(first) if n is None else int(n)
-        rows = self.new_rows(n) if rows is None else rows
-        table = L.DpnPVerifyOut(*[_ptr(rows.get(k)) for k in PV.OUT_FIELDS])
-        L.check(L.load().dpn_pverify_finish(ctypes.byref(self.c_state()), self.n_total, len(self.ids), self.c_thr_col, len(self.thr_col), self.members,
-                                            int(first), n, ctypes.byref(table), _stream()), 'dpn_pverify_finish')
-        return rows
-
 
 class RegionState:
     """Device state of a regional-statistics request (include/dpn_hip.h: DpnRegionPlan, DpnRegionState): the plan's seg, wgt and offs on the device
@@ -1657,9 +1647,7 @@ class RegionState:
             raise ValueError('RegionState: %d products (1..%d), %d thresholds (0..%d)' % (P, L.REG_MAX_COLUMNS, E, L.REG_MAX_THRESHOLDS))
         self.n_slots = S = region_slots(plan, self.nt)
         self.n_points = self.nt * plan.n_sel
-        self.c_ids = (ctypes.c_int32 * P)(*self.ids)
-        self.c_thr_col = (ctypes.c_int32 * max(E, 1))(*self.thr_col)
-        self.c_thr_val = (ctypes.c_float * max(E, 1))(*self.thr_val)
+        self.c_ids, self.c_thr_col, self.c_thr_val = _request_arrays(self.ids, self.thr_col, self.thr_val)
         self.seg, self.wgt, self.offs = (torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in (plan.seg, plan.wgt, plan.offs))
         self.c_plan = L.DpnRegionPlan(_ptr(self.seg), _ptr(self.wgt), _ptr(self.offs), plan.n_sel, plan.n_regions, self.nt)
         self.w, self.wx = (torch.zeros((P, S), dtype=torch.float64, device=device) for _ in range(2))

@@ -15,7 +15,7 @@ from ctypes import Structure, c_void_p
 import numpy as np
 
 from . import verification as VF
-from .verification import ABOVE, BELOW, LANES, check_thresholds, pool_plan          # (re-exported: the request is checked by the same code)
+from .verification import ABOVE, BELOW, LANES, _event, check_thresholds, pool_plan  # (re-exported: the request is checked by the same code)
 
 MAX_MEMBERS = 64                                                           # DPN_PV_MAX_MEMBERS
 MAX_COLUMNS, MAX_THRESHOLDS = VF.MAX_COLUMNS, VF.MAX_THRESHOLDS
@@ -41,14 +41,6 @@ class DpnPVerifyState(Structure):
 class DpnPVerifyOut(Structure):
     """include/dpn_hip.h DpnPVerifyOut: the thirty-two destinations of dpn_pverify_finish."""
     _fields_ = [(n, c_void_p) for n in OUT_FIELDS]
-
-
-def prob_verify_ids(names):
-    """The ids of a sequence of product names (verification.verify_ids: KeyError on an unknown name or none); ValueError past 16 columns."""
-    ids = VF.verify_ids(names)
-    if len(ids) > MAX_COLUMNS:
-        raise ValueError('verify_ensemble: %d products; at most %d in one request' % (len(ids), MAX_COLUMNS))
-    return ids
 
 
 def check_members(M):
@@ -103,11 +95,6 @@ def pverify_stage_reference(plane_f, plane_b, x, b, member, first=0):
     plane_f[member, :, first:first + x.shape[0]] = x.T
     plane_b[member, :, first:first + x.shape[0]] = b.T
     return plane_f, plane_b
-
-
-def _event(z, thr, side):
-    with np.errstate(invalid='ignore'):
-        return z > np.float32(thr) if side == ABOVE else z < np.float32(thr)
 
 
 def pverify_case_reference(state, plane_f, plane_b, o, thr_col=(), thr_val=(), thr_side=(), first=0):

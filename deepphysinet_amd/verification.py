@@ -29,6 +29,7 @@ SCORES = ('bias', 'mae', 'rmse', 'max_abs_error', 'corr', 'base_bias', 'base_mae
 TABLE_SCORES = ('pod', 'far', 'csi', 'fbias', 'ets')
 THRESHOLD_SCORES = TABLE_SCORES + tuple('base_' + k for k in TABLE_SCORES)
 OUT_FIELDS = ('count',) + SCORES + THRESHOLD_SCORES                        # DpnVerifyOut, in its order
+RESULT_KEYS = ('names', 'thresholds', 'point')                             # of verify_at's dict: no grouping may take these names
 
 
 class DpnVerifyState(Structure):

@@ -211,21 +211,22 @@ def test_host_refusals():
     from deepphysinet_amd import prob_verification as PV
     from deepphysinet_amd.interface.interface_physics import InterfacePhysics
     from deepphysinet_amd.point_path import ProbVerifyState
+    request = lambda *args: InterfacePhysics._verify_request(*args, word='verify_ensemble')
     with pytest.raises(ValueError, match='17 products'):
-        InterfacePhysics._pverify_request(['T'] * 17, None)
+        request(['T'] * 17, None)
     with pytest.raises(KeyError, match='vorticity'):
-        InterfacePhysics._pverify_request(['T', 'vorticity'], None)
+        request(['T', 'vorticity'], None)
     with pytest.raises(ValueError, match='not among'):
-        InterfacePhysics._pverify_request(['T'], {'speed': 1.0})
+        request(['T'], {'speed': 1.0})
     for word in ('point', 'members', 'names', 'thresholds'):
         with pytest.raises(ValueError, match='may not be called'):
-            InterfacePhysics._pverify_request(['T'], None, ['station', word])
+            request(['T'], None, ['station', word])
     for bad in (0, 65, -1, 2.5):
         with pytest.raises(ValueError, match='members per case'):
-            InterfacePhysics._pverify_request(['T'], None, None, bad)
-    names, ids, thr = InterfacePhysics._pverify_request(['T', 'speed'], {'T': ('below', 273.15)}, ['station'], 64)
+            request(['T'], None, None, bad)
+    names, ids, thr = request(['T', 'speed'], {'T': ('below', 273.15)}, ['station'], 64)
     assert (names, ids, thr) == (['T', 'speed'], [31, 25], ([0], [float(np.float32(273.15))], [1]))
-    assert PV.prob_verify_ids(['u', 'rel_humidity', 'u']) == [28, 26, 28]
+    assert PV.VF.verify_ids(['u', 'rel_humidity', 'u']) == [28, 26, 28]
     for args in ((0, [31], [], [], [], 3), (4, [], [], [], [], 3), (4, [31] * 17, [], [], [], 3), (4, [31], [0] * 17, [1.0] * 17, [0] * 17, 3),
                  (4, [31], [0], [], [0], 3), (4, [31], [0], [1.0], [], 3), (4, [31], [], [], [], 0), (4, [31], [], [], [], 65)):
         with pytest.raises(ValueError):

@@ -29,7 +29,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tools.ensemble_time import _peak, _timed
-from tools.verify_time import HOURS, PRODUCTS, STATIONS, _baseline, _values
+from tools.verify_time import HOURS, PRODUCTS, STATIONS, _baseline, _values, table_digests
 
 SIZES = ((8, 8), (8, 61))                                       # (cases, members)
 
@@ -124,6 +124,7 @@ def main():
         thr_in = {'T': [('below', float(first[..., 0].nanmedian())), float(first[..., 0].nanquantile(0.75))], 'speed': float(first[..., 1].nanmedian())}
         fused = lambda: m.verify_ensemble_at(cases, xi, yi, hr, PRODUCTS, thresholds=thr_in, by=by_host)
         a = fused()
+        print('\n'.join('sha256 cases_%d_members_%d %s' % (C, M, line) for line in table_digests(a)))
         comp = lambda: composed(m, cases, xi, yi, hr, a['thresholds'], by_dev)
         b = comp()
         differ, ranks_equal = {}, True

@@ -14,6 +14,7 @@ tool reports (`composed_pooled_runs_differ`).  Writes the numbers as JSON (defau
 usage: python tools/verify_time.py [--reps 5] [--out FILE]"""
 import argparse
 import ctypes
+import hashlib
 import json
 import os
 import statistics
@@ -34,6 +35,13 @@ STATIONS, HOURS = 256, 25
 def _values(rows):
     cols = [torch.sqrt(rows[:, 0] * rows[:, 0] + rows[:, 1] * rows[:, 1]) if c is None else rows[:, c] for c in COLUMNS]
     return torch.stack(cols, dim=1)
+
+
+def table_digests(result):
+    """'<table>.<score> <sha256 of the bytes>' of every tensor of every table of a verify_at / verify_ensemble_at result, in the result's order: two
+    commits compute the same when these lines are the same."""
+    return ['%s.%s %s' % (table, k, hashlib.sha256(v.contiguous().cpu().numpy().tobytes()).hexdigest())
+            for table, rows in result.items() if isinstance(rows, dict) for k, v in rows.items() if v is not None]
 
 
 def _baseline(m, sampler, xi, yi, hr):
@@ -124,6 +132,7 @@ def main():
         cases = everyone[:M]
         fused = lambda: m.verify_at(cases, xi, yi, hr, PRODUCTS, thresholds=thr_in, by=by_host)
         a = fused()
+        print('\n'.join('sha256 dates_%d %s' % (M, line) for line in table_digests(a)))
         comp = lambda: composed(m, cases, xi, yi, hr, a['thresholds'], by_dev)
         b = comp()
         differ = {}
