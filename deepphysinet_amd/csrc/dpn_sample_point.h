@@ -9,7 +9,7 @@
 namespace {
 
 // One point of the sampler at position (xr, yr) in fine-grid index units and tr in hours: fp64 weights in the clamped coarse cell, NaN outside the
-// cube, the Coriolis term, one cast to fp32.  The drawn points (dpn_sample_kernel) and the given ones (dpn_sample_at_kernel) share it.
+// cube (more than 1e-9 of a cell beyond a face), the Coriolis term, one cast to fp32.  The drawn points (dpn_sample_kernel) and the given ones (dpn_sample_at_kernel) share it.
 __device__ __forceinline__ void sample_point(const DpnSampler& s, const float* cube, const double xr, const double yr, const double tr, const int64_t i,
                                              float* x, float* y, float* t, float* f, float* coord_data) {
     // trilinear interpolation of the coarse cube [6][lat_in][lon_in][t_in] at (lat, lon, hour)               (:405-411)
@@ -18,8 +18,13 @@ __device__ __forceinline__ void sample_point(const DpnSampler& s, const float* c
     ix = ix < 0 ? 0 : (ix > s.lon_in - 2 ? s.lon_in - 2 : ix);
     iy = iy < 0 ? 0 : (iy > s.lat_in - 2 ? s.lat_in - 2 : iy);
     it = it < 0 ? 0 : (it > s.t_in - 2 ? s.t_in - 2 : it);
-    const double wx = fx - ix, wy = fy - iy, wt = ft - it;
-    const bool inside = wx >= 0.0 && wx <= 1.0 && wy >= 0.0 && wy <= 1.0 && wt >= 0.0 && wt <= 1.0;   // outside -> NaN (xarray)
+    double wx = fx - ix, wy = fy - iy, wt = ft - it;
+    // Inside: every weight within 1e-9 of [0, 1], then clamped to [0, 1]; anything further out -> NaN (xarray).  A position on the cube's last face
+    // can come out an ulp or two of fx beyond it when cells_x is no binary fraction (0.1 / 0.3); that excess is below 5e-10 up to 2^20 cells, and
+    // 1e-9 of a cell moves the result by 1e-9 of the corner spread.  The clamp is the identity on weights already in [0, 1].
+    const double tol = 1e-9;
+    const bool inside = wx >= -tol && wx <= 1.0 + tol && wy >= -tol && wy <= 1.0 + tol && wt >= -tol && wt <= 1.0 + tol;   // (a NaN fails)
+    wx = fmin(fmax(wx, 0.0), 1.0); wy = fmin(fmax(wy, 0.0), 1.0); wt = fmin(fmax(wt, 0.0), 1.0);
     const int64_t sy = (int64_t)s.lon_in * s.t_in, sx = s.t_in, sk = (int64_t)s.lat_in * sy;
     const float* c0 = cube + (int64_t)iy * sy + (int64_t)ix * sx + it;
 #pragma unroll

@@ -45,7 +45,9 @@ class SamplerConfig:
 class Lattice:
     """A regular lattice of nx * ny * nt positions in the sampler's units (fine-grid index units, hours); mirrors DpnLattice.  Point
     g = (it * ny + iy) * nx + ix (ix fastest, it slowest) lies at (x0 + ix * xstep, y0 + iy * ystep, t0 + it * tstep).  A lattice may reach
-    outside the coarse cube: coord_data, and every field evaluated from it, is NaN there."""
+    outside the coarse cube: coord_data, and every field evaluated from it, is NaN there.  Inside rule (sample_point): a position whose weight in
+    its coarse cell lies within 1e-9 of [0, 1] is inside and the weight is clamped to [0, 1]; the last node of a geometry whose cell ratio is no
+    binary fraction (0.1 / 0.3 degrees) is therefore inside, a position more than 1e-9 of a coarse cell beyond a face is NaN."""
     x0: float
     xstep: float
     y0: float

@@ -404,7 +404,11 @@ typedef struct DpnSampler {
  * cube[6][lat_in][lon_in][t_in] (fp32, variable order u10,v10,pres,t2,q2,rio) tri-linearly at them (fp64 weights, result
  * cast to fp32: what xarray's .interp + .float() produce) and writes x, y (metres), t (seconds), f (Coriolis),
  * coord_data[n][6].  labels[t_hours+1][6][lat][lon] / label_out[n][6] (node modes only) and raw[n][3] (the draws as
- * doubles: x index, y index, hour) are optional (NULL). */
+ * doubles: x index, y index, hour) are optional (NULL).
+ * Inside rule: the position in coarse index units is fx = x index * cells_x (fy, ft alike), its cell is floor(fx) clamped to the cube and
+ * its weight is fx - cell.  A weight within 1e-9 of [0, 1] counts as inside and is clamped to [0, 1] before use; anything further out makes
+ * coord_data NaN.  The tolerance absorbs the rounding of fx on the cube's last face when cells_x is no binary fraction (0.1 / 0.3 deg): at
+ * most about 2 ulp(fx) < 5e-10 for an axis of up to 2^20 cells; weights already in [0, 1] are used unchanged. */
 int dpn_sample_points(const DpnSampler* s, const float* cube, const float* labels, int mode, const int32_t* xi, const int32_t* yi,
                       const int32_t* ti, int64_t n, uint64_t seed, uint64_t offset, float* x, float* y, float* t, float* f,
                       float* coord_data, float* label_out, double* raw, void* stream);
@@ -430,7 +434,8 @@ typedef struct DpnLattice {
 } DpnLattice;
 /* The sampler evaluated at GIVEN positions instead of drawn ones: either stations xr, yr, tr [n] (fp64; lattice = NULL, first ignored) or points
  * first .. first + n of *lattice (xr = yr = tr = NULL).  Outputs and arithmetic are dpn_sample_points': x, y (metres), t (seconds), f,
- * coord_data[n][6] (NaN outside the coarse cube).  -1: n <= 0, a NULL pointer, both or neither source, nx / ny / nt < 1, first + n > nx * ny * nt. */
+ * coord_data[n][6] (NaN outside the coarse cube: dpn_sample_points' inside rule, a position within 1e-9 of a coarse cell beyond a face of the cube
+ * is taken as on the face, anything further out is NaN).  -1: n <= 0, a NULL pointer, both or neither source, nx / ny / nt < 1, first + n > nx * ny * nt. */
 int dpn_sample_at(const DpnSampler* s, const float* cube, const double* xr, const double* yr, const double* tr, const DpnLattice* lattice,
                   int64_t first, int64_t n, float* x, float* y, float* t, float* f, float* coord_data, void* stream);
 /* Normalised fields out_n[n][6] -> physical values with dpn_grid_maps' arithmetic (multiply, then add; the squared form; the clip of P, T, q, rho that
