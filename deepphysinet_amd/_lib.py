@@ -6,6 +6,7 @@ from ctypes import POINTER, Structure, c_double, c_float, c_int, c_int32, c_int6
 
 from .verification import DpnVerifyOut, DpnVerifyState          # (the structs of the verification calls live with their restatement)
 from .prob_verification import DpnPVerifyOut, DpnPVerifyState    # (and those of the probabilistic verification with theirs)
+from .neighbourhood import DpnNbhdOut, DpnNbhdState              # (and those of the neighbourhood verification with theirs)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DPN_LIB', os.path.join(_HERE, 'libdpn_hip.so'))    # DPN_LIB: experiment builds only
@@ -248,6 +249,11 @@ EXPORTS = {
                                  c_int, POINTER(DpnPVerifyState), c_void_p]),
     'dpn_pverify_finish': (c_int, [POINTER(DpnPVerifyState), c_int64, c_int, POINTER(c_int32), c_int, c_int, c_int64, c_int64,
                                    POINTER(DpnPVerifyOut), c_void_p]),
+    'dpn_nbhd_stage': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, POINTER(DpnPhysics), c_int, POINTER(c_int32), c_int, POINTER(c_int32),
+                               POINTER(c_float), POINTER(c_int32), c_int, POINTER(DpnLattice), c_int64, c_void_p, c_void_p]),
+    'dpn_nbhd_fold': (c_int, [c_void_p, POINTER(DpnLattice), c_int, POINTER(c_int32), c_int, c_int64, c_int64, c_void_p, POINTER(DpnNbhdState),
+                              c_void_p]),
+    'dpn_nbhd_finish': (c_int, [POINTER(DpnNbhdState), c_int, c_int, c_int, POINTER(DpnNbhdOut), POINTER(DpnNbhdOut), c_void_p]),
     'dpn_traj_stage': (c_int, [POINTER(DpnSampler), c_void_p, POINTER(DpnPhysics), c_void_p, c_int64, POINTER(DpnTrajStage), c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dpn_extreme_scan': (c_int, [POINTER(DpnSampler), c_void_p, POINTER(DpnPhysics), c_int, c_void_p, c_int64, POINTER(c_int32), POINTER(c_int32), c_int,
@@ -318,6 +324,7 @@ REG_GROUP, REG_MAX_COLUMNS, REG_MAX_THRESHOLDS = 64, 16, 16          # DPN_REG_G
 VERIFY_MAX_COLUMNS, VERIFY_MAX_THRESHOLDS = 16, 16                   # DPN_VERIFY_MAX_COLUMNS, DPN_VERIFY_MAX_THRESHOLDS (include/dpn_hip.h)
 VERIFY_ABOVE, VERIFY_BELOW = 0, 1                                    # DPN_VERIFY_ABOVE, _BELOW: a threshold's side
 PV_MAX_MEMBERS = 64                                                  # DPN_PV_MAX_MEMBERS: members per case of dpn_pverify_*
+NBHD_MAX_SCALES = 8                                                  # DPN_NBHD_MAX_SCALES: window half-widths of dpn_nbhd_*
 EXT_MAX_COLUMNS = 32          # DPN_EXT_MAX_COLUMNS (include/dpn_hip.h)
 EXT_MAX, EXT_MIN, EXT_MEAN = 0, 1, 2                                                 # DPN_EXT_MAX, _MIN, _MEAN: a column's sense
 EXT_OK, EXT_BAD_SCAN, EXT_STOPPED, EXT_AT_START, EXT_AT_END = 0, 1, 2, 3, 4         # DPN_EXT_*: a column's status

@@ -11,7 +11,8 @@
 // and the threshold spells dpn_spell_scan / dpn_spell_begin / dpn_spell_refine / dpn_spell_finish (dpn_spell.inc, behind that), and its space axis,
 // the regional statistics dpn_region_accumulate / dpn_region_finish (dpn_region.inc), and the case axis of its value products, the verification
 // against observations dpn_verify_accumulate / dpn_verify_pool / dpn_verify_finish (dpn_verify.inc), and member and case axis together, the
-// probabilistic verification dpn_pverify_stage / dpn_pverify_case / dpn_pverify_pool / dpn_pverify_finish (dpn_pverify.inc, last).
+// probabilistic verification dpn_pverify_stage / dpn_pverify_case / dpn_pverify_pool / dpn_pverify_finish (dpn_pverify.inc), and case axis and
+// space axis together, the neighbourhood verification on lattices dpn_nbhd_stage / dpn_nbhd_fold / dpn_nbhd_finish (dpn_nbhd.inc, last).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/dpn_hip.h"
@@ -112,3 +113,4 @@ int dpn_diagnostics_out(const float* out_n, const float* jac_n, const float* f, 
 #include "dpn_region.inc"            // regional statistics in space: dpn_region_accumulate, dpn_region_finish
 #include "dpn_verify.inc"            // verification against observations: dpn_verify_accumulate, dpn_verify_pool, dpn_verify_finish
 #include "dpn_pverify.inc"           // probabilistic verification of ensembles: dpn_pverify_stage, dpn_pverify_case, dpn_pverify_pool, dpn_pverify_finish
+#include "dpn_nbhd.inc"              // neighbourhood verification on lattices (FSS): dpn_nbhd_stage, dpn_nbhd_fold, dpn_nbhd_finish

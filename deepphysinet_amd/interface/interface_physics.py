@@ -25,13 +25,14 @@ from .. import spells as SP
 from .. import regions as RG
 from .. import verification as VF
 from .. import prob_verification as PV
+from .. import neighbourhood as NB
 from ..losses.builder import builder_loss
 from ..model.physics_net import PhysicsNet
 from ..guard import StepGuard
 from ..lbfgs import FusedLBFGS
 from ..optim import GROUP_KEYS, FusedClipAdam, resolve_param_groups
 from ..point_path import (balance_sumsq, balance_update, balanced_total, data_losses_batch, eval_step, eval_step_batch, grid_maps, label_errors, ParcelState,
-                          EnsembleState, ExtremeState, LOSS_ORDER, OBS_ORDER, PackedField, ProbVerifyState, RegionState, SpellState, VerifyState, pde_losses, pde_losses_batch, point_buffers, point_fields, point_sizes,
+                          EnsembleState, ExtremeState, LOSS_ORDER, NbhdState, OBS_ORDER, PackedField, ProbVerifyState, RegionState, SpellState, VerifyState, pde_losses, pde_losses_batch, point_buffers, point_fields, point_sizes,
                           PointConfig, require_gpu, smooth_l1_data_loss, step_losses, step_losses_batch)
 from ..sampler import SyntheticSamples
 from ..staged_backward import StagedBackward
@@ -666,6 +667,58 @@ class InterfacePhysics(nn.Module):
             for first, n in _chunks(state.n_total, chunk):
                 state.case(obs[first:first + n], first)
         return self._verify_result(state, plans, names, thr, members=M)
+
+    # ------------------------------------------------------------------ neighbourhood verification on lattices
+    @torch.no_grad()
+    def verify_lattice(self, cases, lattice, products, thresholds, scales, with_clip=False, chunk_points=None):
+        """From which spatial scale on is the forecast useful: the fractions skill score (FSS) of the model and of its baseline against gridded
+        analyses on a lattice, over square windows of growing width, over a sequence of cases.  cases: dicts with field_data, forecast_h and
+        sampler (what _inference_samples yields) -- one forecast date each, sharing the fine grid and the hour window -- plus analysis, an
+        [nt, P, ny, nx] fp32 tensor on the device of the analysis at the lattice's own nodes (the layout of diagnostic_lattice's output), in
+        physical units, NaN where there is none.  products: names of deepphysinet_amd.verification.VERIFY_PRODUCTS; thresholds: as verify_at
+        takes them, at least one (the FSS is a score of events); scales: the window widths in lattice nodes, odd, strictly ascending, at most 8
+        (neighbourhood.check_scales), e.g. (1, 3, 5, 9, 17, 33).
+        The baseline is the interpolated coarse forecast (coord_data), de-normalised by the same code as the forecast; with_clip applies to
+        both, never to the analysis.  The cases are the outer loop and one PackedField is alive at a time: a case's lattice is walked in chunks
+        (dpn_sample_at -> fields-only forward -> dpn_nbhd_stage, which writes the event masks), then dpn_nbhd_fold builds an integer
+        summed-area table per (hour, threshold), forms the window fractions of every scale from four corners per node and folds their squares
+        in one fixed order, without atomics, into a state that stays on the device; dpn_nbhd_finish writes the tables.  No host
+        synchronisation before the result; chunk_points changes no bit of it.  A node of a column counts only where forecast, baseline and
+        analysis are all finite; a window is clamped to the lattice and its fractions are taken over its valid nodes.
+        Returns {'names', 'thresholds' [(name, 'above' | 'below', value)], 'scales' (the widths), 'hour': table, 'all': table}; a table is a
+        dict by deepphysinet_amd.neighbourhood.OUT_FIELDS: fss, base_fss fp32 and windows int64 [nt, E, K]; freq_f, freq_b, freq_o, fbias,
+        base_fbias, useful (0.5 + freq_o / 2) fp32, count int64 and skilful_scale, base_skilful_scale int32 (the first scale index whose FSS
+        reaches useful, or -1) [nt, E] -- in 'all' without the leading nt --, on the device; NaN where a score is not defined.  KeyError: an
+        unknown name; ValueError: bad thresholds or none, bad scales, no case, an analysis that is not [nt, P, ny, nx] fp32 on the device,
+        windows that are not shared, a lattice of 2^31 nodes or more -- all before the first launch."""
+        names, ids, thr = self._verify_request(products, thresholds, word='verify_lattice')
+        if not thr[0]:
+            raise ValueError('verify_lattice: no threshold; the fractions skill score is a score of events (thresholds={name: value, ..})')
+        radius = NB.check_scales(scales)
+        cases = list(cases)
+        if not cases:
+            raise ValueError('verify_lattice: no cases (a sequence of dicts with field_data, forecast_h, sampler and analysis)')
+        self._check_shared_window(cases, False, 'verification case', 'cases')
+        dev = cases[0]['sampler'].cube.device
+        shape = (int(lattice.nt), len(ids), int(lattice.ny), int(lattice.nx))
+        for c, case in enumerate(cases):
+            an = case.get('analysis')
+            if not torch.is_tensor(an) or tuple(an.shape) != shape or an.dtype != torch.float32 or an.device != dev:
+                raise ValueError('verification case %d: analysis must be an fp32 tensor %s on %s, got %s'
+                                 % (c, list(shape), dev, (tuple(an.shape), an.dtype, an.device) if torch.is_tensor(an) else type(an).__name__))
+        if lattice.n_points >= 2 ** 31:
+            raise ValueError('verify_lattice: a lattice of %d nodes; fewer than 2^31' % lattice.n_points)
+        chunk = self.chunk_size(lattice.n_points, chunk_points, self.FIELD_POINT_BYTES, self.precision)
+        state = NbhdState(lattice, ids, *thr, radius, dev, self.INFER_BUDGET_BYTES)
+        for case in cases:
+            field = self._inference_weights(case['field_data'].to(dev), case['forecast_h'].to(dev), chunk)
+            analysis = case['analysis'].contiguous()
+            for first, n, x, y, t, _, cd in self._lattice_chunks(case['sampler'], lattice, chunk):
+                field.nbhd_stage(x, y, t, cd, analysis, state, first, with_clip)
+            del field                                                     # before the next case packs its own
+            state.fold()
+        side = {VF.ABOVE: 'above', VF.BELOW: 'below'}
+        return dict(state.finish(), names=names, thresholds=[(names[c], side[s], v) for c, v, s in zip(*thr)], scales=[2 * r + 1 for r in radius])
 
     # ------------------------------------------------------------------ regional statistics in space
     @staticmethod
@@ -2007,6 +2060,14 @@ class InterfacePhysics(nn.Module):
         behind the loop, its dict in self.last_verification and its tables in `<time>_pverify_<point|station|hour|all>_<score>.npy`; K outside
         1..64 (ValueError) fails before the checkpoint is read, a sample count that is no multiple of K or a file with another number of cases
         (ValueError) before the first sample runs.
+        inference_cfg.verify_grid, or the keyword verify_grid= (default absent: no further call) = dict(products=[names of VERIFY_PRODUCTS],
+        analysis=<the path of an .npz, or a dict, with names [P], hours [H] (equally spaced) and analysis [M, H, P, ny, nx] on the fine grid's
+        nodes: neighbourhood.read_analysis>, thresholds={name: value(s) | ('below', value(s))} (at least one), scales=[odd window widths in
+        nodes], default 1, 3, 5, 9, 17, 33): behind the loop ONE verify_lattice call takes all M samples as the cases on the fine grid's nodes at
+        the file's hours, with the same with_clip; its dict stays in self.last_grid_verification, and with log.write_source
+        `<time>_nbhd_<hour|all>_<score>.npy` go next to the maps, <time> the first sample's first time step.  An unknown name (KeyError), bad
+        thresholds or none, bad scales or a bad file (ValueError) fail before the checkpoint is read; a file with another number of cases than
+        the source has samples before the first sample runs, one on other nodes than the fine grid's before the call's first launch.
         inference_cfg.regions (default absent: no further call) = dict(products=[names of deepphysinet_amd.ensemble.ENSEMBLE_PRODUCTS, at most 16],
         labels=<an int plane [ny, nx] over the lattice, -1 = in no region, or the path of its .npy>, weights=None | 'area' | <a plane or its .npy>,
         thresholds={name: [values]}): per sample, after the maps, ONE regional_lattice call on the lattice the loop evaluates, with the same
@@ -2076,6 +2137,21 @@ class InterfacePhysics(nn.Module):
             ver['reports'] = VF.read_observations(ver['obs'], ver['products'])
             ver['points'] = VF.report_points(ver['reports'], ver['by'])
         self.last_verification = None
+        grid = kwargs.get('verify_grid', ic.get('verify_grid'))
+        if grid:
+            unknown = set(grid) - {'products', 'analysis', 'thresholds', 'scales'}
+            if unknown or 'products' not in grid:
+                raise ValueError('inference_cfg.verify_grid: products, analysis, thresholds (scales optional); unknown keys %s' % sorted(unknown))
+            if grid.get('analysis') is None:
+                raise ValueError('inference_cfg.verify_grid: no analysis to verify against -- analysis names an .npz with names, hours and analysis '
+                                 '[M, H, P, ny, nx] (infer.py --verify_analysis); synthetic samples come with none')
+            grid = dict(products=list(grid['products']), thresholds=dict(grid.get('thresholds') or {}), analysis=grid['analysis'],
+                        scales=list(grid.get('scales') or NB.DEFAULT_SCALES))
+            if not self._verify_request(grid['products'], grid['thresholds'], word='verify_lattice')[2][0]:     # KeyError / ValueError: before the
+                raise ValueError('inference_cfg.verify_grid: no threshold; the fractions skill score is a score of events')    # checkpoint is read
+            NB.check_scales(grid['scales'])
+            grid['held'] = NB.read_analysis(grid['analysis'], grid['products'])
+        self.last_grid_verification = None
         reg = ic.get('regions')
         if reg:
             unknown = set(reg) - {'products', 'labels', 'weights', 'thresholds'}
@@ -2123,8 +2199,10 @@ class InterfacePhysics(nn.Module):
             os.makedirs(result_path, exist_ok=True)
         maps = None
         samples = self._inference_samples(kwargs)
-        if ens or ver:
+        if ens or ver or grid:
             samples = list(samples)                                       # the members of the ensemble call / the cases of the verification behind the loop
+        if grid and samples and grid['held']['analysis'].shape[0] != len(samples):
+            raise ValueError('inference_cfg.verify_grid: the analysis holds %d cases, the sample source %d' % (grid['held']['analysis'].shape[0], len(samples)))
         # K consecutive samples are one case: a count that does not fit the reports is refused before the first sample runs (K = 1: an empty
         # source runs through untouched)
         if ver and (ver['members'] > 1 or samples):
@@ -2229,6 +2307,20 @@ class InterfacePhysics(nn.Module):
                     for key, a in v[group].items():
                         if a is not None:
                             np.save(os.path.join(result_path, '%s_%s_%s_%s.npy' % (stamp, word, group, key)), a.cpu().numpy())
+        if grid and first_lattice is not None:
+            held = grid['held']
+            on_nodes = samples[0]['sampler'].lattice(refine=1, hours=held['hours'])          # the fine grid's nodes at the file's hours
+            if held['analysis'].shape[3:] != (on_nodes.ny, on_nodes.nx):
+                raise ValueError('inference_cfg.verify_grid: the analysis lives on %s nodes, the fine grid has %s; regrid beforehand'
+                                 % (held['analysis'].shape[3:], (on_nodes.ny, on_nodes.nx)))
+            cases = [dict(smp, analysis=torch.from_numpy(a).to(device)) for smp, a in zip(samples, held['analysis'])]
+            v = self.verify_lattice(cases, on_nodes, grid['products'], grid['thresholds'], grid['scales'], with_clip=kwargs.get('with_clip', self.with_clip))
+            self.last_grid_verification = v
+            if write_source:
+                stamp = start.strftime('%Y-%m-%d_%H_%M_%S')
+                for group in ('hour', 'all'):
+                    for key, a in v[group].items():
+                        np.save(os.path.join(result_path, '%s_nbhd_%s_%s.npy' % (stamp, group, key)), a.cpu().numpy())
         return maps
 
 

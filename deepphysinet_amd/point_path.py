@@ -26,6 +26,7 @@ from .regions import FLOAT_OUTPUTS as REGION_FLOAT_OUTPUTS, INT_OUTPUTS as REGIO
 from .grad_arena import new_grad, slot_of
 from . import verification as VF
 from . import prob_verification as PV
+from . import neighbourhood as NB
 
 # configs/DeepPhysiNet_NCEP_cfg.py:64-76 -- order u10, v10, pres, t2, q2, rio (network output order)
 OBS_ORDER = ('u10', 'v10', 'pres', 't2', 'q2', 'rio')
@@ -1364,6 +1365,13 @@ class PackedField:
         out_n, _ = self._forward(x, y, t, coord_data)
         state.stage(out_n, coord_data, self._clip_physics(with_clip), member, first, with_clip)
 
+    def nbhd_stage(self, x, y, t, coord_data, analysis, state, first=0, with_clip=False):
+        """This field, as the case that `state` (an NbhdState) is staging, at points first .. first + n of the state's lattice: x, y, t [n],
+        coord_data [n, 6]; the fields-only forward, then one dpn_nbhd_stage launch, which forms the baseline from coord_data itself, reads the
+        analysis [nt, P, ny, nx] at its own nodes and writes their mask bytes.  with_clip as `diagnostics` takes it, on forecast and baseline."""
+        out_n, _ = self._forward(x, y, t, coord_data)
+        state.stage(out_n, coord_data, analysis, self._clip_physics(with_clip), first, with_clip)
+
     def residual_scores(self, x, y, t, f, coord_data, factors, k=1.0):
         """Scores of a pool of candidate points for residual-weighted sampling (CollocationSampler.get_inter_data_adaptive): `residuals` on the m
         points, then dpn_adaptive_scores -- score_i = sum_e factors[e] * res_ie ** 2 in fp64, factors = six floats in LOSS_ORDER.  Returns
@@ -1632,6 +1640,107 @@ class ProbVerifyState(_ScoreState):
         L.check(L.load().dpn_pverify_case(_ptr(self.plane_f), _ptr(self.plane_b), _ptr(obs), n, P, self.c_thr_col, self.c_thr_val, self.c_thr_side,
                                           len(self.thr_col), self.members, int(first), self.n_total, ctypes.byref(self.c_state()), _stream()),
                 'dpn_pverify_case')
+
+
+class NbhdState:
+    """Device state of a neighbourhood verification request (include/dpn_hip.h: DpnNbhdState) on `lattice`: the P columns `ids`, the E >= 1
+    thresholds and the K half-widths `radius` (neighbourhood.check_scales).  The ten arrays of neighbourhood.STATE_FIELDS are views of ONE zeroed
+    byte buffer, laid out as _ScoreState lays its own out (the fp64 arrays first, no gaps; here every array is 8 bytes wide); beside it the
+    staging mask [nt, E, ny, nx] uint8, which `clear` leaves (the next case's stages rewrite every byte), and the scratch of `fold` for
+    `planes_per_fold` planes -- as many as `budget_bytes` hold of tables and row partials, at least one.  `stage` writes one chunk's mask bytes,
+    `fold` folds the staged case in, `finish` turns the state into the two tables.  ValueError: sizes out of range."""
+
+    def __init__(self, lattice, ids, thr_col, thr_val, thr_side, radius, device, budget_bytes):
+        self.lattice, self.ids = lattice, list(ids)
+        self.thr_col, self.thr_val, self.thr_side = list(thr_col), [float(v) for v in thr_val], list(thr_side)
+        self.radius = [int(r) for r in radius]
+        P, E, K = len(self.ids), len(self.thr_col), len(self.radius)
+        nx, ny, nt = int(lattice.nx), int(lattice.ny), int(lattice.nt)
+        if not 1 <= P <= L.VERIFY_MAX_COLUMNS or not 1 <= E <= L.VERIFY_MAX_THRESHOLDS or len(self.thr_val) != E or len(self.thr_side) != E \
+                or not 1 <= K <= L.NBHD_MAX_SCALES or lattice.n_points >= 2 ** 31:
+            raise ValueError('NbhdState: %d products (1..%d), %d thresholds (1..%d), %d scales (1..%d), %d nodes (below 2^31)'
+                             % (P, L.VERIFY_MAX_COLUMNS, E, L.VERIFY_MAX_THRESHOLDS, K, L.NBHD_MAX_SCALES, lattice.n_points))
+        self.c_ids, self.c_thr_col, self.c_thr_val, self.c_thr_side = _request_arrays(self.ids, self.thr_col, self.thr_val, self.thr_side)
+        self.c_radius = (ctypes.c_int32 * K)(*self.radius)
+        self.c_lattice = lattice.c_struct()
+        shapes = [(k, torch.float64, (nt, E, K)) for k in NB.SUMS] + [('windows', torch.int64, (nt, E, K))] \
+            + [(k, torch.int64, (nt, E)) for k in ('n_valid', 'n_f', 'n_b', 'n_o')]
+        sizes = [math.prod(shape) * 8 for _, _, shape in shapes]
+        self.buffer = torch.zeros(sum(sizes), dtype=torch.uint8, device=device)
+        at = 0
+        for (name, dtype, shape), size in zip(shapes, sizes):
+            setattr(self, name, self.buffer[at:at + size].view(dtype).view(shape))
+            at += size
+        self.mask = torch.zeros((nt, E, ny, nx), dtype=torch.uint8, device=device)
+        self.plane_bytes = self.scratch_bytes(nx, ny, K, 1)
+        blocks = max(ny, (nx + 1 + 63) // 64)                                 # dpn_nbhd_fold: one block per (plane, row) and per (plane, 64 columns)
+        self.planes_per_fold = max(1, min(nt * E, int(budget_bytes) // self.plane_bytes, (2 ** 31 - 1) // blocks))
+        self.scratch = torch.empty(self.planes_per_fold * self.plane_bytes, dtype=torch.uint8, device=device)
+
+    @staticmethod
+    def scratch_bytes(nx, ny, K, n_planes):
+        """The scratch of dpn_nbhd_fold for n_planes planes: int32 S [np, ny + 1, nx + 1, 4], fp64 part [np, K, ny, 5], int32 rows [np, K, ny]."""
+        return n_planes * (16 * (ny + 1) * (nx + 1) + 40 * K * ny + 4 * K * ny)
+
+    def scratch_views(self, n_planes):
+        """(S, part, rows) of the scratch as the last fold of n_planes planes left it."""
+        nx, ny, K = int(self.lattice.nx), int(self.lattice.ny), len(self.radius)
+        a, b = 16 * (ny + 1) * (nx + 1) * n_planes, 40 * K * ny * n_planes
+        return (self.scratch[:a].view(torch.int32).view(n_planes, ny + 1, nx + 1, 4), self.scratch[a:a + b].view(torch.float64).view(n_planes, K, ny, 5),
+                self.scratch[a + b:a + b + 4 * K * ny * n_planes].view(torch.int32).view(n_planes, K, ny))
+
+    def clear(self):
+        """Back to the state before the first case: one memset."""
+        self.buffer.zero_()
+
+    def arrays(self):
+        """The arrays by DpnNbhdState's names, in its order."""
+        return {k: getattr(self, k) for k in NB.STATE_FIELDS}
+
+    def c_state(self):
+        return L.DpnNbhdState(*[_ptr(v) for v in self.arrays().values()])
+
+    def stage(self, out_n, coord_data, analysis, ph, first=0, with_clip=False):
+        """dpn_nbhd_stage: one case's out_n [n, 6] and coord_data [n, 6] (fp32, contiguous) at points first .. first + n of the lattice against
+        analysis [nt, P, ny, nx] (fp32, contiguous: the whole array)."""
+        n, lat = out_n.shape[0], self.lattice
+        shape = (int(lat.nt), len(self.ids), int(lat.ny), int(lat.nx))
+        if tuple(analysis.shape) != shape or analysis.dtype != torch.float32 or not analysis.is_contiguous() or tuple(coord_data.shape) != (n, 6):
+            raise ValueError('NbhdState.stage: analysis must be a contiguous fp32 %s and coord_data [%d, 6], got %s %s and %s'
+                             % (list(shape), n, tuple(analysis.shape), analysis.dtype, tuple(coord_data.shape)))
+        L.check(L.load().dpn_nbhd_stage(_ptr(out_n), _ptr(_f32c(coord_data)), _ptr(analysis), n, ctypes.byref(ph), int(bool(with_clip)), self.c_ids,
+                                        len(self.ids), self.c_thr_col, self.c_thr_val, self.c_thr_side, len(self.thr_col),
+                                        ctypes.byref(self.c_lattice), int(first), _ptr(self.mask), _stream()), 'dpn_nbhd_stage')
+
+    def fold(self, planes_per_fold=None):
+        """dpn_nbhd_fold over all nt * E planes of the staged case, `planes_per_fold` at a time (default: what the scratch holds; any number
+        gives the same bits)."""
+        total = int(self.lattice.nt) * len(self.thr_col)
+        step = self.planes_per_fold if planes_per_fold is None else int(planes_per_fold)
+        if not 1 <= step <= self.planes_per_fold:
+            raise ValueError('NbhdState.fold: %d planes per launch; the scratch holds 1..%d' % (step, self.planes_per_fold))
+        for p0, n_planes in _spans(total, step):
+            L.check(L.load().dpn_nbhd_fold(_ptr(self.mask), ctypes.byref(self.c_lattice), len(self.thr_col), self.c_radius, len(self.radius), p0,
+                                           n_planes, _ptr(self.scratch), ctypes.byref(self.c_state()), _stream()), 'dpn_nbhd_fold')
+
+    def finish(self):
+        """dpn_nbhd_finish: {'hour': table, 'all': table}, a table a dict of tensors by neighbourhood.OUT_FIELDS ([nt, E, K] and [nt, E]; [E, K]
+        and [E])."""
+        nt, E, K = int(self.lattice.nt), len(self.thr_col), len(self.radius)
+        dev = self.buffer.device
+        tables = {}
+        for name, lead in (('hour', (nt, E)), ('all', (E,))):
+            tables[name] = {k: torch.empty(lead + ((K,) if k in NB.SCALE_FIELDS else ()), dtype=getattr(torch, np.dtype(NB.OUT_DTYPES[k]).name), device=dev)
+                            for k in NB.OUT_FIELDS}
+        c_out = [L.DpnNbhdOut(*[_ptr(t[k]) for k in NB.OUT_FIELDS]) for t in (tables['hour'], tables['all'])]
+        L.check(L.load().dpn_nbhd_finish(ctypes.byref(self.c_state()), nt, E, K, ctypes.byref(c_out[0]), ctypes.byref(c_out[1]), _stream()),
+                'dpn_nbhd_finish')
+        return tables
+
+
+def _spans(total, step):
+    """(first, n) of the spans of `step` that cover 0 .. total."""
+    return [(first, min(step, total - first)) for first in range(0, total, step)]
 
 
 class RegionState:

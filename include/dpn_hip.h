@@ -894,6 +894,67 @@ int dpn_pverify_pool(const DpnPVerifyState* points, int64_t n_points, const int3
                      int n_products, const int32_t* thr_col /* HOST [n_thr] */, int n_thr, int n_members, const DpnPVerifyState* groups, void* stream);
 int dpn_pverify_finish(const DpnPVerifyState* state, int64_t n_total, int n_products, const int32_t* thr_col /* HOST [n_thr] */, int n_thr,
                        int n_members, int64_t first, int64_t n, const DpnPVerifyOut* rows, void* stream);
+/* Neighbourhood verification on lattices against gridded analyses (csrc/dpn_nbhd.inc, compiled into csrc/dpn_diag.hip): the fractions skill score
+ * (FSS, Roberts & Lean 2008) of the forecast and of the baseline against an analysis that lives on the lattice's own nodes, over square windows
+ * of growing width, folded case by case (one forecast date each) into a resident fp64 state.  No atomics anywhere: two runs give the same bits.
+ * Request: P columns (ids 25, 26, 28..33, 1..DPN_VERIFY_MAX_COLUMNS) and E = n_thr thresholds, 1..DPN_VERIFY_MAX_THRESHOLDS (at least one: the
+ * FSS is a score of events), HOST triples with the strict float32 event test ev(.) of the dpn_verify_* block; K = n_scales half-widths
+ * radius[k] >= 0 in lattice nodes, 1..DPN_NBHD_MAX_SCALES, strictly ascending, the window of half-width r being (2 r + 1)^2 nodes; a lattice with
+ * nx * ny * nt < 2^31.  Plane p = it * E + e.
+ * Values: x from out_n and b from coord_data, formed as dpn_verify_accumulate forms them (with_clip on both); o = analysis[it][j][iy][ix], fp32
+ * [nt][P][ny][nx] on the device (the layout dpn_diagnostics_out writes maps in), physical units, never clipped, NaN = none.  A node of a column
+ * is valid when x, b and o are all finite.
+ * dpn_nbhd_stage takes ONE case's chunk (out_n, coord_data [n][6]: points first .. first + n of *lattice; analysis: the whole array), finds its
+ * own (it, iy, ix) and writes, for every threshold e on column j, mask[it][e][iy][ix] (uint8 [nt][E][ny][nx]):
+ *   bit 0: valid && ev(x);  bit 1: valid && ev(b);  bit 2: valid && ev(o);  bit 3: valid.        One thread per point, plain byte stores.
+ * dpn_nbhd_fold runs once a case's lattice is fully staged, for planes p0 .. p0 + np.  scratch (DEVICE, 16-byte aligned) holds, for the np planes,
+ *   int32 S[np][ny + 1][nx + 1][4]; then double part[np][K][ny][5]; then int32 rows[np][K][ny]                  (no gaps)
+ * S is the exclusive summed-area table of the four counts f, b, o, valid (mask bits 0..3) of a plane, interleaved so that a corner is one 16-byte
+ * load: S[y][x][c] = the number of nodes iy < y, ix < x with bit c set; row 0 and column 0 are zero.  Integer sums are exact: the order of the
+ * scan is free (a row pass by wave shuffles, then a column pass).
+ * The window of node (ix, iy) at half-width r is clamped to the plane: x0 = max(ix - r, 0), x1 = min(ix + r + 1, nx), y0 = max(iy - r, 0),
+ * y1 = min(iy + r + 1, ny); each count c = S[y1][x1] - S[y0][x1] - S[y1][x0] + S[y0][x0] in int32.  A window with c_valid == 0 is skipped.
+ * Otherwise, every operation an fp64 operation rounded on its own (the kernels are compiled without contraction):
+ *   V = (double)c_valid;  Pf = (double)c_f / V;  Pb = (double)c_b / V;  Po = (double)c_o / V;  a = Pf - Po;  g = Pb - Po
+ *   the five terms a * a, Pf * Pf, Po * Po, g * g, Pb * Pb (of sum_fo2, sum_f2, sum_o2, sum_bo2, sum_b2), and the window count + 1.
+ * Order of the reduction: one 64-lane wave per (plane, scale, row iy): lane l adds, from +0.0 and 0, the terms of the nodes ix = l, l + 64, .. in
+ * that order, then lane 0 adds to its own result those of lanes 1..63 in lane order -> part[pl][k][iy][0..4], rows[pl][k][iy].  One wave per
+ * (plane, scale) then folds the rows the same way (lane l the rows l, l + 64, ..; lane 0 the lane results in lane order) and adds the case's
+ * total to the state with one fp64 addition per sum (int64 for the count); the plane totals S[ny][nx] are added to n_f, n_b, n_o, n_valid.  Any
+ * np gives the same bits.
+ * State (DpnNbhdState), zeroed by the caller with one memset:
+ *   double sum_fo2, sum_f2, sum_o2, sum_bo2, sum_b2 [nt][E][K]; int64 windows [nt][E][K]; int64 n_valid, n_f, n_b, n_o [nt][E].
+ * dpn_nbhd_finish writes two tables (DpnNbhdOut), `hour` per (it, e) and `all` per e, the latter from the state's entries added over it = 0 ..
+ * nt - 1 in that order (fp64 and int64).  Every float is an fp32 cast of the fp64 result, NaN where its denominator is 0:
+ *   fss = 1.0 - sum_fo2 / (sum_f2 + sum_o2);  base_fss = 1.0 - sum_bo2 / (sum_b2 + sum_o2);  windows                       [..][K]
+ *   freq_f, freq_b, freq_o = (double)n_. / (double)n_valid;  fbias = (double)n_f / (double)n_o;  base_fbias = (double)n_b / (double)n_o;
+ *   useful = 0.5 + freq_o * 0.5;  count = n_valid;  skilful_scale, base_skilful_scale: the smallest k whose fp64 fss (base_fss) is defined
+ *   and >= the fp64 useful, or -1 (also when n_valid == 0).
+ * -1 (nothing launched, nothing written): a NULL required pointer; stage: n <= 0, first < 0, first + n past the lattice, n_products outside
+ * 1..DPN_VERIFY_MAX_COLUMNS, a thr_col outside 0..n_products - 1, an id other than 25, 26, 28..33, a side other than the two, a threshold that is
+ * not finite; all: n_thr outside 1..DPN_VERIFY_MAX_THRESHOLDS; stage, fold: nx, ny or nt < 1, nx * ny * nt >= 2^31; fold, finish: n_scales
+ * outside 1..DPN_NBHD_MAX_SCALES; fold: a radius < 0 or not strictly ascending, p0 < 0, np <= 0, p0 + np > nt * E, np * ny or np * ceil((nx + 1)
+ * / 64) past 2^31 - 1 (one block per plane and row, and per plane and 64 columns); finish: nt < 1. */
+#define DPN_NBHD_MAX_SCALES 8
+typedef struct DpnNbhdState {
+    double *sum_fo2, *sum_f2, *sum_o2, *sum_bo2, *sum_b2;
+    int64_t* windows;
+    int64_t *n_valid, *n_f, *n_b, *n_o;
+} DpnNbhdState;
+typedef struct DpnNbhdOut {
+    float *fss, *base_fss;
+    int64_t* windows;
+    float *freq_f, *freq_b, *freq_o, *fbias, *base_fbias, *useful;
+    int64_t* count;
+    int32_t *skilful_scale, *base_skilful_scale;
+} DpnNbhdOut;
+int dpn_nbhd_stage(const float* out_n, const float* coord_data, const float* analysis, int64_t n, const DpnPhysics* phys, int with_clip,
+                   const int32_t* products /* HOST, n_products ids */, int n_products, const int32_t* thr_col /* HOST [n_thr] */,
+                   const float* thr_val /* HOST [n_thr] */, const int32_t* thr_side /* HOST [n_thr] */, int n_thr, const DpnLattice* lattice,
+                   int64_t first, uint8_t* mask, void* stream);
+int dpn_nbhd_fold(const uint8_t* mask, const DpnLattice* lattice, int n_thr, const int32_t* radius /* HOST [n_scales] */, int n_scales, int64_t p0,
+                  int64_t np, void* scratch, const DpnNbhdState* state, void* stream);
+int dpn_nbhd_finish(const DpnNbhdState* state, int nt, int n_thr, int n_scales, const DpnNbhdOut* hour, const DpnNbhdOut* all, void* stream);
 
 /* ---------------------------------------------------------------- parcel trajectories through the learned wind (csrc/dpn_traj.hip)
  * One launch = one stage of an explicit Runge-Kutta step for n parcels whose stage positions depend only on the step's start point and the

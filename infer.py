@@ -9,6 +9,8 @@
                     [--regions name[,name...] --region_labels FILE.npy [--region_weights area|FILE.npy] [--region_threshold NAME:V[,V...]]...]
                     [--verify name[,name...] --verify_obs FILE.npz [--verify_threshold NAME:[above|below:]V[,V...]]... [--verify_by station,hour,all]
                      [--verify_members K]]
+                    [--verify_grid name[,name...] --verify_analysis FILE.npz --verify_grid_threshold NAME:[above|below:]V[,V...]...
+                     [--verify_scales 1,3,5,9,17,33]]
 
 Builds the interface from the config (train.py's loader), loads `physics_latest.pth` from --checkpoint_path (or inference_cfg.checkpoints) and
 calls `run_inference_interface`: every field sample is evaluated on the lattice inference_cfg.img_size (x `refine`) at every inference_cfg.dt
@@ -41,7 +43,12 @@ for the interpolated coarse forecast, the skill against it and the contingency s
 and over everything as <time>_verify_*.npy tables.  Without --verify_obs there is nothing to verify against (synthetic samples come with no reports).
 --verify_members K (default 1) takes K consecutive samples as the members of one case (obs then [M / K, H, S, P]) and scores the ensemble as a
 distribution (InterfacePhysics.verify_ensemble_at): CRPS, rank histogram, spread against skill, and per threshold the Brier score with its
-decomposition, the reliability diagram and the ROC area, for the model and the interpolated coarse forecast, as <time>_pverify_*.npy tables."""
+decomposition, the reliability diagram and the ROC area, for the model and the interpolated coarse forecast, as <time>_pverify_*.npy tables.
+--verify_grid T,speed --verify_analysis analysis.npz --verify_grid_threshold T:below:273.15 --verify_grid_threshold speed:15 --verify_scales 1,3,5,9,17,33
+sets inference_cfg.verify_grid: after the per-sample maps, all samples are taken as the cases of a neighbourhood verification on the fine grid
+(InterfacePhysics.verify_lattice) against the gridded analysis of the file -- names [P], hours [H], analysis [M, H, P, ny, nx] on the fine grid's nodes,
+NaN where there is none -- and the fractions skill score of the model and of the interpolated coarse forecast at every window width (in nodes, odd),
+the event frequencies, the frequency biases and the smallest skilful scale are written per hour and over all hours as <time>_nbhd_*.npy tables."""
 import argparse
 
 import torch
@@ -95,6 +102,13 @@ parse.add_argument('--verify_members', default=1, type=int,
                    help='K: inference_cfg.verify.members, K consecutive samples are the members of one case (probabilistic scores; reports [M / K, H, S, P])')
 parse.add_argument('--verify_by', default=['station', 'hour', 'all'], type=lambda s: [n for n in s.split(',') if n],
                    help='station,hour,all: inference_cfg.verify.by, the groupings the point scores are pooled over')
+parse.add_argument('--verify_grid', default=None, type=lambda s: [n for n in s.split(',') if n],
+                   help='name[,name...]: inference_cfg.verify_grid.products, fractions skill scores against a gridded analysis (VERIFY_PRODUCTS)')
+parse.add_argument('--verify_analysis', default=None, type=str, help='FILE.npz: names [P], hours [H], analysis [M, H, P, ny, nx] on the fine grid (NaN: none)')
+parse.add_argument('--verify_grid_threshold', default=[], action='append', type=str,
+                   help='NAME:V[,V...] | NAME:above:V[,V...] | NAME:below:V[,V...] (repeatable): inference_cfg.verify_grid.thresholds, at least one')
+parse.add_argument('--verify_scales', default=None, type=lambda s: [int(v) for v in s.split(',') if v],
+                   help='W[,W...]: inference_cfg.verify_grid.scales, odd window widths in nodes, ascending (default 1,3,5,9,17,33)')
 
 
 def _window_option(args, key, word):
@@ -153,6 +167,38 @@ def regions_option(args):
                 thresholds=_thresholds(args.region_threshold, '--region_threshold'))
 
 
+def _sided_thresholds(items, flag):
+    """{name: [('above' | 'below', value), ...]} of the NAME:[above|below:]V[,V...] items of `flag`."""
+    thresholds = {}
+    for item in items:
+        parts = item.split(':')
+        if len(parts) == 2:
+            parts = [parts[0], 'above', parts[1]]
+        if len(parts) != 3 or not parts[0] or parts[1] not in ('above', 'below') or not parts[2]:
+            parse.error('%s takes NAME:V[,V...], NAME:above:V[,V...] or NAME:below:V[,V...], got %r' % (flag, item))
+        thresholds.setdefault(parts[0], []).extend((parts[1], float(v)) for v in parts[2].split(',') if v)
+    return thresholds
+
+
+def verify_grid_option(args):
+    """inference_cfg['verify_grid'] of --verify_grid / --verify_analysis / --verify_grid_threshold / --verify_scales: dict(products=[...],
+    analysis=FILE.npz, thresholds={name: [('above' | 'below', value), ...]}, scales=[...]), or None without --verify_grid."""
+    if not args.verify_grid:
+        if args.verify_analysis or args.verify_grid_threshold or args.verify_scales:
+            parse.error('--verify_analysis, --verify_grid_threshold and --verify_scales need --verify_grid')
+        return None
+    if not args.verify_analysis:
+        parse.error('--verify_grid needs --verify_analysis FILE.npz (names, hours, analysis [M, H, P, ny, nx]): there is nothing to verify against '
+                    'without an analysis, and --synthetic samples come with none')
+    if not args.verify_grid_threshold:
+        parse.error('--verify_grid needs at least one --verify_grid_threshold NAME:[above|below:]V[,V...]: the fractions skill score is a score of events')
+    option = dict(products=list(args.verify_grid), analysis=args.verify_analysis,
+                  thresholds=_sided_thresholds(args.verify_grid_threshold, '--verify_grid_threshold'))
+    if args.verify_scales:
+        option['scales'] = list(args.verify_scales)
+    return option
+
+
 def verify_option(args):
     """inference_cfg['verify'] of --verify / --verify_obs / --verify_threshold / --verify_by: dict(products=[...], obs=FILE.npz, thresholds={name:
     [values and ('below', value) pairs]}, by=[...]), or None without --verify."""
@@ -163,14 +209,7 @@ def verify_option(args):
     if not args.verify_obs:
         parse.error('--verify needs --verify_obs FILE.npz (lon, lat, hours, names, obs [M, H, S, P]): there is nothing to verify against without '
                     'reports, and --synthetic samples come with none')
-    thresholds = {}
-    for item in args.verify_threshold:
-        parts = item.split(':')
-        if len(parts) == 2:
-            parts = [parts[0], 'above', parts[1]]
-        if len(parts) != 3 or not parts[0] or parts[1] not in ('above', 'below') or not parts[2]:
-            parse.error('--verify_threshold takes NAME:V[,V...], NAME:above:V[,V...] or NAME:below:V[,V...], got %r' % item)
-        thresholds.setdefault(parts[0], []).extend((parts[1], float(v)) for v in parts[2].split(',') if v)
+    thresholds = _sided_thresholds(args.verify_threshold, '--verify_threshold')
     option = dict(products=list(args.verify), obs=args.verify_obs, thresholds=thresholds, by=list(args.verify_by))
     if args.verify_members != 1:
         option['members'] = args.verify_members
@@ -200,6 +239,8 @@ if __name__ == '__main__':
         cfg.setdefault('inference_cfg', {})['regions'] = regions_option(args)
     if verify_option(args):
         cfg.setdefault('inference_cfg', {})['verify'] = verify_option(args)
+    if verify_grid_option(args):
+        cfg.setdefault('inference_cfg', {})['verify_grid'] = verify_grid_option(args)
     model = builder_models(**cfg)
     kwargs = dict(checkpoint_path=args.checkpoint_path)
     if args.synthetic:
@@ -238,4 +279,9 @@ if __name__ == '__main__':
         print('verification %s%s: point %s, pairs counted %d..%d, groupings %s, thresholds %s'
               % (','.join(v['names']), ' of %d members' % v['members'] if 'members' in v else '', tuple(v['point']['bias'].shape),
                  int(v['point']['count'].min()), int(v['point']['count'].max()), [k for k in v if k not in ('names', 'thresholds', 'members', 'point')],
+                 v['thresholds']))
+    if model.last_grid_verification is not None:
+        v = model.last_grid_verification
+        print('neighbourhood verification %s: fss %s, scales %s, nodes counted %d..%d, thresholds %s'
+              % (','.join(v['names']), tuple(v['hour']['fss'].shape), v['scales'], int(v['hour']['count'].min()), int(v['hour']['count'].max()),
                  v['thresholds']))
