@@ -68,8 +68,9 @@ def hyper_weights(state, net, meta_out, fore_h):
     return w1b1, w2b2, e
 
 
-def phase_a(W, pe, dpe, pe6, ref, prec, fused=False):
+def phase_a(W, pe, dpe, pe6, ref, prec, fused=False, masks=None):
     """fwd value + reverse sweep.  Returns normalised out [N], J_xi [N,3] and the saved per-point state.
+    masks = (m1, m2) [N, 256] forces the two ReLU masks (tests/wgrad_cases.py: the masks a kernel saved) instead of taking them from the pre-activations.
 
     fused (round 5, csrc/dpn_fwd_tiles.h + dpn_layout.h): W1 = cat_fc1.fc.0.weight only ever multiplies c = w2 h1 + Wd pe6 + cvec and W1^T only
     ever meets w2^T on the way back, so with A = W1 w2 and B = W1 Wd formed once per net (exact)
@@ -77,7 +78,7 @@ def phase_a(W, pe, dpe, pe6, ref, prec, fused=False):
     five GEMMs per point and net instead of seven; c and v = d out / d c are never formed (the backward pass needs neither: phase_b)."""
     w1, b1, w2, b2 = W['w1b1'][:, :192], W['w1b1'][:, 192], W['w2b2'][:, :256], W['w2b2'][:, 256]
     pre1 = mm(pe, w1.T, prec) + b1
-    m1 = (pre1 > 0).to(pe.dtype)
+    m1 = (pre1 > 0).to(pe.dtype) if masks is None else masks[0].to(pe.dtype)
     h1 = pre1 * m1
     cvec = b2 + W['bd'] + W['e']
     u = W['W2'].T @ W['wo']                                            # [256]
@@ -85,14 +86,14 @@ def phase_a(W, pe, dpe, pe6, ref, prec, fused=False):
         A, B = W['W1'] @ w2, W['W1'] @ W['Wd']
         a2 = w2.T @ W['wo']
         pre2 = mm(h1, A.T, prec) + mm(pe6, B.T, prec) + (W['W1'] @ cvec + W['bf1'])
-        m2 = (pre2 > 0).to(pe.dtype)
+        m2 = (pre2 > 0).to(pe.dtype) if masks is None else masks[1].to(pe.dtype)
         out = (pre2 * m2) @ u + 2.0 * (h1 @ a2 + pe6 @ (W['Wd'].T @ W['wo']) + W['wo'] @ cvec) + (W['wo'] @ W['bf2'] + W['bo']) + ref
         y = mm(m2 * u, A, prec) + 2.0 * a2
         v = None
     else:
         c = mm(h1, w2.T, prec) + mm(pe6, W['Wd'].T, prec) + cvec
         pre2 = mm(c, W['W1'].T, prec) + W['bf1']
-        m2 = (pre2 > 0).to(pe.dtype)
+        m2 = (pre2 > 0).to(pe.dtype) if masks is None else masks[1].to(pe.dtype)
         a = pre2 * m2
         out = a @ u + 2.0 * (c @ W['wo']) + (W['wo'] @ W['bf2'] + W['bo']) + ref
         t2 = m2 * u
@@ -166,8 +167,9 @@ def residuals(out_n, jn, f, with_clip=True, factors=O.LOSS_FACTOR):
     return losses, gval * sm, gJ * sm[:, :, None], val, J
 
 
-def phase_b(W, S, pe, dpe, pe6, gout, gjxi, prec):
+def phase_b(W, S, pe, dpe, pe6, gout, gjxi, prec, z1=None):
     """Parameter gradients of one net from per-point cotangents gout [N] (on out) and gjxi [N,3] (on J_xi).
+    z1 [N, 256]: a given Z1 (tests/wgrad_cases.py: the one a kernel wrote) in place of m1 (.) (Z0 w1^T + g b1).
 
     Round 5: every product with the second ReLU mask on the X side factors through the mask-side sums
         S1 = M2^T Z1 [256, 256],  S2 = M2^T (g pe6) [256, 192],  mvec = M2^T g,   q1 = colsum(Z1), q6 = colsum(g pe6), sg = sum g
@@ -179,7 +181,7 @@ def phase_b(W, S, pe, dpe, pe6, gout, gjxi, prec):
     N = pe.shape[0]
     pt = (dpe * gjxi[:, None, None, :]).reshape(N, -1)                 # sum_c gJ_c * dpe_c  (disjoint channels)
     Z0 = gout[:, None] * pe + pt
-    Z1 = S['m1'] * (mm(Z0, w1.T, prec) + gout[:, None] * b1)
+    Z1 = S['m1'] * (mm(Z0, w1.T, prec) + gout[:, None] * b1) if z1 is None else z1
     gpe6 = gout[:, None] * pe6
     cvec = W['w2b2'][:, 256] + W['bd'] + W['e']
     S1 = mm(S['m2'].T, Z1, prec)                                        # [256 o, 256 j]

@@ -35,18 +35,18 @@ def all_cases():
     return [('raw', n, p) for n in SIZES for p in PRECS] + [('pe_in', 70, p) for p in PRECS]
 
 
-def _model(prec):
+def _model(prec, gain=1.0):
     import torch
     from deepphysinet_amd.configs import ncep_config
     from deepphysinet_amd.interface import builder_models
     from oracle.fill import fill_state_dict_
-    if prec not in _models:
+    if (prec, gain) not in _models:
         m = builder_models(**ncep_config(), precision=prec)
         sd = m.physics_net.state_dict()
-        fill_state_dict_(sd)
+        fill_state_dict_(sd, gain=gain)
         m.physics_net.load_state_dict(sd)
-        _models[prec] = m.to(torch.device('cuda:0'))
-    return _models[prec]
+        _models[(prec, gain)] = m.to(torch.device('cuda:0'))
+    return _models[(prec, gain)]
 
 
 def _randn(shape, seed, dev):
@@ -54,14 +54,18 @@ def _randn(shape, seed, dev):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)).to(dev)
 
 
-def run_case(route, n, prec, zero_cotangents=False, bwd_kernel=None):
+def run_case(route, n, prec, zero_cotangents=False, bwd_kernel=None, cotangents=None, scale=G_SCALE, gain=1.0, keep=False):
     """One pass pack -> dpn_fwd_ref -> dpn_bwd_points_scaled (route 'raw': raw coordinates, g_out and g_jxi, scale 0.75) or dpn_bwd_points (route
-    'pe_in': caller-encoded coordinates, g_out only) -> dpn_wgrad -> dpn_wgrad_finish.  Returns {'operands', 'g_heads', 'g_evec', 'static_00' ..}."""
+    'pe_in': caller-encoded coordinates, g_out only) -> dpn_wgrad -> dpn_wgrad_finish.  Returns {'operands', 'g_heads', 'g_evec', 'static_00' ..}.
+    cotangents = (g_out [n, 6], g_jxi [n, 6, 3] or None), host or device tensors, in place of the seeded normal ones (route 'pe_in' takes g_out alone);
+    scale: the scalar of dpn_bwd_points_scaled; gain: fill_state_dict_'s.  keep: the result also holds 'saved', 'partials' (zeroed before the launch:
+    the ranges no product writes stay zero) and 'inputs' = what the launches were handed (heads, evec, statics, x, y, t, coord_data, pe_in, g_out,
+    g_jxi, scale, geometry, k_splits = the point ranges of dpn_sizes) -- tests/test_gpu_wgrad_fp64.py compares the outputs with an fp64 evaluation of the same operation on them."""
     import torch
     from deepphysinet_amd import _lib as L
     from deepphysinet_amd import point_path as P
     from oracle.fill import synthetic_inputs
-    m = _model(prec)
+    m = _model(prec, gain)
     dev = torch.device('cuda:0')
     g = {k: v.to(dev) for k, v in synthetic_inputs(n, tag='inter').items()}
     cfg = m.point_config()
@@ -80,11 +84,14 @@ def run_case(route, n, prec, zero_cotangents=False, bwd_kernel=None):
         pe_in = torch.sin(_randn((n, 192), 4, dev) * 3.0).contiguous()               # any finite features in [-1, 1]
     g_out = _randn((n, 6), 1, dev)
     g_jxi = _randn((n, 6, 3), 2, dev) if route == 'raw' else None
+    if cotangents is not None:
+        g_out = cotangents[0].to(dev, torch.float32).contiguous()
+        g_jxi = cotangents[1].to(dev, torch.float32).contiguous() if (route == 'raw' and cotangents[1] is not None) else None
     if zero_cotangents:
         g_out.zero_()
         if g_jxi is not None:
             g_jxi.zero_()
-    scale = torch.full((1,), G_SCALE, device=dev)
+    scale = torch.full((1,), float(scale), device=dev)
     prev = os.environ.get('DPN_BWD_KERNEL')
     if bwd_kernel:
         os.environ['DPN_BWD_KERNEL'] = bwd_kernel
@@ -93,7 +100,7 @@ def run_case(route, n, prec, zero_cotangents=False, bwd_kernel=None):
         out = torch.empty(n, 6, device=dev)
         saved = torch.zeros(ws.sizes.saved, dtype=torch.uint8, device=dev)            # (zeroed: the buffers have bytes no kernel writes)
         operands = torch.zeros(ws.sizes.operands, dtype=torch.uint8, device=dev)
-        partials = torch.empty(ws.sizes.partials, dtype=torch.uint8, device=dev)
+        partials = (torch.zeros if keep else torch.empty)(ws.sizes.partials, dtype=torch.uint8, device=dev)
         xyt = (P._ptr(x), P._ptr(y), P._ptr(t)) if pe_in is None else (None, None, None)
         jac = torch.empty(n, 6, 3, device=dev) if pe_in is None else None
         L.check(lib.dpn_fwd_ref(*xyt, P._ptr(pe_in), P._ptr(cd), None, n, P._ptr(fr), ctypes.byref(geo), P._ptr(ws.packed), cfg.prec, P._ptr(out), P._ptr(jac),
@@ -119,6 +126,10 @@ def run_case(route, n, prec, zero_cotangents=False, bwd_kernel=None):
     res = {'operands': operands, 'g_heads': g_heads, 'g_evec': g_evec}
     for i, s in enumerate(g_stat):
         res['static_%02d' % i] = s
+    if keep:
+        res.update(saved=saved, partials=partials,
+                   inputs=dict(heads=heads, evec=evec, statics=statics, x=x, y=y, t=t, coord_data=cd, pe_in=pe_in, g_out=g_out, g_jxi=g_jxi,
+                               scale=scale, geometry=(geo.dx, geo.dy, geo.lon_m1, geo.lat_m1, geo.pred_t_span), k_splits=int(ws.sizes.k_splits)))
     return res
 
 
