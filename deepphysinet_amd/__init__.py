@@ -7,7 +7,8 @@ Drop-in surfaces (same names / arguments as the reference, /root/reference/DeepP
     deepphysinet_amd.interface.InterfacePhysics, builder_models        (interface/interface_physics.py, build.py)
     deepphysinet_amd.sampler.CollocationSampler                        (dataset/physics_dataset.py:323-587, on the device)
     deepphysinet_amd.sampler.Lattice, InterfacePhysics.predict_points / predict_lattice / residuals_at / run_inference_interface
-                                                                       (inference at stations and on lattices, interface_physics.py:1407-1530)
+                                                                       (inference at stations and on lattices, interface_physics.py:1407-1530;
+                                                                        the run and its table of products: interface/inference_run.py)
     deepphysinet_amd.optim.FusedClipAdam, distributed.GradientAllReduce (clip_grad_norm_ + Adam, DDP gradient averaging)
     deepphysinet_amd.lbfgs.FusedLBFGS                                  (L-BFGS refinement with a strong-Wolfe line search on the flat buffers)
 The per-point arithmetic runs in libdpn_hip.so (hand-written HIP for gfx950, C ABI in include/dpn_hip.h).

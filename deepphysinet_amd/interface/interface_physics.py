@@ -19,7 +19,7 @@ from ..balance import LossBalance
 from ..causal import CausalWeights
 from ..diagnostics import product_ids
 from ..ensemble import check_thresholds, ensemble_ids
-from ..trajectory import check_request, domain_of, stage_table
+from ..trajectory import check_request, domain_of
 from .. import extremes as X
 from .. import spells as SP
 from .. import regions as RG
@@ -38,6 +38,7 @@ from ..sampler import SyntheticSamples
 from ..staged_backward import StagedBackward
 from ..utils.position_encoding import SineCosPE
 from .. import _lib as L, encoder_ops, grad_arena, validation as V
+from .inference_run import PRODUCTS, run_inference
 
 
 def _loop_option(kwargs, train_cfg, name, section, known, true_is_empty, instance_of, build):
@@ -91,11 +92,8 @@ class InterfacePhysics(nn.Module):
         self.precision = L.PREC_NAMES[precision]
         self._cfg_cache = None
         self.loss_balance_state = None          # training_step(balance=...): {'groups', 'lam' (fp32 [K], device), 'step', 'diag' (device or None)}
-        self.last_trajectories = None           # run_inference_interface with inference_cfg.trajectories: the last sample's trajectories() dict (lonlat)
-        self.last_diagnostics = None            # run_inference_interface with log.export_diagnostic: {'names', 'maps' [nt, P, ny, nx]} of the last sample
-        self.last_verification = None           # run_inference_interface with inference_cfg.verify: verify_at's dict over all samples
-        self.last_ensemble = None               # run_inference_interface with inference_cfg.ensemble: ensemble_lattice's dict over all samples
-        self.last_regions = None                # run_inference_interface with inference_cfg.regions: the last sample's regional_lattice dict
+        for p in PRODUCTS:                      # run_inference_interface: where each product's result of the last run stays (inference_run.PRODUCTS)
+            setattr(self, p.last, None)
 
     # ------------------------------------------------------------------ configuration of the HIP path
     def point_config(self, loss_factor=None, criterion=None) -> PointConfig:
@@ -963,11 +961,6 @@ class InterfacePhysics(nn.Module):
         xd, yd = self._window_lattice(lattice, field_data.device)
         out = self._window_run(SpellState, field_data, sampler, xd, yd, req, forecast_h, with_clip, chunk_points)
         return dict({k: v.view(len(req.ids), lattice.ny, lattice.nx) for k, v in out.items()}, names=req.names)
-
-    # the inference loop's time-window keys: inference_cfg key, file word, the request check, the lattice method, the station method, where the last
-    # sample's result stays
-    _WINDOW_PRODUCTS = (('extremes', 'extreme', X.check_request, 'extreme_lattice', 'extremes_at', 'last_extremes'),
-                        ('spells', 'spell', SP.check_request, 'spell_lattice', 'spells_at', 'last_spells'))
 
     @torch.no_grad()
     def adaptive_interior(self, batch: dict, sampler, pool_factor=8, k=1.0, c=1.0):
@@ -2022,306 +2015,11 @@ class InterfacePhysics(nn.Module):
         log.write_source one `<time>_<variable>.npy` [lat, lon] per time step and exported variable goes to log.result_path (start_time only labels
         the files).  Returns the maps [nt, 6, ny, nx] of the last sample (None without samples).  kwargs: checkpoint_path, samples, device, with_clip,
         weights ('ema': the checkpoint's averaged weights `model_ema` in place of `model`; KeyError when it carries none).
-        log.export_diagnostic (a list of names of deepphysinet_amd.diagnostics.PRODUCTS, default absent: no further call): per sample ONE
-        diagnostic_lattice call on the same lattice with the same with_clip, with log.write_source one `<time>_<name>.npy` [lat, lon] per time step and
-        product next to the variables' files; the last sample's {'names', 'maps' [nt, P, ny, nx]} stay in self.last_diagnostics (None without the key
-        or without samples).  An unknown name is a KeyError before the checkpoint is read.
-        inference_cfg.trajectories (default absent: no further call): dict(lonlat=[(lon, lat), ...], start=H, hours=D, step=S, method='rk4'): per
-        sample ONE trajectories call (lonlat, with_fields, the same with_clip) for parcels started at those places at hour H of the sample's window and
-        followed for D hours (negative: backward) in steps of S hours; the last sample's result stays in self.last_trajectories, and with
-        log.write_source `<time>_traj_positions.npy` [K + 1, N, 2] (degrees), `_traj_hours.npy`, `_traj_status.npy`, `_traj_steps.npy` and
-        `_traj_fields.npy` [K + 1, N, 6] go next to the maps, <time> the sample's first time step.  A bad request fails before the checkpoint is read.
-        inference_cfg.ensemble (default absent: no further call) = dict(products=[names of deepphysinet_amd.ensemble.ENSEMBLE_PRODUCTS],
-        thresholds={name: [values]}): the per-sample loop runs as without it, then ONE ensemble_lattice call takes all samples as the members of an
-        ensemble on the first sample's lattice with the same with_clip; its dict stays in self.last_ensemble, and with log.write_source
-        `<time>_ens_<mean|spread|min|max|count>_<name>.npy` and `<time>_ens_prob_<name>_gt_<value>.npy` [lat, lon] are written per time step, <time>
-        the first sample's stamps.  An unknown name (KeyError) or a bad threshold (ValueError) fails before the checkpoint is read.
-        inference_cfg.extremes (default absent: no further call) = dict(columns=['T:max', 'T:min', 'speed:max'], window=(H0, H1), scan_hours=1.0,
-        refine=10, lonlat=[(lon, lat), ...] or absent): per sample ONE extreme_lattice call on the positions of the sample's lattice -- or, with lonlat,
-        ONE extremes_at call at those stations -- over the hours H0..H1 of the sample's window, with the same with_clip; the last sample's dict stays in
-        self.last_extremes, and with log.write_source `<time>_extreme_<value|hour|lo|hi|status>_<product>_<sense>.npy` [lat, lon] (stations: one
-        `<time>_extreme_<value|...>.npy` [N, C] each) go next to the maps, <time> the sample's first time step.  An unknown column (KeyError) or a
-        bad window, scan step or round count (ValueError) fails before the checkpoint is read.
-        inference_cfg.spells (default absent: no further call) = dict(columns=['T:below:273.15', 'speed:above:15'], window=(H0, H1), scan_hours=1.0,
-        refine=10, lonlat=[(lon, lat), ...] or absent): the same for the threshold spells -- per sample ONE spell_lattice (with lonlat: spells_at) call;
-        the last sample's dict stays in self.last_spells, and with log.write_source
-        `<time>_spell_<hours|first|last|first_lo|last_hi|excess|crossings|status>_<product>_<side>_<threshold>.npy` [lat, lon] (stations: one
-        `<time>_spell_<hours|...>.npy` [N, C] each) go next to the maps.  A malformed column (KeyError) or a bad threshold, window, scan step or round
-        count (ValueError) fails before the checkpoint is read.
-        inference_cfg.verify, or the keyword verify= (default absent: no further call) = dict(products=[names of
-        deepphysinet_amd.verification.VERIFY_PRODUCTS], obs=<the path of an .npz, or a dict, with lon [S], lat [S], hours [H], names [P], obs
-        [M, H, S, P]: verification.read_observations>, thresholds={name: value(s) | ('below', value(s))}, by=['station', 'hour', 'all']): the
-        per-sample loop runs as without it, then ONE verify_at call takes all M samples as the cases, in the source's order, at the points
-        i = h * S + s of the file (lonlat) with the same with_clip; its dict stays in self.last_verification, and with log.write_source
-        `<time>_verify_<point|station|hour|all>_<score>.npy` [G, P] ([G, E] for the threshold scores) go next to the maps, <time> the first sample's
-        first time step.  An unknown name (KeyError), a bad threshold, grouping or file (ValueError) fails before the checkpoint is read; a file with
-        another number of cases than the source has samples (ValueError) before the first sample runs.  The optional key members=K (default 1: all of the above,
-        unchanged) takes K consecutive samples of the source as the members of one case, obs then [M / K, H, S, P]: ONE verify_ensemble_at call
-        behind the loop, its dict in self.last_verification and its tables in `<time>_pverify_<point|station|hour|all>_<score>.npy`; K outside
-        1..64 (ValueError) fails before the checkpoint is read, a sample count that is no multiple of K or a file with another number of cases
-        (ValueError) before the first sample runs.
-        inference_cfg.verify_grid, or the keyword verify_grid= (default absent: no further call) = dict(products=[names of VERIFY_PRODUCTS],
-        analysis=<the path of an .npz, or a dict, with names [P], hours [H] (equally spaced) and analysis [M, H, P, ny, nx] on the fine grid's
-        nodes: neighbourhood.read_analysis>, thresholds={name: value(s) | ('below', value(s))} (at least one), scales=[odd window widths in
-        nodes], default 1, 3, 5, 9, 17, 33): behind the loop ONE verify_lattice call takes all M samples as the cases on the fine grid's nodes at
-        the file's hours, with the same with_clip; its dict stays in self.last_grid_verification, and with log.write_source
-        `<time>_nbhd_<hour|all>_<score>.npy` go next to the maps, <time> the first sample's first time step.  An unknown name (KeyError), bad
-        thresholds or none, bad scales or a bad file (ValueError) fail before the checkpoint is read; a file with another number of cases than
-        the source has samples before the first sample runs, one on other nodes than the fine grid's before the call's first launch.
-        inference_cfg.regions (default absent: no further call) = dict(products=[names of deepphysinet_amd.ensemble.ENSEMBLE_PRODUCTS, at most 16],
-        labels=<an int plane [ny, nx] over the lattice, -1 = in no region, or the path of its .npy>, weights=None | 'area' | <a plane or its .npy>,
-        thresholds={name: [values]}): per sample, after the maps, ONE regional_lattice call on the lattice the loop evaluates, with the same
-        with_clip; the last sample's dict stays in self.last_regions, and with log.write_source
-        `<time>_region_<mean|total|weight|min|max|where_min|where_max|count>_<name>.npy` [nt, R] (where_*: [nt, R, 2], ix and iy) and
-        `<time>_region_frac_<name>_gt_<value>.npy` [nt, R] go next to the maps, <time> the sample's first time step.  An unknown name (KeyError) or
-        a bad threshold, label plane or weight (ValueError) fails before the checkpoint is read; labels of another shape than the lattice's at
-        the first sample.
+        The product keys, each read, checked and refused before the checkpoint is read, each with a `last_*` attribute that is None again at the start
+        of every run (inference_run.PRODUCTS, in its order; every entry carries its paragraph): log.export_diagnostic, inference_cfg.trajectories,
+        .ensemble, .verify (or the keyword verify=), .verify_grid (or the keyword verify_grid=), .regions, .extremes, .spells.
         Plotting (log.with_vis: Basemap) is not built."""
-        import datetime
-        ic = self.inference_cfg or {}
-        device = torch.device(kwargs.get('device', ic.get('device', 'cuda:0')))
-        img_size = ic.get('img_size', (self.lat_size, self.lon_size))
-        if isinstance(img_size, (int, float)):
-            lat_size, lon_size = int(img_size), int(img_size)
-        elif isinstance(img_size, (list, tuple)) and len(img_size) == 2:
-            lat_size, lon_size = (int(v) for v in img_size)
-        else:
-            raise NotImplementedError
-        refine = int(ic.get('refine', 1))
-        dt = float(ic.get('dt', 3600))
-        checkpoint_path = kwargs.get('checkpoint_path') or ic.get('checkpoints', {}).get('checkpoints_path')
-        log = ic.get('log', {})
-        write_source, result_path = bool(log.get('write_source', False)), log.get('result_path') or ''
-        export_variable = list(log.get('export_variable', ['T']))
-        if log.get('with_vis', False):
-            print('run_inference_interface: with_vis is set, but the Basemap plots of the reference are not built here; continuing without them')
-        if not write_source:
-            print('warning: write_source is False. No result will be saved.')
-        elif not result_path:
-            raise ValueError("run_inference_interface: log.write_source needs log.result_path")
-        names = {'U': 0, 'V': 1, 'P': 2, 'T': 3, 'Q': 4, 'RIO': 5}
-        for v in export_variable:
-            if v.upper() not in names:
-                raise KeyError('export_variable %r: one of %s' % (v, sorted(names)))
-        export_diagnostic = list(log.get('export_diagnostic') or [])
-        if export_diagnostic:
-            product_ids(export_diagnostic)                                # an unknown name: KeyError, before the checkpoint is read
-        self.last_diagnostics = None
-        traj = ic.get('trajectories')
-        if traj:
-            traj = dict({'method': 'rk4'}, **traj)
-            stage_table(traj['method'])                                   # an unknown method, a missing key, no place: before the checkpoint is read
-            traj_lon, traj_lat = ([float(p[j]) for p in traj['lonlat']] for j in (0, 1))
-            if not traj_lon or float(traj['step']) == 0.0 or float(traj['hours']) == 0.0:
-                raise ValueError('inference_cfg.trajectories: at least one (lon, lat), a non-zero step and a non-zero duration')
-            float(traj['start'])
-        self.last_trajectories = None
-        ens = ic.get('ensemble')
-        if ens:
-            ens = dict(products=list(ens['products']), thresholds=dict(ens.get('thresholds') or {}))
-            ensemble_ids(ens['products'])                                 # an unknown name (KeyError), a bad threshold (ValueError): before the
-            check_thresholds(ens['products'], ens['thresholds'])          # checkpoint is read
-        self.last_ensemble = None
-        ver = kwargs.get('verify', ic.get('verify'))
-        if ver:
-            unknown = set(ver) - {'products', 'obs', 'thresholds', 'by', 'members'}
-            if unknown or 'products' not in ver:
-                raise ValueError('inference_cfg.verify: products and obs (thresholds, by, members optional); unknown keys %s' % sorted(unknown))
-            if ver.get('obs') is None:
-                raise ValueError('inference_cfg.verify: no reports to verify against -- obs names an .npz with lon, lat, hours, names and obs '
-                                 '[M, H, S, P] (infer.py --verify_obs); synthetic samples come with none')
-            ver = dict(products=list(ver['products']), thresholds=dict(ver.get('thresholds') or {}), by=list(ver.get('by') or ()), obs=ver['obs'],
-                       members=ver.get('members', 1))
-            self._verify_request(ver['products'], ver['thresholds'], ver['by'], None if ver['members'] == 1 else ver['members'],
-                                 'verify' if ver['members'] == 1 else 'verify_ensemble')       # KeyError / ValueError: before the checkpoint is read
-            ver['reports'] = VF.read_observations(ver['obs'], ver['products'])
-            ver['points'] = VF.report_points(ver['reports'], ver['by'])
-        self.last_verification = None
-        grid = kwargs.get('verify_grid', ic.get('verify_grid'))
-        if grid:
-            unknown = set(grid) - {'products', 'analysis', 'thresholds', 'scales'}
-            if unknown or 'products' not in grid:
-                raise ValueError('inference_cfg.verify_grid: products, analysis, thresholds (scales optional); unknown keys %s' % sorted(unknown))
-            if grid.get('analysis') is None:
-                raise ValueError('inference_cfg.verify_grid: no analysis to verify against -- analysis names an .npz with names, hours and analysis '
-                                 '[M, H, P, ny, nx] (infer.py --verify_analysis); synthetic samples come with none')
-            grid = dict(products=list(grid['products']), thresholds=dict(grid.get('thresholds') or {}), analysis=grid['analysis'],
-                        scales=list(grid.get('scales') or NB.DEFAULT_SCALES))
-            if not self._verify_request(grid['products'], grid['thresholds'], word='verify_lattice')[2][0]:     # KeyError / ValueError: before the
-                raise ValueError('inference_cfg.verify_grid: no threshold; the fractions skill score is a score of events')    # checkpoint is read
-            NB.check_scales(grid['scales'])
-            grid['held'] = NB.read_analysis(grid['analysis'], grid['products'])
-        self.last_grid_verification = None
-        reg = ic.get('regions')
-        if reg:
-            unknown = set(reg) - {'products', 'labels', 'weights', 'thresholds'}
-            if unknown or 'products' not in reg or reg.get('labels') is None:
-                raise ValueError('inference_cfg.regions: products and labels (weights, thresholds optional); unknown keys %s' % sorted(unknown))
-            reg = dict(products=list(reg['products']), thresholds=dict(reg.get('thresholds') or {}), labels=reg['labels'], weights=reg.get('weights'))
-            self._region_request(reg['products'], reg['thresholds'])      # an unknown name (KeyError), a bad threshold (ValueError), and below a
-            for key in ('labels', 'weights'):                             # bad label plane or weight (ValueError): before the checkpoint is read
-                if isinstance(reg[key], os.PathLike) or (isinstance(reg[key], str) and reg[key].endswith('.npy')):
-                    reg[key] = np.load(reg[key])
-            rows = RG.region_plan(reg['labels']).shape[0]                 # (the shape itself is the first sample's lattice's to refuse)
-            RG.region_plan(reg['labels'], reg['weights'], np.zeros(rows) if isinstance(reg['weights'], str) else None)
-        self.last_regions = None
-        windows = []                                                      # (a row of _WINDOW_PRODUCTS, its options) of the keys that are set
-        for row in self._WINDOW_PRODUCTS:
-            key, _, check, _, _, last = row
-            opt = ic.get(key)
-            if opt:
-                opt = dict({'scan_hours': 1.0, 'refine': 10, 'lonlat': None}, **opt)
-                check(opt['columns'], opt['window'], opt['scan_hours'], opt['refine'], float('inf'))      # a bad request: before the checkpoint is read
-                if opt['lonlat'] is not None:
-                    opt['lonlat'] = [[float(p[j]) for p in opt['lonlat']] for j in (0, 1)]       # (lons, lats)
-                    if not opt['lonlat'][0]:
-                        raise ValueError('inference_cfg.%s: lonlat names no station (leave the key out for maps)' % key)
-                windows.append((row, opt))
-            setattr(self, last, None)
-        self.physics_net.to(device)
-        self.pe.to(device)
-        state_dict, current_epoch, global_step = (None, 0, 0) if not checkpoint_path else self.load_model(checkpoint_path, prefix='physics', map_location=device)
-        if state_dict is None:
-            raise NotImplementedError(checkpoint_path)
-        print('resume from epoch %d global_step %d' % (current_epoch, global_step))
-        which = kwargs.get('weights')
-        if which not in (None, 'raw', 'ema'):
-            raise ValueError("weights=%r: 'ema' or None" % (which,))
-        if which == 'ema' and 'model_ema' not in state_dict:
-            raise KeyError("the checkpoint %s carries no 'model_ema' (train with ema_weights / train.py --ema)" % checkpoint_path)
-        self.physics_net.load_state_dict(state_dict['model_ema' if which == 'ema' else 'model'], strict=True)
-        cfg_span = ic.get('pred_t_span', -1)
-        self.pred_t_span = float(self.gather_key_from_state('pred_t_span', state_dict, cfg_span if cfg_span and cfg_span > 0 else self.pred_t_span))
-        self.obs_norm_cfg = self.gather_key_from_state('obs_norm_cfg', state_dict, self.obs_norm_cfg)
-        self.physics_net.eval()
-        start = datetime.datetime.strptime(ic.get('start_time', '1970-01-01_00_00_00'), '%Y-%m-%d_%H_%M_%S')
-        if write_source:
-            os.makedirs(result_path, exist_ok=True)
-        maps = None
-        samples = self._inference_samples(kwargs)
-        if ens or ver or grid:
-            samples = list(samples)                                       # the members of the ensemble call / the cases of the verification behind the loop
-        if grid and samples and grid['held']['analysis'].shape[0] != len(samples):
-            raise ValueError('inference_cfg.verify_grid: the analysis holds %d cases, the sample source %d' % (grid['held']['analysis'].shape[0], len(samples)))
-        # K consecutive samples are one case: a count that does not fit the reports is refused before the first sample runs (K = 1: an empty
-        # source runs through untouched)
-        if ver and (ver['members'] > 1 or samples):
-            K, cases_held = ver['members'], ver['reports']['obs'].shape[0]
-            if len(samples) % K:
-                raise ValueError('inference_cfg.verify: %d samples are not a multiple of members = %d' % (len(samples), K))
-            if cases_held != len(samples) // K:
-                raise ValueError('inference_cfg.verify: the reports hold %d cases, the sample source %d' % (cases_held, len(samples) // K)
-                                 + (' of %d members' % K if K > 1 else ''))
-        first_lattice = None
-        for k, smp in enumerate(samples):
-            sampler = smp['sampler']
-            c = sampler.cfg
-            if (lat_size, lon_size) != (c.lat_size, c.lon_size):
-                raise ValueError('inference img_size %s is not the fine grid of the sample (%d, %d); finer output: inference_cfg["refine"]'
-                                 % ((lat_size, lon_size), c.lat_size, c.lon_size))
-            window_h = c.input_time_step * c.input_time_step_nums
-            nt = int(window_h * 3600.0 / dt + 1e-9) + 1                   # every dt inside [0, window], both ends
-            lattice = sampler.lattice(refine=refine, hours=(0.0, dt / 3600.0, nt))
-            first_lattice = first_lattice or lattice
-            maps = self.predict_lattice(smp['field_data'].to(device), sampler, lattice, smp['forecast_h'].to(device),
-                                        with_clip=kwargs.get('with_clip', self.with_clip))
-            diag = None
-            if export_diagnostic:
-                diag = self.diagnostic_lattice(smp['field_data'].to(device), sampler, lattice, smp['forecast_h'].to(device), export_diagnostic,
-                                               with_clip=kwargs.get('with_clip', self.with_clip))
-                self.last_diagnostics = dict(names=list(export_diagnostic), maps=diag)
-            if traj:
-                self.last_trajectories = self.trajectories(smp['field_data'].to(device), sampler, traj_lon, traj_lat, float(traj['start']),
-                                                           smp['forecast_h'].to(device), float(traj['hours']), float(traj['step']), traj['method'],
-                                                           lonlat=True, with_fields=True, with_clip=kwargs.get('with_clip', self.with_clip))
-            for (_, _, _, on_lattice, at_stations, last), opt in windows:
-                args = (smp['field_data'].to(device), sampler)
-                kw = dict(window=opt['window'], forecast_h=smp['forecast_h'].to(device), columns=opt['columns'], scan_hours=opt['scan_hours'],
-                          refine=opt['refine'], with_clip=kwargs.get('with_clip', self.with_clip))
-                if opt['lonlat'] is None:
-                    setattr(self, last, getattr(self, on_lattice)(*args, sampler.lattice(refine=refine, hours=0.0), **kw))
-                else:
-                    setattr(self, last, getattr(self, at_stations)(*args, *opt['lonlat'], lonlat=True, **kw))
-            if reg:
-                self.last_regions = self.regional_lattice(smp['field_data'].to(device), sampler, lattice, smp['forecast_h'].to(device), reg['labels'],
-                                                          reg['products'], weights=reg['weights'], thresholds=reg['thresholds'],
-                                                          with_clip=kwargs.get('with_clip', self.with_clip))
-            if write_source:
-                stamp = (start + datetime.timedelta(seconds=k * window_h * 3600.0)).strftime('%Y-%m-%d_%H_%M_%S')      # the sample's first time step
-                if reg:
-                    r = self.last_regions
-                    for key in RG.OUTPUTS:                                # one [nt, R] table per result and product (where_*: [nt, R, 2] = ix, iy)
-                        a = r[key].cpu().numpy()
-                        for j, name in enumerate(r['names']):
-                            np.save(os.path.join(result_path, '%s_region_%s_%s.npy' % (stamp, key, name)), a[:, :, j])
-                    for j, (name, value) in enumerate(r['thresholds']):
-                        np.save(os.path.join(result_path, '%s_region_frac_%s_gt_%g.npy' % (stamp, name, value)), r['frac'][:, :, j].cpu().numpy())
-                for (_, word, _, _, _, last), opt in reversed(windows):       # (the spells' files before the extremes')
-                    result = dict(getattr(self, last))
-                    columns = result.pop('names')
-                    for key, v in result.items():                         # the product's results in its state's order
-                        a = v.cpu().numpy()
-                        if opt['lonlat'] is not None:                     # stations: one [N, C] table per result
-                            np.save(os.path.join(result_path, '%s_%s_%s.npy' % (stamp, word, key)), a)
-                            continue
-                        for j, name in enumerate(columns):                # maps: one [lat, lon] file per result and column
-                            np.save(os.path.join(result_path, '%s_%s_%s_%s.npy' % (stamp, word, key, name.replace(':', '_'))), a[j])
-                if traj:
-                    for key, name in (('positions', 'positions'), ('hours', 'hours'), ('status', 'status'), ('steps_done', 'steps'), ('fields', 'fields')):
-                        np.save(os.path.join(result_path, '%s_traj_%s.npy' % (stamp, name)), self.last_trajectories[key].cpu().numpy())
-                host = maps.cpu().numpy()
-                host_diag = None if diag is None else diag.cpu().numpy()
-                for it in range(nt):
-                    stamp = (start + datetime.timedelta(seconds=k * window_h * 3600.0 + it * dt)).strftime('%Y-%m-%d_%H_%M_%S')
-                    for v in export_variable:
-                        np.save(os.path.join(result_path, '%s_%s.npy' % (stamp, v)), host[it, names[v.upper()]])
-                    for j, name in enumerate(export_diagnostic):
-                        np.save(os.path.join(result_path, '%s_%s.npy' % (stamp, name)), host_diag[it, j])
-        if ens and first_lattice is not None:
-            e = self.ensemble_lattice(samples, first_lattice, ens['products'], ens['thresholds'], with_clip=kwargs.get('with_clip', self.with_clip))
-            self.last_ensemble = e
-            if write_source:
-                host = {key: e[key].cpu().numpy() for key in ('mean', 'spread', 'min', 'max', 'count')}
-                prob = None if e['prob'] is None else e['prob'].cpu().numpy()
-                for it in range(first_lattice.nt):                        # the stamps of the first sample
-                    stamp = (start + datetime.timedelta(seconds=it * dt)).strftime('%Y-%m-%d_%H_%M_%S')
-                    for j, name in enumerate(e['names']):
-                        for key, a in host.items():
-                            np.save(os.path.join(result_path, '%s_ens_%s_%s.npy' % (stamp, key, name)), a[it, j])
-                    for j, (name, value) in enumerate(e['thresholds']):
-                        np.save(os.path.join(result_path, '%s_ens_prob_%s_gt_%g.npy' % (stamp, name, value)), prob[it, j])
-        if ver and first_lattice is not None:
-            K = ver['members']
-            lon, lat, hrs, groups = ver['points']
-            reports = [torch.from_numpy(o.reshape(lon.size, -1)).to(device) for o in ver['reports']['obs']]
-            if K == 1:
-                call, word, cases = self.verify_at, 'verify', [dict(smp, obs=o) for smp, o in zip(samples, reports)]
-            else:
-                call, word = self.verify_ensemble_at, 'pverify'
-                cases = [dict(members=samples[c * K:(c + 1) * K], obs=o) for c, o in enumerate(reports)]
-            v = call(cases, lon, lat, hrs, ver['products'], ver['thresholds'], by=groups, with_clip=kwargs.get('with_clip', self.with_clip), lonlat=True)
-            self.last_verification = v
-            if write_source:
-                stamp = start.strftime('%Y-%m-%d_%H_%M_%S')
-                for group in ['point'] + list(groups):
-                    for key, a in v[group].items():
-                        if a is not None:
-                            np.save(os.path.join(result_path, '%s_%s_%s_%s.npy' % (stamp, word, group, key)), a.cpu().numpy())
-        if grid and first_lattice is not None:
-            held = grid['held']
-            on_nodes = samples[0]['sampler'].lattice(refine=1, hours=held['hours'])          # the fine grid's nodes at the file's hours
-            if held['analysis'].shape[3:] != (on_nodes.ny, on_nodes.nx):
-                raise ValueError('inference_cfg.verify_grid: the analysis lives on %s nodes, the fine grid has %s; regrid beforehand'
-                                 % (held['analysis'].shape[3:], (on_nodes.ny, on_nodes.nx)))
-            cases = [dict(smp, analysis=torch.from_numpy(a).to(device)) for smp, a in zip(samples, held['analysis'])]
-            v = self.verify_lattice(cases, on_nodes, grid['products'], grid['thresholds'], grid['scales'], with_clip=kwargs.get('with_clip', self.with_clip))
-            self.last_grid_verification = v
-            if write_source:
-                stamp = start.strftime('%Y-%m-%d_%H_%M_%S')
-                for group in ('hour', 'all'):
-                    for key, a in v[group].items():
-                        np.save(os.path.join(result_path, '%s_nbhd_%s_%s.npy' % (stamp, group, key)), a.cpu().numpy())
-        return maps
+        return run_inference(self, **kwargs)
 
 
 class StagedPdeStep:
