@@ -45,6 +45,7 @@ ACC_U = 2.0 ** -23    # one step of an fp32 accumulator whose rounding mode is n
 MFMA_TERMS = 16       # the 16 products of one v_mfma_f32_32x32x16_bf16 are added inside the instruction: at most one accumulator step each
 MAX_SPLITS = 20       # kMaxSplits of dpn_wgrad.hip: point ranges per product, added by dpn_finish_rows_kernel in fp32, one step each
 FORM_OPS = 4          # Z0 = fmaf(g, own, +-(gJ fr) partner): the product gJ fr, the product with the partner, the fmaf, one of slack
+GH_OPS = 2            # Z0 with the second derivatives' cotangent (z0_frag_derivs): gs = fmaf(-(gH fr), fr, g) in place of g -- the product gH fr and the fmaf
 FIN_SLACK = 8         # finish stage, beside the K terms of a reduction: the fold of four waves' partial tiles (3), the rank-one term's two
 #                       products and its addition (3), two of slack
 SC_FAST = 2.0 ** -14  # plain bf16 mode: hardware v_sin / v_cos behind __sinf / __cosf.  Not derivable here and no CPU model exists; the features are
@@ -210,7 +211,8 @@ def freqs():
 class Features:
     """The coordinate and data features of n points: fp64 sin / cos of the fp32 angles the kernels form (two fp32 divisions, the fp32 product with
     point_path._freqs), in the reference's channel order (pe [n, 192]: f 6 + fn 3 + c; dpe [n, 32, 2, 3]; pe6 [n, 192]: f 12 + fn 6 + c6).
-    pe_in [n, 192]: caller-encoded coordinates in place of x, y, t (no tangent).  fr [192]: the frequency of each pe channel."""
+    pe_in [n, 192]: caller-encoded coordinates in place of x, y, t (no tangent).  fr [192]: the frequency of each pe channel.
+    d2pe = -fr^2 pe and d3pe = -fr^2 dpe, in dpe's layout: the second and third derivatives along xi_c (tests/value_cases.py)."""
 
     def __init__(self, x, y, t, coord_data, geometry=GEOMETRY, pe_in=None, prec='bf16x2'):
         fr = freqs()
@@ -231,25 +233,35 @@ class Features:
             f = fr[:32].double()[None, :, None]
             self.pe = torch.stack([s, c], 2).reshape(n, -1)
             self.dpe = torch.stack([c * f, -s * f], 2)
+            self.d2pe, self.d3pe = torch.stack([-s * f * f, -c * f * f], 2), -self.dpe * f[:, :, None] * f[:, :, None]
         else:
             self.ang = None
             self.pe, self.dpe = pe_in.double(), torch.zeros(n, 32, 2, 3, dtype=F64)
+            self.d2pe, self.d3pe = torch.zeros_like(self.dpe), torch.zeros_like(self.dpe)
         # absolute error of a feature as the kernels hold it in fp32 (before any split): measured for the hi+lo mode's formulas, SC_FAST in the plain mode
         self.sc = sincos_error(angles) if prec == 'bf16x2' else SC_FAST
         self.sc3 = self.sc if pe_in is None else 0.0
 
-    def z0(self, g, gj):
-        """Z0 = g pe + sum_c gJ_c d pe / d xi_c [n, 192] and its absolute-value companion; g [n], gj [n, 3] fp64."""
+    def z0(self, g, gj, gh=None):
+        """Z0 = g pe + sum_c gJ_c d pe / d xi_c [+ sum_c gH_c d2 pe / d xi_c^2] [n, 192] and its absolute-value companion; g [n], gj, gh [n, 3] fp64."""
         n = self.n
         z = g[:, None] * self.pe + (self.dpe * gj[:, None, None, :]).reshape(n, -1)
         za = g.abs()[:, None] * self.pe.abs() + (self.dpe.abs() * gj.abs()[:, None, None, :]).reshape(n, -1)
+        if gh is not None:
+            z = z + (self.d2pe * gh[:, None, None, :]).reshape(n, -1)
+            za = za + (self.d2pe.abs() * gh.abs()[:, None, None, :]).reshape(n, -1)
         return z, za
 
-    def z0_error(self, g, gj, za):
-        """|Z0 as the kernels form it in fp32 - Z0|: the features' error through g and gJ fr, and FORM_OPS roundings (one for caller-encoded features)."""
+    def z0_error(self, g, gj, za, gh=None):
+        """|Z0 as the kernels form it in fp32 - Z0|: the features' error through g, gJ fr [and gH fr^2], and FORM_OPS [+ GH_OPS] roundings (one for
+        caller-encoded features)."""
         n = self.n
-        gjf = (gj.abs()[:, None, None, :] * self.fr.reshape(32, 2, 3)[None]).reshape(n, -1)
-        return self.sc3 * (g.abs()[:, None] + gjf) + (FORM_OPS if self.raw else 1) * U * za
+        fr = self.fr.reshape(32, 2, 3)[None]
+        gjf = (gj.abs()[:, None, None, :] * fr).reshape(n, -1)
+        if gh is None:
+            return self.sc3 * (g.abs()[:, None] + gjf) + (FORM_OPS if self.raw else 1) * U * za
+        ghf = (gh.abs()[:, None, None, :] * fr * fr).reshape(n, -1)
+        return self.sc3 * (g.abs()[:, None] + gjf + ghf) + (FORM_OPS + GH_OPS) * U * za
 
 
 def weights_of(heads, evec, statics):
@@ -342,11 +354,14 @@ def pe_in_of(n):
     return torch.sin(torch.randn(n, 192, generator=torch.Generator().manual_seed(4)) * 3.0)
 
 
-def scaled(c, g_out, g_jxi):
-    """What stage 1 multiplies: g = scale g_out, gJ = scale g_jxi, ONE fp32 product each (gnet must equal it bit for bit), as fp64 [6, n], [6, n, 3]."""
+def scaled(c, g_out, g_jxi, g_hxi=None):
+    """What stage 1 multiplies: g = scale g_out, gJ = scale g_jxi, ONE fp32 product each (gnet must equal it bit for bit), as fp64 [6, n], [6, n, 3];
+    with g_hxi also gH = scale g_hxi (a third value)."""
     s = torch.tensor(c.scale, dtype=torch.float32)
     g = (s * g_out.float()).double().t().contiguous()
     gj = torch.zeros(6, c.n, 3, dtype=F64) if g_jxi is None else (s * g_jxi.float()).double().permute(1, 0, 2).contiguous()
+    if g_hxi is not None:
+        return g, gj, (s * g_hxi.float()).double().permute(1, 0, 2).contiguous()
     return g, gj
 
 
@@ -371,30 +386,39 @@ def flipped_points(ma, mb):
     return ((ma[0] != mb[0]) | (ma[1] != mb[1])).any(2).any(0)
 
 
-def reference(W, masks, pe, dpe, pe6, g_out, g_jxi, scale, t1=None, z1=None):
+def reference(W, masks, pe, dpe, pe6, g_out, g_jxi, scale, t1=None, z1=None, g_hxi=None, d2pe=None):
     """The eleven gradients of ONE net (kernel_model.phase_b's dict, fp64) under the forced masks (m1, m2) [n, 256].  g_out [n], g_jxi [n, 3]: this
     net's cotangents (fp32 values), scale: stage 1's scalar (the product is the kernels' single fp32 one).  t1 = m1 (.) y with y from phase_a's fused
     formulas under the masks, Z1 = m1 (.) (Z0 w1^T + g b1) -- or the given t1 / z1 [n, 256] (the tensors a kernel saved: the reference then
-    starts from them)."""
+    starts from them).  g_hxi [n, 3] with d2pe (Features.d2pe): the second derivatives' cotangent, Z0 += sum_c gH_c d2 pe / d xi_c^2 -- behind a given Z1
+    it reaches d w1 = T1^T Z0 alone."""
     m1, m2 = masks[0].double(), masks[1].double()
     g, gj = (torch.tensor(scale, dtype=g_out.dtype) * g_out).double(), (torch.tensor(scale, dtype=g_jxi.dtype) * g_jxi).double()     # fp32 cotangents: ONE fp32 product
     z = torch.zeros(pe.shape[0], dtype=F64)
     S = KM.phase_a(W, pe, dpe, pe6, z, 'fp64', fused=True, masks=(m1, m2))[2]
     if t1 is not None:
         S = dict(S, t1=t1)
-    return KM.phase_b(W, S, pe, dpe, pe6, g, gj, 'fp64', z1=z1)
+    if g_hxi is None:
+        return KM.phase_b(W, S, pe, dpe, pe6, g, gj, 'fp64', z1=z1)
+    zh = (d2pe * (torch.tensor(scale, dtype=g_hxi.dtype) * g_hxi).double()[:, None, None, :]).reshape(pe.shape[0], -1)
+    if z1 is None:
+        z0 = g[:, None] * pe + (dpe * gj[:, None, None, :]).reshape(pe.shape[0], -1) + zh
+        z1 = S['m1'] * (z0 @ W['w1b1'][:, :192].T + g[:, None] * W['w1b1'][:, 192])
+    gr = KM.phase_b(W, S, pe, dpe, pe6, g, gj, 'fp64', z1=z1)
+    gr['w1b1'] = torch.cat([gr['w1b1'][:, :192] + S['t1'].T @ zh, gr['w1b1'][:, 192:]], 1)
+    return gr
 
 
-def stage1_reference(c, W, F, m1, g, gj):
+def stage1_reference(c, W, F, m1, g, gj, gh=None):
     """(Z1, bound): Z1 = m1 (.) (Z0 w1^T + g b1) of one net and
         m1 (.) [ (HL + acc_steps(12) ACC_U) (|Z0||w1|^T + |g||b1|) + SECOND E_Z0 |w1|^T + SPLIT |pre| ]
     -- the three-product (or plain) GEMM over 12 k-steps, the features' and the forming's error E_Z0 through |w1|, and the planes Z1 is written as."""
     w1, b1 = W['w1b1'][:, :192], W['w1b1'][:, 192]
-    z0, z0a = F.z0(g, gj)
+    z0, z0a = F.z0(g, gj, gh)
     pre = z0 @ w1.T + g[:, None] * b1
     prea = z0a @ w1.abs().T + g.abs()[:, None] * b1.abs()
     hl = C_HL * 2.0 ** -16 if c.prec == 'bf16x2' else C_B * 2.0 ** -8
-    bound = (hl + acc_steps(12) * ACC_U) * prea + SECOND * (F.z0_error(g, gj, z0a) @ w1.abs().T) + SPLIT[c.prec] * pre.abs()
+    bound = (hl + acc_steps(12) * ACC_U) * prea + SECOND * (F.z0_error(g, gj, z0a, gh) @ w1.abs().T) + SPLIT[c.prec] * pre.abs()
     return m1 * pre, m1 * bound
 
 
@@ -421,8 +445,8 @@ def v_add(*ts):
     return V(v, sum(t.e for t in ts) + (len(ts) - 1) * U * sum(t.v.abs() for t in ts))
 
 
-def t1_reference(c, W, F, m1, m2):
-    """(T1, bound) of one net under the forced masks: T1 = m1 (.) y,
+def t1_reference(c, W, F, m1, m2, fused=None):
+    """(T1, bound) of one net under the forced masks (fused: the packed form, default the one of the case's route): T1 = m1 (.) y,
         fused (tile kernels):  y = (m2 (.) u) A + 2 a2,   A = W1 w2, a2 = w2^T wo, u = W2^T wo formed in fp32 by the pack kernel (256 terms each)
         ring kernels:          v = (m2 (.) u) W1 + 2 wo,  y = v w2
     each GEMM with HL of its absolute-value evaluation and acc_steps(16) accumulator steps, y written as planes."""
@@ -431,7 +455,7 @@ def t1_reference(c, W, F, m1, m2):
     acc = acc_steps(16) * ACC_U
     u = V(W['W2'].T @ W['wo'], (256 + FIN_SLACK) * U * (W['W2'].abs().T @ W['wo'].abs()))
     t2, t2e = m2 * u.v, m2 * u.e
-    if fused_route(c):
+    if fused_route(c) if fused is None else fused:
         A = v_mm(V(W['W1']), V(w2), 256)
         a2 = V(w2.T @ W['wo'], (256 + FIN_SLACK) * U * (w2.abs().T @ W['wo'].abs()))
         y = t2 @ A.v + 2.0 * a2.v
@@ -446,7 +470,7 @@ def t1_reference(c, W, F, m1, m2):
     return m1 * y, m1 * (e + SPLIT[c.prec] * y.abs())
 
 
-def wgrad_reference(c, F, m2, T1, Z1, g, gj):
+def wgrad_reference(c, F, m2, T1, Z1, g, gj, gh=None):
     """The eight sums of one net from the DECODED T1 and Z1 (fp64 values of bf16 planes: no operand error), (values, bounds, companion):
         S1 = M2^T Z1                 acc |M2|^T|Z1|                         (0 / 1 times a bf16 number: the products are exact)
         S2 = M2^T G6, G6 = g pe6     M2^T E_G6 + acc |M2|^T|G6|,            E_G6 = |g| (sc + SPLIT |pe6|) + (U + SPLIT) |G6|: the table's features and
@@ -460,8 +484,8 @@ def wgrad_reference(c, F, m2, T1, Z1, g, gj):
     ga = g.abs()
     g6, g6a = g[:, None] * F.pe6, ga[:, None] * F.pe6.abs()
     e_g6 = ga[:, None] * (F.sc + sp * F.pe6.abs()) + (U + sp) * g6a
-    z0, z0a = F.z0(g, gj)
-    e_z0 = F.z0_error(g, gj, z0a) + (sp + lolo) * z0a
+    z0, z0a = F.z0(g, gj, gh)
+    e_z0 = F.z0_error(g, gj, z0a, gh) + (sp + lolo) * z0a
     t1a, z1a = T1.abs(), Z1.abs()
     val = {'S1': m2.T @ Z1, 'S2': m2.T @ g6, 'dw1': T1.T @ z0, 'mv': m2.T @ g, 'db1': T1.T @ g, 'sg': g.sum(), 'q1': Z1.sum(0), 'q6': g6.sum(0)}
     comp = {'S1': m2.T @ z1a, 'S2': m2.T @ g6a, 'dw1': t1a.T @ z0a, 'mv': m2.T @ ga, 'db1': t1a.T @ ga, 'sg': ga.sum(), 'q1': z1a.sum(0), 'q6': g6a.sum(0)}
@@ -542,14 +566,18 @@ def _planes(x, prec):
     return KM._split(x, prec) if prec == 'bf16x2' else [KM._split(x, 'bf16')[0]]
 
 
-def emulate(c, Ws, x, y, t, coord_data, g_out, g_jxi, pe_in=None, alters=(None,)):
+def emulate(c, Ws, x, y, t, coord_data, g_out, g_jxi, pe_in=None, alters=(None,), g_hxi=None, z0_seed=None, geometry=GEOMETRY):
     """One pass of the kernels' arithmetic for case c in fp32 torch: kernel_model.phase_a / mm in the case's precision for the forward pass and
     stage 1, the planes of T1, Z1, G6, Z0 as the kernels write them, the weight-gradient products plane by plane, the finish in fp32.  Returns
     {alter: what the GPU test reads back, as fp64: {'m1', 'm2', 'T1', 'Z1', 'gnet', 'sums', 'sums_abs', 'grads', 'features'}} for every alter in
-    `alters` (None: the faithful pass; the others: ALTERS, the seeded mistakes -- all of them sit behind stage 1, which is evaluated once)."""
-    F = Features(x, y, t, coord_data, pe_in=pe_in, prec=c.prec)
+    `alters` (None: the faithful pass; the others: ALTERS, the seeded mistakes -- all of them sit behind stage 1, which is evaluated once).
+    g_hxi [n, 6, 3]: the second derivatives' cotangent in the seed, Z0 = fmaf(gs, own, +-(gJ fr) partner) with gs = fmaf(-(gH fr), fr, g) as z0_frag_derivs
+    forms it; the pass then also holds 'Z0' [6, n, 192], the stored rows (hi + lo).  z0_seed (with g_hxi), a mistake IN the seed: 'gh_fr' (gH fr for
+    gH fr^2) | 'z0_lo_no_gh' (the stored lo plane taken from the Z0 without the gH term; the multiplied Z0 is right)."""
+    F = Features(x, y, t, coord_data, geometry=geometry, pe_in=pe_in, prec=c.prec)
     n, prec = c.n, c.prec
     g_all, gj_all = scaled(c, g_out, g_jxi)
+    gh_all = None if g_hxi is None else scaled(c, g_out, g_jxi, g_hxi)[2]
     fr = freqs()
     if pe_in is None:                       # the features as the device forms them: its own sin / cos in the hi+lo mode
         if prec == 'bf16x2':
@@ -566,21 +594,29 @@ def emulate(c, Ws, x, y, t, coord_data, g_out, g_jxi, pe_in=None, alters=(None,)
     else:
         s6, c6 = torch.sin(F.ang6), torch.cos(F.ang6)
     pe6_32 = torch.stack([s6, c6], 2).reshape(n, -1)
-    passes = {a: {'m1': [], 'm2': [], 'T1': [], 'Z1': [], 'gnet': [], 'grads': [], 'sums': {k: [] for k in SUMS}} for a in alters}
+    passes = {a: {'m1': [], 'm2': [], 'T1': [], 'Z1': [], 'Z0': [], 'gnet': [], 'grads': [], 'sums': {k: [] for k in SUMS}} for a in alters}
     for k in range(6):
         W = {kk: v.float() for kk, v in Ws[k].items()}
         S = KM.phase_a(W, pe32, dpe32, pe6_32, torch.zeros(n), prec, fused=fused_route(c))[2]
         m1, m2 = S['m1'], S['m2']
         g, gj = g_all[k].float(), gj_all[k].float()
         z0 = g[:, None] * pe32 + (dpe32 * gj[:, None, None, :]).reshape(n, -1)
+        if gh_all is not None:
+            f3 = fr[:32][None, :, None, None].expand(n, 32, 2, 3)
+            ghf = gh_all[k].float()[:, None, None, :] * f3
+            gs = (g[:, None, None, None] - ghf * (1.0 if z0_seed == 'gh_fr' else f3)).reshape(n, -1)
+            z0_plain, z0 = z0, gs * pe32 + (dpe32 * gj[:, None, None, :]).reshape(n, -1)
         w1, b1 = W['w1b1'][:, :192], W['w1b1'][:, 192]
         z1 = m1 * (KM.mm(z0, w1.T, prec) + g[:, None] * b1)
         T1p, Z1p, Z0p = _planes(S['t1'], prec), _planes(z1, prec), _planes(z0, prec)
+        if gh_all is not None and z0_seed == 'z0_lo_no_gh' and prec == 'bf16x2':
+            Z0p = [Z0p[0], _planes(z0_plain, prec)[1]]
         G6p = _planes(g[:, None] * sum(_planes(pe6_32, prec)), prec)
         for alter in alters:
             res = passes[alter]
             res['m1'].append(m1 > 0), res['m2'].append(m2 > 0)
             res['T1'].append(sum(p.double() for p in T1p)), res['Z1'].append(sum(p.double() for p in Z1p)), res['gnet'].append(g.double())
+            res['Z0'].append(sum(p.double() for p in Z0p))
             # ---- dpn_wgrad: the products plane by plane, fp32 accumulation
             keep = torch.ones(n, 1)
             if alter == 'last_point':
@@ -609,7 +645,7 @@ def emulate(c, Ws, x, y, t, coord_data, g_out, g_jxi, pe_in=None, alters=(None,)
             res['grads'].append({kk: v.double() for kk, v in gr.items()})
     out = {}
     for a, res in passes.items():
-        o = {k: torch.stack(res[k]) for k in ('m1', 'm2', 'T1', 'Z1', 'gnet')}
+        o = {k: torch.stack(res[k]) for k in ('m1', 'm2', 'T1', 'Z1', 'Z0', 'gnet')}
         o['grads'], o['features'] = res['grads'], F
         o['sums'] = {k: torch.stack(v) for k, v in res['sums'].items()}
         o['sums_abs'] = {k: v.abs() for k, v in o['sums'].items()}            # one range
@@ -625,24 +661,30 @@ def ratio(got, ref, bound):
     return float(r.max()) if r.numel() else 0.0
 
 
-def check(c, Ws, F, obs, g_out, g_jxi, stages=('stage1', 'saved', 'wgrad', 'finish', 'chain')):
-    """{(stage, tensor): worst error-to-bound ratio over the six nets} of what a pass `obs` (emulate() or the GPU's read-back) holds."""
+def check(c, Ws, F, obs, g_out, g_jxi, stages=('stage1', 'saved', 'wgrad', 'finish', 'chain'), g_hxi=None):
+    """{(stage, tensor): worst error-to-bound ratio over the six nets} of what a pass `obs` (emulate() or the GPU's read-back) holds.  g_hxi [n, 6, 3]:
+    the second derivatives' cotangent (dpn_bwd_points_derivs), carried through every stage; stage 'z0' (only where asked for): the stored Z0 rows
+    obs['Z0'] [6, n, 192] against Z0 itself, bound: the forming's error and the planes it is written as."""
     g_all, gj_all = scaled(c, g_out, g_jxi)
+    gh_all = [None] * 6 if g_hxi is None else scaled(c, g_out, g_jxi, g_hxi)[2]
     out = {}
 
     def put(stage, name, r):
         out[(stage, name)] = max(out.get((stage, name), 0.0), r)
     for k in range(6):
-        W, g, gj = Ws[k], g_all[k], gj_all[k]
+        W, g, gj, gh = Ws[k], g_all[k], gj_all[k], gh_all[k]
         m1, m2 = obs['m1'][k].double(), obs['m2'][k].double()
         T1, Z1 = obs['T1'][k], obs['Z1'][k]
+        if 'z0' in stages:
+            z0, z0a = F.z0(g, gj, gh)
+            put('z0', 'Z0', ratio(obs['Z0'][k], z0, F.z0_error(g, gj, z0a, gh) + SPLIT[c.prec] * z0a))
         if 'stage1' in stages:
-            ref, bound = stage1_reference(c, W, F, m1, g, gj)
+            ref, bound = stage1_reference(c, W, F, m1, g, gj, gh)
             put('stage1', 'Z1', ratio(Z1, ref, bound))
         if 'saved' in stages:
             ref, bound = t1_reference(c, W, F, m1, m2)
             put('saved', 'T1', ratio(T1, ref, bound))
-        val, bound, comp = wgrad_reference(c, F, m2, T1, Z1, g, gj)
+        val, bound, comp = wgrad_reference(c, F, m2, T1, Z1, g, gj, gh)
         got = {kk: obs['sums'][kk][k] for kk in SUMS}
         if 'wgrad' in stages:
             for kk in SUMS:
@@ -652,7 +694,8 @@ def check(c, Ws, F, obs, g_out, g_jxi, stages=('stage1', 'saved', 'wgrad', 'fini
             for nm in NAMES:
                 put('finish', nm, ratio(obs['grads'][k][nm], fb[nm].v, fb[nm].e))
         if 'chain' in stages:       # the oracle's phase_b on the pass's m1, m2, T1, Z1: the weight kernels' own bounds, carried through the finish
-            ref = reference(W, (m1, m2), F.pe, F.dpe, F.pe6, g_out[:, k], g_jxi[:, k] if g_jxi is not None else torch.zeros(c.n, 3), c.scale, t1=T1, z1=Z1)
+            ref = reference(W, (m1, m2), F.pe, F.dpe, F.pe6, g_out[:, k], g_jxi[:, k] if g_jxi is not None else torch.zeros(c.n, 3), c.scale, t1=T1, z1=Z1,
+                            g_hxi=None if g_hxi is None else g_hxi[:, k], d2pe=F.d2pe)
             fb = finish_bounds(W, val, {kk: bound[kk] + MAX_SPLITS * U * comp[kk] for kk in SUMS})
             for nm in NAMES:
                 put('chain', nm, ratio(obs['grads'][k][nm], ref[nm].reshape(fb[nm].v.shape), fb[nm].e))
